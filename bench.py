@@ -13,19 +13,25 @@ voting, Hough NMS, line sort/decode) over ONE batch of FRAMES_PER_GPU frames alr
 Cache from the step before last, and the two batches in flight are always different ones).  Frames are independent units: ranks
 process disjoint batches, no data-path collective (weak scaling: per-GPU batch fixed).  --scatter adds the RCCL data path of SURVEY 8(e):
 the step's batch is born on rank 0 and scattered, the per-frame line counts and strongest lines are all-gathered.
-Timing: barrier + synchronize, K steps, synchronize + barrier, MAX over ranks; median of --reps repetitions.
+Timing: barrier + synchronize, K steps, synchronize + barrier, MAX over ranks; median of --reps repetitions (default 1: --steps is the
+number of timed steps).
 
-After the timed region every one of the 256 frames is checked against tests/golden/golden_batch.json (edge-map MD5, edge count, line
-count, strength sum, line-set hash -- all produced by the real CompV library, tests/golden/make_golden_batch.py), in the same two-lane
-asynchronous mode the timed steps use; a mismatch raises and NO number is printed.
+A plain run sets up, warms up, times the steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the JSON line.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32): counts (lines per frame), lines
+(the valid compvhip_line records of every frame, frame after frame: rho, theta, strength, row, col), edge_rows (edge pixels per frame row)
+and edges_sample (a fixed, seeded sample of the edge maps' pixels).
 
-Extra objects on the JSON line:
+--full adds everything else, as separate passes around the timed region:
+  verified        every one of the 256 frames checked against tests/golden/golden_batch.json (edge-map MD5, edge count, line count,
+                  strength sum, line-set hash -- all produced by the real CompV library, tests/golden/make_golden_batch.py), in the same
+                  two-lane asynchronous mode the timed steps use; a mismatch raises and NO number is printed
   roofline        dominant kernel (by measured time): algorithmic bytes / average launch duration (HIP events on the launch stream)
   roofline_canny  the fused Sobel->Canny tile kernel on the same basis (north_star's 40 % target is quoted on it) + its VALU-issue floor
   cpu_baseline    the REAL CompV CPU library (oracle/_ref, AVX2 intrinsics path) timed on a bounded sample of the same workload, at its
                   best thread count and frame-parallel (P processes x T threads over independent frames)
   host_api        latency of the host-pointer (drop-in) entry points on one 4K frame, PCIe transfers included
   kht             the batched KHT path on this run's edge maps (BASELINE config 5)
+  kernels_extra, configs_extra, kernels_ms_per_step   the other kernels of the path, the 1080p configuration, per-kernel times
 """
 import argparse
 import hashlib
@@ -47,6 +53,8 @@ T_LOW, T_HIGH = 59.0, 119.0
 THETA_DEG, SHT_THRESHOLD = 1.0, 100
 GOLDEN_FRAMES = 256
 M64 = (1 << 64) - 1
+DUMP_SEED = 20240611                               # --dump-outputs: the pixel sample is the same in every run and build
+DUMP_EDGE_SAMPLES, DUMP_LINES_MAX = 1 << 22, 1 << 21   # 16.8 MB + at most 41.9 MB of float32: under 64 MB with edge_rows
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -319,6 +327,29 @@ def check_batch(torch, q, seeds, golden, W, H, line_cap, dev):
     return F, int(n_e.sum()), int(counts.sum())
 
 
+def dump_outputs(out_dir, torch, q):
+    """--dump-outputs: what the last timed step handed its caller (lane q's line counts, lines and edge maps), as float32 .npy files.  The lines
+    of all frames fit the budget at the benchmark's sizes (1.8 M at 4K); beyond DUMP_LINES_MAX a seeded sample of them is written instead."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    counts = q["counts"].cpu().numpy().astype(np.int64)
+    cap = q["lines"].shape[1]
+    lines = q["lines"].cpu().numpy()
+    lines = lines[np.arange(cap)[None, :] < np.minimum(counts, cap)[:, None]]           # (sum of counts, 5): frame after frame
+    if len(lines) > DUMP_LINES_MAX:
+        lines = lines[np.sort(rng.choice(len(lines), DUMP_LINES_MAX, replace=False))]
+    rec = np.empty(lines.shape, dtype=np.float32)
+    rec[:, :2] = lines[:, :2].view(np.float32)                                            # rho, theta
+    rec[:, 2:] = lines[:, 2:]                                                             # strength, row, col: exact in float32
+    edges = q["edges"]
+    idx = torch.from_numpy(np.sort(rng.integers(0, edges.numel(), DUMP_EDGE_SAMPLES))).to(edges.device)
+    arrays = {"counts": counts.astype(np.float32), "lines": rec,
+              "edge_rows": (edges != 0).sum(dim=2).cpu().numpy().astype(np.float32),
+              "edges_sample": edges.reshape(-1)[idx].cpu().numpy().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def extra_config(torch, capi, sharding, ctx, dev, W, H, F, NB, steps, warmup, reps, fixture):
     """The same pipeline at another frame size (north_star: throughput on 1080p as well as 4K), same two-lane asynchronous mode, every frame of the
     rotating batches checked against its own reference-derived fixture after the timed region."""
@@ -421,19 +452,22 @@ def self_launch(gpus, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=512, help="timed steps per repetition (512 x 0.66 ms x 3 repetitions: a second of timed GPU work)")
+    ap.add_argument("--steps", type=int, default=512, help="timed steps per repetition")
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--frames-per-gpu", type=int, default=32)   # BASELINE config 4: 256 frames over 8 GPUs
     ap.add_argument("--batches", type=int, default=8, help="distinct resident batches the steps rotate over (8 x 32 = config 4's 256 frames)")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host_api / kht objects")
-    ap.add_argument("--no-verify", action="store_true", help="experiment only: skip the golden check of all frames (the JSON line says so)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="experiment: no per-kernel HIP events in the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify every frame, time the kernels (HIP events, rooflines) and run the extra objects and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline object")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the host_api / kht / kernels_extra / configs_extra objects")
+    ap.add_argument("--no-verify", action="store_true", help="with --full, experiment only: skip the golden check of all frames (the JSON line says so)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full, experiment: no per-kernel HIP events in the timed steps")
     ap.add_argument("--event-every", type=int, default=8,
-                    help="HIP events around the dominant kernel on every N-th step of a lane in the timed region (1 = every step: ~1 %% slower, the events are stream operations)")
-    ap.add_argument("--reps", type=int, default=3, help="repetitions of the timed K-step loop; the MEDIAN repetition is reported")
+                    help="with --full: HIP events around the dominant kernel on every N-th step of a lane in the timed region (1 = every step: ~1 %% slower, the events are stream operations)")
+    ap.add_argument("--reps", type=int, default=1, help="repetitions of the timed K-step loop; the MEDIAN repetition is reported")
     ap.add_argument("--inflight", type=int, default=2,
                     help="batches in flight: N plans (own buffers) on N HIP streams take the steps in turn, so the latency-bound kernels of one "
                          "batch (key sort, decode, hysteresis rounds) run under the wide kernels of the other; 1 = one stream, kernels never overlap")
@@ -486,7 +520,7 @@ def main():
     # frame f of block b has the global index b * F + f and the seed 12345 + (index mod 256); rank r runs block (r + k) % NB at step k
     block_seeds = sharding.block_seeds(F, NB, GOLDEN_FRAMES)
     blocks = [synth.batch(s) for s in block_seeds]
-    if rank == 0:   # the device generator against the host one (one frame: the generators are checked exhaustively in tests/)
+    if rank == 0 and args.full:   # the device generator against the host one (one frame: the generators are checked exhaustively in tests/)
         from oracle_bindings import synth_frame
         if not np.array_equal(blocks[0][0].cpu().numpy(), synth_frame(W, H, block_seeds[0][0])):
             raise RuntimeError("device frame generator disagrees with tests/oracle_bindings.synth_frame")
@@ -566,8 +600,9 @@ def main():
         q["plan"].pipeline(blocks[b].data_ptr(), T_LOW, T_HIGH, SHT_THRESHOLD, 0, q["edges"].data_ptr(), q["lines"].data_ptr(), line_cap,
                            q["counts"].data_ptr(), q["stream"].cuda_stream)
 
+    events = args.full and not args.no_kernel_events
     dominant = "sht_vote_kernel"
-    if not args.no_kernel_events:
+    if events:
         plan.set_timing(1)
         one_sync_step(lanes[0], 0)
         per = {}
@@ -582,8 +617,8 @@ def main():
     # breakdown, and the Canny tile kernel's duration when it is not the dominant one, come from a second, untimed, instrumented pass.
     timed_mode = TIMING_MODES.get(dominant, 2)
     for q in lanes:
-        q["plan"].set_timing(0 if args.no_kernel_events else timed_mode)
-    if not args.no_kernel_events and not args.sync_steps:
+        q["plan"].set_timing(timed_mode if events else 0)
+    if events and not args.sync_steps:
         sample_every[0], sample_mode[0] = max(1, args.event_every), timed_mode
     per_kernel = {}
 
@@ -610,6 +645,8 @@ def main():
         rep_elapsed.append(sharding.max_over_ranks(e, dist if dist_on else None, comm_dev))
         collect(per_kernel)   # the dominant kernel's events of this repetition's K steps (read after the closing bracket)
     elapsed = sorted(rep_elapsed)[len(rep_elapsed) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, lanes[0] if args.sync_steps else lanes[(step_no[0] - 1) % len(lanes)])
 
     # second pass, untimed: ONE batch at a time on ONE stream with HIP events around every launch -- the per-kernel durations a kernel
     # has when it owns the GPU (in the timed region two batches are in flight and kernels of different batches share the CUs)
@@ -618,7 +655,7 @@ def main():
         q["plan"].set_timing(0)
     breakdown = {}
     iso_steps = min(args.steps, 64)
-    if rank == 0 and not args.no_kernel_events:
+    if rank == 0 and events:
         plan.set_timing(1)
         for k in range(iso_steps):
             one_sync_step(lanes[0], k % NB)
@@ -629,7 +666,9 @@ def main():
     golden = None
     verify_note = None
     gpath = os.path.join(ROOT, "tests", "golden", "golden_batch.json")
-    if args.no_verify:
+    if not args.full:
+        verify_note = "not checked in a plain run (--full checks every frame against tests/golden/golden_batch.json)"
+    elif args.no_verify:
         verify_note = "skipped (--no-verify)"
     elif (W, H) != (3840, 2160) or not os.path.exists(gpath):
         verify_note = "no reference-derived fixture for this geometry: outputs of the two lanes compared with each other only"
@@ -641,7 +680,7 @@ def main():
     total_lines = 0
     lines_frame0 = None
     checked = 0
-    for b0 in range(0, NB, len(lanes)):
+    for b0 in range(0, NB if args.full else 0, len(lanes)):
         todo = [(lanes[i], b0 + i) for i in range(len(lanes)) if b0 + i < NB]
         if args.sync_steps:
             for q, b in todo:
@@ -659,7 +698,7 @@ def main():
             total_lines += nl
             if b == 0:
                 lines_frame0 = int(q["counts"][0].item())
-    if golden is None and len(lanes) > 1 and not args.no_verify:
+    if golden is None and len(lanes) > 1 and args.full and not args.no_verify:
         # no fixture: at least the lanes must agree on one common batch
         for q in lanes:
             one_sync_step(q, 0)
@@ -686,7 +725,32 @@ def main():
     total_px = n_ranks * F * W * H * args.steps
     value = total_px / elapsed / 1e6
 
+    overlapped = len(lanes) > 1 and not args.sync_steps
     if rank == 0:
+        out = {
+            "metric": "Mpixels/s Sobel->Canny->HoughSHT on 4K uint8",
+            "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+            "reps": len(rep_elapsed), "reps_ms_per_step": [round(e / args.steps * 1e3, 4) for e in rep_elapsed],
+            "timing": "median of %d repetitions of the K-step region (each: barrier + synchronize, K steps, synchronize + barrier, MAX over ranks)" % len(rep_elapsed),
+            "step_mode": "synchronous (host reads the hysteresis flag every step)" if args.sync_steps else
+                         "pipelined (compvhip_plan_pipeline_async: step k's hysteresis flag is read while step k+1 runs), %d batch(es) in flight "
+                         "(one plan + HIP stream each, steps dealt round-robin)" % len(lanes),
+            "batches_in_flight": len(lanes),
+            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "dist_backend": (dist.get_backend() if dist_on else None),
+            "rccl_version": rccl_version, "n_ranks_seen": len(seen), "ranks_seen": seen,
+            "config": {"workload": "batched %dx%d uint8 frames, Sobel3x3 -> Canny(59,119) -> HoughSHT(rho=1, theta=1deg, thr=100); %d distinct frames "
+                                   "resident per GPU as %d batches of %d, a step processes one batch, steps rotate over the batches"
+                                   % (W, H, min(NB * F, GOLDEN_FRAMES), NB, F),
+                       "frames_per_gpu": F, "resident_batches": NB, "global_frames_per_step": world * F,
+                       "parallelism": ("frames sharded across %d GPU(s), no data-path collective" % world) if not args.scatter else
+                                      ("step batch scattered from rank 0 over %s (grouped send/recv), line counts + top-%d lines all-gathered" % (args.dist_backend, TOPK))},
+            "verified": ({"frames_checked": checked, "against": "tests/golden/golden_batch.json (real CompV: edge-map MD5, edge count, line count, strength sum, line-set hash)",
+                          "mode": "two lanes in flight, asynchronous steps" if overlapped else "one lane"} if golden is not None else verify_note),
+            "lines_last_step_all_ranks": (int(sum(all_counts)) if all_counts is not None else None),
+        }
+    if rank == 0 and args.full:
         R = 2 * (W + H) + 1
         T = 180
         nsteps_timed = args.steps * max(1, args.reps)
@@ -726,7 +790,6 @@ def main():
             floor_ms = n * cpi / SIMDS / (CLOCK_GHZ * 1e9) * 1e3
             return {"SQ_INSTS_VALU": int(n), "cycles_per_wave_instruction": cpi, "simds": SIMDS, "clock_ghz": CLOCK_GHZ,
                     "floor_ms": round(floor_ms, 4), "frac": round(floor_ms / ms, 4)}
-        overlapped = len(lanes) > 1 and not args.sync_steps
         iso = {k: v[0] / v[1] for k, v in breakdown.items()}
         roofline = None
         if dom:
@@ -777,27 +840,7 @@ def main():
                     "timing": "sum of the stage's launches in the single-stream instrumented pass (HIP events), one batch per step"}
         canny_stage = {"canny_tile_kernel", "canny_resolve_kernel", "canny_mean_thresholds", "otsu_kernels"}
         sht_stage = {k for k in breakdown if k.startswith("sht_")}
-        out = {
-            "metric": "Mpixels/s Sobel->Canny->HoughSHT on 4K uint8",
-            "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "reps": len(rep_elapsed), "reps_ms_per_step": [round(e / args.steps * 1e3, 4) for e in rep_elapsed],
-            "timing": "median of %d repetitions of the K-step region (each: barrier + synchronize, K steps, synchronize + barrier, MAX over ranks)" % len(rep_elapsed),
-            "step_mode": "synchronous (host reads the hysteresis flag every step)" if args.sync_steps else
-                         "pipelined (compvhip_plan_pipeline_async: step k's hysteresis flag is read while step k+1 runs), %d batch(es) in flight "
-                         "(one plan + HIP stream each, steps dealt round-robin)" % len(lanes),
-            "batches_in_flight": len(lanes),
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "dist_backend": (dist.get_backend() if dist_on else None),
-            "rccl_version": rccl_version, "n_ranks_seen": len(seen), "ranks_seen": seen,
-            "config": {"workload": "batched %dx%d uint8 frames, Sobel3x3 -> Canny(59,119) -> HoughSHT(rho=1, theta=1deg, thr=100); %d distinct frames "
-                                   "resident per GPU as %d batches of %d, a step processes one batch, steps rotate over the batches"
-                                   % (W, H, min(NB * F, GOLDEN_FRAMES), NB, F),
-                       "frames_per_gpu": F, "resident_batches": NB, "global_frames_per_step": world * F,
-                       "parallelism": ("frames sharded across %d GPU(s), no data-path collective" % world) if not args.scatter else
-                                      ("step batch scattered from rank 0 over %s (grouped send/recv), line counts + top-%d lines all-gathered" % (args.dist_backend, TOPK))},
-            "verified": ({"frames_checked": checked, "against": "tests/golden/golden_batch.json (real CompV: edge-map MD5, edge count, line count, strength sum, line-set hash)",
-                          "mode": "two lanes in flight, asynchronous steps" if overlapped else "one lane"} if golden is not None else verify_note),
+        out.update({
             "roofline": roofline, "roofline_canny": rc,
             # the same algorithmic bytes priced against the whole STAGE (every launch of it), not one kernel
             "roofline_stage_canny": stage_roof(canny_stage, alg["canny_tile_kernel"], "Sobel -> NMS -> hysteresis (tile kernel + resolve rounds), 1 B/px read"),
@@ -808,8 +851,7 @@ def main():
             "edge_pixels_per_batch": total_edges // NB,
             "lines_frame0": lines_frame0,
             "lines_per_batch": total_lines // NB,
-            "lines_last_step_all_ranks": (int(sum(all_counts)) if all_counts is not None else None),
-        }
+        })
         if world == 1 and not args.no_extras:
             try:
                 out["host_api"] = host_api_latency(capi, local_rank if dist_on else 0, blocks[0][0].cpu().numpy())
@@ -834,6 +876,7 @@ def main():
                 out["cpu_baseline"] = cpu_baseline(W, H)
             except Exception as e:  # the baseline is reporting only; never let it hide the GPU number
                 out["cpu_baseline"] = {"error": str(e)}
+    if rank == 0:
         print(json.dumps(out))
     for q in lanes:
         q["plan"].close()

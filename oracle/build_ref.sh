@@ -10,6 +10,8 @@
 # Outputs:
 #   oracle/_ref/libcompv_ref.so      base + core + gpu modules of CompV (no GL/camera/drawing)
 #   oracle/_ref/libcompv_refshim.so  oracle/ref_shim.cxx : flat C wrappers over the CompV C++ API
+#   oracle/_ref/libcompv_hip_plugin.so, oracle/_ref/headless_samples
+#                                    integration/ : the HIP factories inside the real CompV, and the samples' call sequences
 #
 # Usage: oracle/build_ref.sh [REF_ROOT]   (default /root/reference); no-op when REF_ROOT is absent.
 set -euo pipefail
@@ -55,3 +57,19 @@ g++ -include limits -std=c++11 -O2 -fPIC -w -mavx2 -msse4.1 -DCOMPV_ASM=0 \
   -shared -o "$OUT/libcompv_refshim.so" "$HERE/ref_shim.cxx" \
   -L"$OUT" -lcompv_ref -Wl,-rpath,'$ORIGIN' -ldl -lpthread
 echo "build_ref: OK -> $OUT/libcompv_ref.so, $OUT/libcompv_refshim.so"
+
+# The real-CompV plugin (integration/compv_hip_plugin.cxx) and its headless sample driver (integration/headless_samples.cxx)
+# need the CompV headers as well, so they are built here, next to the library they link, and travel with oracle/_ref/.
+ROOT="$(dirname "$HERE")"
+if [ ! -f "$ROOT/compv_amd/lib/libcompv_hip.so" ]; then
+  echo "build_ref: compv_amd/lib/libcompv_hip.so not built yet -> plugin and headless_samples skipped"; exit 0
+fi
+INC="-I$REF/base/include -I$REF/core/include -I$REF/gpu/include"
+FLAGS="-include limits -std=c++11 -O2 -fPIC -w -DCOMPV_ASM=0"
+g++ $FLAGS $INC -shared -o "$OUT/libcompv_hip_plugin.so" "$ROOT/integration/compv_hip_plugin.cxx" \
+  -L"$ROOT/compv_amd/lib" -lcompv_hip -L"$OUT" -lcompv_ref \
+  -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/../../compv_amd/lib'
+g++ $FLAGS $INC -o "$OUT/headless_samples" "$ROOT/integration/headless_samples.cxx" \
+  -L"$OUT" -lcompv_hip_plugin -lcompv_ref -L"$ROOT/compv_amd/lib" -lcompv_hip \
+  -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/../../compv_amd/lib' -ldl -lpthread
+echo "build_ref: OK -> $OUT/libcompv_hip_plugin.so, $OUT/headless_samples"

@@ -21,7 +21,7 @@ def test_header_declares_the_binding_list():
 
 def test_library_exports_every_declared_symbol():
     from compv_amd import capi
-    lib = ctypes.CDLL(capi.LIB_PATH)
+    lib = capi.load()   # not a bare CDLL: that would load the system HIP runtime beside torch's bundled one (capi._share_hip_runtime_with_torch)
     for s in _declared():
         assert hasattr(lib, s), s
 

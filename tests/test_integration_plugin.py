@@ -1,21 +1,21 @@
-"""GPU test of the drop-in boundary against the REAL CompV library: integration/_build/headless_samples runs the
+"""GPU test of the drop-in boundary against the REAL CompV library: oracle/_ref/headless_samples runs the
 samples' call sequences (samples/edges_canny, samples/hough_lines) through CompVEdgeDete::newObj / CompVHough::newObj
 twice -- stock CPU factories, then the HIP factories registered by id with CompVFeature::addFactory -- and compares.
-The binary is built in the build container (integration/build.sh needs the CompV checkout) and travels as a prebuilt."""
+The binary is built with the reference library (oracle/build_ref.sh needs the CompV sources) and travels with oracle/_ref/."""
 import os
 import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "integration", "_build", "headless_samples")
+BIN = os.path.join(ROOT, "oracle", "_ref", "headless_samples")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("W,H,frames", [(641, 480, 1), (1280, 720, 2), (1920, 1080, 1)])
 def test_real_compv_with_hip_factories(W, H, frames):
     # on a GPU box the prebuilt drop-in binary must be there: a missing one is a failure of the build / snapshot, not a reason to skip
-    assert os.path.exists(BIN), "integration/_build/headless_samples is missing: run __graft_entry__.build() where the CompV checkout is (integration/build.sh)"
+    assert os.path.exists(BIN), "oracle/_ref/headless_samples is missing: run __graft_entry__.build() where the CompV sources are (oracle/build_ref.sh)"
     r = subprocess.run([BIN, str(W), str(H), str(frames)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert "DROP-IN PARITY OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     assert r.returncode == 0
@@ -33,7 +33,7 @@ def test_bench_under_torchrun_nccl_single_rank(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29617",
            os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "1", "--reps", "2", "--frames-per-gpu", "2",
-           "--width", "1280", "--height", "720", "--no-cpu-baseline"]
+           "--width", "1280", "--height", "720", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -51,7 +51,7 @@ def _two_rank_scatter_run(backend, port):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--gpus", "2", "--shared-gpu", "--scatter", "--steps", "4", "--warmup", "2", "--reps", "2", "--frames-per-gpu", "2",
-           "--batches", "4", "--width", "1280", "--height", "720", "--no-cpu-baseline", "--no-extras", "--dist-backend", backend]
+           "--batches", "4", "--width", "1280", "--height", "720", "--no-cpu-baseline", "--no-extras", "--full", "--dist-backend", backend]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     res = None
     if r.returncode == 0:
@@ -86,6 +86,44 @@ def test_bench_two_ranks_on_one_gpu_gloo_host_staged(tmp_path):
     assert res["dist_backend"] == "gloo" and res["ranks_seen"] == [0, 1]
     assert res["n_gpus"] == 2 and res["value"] > 0 and "scattered from rank 0 over gloo" in res["config"]["parallelism"]
     assert res["lines_last_step_all_ranks"] is not None and res["lines_frame0"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_dumps_the_last_step_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline only; --dump-outputs writes what the last timed step returned,
+    and those outputs match the reference-derived fixture of the frames that step processed (line counts, strength sums, line-set hashes, edge counts)."""
+    import json
+    import sys
+    import numpy as np
+    from compv_amd import sharding
+    steps, warmup, F, NB, W, H = 3, 1, 2, 2, 3840, 2160
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--frames-per-gpu", str(F),
+           "--batches", str(NB), "--width", str(W), "--height", str(H), "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(out) == 1, r.stdout[-2000:]
+    res = json.loads(out[0])
+    assert res["metric"].startswith("Mpixels/s") and res["unit"] == "Mpixels/s" and res["higher_is_better"] is True and res["dtype"] == "u8"
+    assert res["steps"] == steps and res["reps"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+    assert abs(res["value"] - F * W * H / (res["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * res["value"] + 1
+    assert "roofline" not in res and "cpu_baseline" not in res and "kht" not in res
+    arrays = {n[:-4]: np.load(str(tmp_path / n)) for n in os.listdir(str(tmp_path))}
+    assert sorted(arrays) == ["counts", "edge_rows", "edges_sample", "lines"]
+    assert all(a.dtype == np.float32 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    with open(os.path.join(ROOT, "tests", "golden", "golden_batch.json")) as f:
+        golden = {g["seed"]: g for g in json.load(f)["frames"]}
+    seeds = sharding.block_seeds(F, NB)[sharding.block_of_step(0, warmup + steps - 1, NB)]
+    counts = arrays["counts"].astype(np.int64)
+    assert len(arrays["lines"]) == counts.sum() and arrays["edge_rows"].shape == (F, H)
+    first = 0
+    for f, seed in enumerate(seeds):
+        g = golden[seed]
+        ln = arrays["lines"][first:first + counts[f]].astype(np.int64)
+        first += counts[f]
+        h = sum(((W + H) - int(row) + 32768) * 1000003 + int(col) * 7919 + int(st) * 31337 for st, row, col in ln[:, 2:]) & ((1 << 64) - 1)
+        got = (int(counts[f]), int(ln[:, 2].sum()), "%016x" % h, int(arrays["edge_rows"][f].sum()))
+        assert got == (g["lines"], g["sum_strength"], g["line_hash"], g["edges"]), (seed, got)
 
 
 @pytest.mark.gpu

@@ -3,7 +3,7 @@
 TAG=${1:-grid_ab}; CAPS=${2:-"1264 1072"}; REPS=${3:-3}
 O=gpurun_out/$TAG; mkdir -p $O
 for rep in $(seq 1 $REPS); do for cap in $CAPS; do
-  COMPVHIP_VOTE_MAX_WINDOW=$cap python bench.py --no-cpu-baseline > $O/bench_${cap}_$rep.json 2> $O/bench_${cap}_$rep.err
+  COMPVHIP_VOTE_MAX_WINDOW=$cap python bench.py --full --reps 3 --no-cpu-baseline > $O/bench_${cap}_$rep.json 2> $O/bench_${cap}_$rep.err
   python - $O/bench_${cap}_$rep.json $cap $rep <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ CAPS=${2:-"1264 1072 960 848 784 736 672"}
 O=gpurun_out/$TAG
 mkdir -p $O
 for cap in $CAPS; do
-  COMPVHIP_VOTE_MAX_WINDOW=$cap python bench.py --no-cpu-baseline --no-extras --steps 256 > $O/bench_$cap.json 2> $O/bench_$cap.err
+  COMPVHIP_VOTE_MAX_WINDOW=$cap python bench.py --full --reps 3 --no-cpu-baseline --no-extras --steps 256 > $O/bench_$cap.json 2> $O/bench_$cap.err
   python - $O/bench_$cap.json $cap <<'PY'
 import json, sys, ctypes
 try:

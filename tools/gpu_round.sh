@@ -6,7 +6,7 @@ mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1
 echo "pytest exit $?" >> $O/pytest.log
 tail -4 $O/pytest.log
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --reps 3 --no-cpu-baseline"
 $B > $O/bench_default.json 2> $O/bench_default.err
 for f in $O/bench_*.json; do python - "$f" <<'PY'
 import json,sys
