@@ -314,7 +314,7 @@ void shtTables(float thetaDeg, size_t T, std::vector<int32_t>& sinQ, std::vector
 // of one and a half: no change, that step is bound by the launch chain; 32 x 720p on 4 x 2 instead of 2 x 1: 0.180 against 0.170 ms per step).
 // Lab knob (like COMPVHIP_RESOLVE_WRAP): COMPVHIP_VOTE_MAX_WINDOW=<rows> caps a voting workgroup's window below the 1264 rows the LDS holds, i.e. forces a
 // finer tile grid that leaves LDS free beside a voting workgroup (co-residency experiments, profiles/r06/coresidency.md).  Results are identical for any
-// grid (tests/test_gpu_parity.py::test_vote_window_knob_is_bit_exact); unset = the product's choice.
+// grid (tests/test_gpu_plan_geometry.py::test_vote_window_knob_is_bit_exact); unset = the product's choice.
 static size_t voteMaxWindow()   // read whenever a plan is made: one process can hold plans on different grids (tools/coresidency/grid_ab.py)
 {
 	const char* e = getenv("COMPVHIP_VOTE_MAX_WINDOW");

@@ -327,7 +327,8 @@ COMPVHIP_API int compvhip_plan_acc(compvhip_plan* plan, size_t frame, const uint
 /* Copies the accumulator of frame f into a caller DEVICE buffer in the reference layout: int32 [R][outStride]
  * (outStride >= T), i.e. acc[(barrier - rho) * outStride + t] (houghsht.cxx:430-431). */
 COMPVHIP_API int compvhip_plan_acc_export(compvhip_plan* plan, size_t frame, int32_t* d_out, size_t outStride, void* stream);
-/* Number of edge pixels per frame found by the last canny/houghsht of this plan (device int32[frames]). */
+/* Number of edge pixels per frame voted by the last houghsht / pipeline step of this plan (device int32[frames]).  The SHT's voting
+ * kernel counts them: a compvhip_plan_canny call alone resets them to zero, and before the plan's first SHT the call is refused. */
 COMPVHIP_API int compvhip_plan_edge_counts(compvhip_plan* plan, const int32_t** d_edge_counts);
 
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
