@@ -40,8 +40,11 @@ EXPORTS = [
     "compvhip_plan_pipeline_async", "compvhip_plan_wait", "compvhip_houghsht_to_cartesian", "compvhip_houghkht_to_cartesian",
     "compvhip_houghkht_kernels_u8", "compvhip_houghkht_stage_ms", "compvhip_convlt1_8u16s16s", "compvhip_convlt1_16s16s16s",
     "compvhip_plan_pipeline_ex", "compvhip_plan_houghkht", "compvhip_plan_houghkht_stage_ms", "compvhip_houghkht_link_u8",
-    "compvhip_houghkht_dims", "compvhip_host_cpu_budget",
+    "compvhip_houghkht_dims", "compvhip_host_cpu_budget", "compvhip_plan_houghkht_ex", "compvhip_houghkht_ex_u8",
 ]
+
+KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
+KHT_ORDERS = {"reference": KHT_ORDER_REFERENCE, "canonical": KHT_ORDER_CANONICAL}
 
 
 class Line(C.Structure):
@@ -55,6 +58,18 @@ class PipelineOpts(C.Structure):
     """compvhip_pipeline_opts (include/compv_hip.h)"""
     _fields_ = [("tLow", C.c_float), ("tHigh", C.c_float), ("threshold", C.c_int), ("maxLines", C.c_int), ("ksize", C.c_int),
                 ("thresholdType", C.c_int), ("pixfmt", C.c_int), ("d_gray", C.c_void_p), ("d_otsu", C.c_void_p), ("d_cart", C.c_void_p)]
+
+
+class KhtOpts(C.Structure):
+    """compvhip_kht_opts (include/compv_hip.h): a zero field takes the default"""
+    _fields_ = [("rho", C.c_float), ("thetaDeg", C.c_float), ("threshold", C.c_int), ("maxLines", C.c_int), ("clusterMinDeviation", C.c_double),
+                ("clusterMinSize", C.c_size_t), ("kernelMinHeight", C.c_double), ("hostThreads", C.c_int), ("order", C.c_int)]
+
+
+def _kht_order(order):
+    if order not in KHT_ORDERS:
+        raise ValueError("order must be one of %s, not %r" % (sorted(KHT_ORDERS), order))
+    return KHT_ORDERS[order]
 
 
 class CompvHipError(RuntimeError):
@@ -129,6 +144,8 @@ def load():
     L.compvhip_plan_wait.argtypes = [vp, i32]
     L.compvhip_plan_houghkht.argtypes = [vp, vp, C.c_float, C.c_float, i32, i32, C.c_double, sz, C.c_double, vp, sz, vp, vp, i32]
     L.compvhip_plan_houghkht_stage_ms.argtypes = [vp, vp, C.POINTER(C.c_double), C.POINTER(i32)]
+    L.compvhip_plan_houghkht_ex.argtypes = [vp, vp, C.POINTER(KhtOpts), vp, sz, vp, vp]
+    L.compvhip_houghkht_ex_u8.argtypes = [vp, vp, sz, sz, sz, C.POINTER(KhtOpts), vp, sz, C.POINTER(sz), C.POINTER(C.c_double)]
     L.compvhip_plan_pipeline_ex.argtypes = [vp, vp, C.POINTER(PipelineOpts), vp, vp, sz, vp, vp, C.POINTER(i32)]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
@@ -250,16 +267,22 @@ class Context:
         return (lines, acc) if want_acc else lines
 
 
-    def houghkht(self, edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14):
-        """Returns (lines, GS); lines['row'] / ['col'] hold the rho / theta indices."""
+    def houghkht(self, edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, order="reference"):
+        """Returns (lines, GS); lines['row'] / ['col'] hold the rho / theta indices.  order: "reference" (compvhip_houghkht_u8: the reference's tie
+        order) or "canonical" (compvhip_houghkht_ex_u8: count descending, ties by emission key, peaks found and sorted on the GPU)."""
         H, W = edges.shape
+        o = _kht_order(order)
         lines = np.zeros(cap, LINE_DTYPE)
         n = C.c_size_t(0)
         gs = C.c_double(1.0)
-        rc = self.lib.compvhip_houghkht_u8(self.h, _ptr(edges), W, H, edges.strides[0], rho, theta_deg, threshold, max_lines, min_dev, min_size,
-                                           min_height, _ptr(lines), cap, C.byref(n), C.byref(gs))
+        if o == KHT_ORDER_REFERENCE:
+            rc = self.lib.compvhip_houghkht_u8(self.h, _ptr(edges), W, H, edges.strides[0], rho, theta_deg, threshold, max_lines, min_dev, min_size,
+                                               min_height, _ptr(lines), cap, C.byref(n), C.byref(gs))
+        else:
+            opts = KhtOpts(rho, theta_deg, threshold, max_lines, min_dev, min_size, min_height, 0, o)
+            rc = self.lib.compvhip_houghkht_ex_u8(self.h, _ptr(edges), W, H, edges.strides[0], C.byref(opts), _ptr(lines), cap, C.byref(n), C.byref(gs))
         if rc == E_OUT_OF_BOUND and n.value > cap:
-            return self.houghkht(edges, rho, theta_deg, threshold, max_lines, min_dev, min_size, min_height, cap=n.value)
+            return self.houghkht(edges, rho, theta_deg, threshold, max_lines, min_dev, min_size, min_height, cap=n.value, order=order)
         self._chk(rc)
         return lines[:n.value], gs.value
 
@@ -348,14 +371,21 @@ class Plan:
                                                          C.byref(t) if asynchronous else None))
         return t.value if asynchronous else None
 
-    def houghkht(self, d_edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, threads=0):
-        """CompVHoughKht::process on the plan's device edge maps; returns ([lines of frame f as a LINE_DTYPE array], [GS of frame f or None])."""
+    def houghkht(self, d_edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, threads=0,
+                 order="reference"):
+        """CompVHoughKht::process on the plan's device edge maps; returns ([lines of frame f as a LINE_DTYPE array], [GS of frame f or None]).
+        order: "reference" (compvhip_plan_houghkht) or "canonical" (compvhip_plan_houghkht_ex: peaks found and sorted on the GPU)."""
         F = self.frames
+        o = _kht_order(order)
         lines = np.zeros((F, cap), LINE_DTYPE)
         counts = np.zeros(F, np.uint64)
         gs = np.full(F, np.nan, np.float64)
-        self.ctx._chk(self.lib.compvhip_plan_houghkht(self.h, d_edges, rho, theta_deg, threshold, max_lines, min_dev, min_size, min_height,
-                                                      _ptr(lines), cap, _ptr(counts), _ptr(gs), threads))
+        if o == KHT_ORDER_REFERENCE:
+            self.ctx._chk(self.lib.compvhip_plan_houghkht(self.h, d_edges, rho, theta_deg, threshold, max_lines, min_dev, min_size, min_height,
+                                                          _ptr(lines), cap, _ptr(counts), _ptr(gs), threads))
+        else:
+            opts = KhtOpts(rho, theta_deg, threshold, max_lines, min_dev, min_size, min_height, threads, o)
+            self.ctx._chk(self.lib.compvhip_plan_houghkht_ex(self.h, d_edges, C.byref(opts), _ptr(lines), cap, _ptr(counts), _ptr(gs)))
         return [lines[f][:int(counts[f])] for f in range(F)], [None if np.isnan(g) else float(g) for g in gs]
 
     def houghkht_stage_ms(self):

@@ -41,6 +41,12 @@ constexpr int kAsyncDepth = 4;            // outstanding compvhip_plan_pipeline_
 constexpr size_t kMaxTimeline = 4096;     // timing entries kept while nobody reads them (asynchronous steps)
 } // namespace
 
+// device tables of the canonical KHT path's line fields (khtCanonTables), built once per geometry
+struct KhtCanonTabs {
+	float* rho = nullptr; float* theta = nullptr;
+	size_t W = 0, H = 0; double dRho = 0.0, dTheta = 0.0;
+};
+
 // Device + host scratch of ONE KHT frame in flight: the context owns one for its host entry point, a plan one per worker thread of
 // compvhip_plan_houghkht (every worker has its own HIP stream; nothing in here is shared between threads).
 struct KhtScratch {
@@ -60,6 +66,7 @@ struct KhtScratch {
 	KhtPoint* linked = nullptr; size_t linkedCap = 0;         // points of the strings, string after string: PINNED host memory, written by the linker, uploaded without staging
 	KhtPeaksWork peaks;                                        // sort records, visited map, axes of the peak stage
 	std::vector<KhtCell> cellsHost;                            // the vote cells of the frame, downloaded
+	KhtCanonTabs tabs; KhtLine* canonLines = nullptr; size_t canonLinesCap = 0; int32_t* canonCount = nullptr;   // canonical order: the frame's sorted lines, their count
 	double stageMs[6] = {};   // link, subdivide (GPU), statistics (GPU), prune + Gmin, vote + peaks (GPU), sort + sweep of the last call
 	std::string err;
 };
@@ -87,6 +94,8 @@ struct KhtBatchState {
 	int32_t* counts = nullptr; size_t countsElems = 0;
 	KhtVoteParams* params = nullptr; size_t paramsCap = 0; KhtVoteParams* paramsHost = nullptr; size_t paramsHostCap = 0;
 	KhtCell* cells = nullptr; size_t cellsCap = 0; int* cellCount = nullptr; KhtCell* cellsHost = nullptr; size_t cellsHostCap = 0;
+	KhtCanonTabs tabs; KhtLine* canonLines = nullptr; size_t canonLinesCap = 0; int32_t* canonCounts = nullptr;       // canonical order: [frames][cap] sorted lines, [kKhtBatch] counts (device)
+	KhtLine* canonLinesHost = nullptr; size_t canonLinesHostCap = 0;                                                  // pinned
 	std::vector<KhtBatchFrame> frames;
 	hipEvent_t syncEv = nullptr;   // blocking-sync event: a controller that waits for a GPU stage SLEEPS (hipStreamSynchronize spins on a CPU of the quota the workers need)
 	double stageMs[6] = {};   // of the groups this state handled in the current call
@@ -222,6 +231,7 @@ void khtScratchFree(compvhip_ctx* ctx, KhtScratch& k)
 	dfree(ctx, k.counts); dfree(ctx, k.params); dfree(ctx, k.cells); dfree(ctx, k.cellCount);
 	dfree(ctx, k.pts); dfree(ctx, k.spans); dfree(ctx, k.kernelsDev);
 	dfree(ctx, k.strings); dfree(ctx, k.counts32); dfree(ctx, k.scratch); dfree(ctx, k.stack);
+	dfree(ctx, k.tabs.rho); dfree(ctx, k.tabs.theta); dfree(ctx, k.canonLines); dfree(ctx, k.canonCount); k.canonLinesCap = 0;
 	if (k.linked) { (void)hipHostFree(k.linked); k.linked = nullptr; k.linkedCap = 0; }
 	if (k.ownStream && k.stream) { (void)hipStreamDestroy(k.stream); k.stream = nullptr; }
 }
@@ -232,6 +242,8 @@ void khtBatchFree(compvhip_ctx* ctx, KhtBatchState* b)
 	dfree(ctx, b->dBits); dfree(ctx, b->pts); dfree(ctx, b->strings); dfree(ctx, b->counts32); dfree(ctx, b->totals);
 	dfree(ctx, b->spans); dfree(ctx, b->scratch); dfree(ctx, b->stack); dfree(ctx, b->kernelsDev);
 	dfree(ctx, b->counts); dfree(ctx, b->params); dfree(ctx, b->cells); dfree(ctx, b->cellCount);
+	dfree(ctx, b->tabs.rho); dfree(ctx, b->tabs.theta); dfree(ctx, b->canonLines); dfree(ctx, b->canonCounts);
+	if (b->canonLinesHost) (void)hipHostFree(b->canonLinesHost);
 	if (b->hostBits) (void)hipHostFree(b->hostBits);
 	if (b->linked) (void)hipHostFree(b->linked);
 	if (b->stringsHost) (void)hipHostFree(b->stringsHost);
@@ -1893,14 +1905,34 @@ static int khtBuildKernels(compvhip_ctx* ctx, KhtScratch& K, size_t W, size_t H,
 	return COMPVHIP_OK;
 }
 
-// one frame, host edge map -> lines in the reference's order (the body of CompVHoughKht::process, houghkht.cxx:208-447)
+// the device tables of the line fields for this geometry (uploaded when it changes; synchronous: the host vectors die here)
+static hipError_t khtCanonTabs(compvhip_ctx* ctx, KhtCanonTabs& t, const KhtAxes& ax, hipStream_t st)
+{
+	if (t.rho && t.W == ax.W && t.H == ax.H && t.dRho == ax.dRho && t.dTheta == ax.dThetaDeg) return hipSuccess;
+	dfree(ctx, t.rho); dfree(ctx, t.theta);
+	std::vector<float> rho, theta;
+	khtCanonTables(ax, rho, theta);
+	hipError_t e = dmalloc(ctx, &t.rho, rho.size());
+	if (e == hipSuccess) e = dmalloc(ctx, &t.theta, theta.size());
+	if (e == hipSuccess) e = hipMemcpyAsync(t.rho, rho.data(), rho.size() * sizeof(float), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(t.theta, theta.data(), theta.size() * sizeof(float), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e != hipSuccess) { dfree(ctx, t.rho); dfree(ctx, t.theta); return e; }
+	t.W = ax.W; t.H = ax.H; t.dRho = ax.dRho; t.dTheta = ax.dThetaDeg;
+	return hipSuccess;
+}
+
+// one frame, host edge map -> lines (the body of CompVHoughKht::process, houghkht.cxx:208-447) in the reference's order, or in the canonical order
+// (compvhip_kht_opts.order) with the peak stage on the GPU; *found = the lines after the maxLines cut, of which out holds the first min(found, cap) (all of
+// them in the reference order)
 // (the frame's edge map is K.plane: packed by the caller, destroyed by the linker)
 static int khtFrame(compvhip_ctx* ctx, KhtScratch& K, size_t W, size_t H, const KhtAxes& ax, int threshold, int maxLines,
-                    double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight, std::vector<KhtLine>& out, double* gs)
+                    double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight, int order, size_t cap, std::vector<KhtLine>& out, size_t* found, double* gs)
 {
 	using clk = std::chrono::steady_clock;
 	auto msSince = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
 	out.clear();
+	*found = 0;
 	std::vector<KhtKernel> kernels;
 	double hmax = 0.0;
 	const int rck = khtBuildKernels(ctx, K, W, H, clusterMinDeviation, clusterMinSize, kernels, hmax);
@@ -1935,6 +1967,29 @@ static int khtFrame(compvhip_ctx* ctx, KhtScratch& K, size_t W, size_t H, const 
 	KhtBatchVote onev{};
 	onev.frames = 1; onev.paramsBase[0] = 0; onev.nKernels[0] = a.nKernels; onev.gs[0] = GS; onev.mapElems = countsElems; onev.cellCap = cellCap;
 	KCHK(K, launch_kht_vote(a, onev, st));
+	if (order == COMPVHIP_KHT_ORDER_CANONICAL) {
+		// peaks, line test and sort on the device: only the lines come back
+		KCHK(K, khtCanonTabs(ctx, K.tabs, ax, st));
+		const size_t capDev = std::min(cap, cellCap);
+		if (capDev) KCHK(K, growDevice(ctx, K.canonLines, K.canonLinesCap, capDev));
+		if (!K.canonCount) KCHK(K, dmalloc(ctx, &K.canonCount, 1));
+		KCHK(K, launch_kht_canon_peaks(a, onev, st));
+		KhtCanonOut o;
+		o.rho = K.tabs.rho; o.theta = K.tabs.theta; o.lines = K.canonLines; o.cap = static_cast<int>(capDev); o.counts = K.canonCount; o.maxLines = maxLines;
+		KCHK(K, launch_kht_canon_sort(a, onev, o, st));
+		int32_t n = 0;
+		KCHK(K, hipMemcpyAsync(&n, K.canonCount, sizeof(n), hipMemcpyDeviceToHost, st));
+		KCHK(K, hipStreamSynchronize(st));
+		if (n < 0) { K.err = "canonical KHT: merge scratch too small"; return COMPVHIP_E_INVALID_STATE; }   // cannot happen (kht_canon_sort_kernel)
+		*found = static_cast<size_t>(n);
+		out.resize(std::min(*found, capDev));
+		if (!out.empty()) {
+			KCHK(K, hipMemcpyAsync(out.data(), K.canonLines, out.size() * sizeof(KhtLine), hipMemcpyDeviceToHost, st));
+			KCHK(K, hipStreamSynchronize(st));
+		}
+		K.stageMs[4] += msSince(t3);
+		return COMPVHIP_OK;
+	}
 	KCHK(K, launch_kht_peaks(a, onev, st));
 	int cellCount = 0;
 	KCHK(K, hipMemcpyAsync(&cellCount, K.cellCount, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1949,6 +2004,7 @@ static int khtFrame(compvhip_ctx* ctx, KhtScratch& K, size_t W, size_t H, const 
 	t3 = clk::now();
 	// host: sort + sweep (order dependent, :1195-1247)
 	khtPeaks(ax, cells, maxLines, out, K.peaks);
+	*found = out.size();
 	K.stageMs[5] += msSince(t3);
 	return COMPVHIP_OK;
 }
@@ -2031,10 +2087,9 @@ int compvhip_houghkht_stage_ms(compvhip_ctx* ctx, double* ms6)
 	return COMPVHIP_OK;
 }
 
-int compvhip_houghkht_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float rho, float thetaDeg, int threshold, int maxLines,
-                         double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight, compvhip_line* lines, size_t cap, size_t* n, double* gs)
+static int khtHostEntry(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float rho, float thetaDeg, int threshold, int maxLines,
+                        double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight, int order, compvhip_line* lines, size_t cap, size_t* n, double* gs)
 {
-	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
 	if (!edges || !n || (cap && !lines) || S < W || !W || !H) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument"); // houghkht.cxx:210-211
 	KhtAxes ax;
 	int rc = khtCheckParams(ctx, W, H, rho, thetaDeg, threshold, clusterMinSize, kernelMinHeight, ax);
@@ -2048,12 +2103,45 @@ int compvhip_houghkht_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size
 		khtPackBytes(edges, W, H, S, ctx->kht.plane);   // host bytes -> the linker's bit plane (the linker never touches the caller's map)
 		ctx->kht.stageMs[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
 	}
-	rc = khtFrame(ctx, ctx->kht, W, H, ax, threshold, maxLines, clusterMinDeviation, clusterMinSize, kernelMinHeight, out, gs);
+	size_t found = 0;
+	rc = khtFrame(ctx, ctx->kht, W, H, ax, threshold, maxLines, clusterMinDeviation, clusterMinSize, kernelMinHeight, order, cap, out, &found, gs);
 	if (rc) return fail(ctx, rc, ctx->kht.err.c_str());
-	*n = out.size();
+	*n = found;
 	khtCopyLines(out, lines, cap);
-	if (out.size() > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "line buffer too small");
+	if (found > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "line buffer too small");
 	return COMPVHIP_OK;
+}
+
+int compvhip_houghkht_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float rho, float thetaDeg, int threshold, int maxLines,
+                         double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight, compvhip_line* lines, size_t cap, size_t* n, double* gs)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	return khtHostEntry(ctx, edges, W, H, S, rho, thetaDeg, threshold, maxLines, clusterMinDeviation, clusterMinSize, kernelMinHeight,
+	                    COMPVHIP_KHT_ORDER_REFERENCE, lines, cap, n, gs);
+}
+
+// compvhip_kht_opts with its zero fields replaced by the defaults; false for an unknown order
+static bool khtResolveOpts(const compvhip_kht_opts* o, compvhip_kht_opts& k)
+{
+	if (o->order != COMPVHIP_KHT_ORDER_REFERENCE && o->order != COMPVHIP_KHT_ORDER_CANONICAL) return false;
+	k = *o;
+	if (k.rho == 0.f) k.rho = 1.f;
+	if (k.thetaDeg == 0.f) k.thetaDeg = 1.f;
+	if (k.threshold == 0) k.threshold = 1;
+	if (k.clusterMinDeviation == 0.0) k.clusterMinDeviation = 2.0;   // houghkht.cxx:38-40
+	if (k.clusterMinSize == 0) k.clusterMinSize = 10;
+	if (k.kernelMinHeight == 0.0) k.kernelMinHeight = 0.002;
+	return true;
+}
+
+int compvhip_houghkht_ex_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, const compvhip_kht_opts* opts,
+                            compvhip_line* lines, size_t cap, size_t* n, double* gs)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_kht_opts k;
+	if (!opts || !khtResolveOpts(opts, k)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null options or unknown KHT order");
+	return khtHostEntry(ctx, edges, W, H, S, k.rho, k.thetaDeg, k.threshold, k.maxLines, k.clusterMinDeviation, k.clusterMinSize, k.kernelMinHeight,
+	                    k.order, lines, cap, n, gs);
 }
 
 // CompVHoughKht::process on the plan's `frames` device edge maps.  The chain walk of the linker (Appendix A) is sequential per frame and
@@ -2069,8 +2157,8 @@ int compvhip_houghkht_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size
 // GPU-touching stages took 5-9 x their single-frame time -- a launch / synchronisation pile-up, not compute.)
 // one group of up to kKhtBatch frames
 static int khtBatchGroup(compvhip_plan* p, KhtBatchState& B, KhtPool& pool, const uint8_t* d_edges, size_t G, const KhtAxes& ax, int threshold, int maxLines,
-                         double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight, compvhip_line* lines, size_t cap, size_t* counts, double* gs, bool* overflow,
-                         std::string& err)
+                         double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight, int order, compvhip_line* lines, size_t cap, size_t* counts, double* gs,
+                         bool* overflow, std::string& err)
 {
 	using clk = std::chrono::steady_clock;
 	auto msSince = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
@@ -2228,6 +2316,9 @@ static int khtBatchGroup(compvhip_plan* p, KhtBatchState& B, KhtPool& pool, cons
 	if (rc) return rc;
 
 	// ---- E. Gaussian voting + smoothing / threshold of ALL frames' vote maps: one launch each, the cell counts, then the cells ----
+	// (canonical order: voting, then peaks + line test and the sort of every frame's lines on the GPU; the line counts, then the lines)
+	const bool canon = order == COMPVHIP_KHT_ORDER_CANONICAL;
+	int32_t lineCount[kKhtBatch] = {};
 	tc = clk::now();
 	const int stride = static_cast<int>(alignUp(ax.rhoN + 2, 16));
 	const size_t mapElems = (ax.T + 2) * static_cast<size_t>(stride), cellCap = ax.T * ax.rhoN;
@@ -2253,24 +2344,75 @@ static int khtBatchGroup(compvhip_plan* p, KhtBatchState& B, KhtPool& pool, cons
 		a.rhoN = static_cast<int>(ax.rhoN); a.T = static_cast<int>(ax.T); a.dRho = ax.dRho; a.dThetaDeg = ax.dThetaDeg; a.gs = 1.0;
 		a.threshold = threshold; a.cells = B.cells; a.cellCount = B.cellCount; a.cellCap = static_cast<int>(cellCap);
 		BCHK(launch_kht_vote(a, tabV, st));
-		BCHK(launch_kht_peaks(a, tabV, st));
-		int cc[kKhtBatch];
-		BCHK(hipMemcpyAsync(cc, B.cellCount, sizeof(cc), hipMemcpyDeviceToHost, st));
-		BCHK(sleepSync());
-		size_t nCells = 0;
-		for (size_t f = 0; f < G; ++f) {
-			KhtBatchFrame& fr = B.frames[f];
-			fr.cellCount = fr.params.empty() ? 0 : std::min<int>(cc[f], static_cast<int>(cellCap));
-			fr.cellOff = nCells; nCells += static_cast<size_t>(fr.cellCount);
-		}
-		if (nCells) {
-			BCHK(growPinned(B.cellsHost, B.cellsHostCap, nCells));
-			for (size_t f = 0; f < G; ++f) {
-				const KhtBatchFrame& fr = B.frames[f];
-				if (fr.cellCount) BCHK(hipMemcpyAsync(B.cellsHost + fr.cellOff, B.cells + f * cellCap, static_cast<size_t>(fr.cellCount) * sizeof(KhtCell), hipMemcpyDeviceToHost, st));
-			}
+		if (canon) {
+			BCHK(khtCanonTabs(ctx, B.tabs, ax, st));
+			const size_t capDev = std::min(cap, cellCap);
+			if (capDev) BCHK(growDevice(ctx, B.canonLines, B.canonLinesCap, capDev * G));
+			if (!B.canonCounts) BCHK(dmalloc(ctx, &B.canonCounts, kKhtBatch));
+			BCHK(launch_kht_canon_peaks(a, tabV, st));
+			KhtCanonOut o;
+			o.rho = B.tabs.rho; o.theta = B.tabs.theta; o.lines = B.canonLines; o.cap = static_cast<int>(capDev); o.counts = B.canonCounts; o.maxLines = maxLines;
+			BCHK(launch_kht_canon_sort(a, tabV, o, st));
+			BCHK(hipMemcpyAsync(lineCount, B.canonCounts, G * sizeof(int32_t), hipMemcpyDeviceToHost, st));
 			BCHK(sleepSync());
+			size_t nLines = 0;
+			for (size_t f = 0; f < G; ++f) {
+				if (B.frames[f].params.empty()) lineCount[f] = 0;   // (no launch covered it: nKernels == 0)
+				if (lineCount[f] < 0) { err = "canonical KHT: merge scratch too small"; return COMPVHIP_E_INVALID_STATE; }   // cannot happen (kht_canon_sort_kernel)
+				nLines += std::min(static_cast<size_t>(lineCount[f]), capDev);
+			}
+			if (nLines) {
+				BCHK(growPinned(B.canonLinesHost, B.canonLinesHostCap, nLines));
+				size_t off = 0;
+				for (size_t f = 0; f < G; ++f) {
+					const size_t nf = std::min(static_cast<size_t>(lineCount[f]), capDev);
+					if (nf) BCHK(hipMemcpyAsync(B.canonLinesHost + off, B.canonLines + f * capDev, nf * sizeof(KhtLine), hipMemcpyDeviceToHost, st));
+					off += nf;
+				}
+				BCHK(sleepSync());
+				off = 0;
+				for (size_t f = 0; f < G; ++f) {
+					const size_t nf = std::min(static_cast<size_t>(lineCount[f]), capDev);
+					for (size_t i = 0; i < nf; ++i) {
+						const KhtLine& l = B.canonLinesHost[off + i];
+						compvhip_line& d = lines[f * cap + i];
+						d.rho = l.rho; d.theta = l.theta; d.strength = l.strength; d.row = l.rhoIndex; d.col = l.thetaIndex;
+					}
+					off += nf;
+				}
+			}
 		}
+		else {
+			BCHK(launch_kht_peaks(a, tabV, st));
+			int cc[kKhtBatch];
+			BCHK(hipMemcpyAsync(cc, B.cellCount, sizeof(cc), hipMemcpyDeviceToHost, st));
+			BCHK(sleepSync());
+			size_t nCells = 0;
+			for (size_t f = 0; f < G; ++f) {
+				KhtBatchFrame& fr = B.frames[f];
+				fr.cellCount = fr.params.empty() ? 0 : std::min<int>(cc[f], static_cast<int>(cellCap));
+				fr.cellOff = nCells; nCells += static_cast<size_t>(fr.cellCount);
+			}
+			if (nCells) {
+				BCHK(growPinned(B.cellsHost, B.cellsHostCap, nCells));
+				for (size_t f = 0; f < G; ++f) {
+					const KhtBatchFrame& fr = B.frames[f];
+					if (fr.cellCount) BCHK(hipMemcpyAsync(B.cellsHost + fr.cellOff, B.cells + f * cellCap, static_cast<size_t>(fr.cellCount) * sizeof(KhtCell), hipMemcpyDeviceToHost, st));
+				}
+				BCHK(sleepSync());
+			}
+		}
+	}
+	if (canon) {
+		B.stageMs[4] += msSince(tc);
+		for (size_t f = 0; f < G; ++f) {
+			const KhtBatchFrame& fr = B.frames[f];
+			if (fr.haveGS && gs) gs[f] = fr.GS;
+			counts[f] = static_cast<size_t>(lineCount[f]);
+			if (counts[f] > cap) *overflow = true;
+			B.stageMs[0] += fr.ms[0]; B.stageMs[2] += fr.ms[2]; B.stageMs[3] += fr.ms[3];
+		}
+		return COMPVHIP_OK;
 	}
 	B.stageMs[4] += msSince(tc);
 
@@ -2301,10 +2443,9 @@ static int khtBatchGroup(compvhip_plan* p, KhtBatchState& B, KhtPool& pool, cons
 	return COMPVHIP_OK;
 }
 
-int compvhip_plan_houghkht(compvhip_plan* p, const uint8_t* d_edges, float rho, float thetaDeg, int threshold, int maxLines, double clusterMinDeviation,
-                           size_t clusterMinSize, double kernelMinHeight, compvhip_line* lines, size_t cap, size_t* counts, double* gs, int hostThreads)
+static int khtPlanEntry(compvhip_plan* p, const uint8_t* d_edges, float rho, float thetaDeg, int threshold, int maxLines, double clusterMinDeviation,
+                        size_t clusterMinSize, double kernelMinHeight, int order, compvhip_line* lines, size_t cap, size_t* counts, double* gs, int hostThreads)
 {
-	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_edges || !counts || (cap && !lines)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
 	const size_t W = p->W, H = p->H, S = p->S, F = p->frames;
@@ -2372,7 +2513,7 @@ int compvhip_plan_houghkht(compvhip_plan* p, const uint8_t* d_edges, float rho, 
 				const size_t g0 = g * group, G = std::min<size_t>(group, F - g0);
 				bool overflow = false;
 				const int r = khtBatchGroup(p, *p->khtBatch[k], pool, d_edges + g0 * S * H, G, ax, threshold, maxLines, clusterMinDeviation, clusterMinSize, kernelMinHeight,
-				                            lines ? lines + g0 * cap : nullptr, cap, counts + g0, gs ? gs + g0 : nullptr, &overflow, errs[k]);
+				                            order, lines ? lines + g0 * cap : nullptr, cap, counts + g0, gs ? gs + g0 : nullptr, &overflow, errs[k]);
 				if (overflow) overflowAny.store(1);
 				if (r) { codes[k] = r; badGroup[k] = g0; nextGroup.store(nGroups); break; }   // the other controllers finish the group they are in and stop
 			}
@@ -2398,6 +2539,23 @@ int compvhip_plan_houghkht(compvhip_plan* p, const uint8_t* d_edges, float rho, 
 	catch (const std::exception& ex) { return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, (std::string("exception in the batched KHT: ") + ex.what()).c_str()); }
 	catch (...) { return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "exception in the batched KHT"); }
 	return COMPVHIP_OK;
+}
+
+int compvhip_plan_houghkht(compvhip_plan* p, const uint8_t* d_edges, float rho, float thetaDeg, int threshold, int maxLines, double clusterMinDeviation,
+                           size_t clusterMinSize, double kernelMinHeight, compvhip_line* lines, size_t cap, size_t* counts, double* gs, int hostThreads)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	return khtPlanEntry(p, d_edges, rho, thetaDeg, threshold, maxLines, clusterMinDeviation, clusterMinSize, kernelMinHeight, COMPVHIP_KHT_ORDER_REFERENCE,
+	                    lines, cap, counts, gs, hostThreads);
+}
+
+int compvhip_plan_houghkht_ex(compvhip_plan* p, const uint8_t* d_edges, const compvhip_kht_opts* opts, compvhip_line* lines, size_t cap, size_t* counts, double* gs)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_kht_opts k;
+	if (!opts || !khtResolveOpts(opts, k)) return fail(p->ctx, COMPVHIP_E_INVALID_PARAMETER, "null options or unknown KHT order");
+	return khtPlanEntry(p, d_edges, k.rho, k.thetaDeg, k.threshold, k.maxLines, k.clusterMinDeviation, k.clusterMinSize, k.kernelMinHeight, k.order,
+	                    lines, cap, counts, gs, k.hostThreads);
 }
 
 int compvhip_plan_houghkht_stage_ms(compvhip_plan* p, double* ms6, double* wallMs, int* threads)

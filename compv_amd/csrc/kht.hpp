@@ -95,4 +95,24 @@ hipError_t launch_kht_subdivide(const KhtSubdivArgs& a, const KhtBatchStrings& t
 hipError_t launch_kht_vote(const KhtGpuArgs& a, const KhtBatchVote& tab, hipStream_t stream);
 hipError_t launch_kht_peaks(const KhtGpuArgs& a, const KhtBatchVote& tab, hipStream_t stream);
 
+// Canonical order (COMPVHIP_KHT_ORDER_CANONICAL, include/compv_hip.h): records sorted by smoothed count descending, then emission key ascending; a record is
+// a line iff no record at ANOTHER position of its 8-neighbourhood comes earlier in that order -- a local test, so the peak stage runs on the GPU.
+//   kht_canon_peaks_kernel: one workgroup per strip of kKhtCanonRows x kKhtCanonCols record positions of one frame (vote map staged in LDS with a 2-cell
+//                           halo); appends the strip's LINES as KhtCell (order = emission key, count = smoothed count) to the frame's cell list (a.cells,
+//                           a.cellCount: the same buffers kht_peaks_kernel fills)
+//   kht_canon_sort_kernel:  one workgroup per frame; sorts the frame's lines in LDS (up to kKhtCanonSortLds) or, beyond, by LDS-sorted chunks merged in
+//                           global memory (the two halves of the frame's cell list: its lines fill at most half of it); cuts at maxLines, writes KhtLine
+constexpr int kKhtCanonRows = 8, kKhtCanonCols = 256;
+constexpr int kKhtCanonSortLds = 2048;
+struct KhtCanonOut {
+	const float* rho; const float* theta;   // (float)rho[i] / (float)((theta[i] * pi) / 180): rhoN / T entries, built on the host (khtCanonTables)
+	KhtLine* lines; int cap;                // [frames][cap]: the first min(count, cap) lines of every frame
+	int32_t* counts;                        // [frames]: lines after the maxLines cut; -1: the merge scratch did not fit (cannot happen, see kht_kernels.hip)
+	int maxLines;
+};
+static_assert(sizeof(KhtLine) == 20, "KhtLine has compvhip_line's layout");
+void khtCanonTables(const KhtAxes& ax, std::vector<float>& rho, std::vector<float>& theta);
+hipError_t launch_kht_canon_peaks(const KhtGpuArgs& a, const KhtBatchVote& tab, hipStream_t stream);
+hipError_t launch_kht_canon_sort(const KhtGpuArgs& a, const KhtBatchVote& tab, const KhtCanonOut& o, hipStream_t stream);
+
 } // namespace compvhip

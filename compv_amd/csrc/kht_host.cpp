@@ -437,4 +437,14 @@ void khtPeaks(const KhtAxes& ax, std::vector<KhtCell>& cells, int maxLines, std:
 	if (maxLines > 0 && lines.size() > static_cast<size_t>(maxLines)) lines.resize(static_cast<size_t>(maxLines));
 }
 
+// the line fields of the canonical path's device tables: rho[i] and theta[i] exactly as khtPeaks converts them
+void khtCanonTables(const KhtAxes& ax, std::vector<float>& rhoF, std::vector<float>& thetaF)
+{
+	std::vector<double> rho, theta;
+	khtFillAxes(ax, rho, theta);
+	rhoF.resize(rho.size()); thetaF.resize(theta.size());
+	for (size_t i = 0; i < rho.size(); ++i) rhoF[i] = static_cast<float>(rho[i]);
+	for (size_t i = 0; i < theta.size(); ++i) thetaF[i] = static_cast<float>((theta[i] * kPi) / 180.0); // COMPV_MATH_DEGREE_TO_RADIAN
+}
+
 } // namespace compvhip

@@ -16,6 +16,8 @@
 //   kht_peaks_kernel  peaks_Section3_4_VotesCount (:1151-1192,1282-1308 and intrin_sse2.cxx:20-96): 3x3 binomial
 //                     smoothing of the non-zero cells, threshold, compaction of the surviving cells (with their position
 //                     in the reference's emission order, which the host needs for the order-dependent sweep).
+//   kht_canon_peaks_kernel, kht_canon_sort_kernel  the canonical order (include/compv_hip.h): the line test is local under a total order of the
+//                     records, so the peaks are found, tested and sorted here and only the lines leave the device (below, at the kernels).
 //
 // Built with -ffp-contract=off: the float64 expressions below must round once per operation, like the reference's SSE2
 // code, or the integer votes differ.  The voting loop has no division or square root (KhtVoteParams holds them); the statistics
@@ -324,6 +326,195 @@ __global__ __launch_bounds__(256) void kht_peaks_kernel(KhtGpuArgs a, KhtBatchVo
 	}
 }
 
+// ---- canonical order (kht.hpp, include/compv_hip.h) -----------------------------------------------------------------------------------------------
+// The reference marks EVERY swept cell as visited (:1231-1245), so under a total order of the records a record becomes a line iff none of the 8
+// positions around it holds a record that comes earlier: "larger count, or equal count and smaller emission key".  One thread decides one record.
+
+// rec(p) > rec(r) in the canonical order: s' > s, or s' == s and e' < e (s' == 0: no record -- records have s >= threshold >= 1)
+__device__ __forceinline__ bool khtEarlier(int s2, uint32_t e2, int s, uint32_t e) { return s2 > s || (s2 == s && e2 < e); }
+
+__global__ __launch_bounds__(kKhtCanonCols) void kht_canon_peaks_kernel(KhtGpuArgs a, KhtBatchVote tab, int mainEnd, int mainPositive, int q6Col)
+{
+	constexpr int R = kKhtCanonRows, C = kKhtCanonCols;
+	constexpr int LW = C + 4, RW = C + 2;        // LDS rows: counts of columns c0-2 .. c0+C+1; records of the ring, columns c0-1 .. c0+C
+	__shared__ int32_t s_cnt[(R + 4) * LW];
+	__shared__ int32_t s_rec[(R + 2) * RW];     // smoothed count of the main-scan record at that position, 0: none
+	__shared__ int32_t s_q6[R + 2];             // smoothed count of the Q6 record at position (row, 1), 0: none
+	const int f = blockIdx.z;
+	if (tab.nKernels[f] <= 0) return;           // a frame without kernels has no votes (the reference returns before this stage)
+	const int t0 = 1 + (int)blockIdx.y * R, c0 = 1 + (int)blockIdx.x * C;
+	const int32_t* __restrict__ counts = a.counts + (size_t)f * tab.mapElems;
+	// the strip's counts with a 2-cell halo; zero outside the (T + 2) x (rhoN + 2) map
+	for (int i = threadIdx.x; i < (R + 4) * LW; i += C) {
+		const int r = t0 - 2 + i / LW, c = c0 - 2 + i % LW;
+		s_cnt[i] = (r >= 0 && r <= a.T + 1 && c >= 0 && c <= a.rhoN + 1) ? counts[(size_t)r * a.stride + c] : 0;
+	}
+	if (threadIdx.x < R + 2) {
+		// Q6: the scalar remainder pushes the smoothed count of column q6Col as position (row, 1) (kht_peaks_kernel: v != 0, no sign test).  Only the
+		// strips that hold positions 1 and 2 have it as a neighbour.
+		const int r = t0 - 1 + (int)threadIdx.x;
+		int s = 0;
+		if (q6Col >= 0 && c0 == 1 && r >= 1 && r < a.T) {
+			const int32_t* p = counts + (size_t)r * a.stride + q6Col;
+			if (*p) { const int sm = smooth3x3(p, a.stride); if (sm >= a.threshold) s = sm; }
+		}
+		s_q6[threadIdx.x] = s;
+	}
+	__syncthreads();
+	// the records of the strip and of its 1-cell ring: kht_peaks_kernel's emission rule for the main scan
+	for (int i = threadIdx.x; i < (R + 2) * RW; i += C) {
+		const int rr = i / RW, cc = i % RW;
+		const int r = t0 - 1 + rr, c = c0 - 1 + cc;
+		int s = 0;
+		if (r >= 1 && r < a.T && c >= 1 && c < mainEnd) {
+			const int32_t* p = s_cnt + (rr + 1) * LW + (cc + 1);
+			const int v = *p;
+			if (mainPositive ? v > 0 : v != 0) { const int sm = smooth3x3(p, LW); if (sm >= a.threshold) s = sm; }
+		}
+		s_rec[i] = s;
+	}
+	__syncthreads();
+	const uint32_t vs = (uint32_t)a.rhoN + 2u, row2 = 2u * vs;
+	int* lineCount = a.cellCount + f;
+	KhtCell* out = a.cells + (size_t)f * tab.cellCap;
+	// main-scan records of the strip: thread = column, R rows
+	for (int rr = 1; rr <= R; ++rr) {
+		const int cc = (int)threadIdx.x + 1;
+		const int r = t0 + rr - 1, c = c0 + cc - 1;
+		const int s = s_rec[rr * RW + cc];
+		if (!s) continue;
+		const uint32_t e = (uint32_t)r * row2 + (uint32_t)c;
+		bool line = true;
+#pragma unroll
+		for (int dr = -1; dr <= 1; ++dr)
+#pragma unroll
+			for (int dc = -1; dc <= 1; ++dc) {
+				if (!dr && !dc) continue;
+				const uint32_t e2 = (uint32_t)(r + dr) * row2 + (uint32_t)(c + dc);
+				if (khtEarlier(s_rec[(rr + dr) * RW + cc + dc], e2, s, e)) line = false;
+			}
+		if (q6Col >= 0 && c <= 2) {              // the Q6 records at (r + dr, 1); the one at this record's own position does not count
+			for (int dr = -1; dr <= 1; ++dr) {
+				if (c == 1 && !dr) continue;
+				if (khtEarlier(s_q6[rr + dr], (uint32_t)(r + dr) * row2 + vs + 1u, s, e)) line = false;
+			}
+		}
+		if (line) {
+			const int idx = atomicAdd(lineCount, 1);
+			if (idx < a.cellCap) { KhtCell o; o.order = e; o.count = s; out[idx] = o; }
+		}
+	}
+	// Q6 records of the strip (position (r, 1), emission key r * 2 vs + vs + 1)
+	if (q6Col >= 0 && c0 == 1 && threadIdx.x < R) {
+		const int rr = (int)threadIdx.x + 1, r = t0 + rr - 1;
+		const int s = s_q6[rr];
+		if (s) {
+			const uint32_t e = (uint32_t)r * row2 + vs + 1u;
+			bool line = true;
+			for (int dr = -1; dr <= 1; ++dr) {
+				for (int dc = -1; dc <= 1; ++dc) {     // main-scan records around position 1 (ring column cc = 1 + dc)
+					if (!dr && !dc) continue;
+					if (khtEarlier(s_rec[(rr + dr) * RW + 1 + dc], (uint32_t)(r + dr) * row2 + (uint32_t)(1 + dc), s, e)) line = false;
+				}
+				if (dr && khtEarlier(s_q6[rr + dr], (uint32_t)(r + dr) * row2 + vs + 1u, s, e)) line = false;
+			}
+			if (line) {
+				const int idx = atomicAdd(lineCount, 1);
+				if (idx < a.cellCap) { KhtCell o; o.order = e; o.count = s; out[idx] = o; }
+			}
+		}
+	}
+}
+
+// ascending 64-bit key of the canonical order: count descending, then emission key ascending (keys are unique: so are the emission keys)
+__device__ __forceinline__ uint64_t khtCanonKey(KhtCell c) { return ((uint64_t)(0xFFFFFFFFu - (uint32_t)c.count) << 32) | c.order; }
+
+// bitonic sort of P (a power of two) keys in LDS by the whole workgroup
+__device__ void khtBitonicLds(uint64_t* k, int P)
+{
+	for (int size = 2; size <= P; size <<= 1)
+		for (int stride = size >> 1; stride > 0; stride >>= 1) {
+			for (int i = threadIdx.x; i < P / 2; i += blockDim.x) {
+				const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+				const uint64_t x = k[lo], y = k[hi];
+				if ((x > y) == ((lo & size) == 0)) { k[lo] = y; k[hi] = x; }
+			}
+			__syncthreads();
+		}
+}
+
+// keys [0, n) of src -> LDS, padded with ~0 up to the next power of two >= 2; returns it
+__device__ int khtLoadLds(uint64_t* k, const KhtCell* cells, const uint64_t* keys, int n)
+{
+	int P = 2;
+	while (P < n) P <<= 1;
+	for (int i = threadIdx.x; i < P; i += blockDim.x) k[i] = i < n ? (cells ? khtCanonKey(cells[i]) : keys[i]) : ~0ull;
+	__syncthreads();
+	return P;
+}
+
+// number of keys of the sorted run [b, b + len) below key
+__device__ __forceinline__ int khtRankIn(const uint64_t* b, int len, uint64_t key)
+{
+	int lo = 0, hi = len;
+	while (lo < hi) { const int m = (lo + hi) >> 1; if (b[m] < key) lo = m + 1; else hi = m; }
+	return lo;
+}
+
+__global__ __launch_bounds__(1024) void kht_canon_sort_kernel(KhtGpuArgs a, KhtBatchVote tab, KhtCanonOut o)
+{
+	__shared__ uint64_t s_k[kKhtCanonSortLds];
+	const int f = blockIdx.x;
+	KhtCell* cells = a.cells + (size_t)f * tab.cellCap;
+	const int n = min(a.cellCount[f], a.cellCap);
+	const uint64_t* sorted = s_k;
+	if (n > kKhtCanonSortLds) {
+		// Fallback: the frame's cell list holds the lines in its first half (lines are records no two of which are 8-neighbours, bar the one Q6 column:
+		// at most ceil((T-1)/2) ceil((rhoN-1)/2) + T - 1 <= T rhoN / 2 of them); its second half is the merge scratch.  Chunks of kKhtCanonSortLds
+		// keys are sorted in LDS, then runs are merged pairwise: every key lands at its index in its run + its rank in the partner run.
+		const int half = (int)(tab.cellCap / 2);
+		if (n > half) { if (threadIdx.x == 0) o.counts[f] = -1; return; }
+		uint64_t* A = reinterpret_cast<uint64_t*>(cells);
+		uint64_t* B = A + half;
+		for (int base = 0; base < n; base += kKhtCanonSortLds) {
+			const int len = min(kKhtCanonSortLds, n - base);
+			const int P = khtLoadLds(s_k, cells + base, nullptr, len);
+			khtBitonicLds(s_k, P);
+			for (int i = threadIdx.x; i < len; i += blockDim.x) A[base + i] = s_k[i];   // (the chunk's cells were read into LDS above)
+			__syncthreads();
+		}
+		uint64_t* src = A; uint64_t* dst = B;
+		for (int w = kKhtCanonSortLds; w < n; w <<= 1) {
+			for (int i = threadIdx.x; i < n; i += blockDim.x) {
+				const int lo = (i / (2 * w)) * (2 * w), mid = min(lo + w, n), end = min(lo + 2 * w, n);
+				const uint64_t key = src[i];
+				dst[i < mid ? i + khtRankIn(src + mid, end - mid, key) : i - (mid - lo) + khtRankIn(src + lo, mid - lo, key)] = key;
+			}
+			__syncthreads();
+			uint64_t* t = src; src = dst; dst = t;
+		}
+		sorted = src;
+	}
+	else {
+		const int P = khtLoadLds(s_k, cells, nullptr, n);
+		khtBitonicLds(s_k, P);
+	}
+	const int cut = (o.maxLines > 0 && n > o.maxLines) ? o.maxLines : n;
+	if (threadIdx.x == 0) o.counts[f] = cut;
+	const int nw = min(cut, o.cap);
+	KhtLine* out = o.lines + (size_t)f * (size_t)(o.cap > 0 ? o.cap : 0);
+	const uint32_t vs = (uint32_t)a.rhoN + 2u, row2 = 2u * vs;
+	for (int i = threadIdx.x; i < nw; i += blockDim.x) {
+		const uint64_t key = sorted[i];
+		const uint32_t e = (uint32_t)key, ti = e / row2, rem = e - ti * row2, ri = rem >= vs ? rem - vs : rem;
+		KhtLine l;
+		l.rho = o.rho[ri]; l.theta = o.theta[ti];
+		l.strength = (int32_t)(0xFFFFFFFFu - (uint32_t)(key >> 32));
+		l.rhoIndex = (int32_t)ri; l.thetaIndex = (int32_t)ti;
+		out[i] = l;
+	}
+}
+
 hipError_t launch_kht_subdivide(const KhtSubdivArgs& a, const KhtBatchStrings& tab, hipStream_t stream)
 {
 	if (a.nStrings <= 0 || tab.frames <= 0) return hipSuccess;
@@ -350,21 +541,47 @@ hipError_t launch_kht_vote(const KhtGpuArgs& a, const KhtBatchVote& tab, hipStre
 	return hipGetLastError();
 }
 
+// column coverage of the reference's scan (:1166-1187): SSE2 groups of 4 from column 1 while rho_index < rhoN-3, then a scalar remainder that
+// starts at (rhoN & ~3) + 1 (quirk Q6); rhoN <= 4: one scalar loop over columns 1 .. rhoN-1
+struct KhtScan { int simd, sseCovEnd, consumed, remains; };
+static KhtScan khtScan(int rhoN)
+{
+	KhtScan sc;
+	sc.simd = rhoN > 4;
+	sc.sseCovEnd = 1; sc.consumed = rhoN + 1; sc.remains = 0;
+	if (sc.simd) {
+		const int sseEnd = rhoN - 3;
+		const int iters = (sseEnd - 1 + 3) / 4; // ri = 1, 5, ... < sseEnd
+		sc.sseCovEnd = 1 + 4 * (iters > 0 ? iters : 0);
+		sc.consumed = (rhoN & ~3) + 1;
+		sc.remains = rhoN > sc.consumed ? rhoN - sc.consumed : 0;
+	}
+	return sc;
+}
+
 hipError_t launch_kht_peaks(const KhtGpuArgs& a, const KhtBatchVote& tab, hipStream_t stream)
 {
-	// column coverage of the reference's scan (:1166-1187): SSE2 groups of 4 from column 1 while rho_index < rhoN-3, then a
-	// scalar remainder that starts at (rhoN & ~3) + 1
-	const int simd = a.rhoN > 4;
-	int sseCovEnd = 1, consumed = a.rhoN + 1, remains = 0;
-	if (simd) {
-		const int sseEnd = a.rhoN - 3;
-		const int iters = (sseEnd - 1 + 3) / 4; // ri = 1, 5, ... < sseEnd
-		sseCovEnd = 1 + 4 * (iters > 0 ? iters : 0);
-		consumed = (a.rhoN & ~3) + 1;
-		remains = a.rhoN > consumed ? a.rhoN - consumed : 0;
-	}
+	const KhtScan sc = khtScan(a.rhoN);
 	dim3 grid((a.rhoN + 255) / 256, a.T > 1 ? a.T - 1 : 1, tab.frames);
-	hipLaunchKernelGGL(kht_peaks_kernel, grid, dim3(256), 0, stream, a, tab, sseCovEnd, consumed, remains, simd);
+	hipLaunchKernelGGL(kht_peaks_kernel, grid, dim3(256), 0, stream, a, tab, sc.sseCovEnd, sc.consumed, sc.remains, sc.simd);
+	return hipGetLastError();
+}
+
+hipError_t launch_kht_canon_peaks(const KhtGpuArgs& a, const KhtBatchVote& tab, hipStream_t stream)
+{
+	const KhtScan sc = khtScan(a.rhoN);
+	const int mainEnd = sc.simd ? sc.sseCovEnd : a.rhoN;     // main-scan records at columns [1, mainEnd)
+	// the remainder covers columns (consumed, consumed + remains) as positions 1 .. remains - 1, and remains <= 2: one Q6 column at most (rhoN % 4 == 3)
+	const int q6Col = (sc.simd && sc.remains >= 2) ? sc.consumed + 1 : -1;
+	dim3 grid((mainEnd - 1 + kKhtCanonCols - 1) / kKhtCanonCols, (a.T - 1 + kKhtCanonRows - 1) / kKhtCanonRows, tab.frames);
+	if (grid.x < 1 || grid.y < 1) return hipSuccess;
+	hipLaunchKernelGGL(kht_canon_peaks_kernel, grid, dim3(kKhtCanonCols), 0, stream, a, tab, mainEnd, sc.simd, q6Col);
+	return hipGetLastError();
+}
+
+hipError_t launch_kht_canon_sort(const KhtGpuArgs& a, const KhtBatchVote& tab, const KhtCanonOut& o, hipStream_t stream)
+{
+	hipLaunchKernelGGL(kht_canon_sort_kernel, dim3(tab.frames), dim3(1024), 0, stream, a, tab, o);
 	return hipGetLastError();
 }
 

@@ -321,6 +321,41 @@ COMPVHIP_API int compvhip_plan_houghkht(compvhip_plan* plan, const uint8_t* d_ed
                                         compvhip_line* lines, size_t cap, size_t* counts, double* gs, int hostThreads);
 COMPVHIP_API int compvhip_plan_houghkht_stage_ms(compvhip_plan* plan, double* ms6, double* wallMs, int* threads);
 
+/* KHT line order.  REFERENCE (0): what compvhip_houghkht_u8 / compvhip_plan_houghkht return -- descending smoothed count, ties as the reference's unstable
+ * std::sort leaves them; the visited-map sweep runs on the host.  CANONICAL (1): the order a STABLE sort of the reference's emission list gives, with the
+ * peak stage on the GPU:
+ *  - Records: exactly the vote cells the reference's peak scan emits (same coverage, threshold and quirk Q6).  Record r has a position p = (thetaIndex,
+ *    rhoIndex), a smoothed count s and an emission key e = thetaIndex * 2 (rhoN + 2) + rhoIndex; a record of the scalar remainder (Q6, rhoN % 4 == 3:
+ *    position (theta, 1), counts of column rhoN - 1) has e = thetaIndex * 2 (rhoN + 2) + (rhoN + 2) + rhoIndex.  e is unique and below 2^32.
+ *  - Order: s descending, then e ascending (the KHT twin of the plan SHT's canonical order).
+ *  - Lines: r is a line iff no record r' at a position q != p of p's 8-neighbourhood has s' > s, or s' == s and e' < e.  (The reference marks every swept
+ *    cell as visited and never tests a cell's own position: a Q6 record and a main-scan record at the same position do not block each other.)
+ *  - Output: the lines in that order, cut at maxLines when maxLines > 0; fields as in the reference order (rho = (float)rho[rhoIndex], theta =
+ *    (float)((theta[thetaIndex] * pi) / 180), strength = s, row = rhoIndex, col = thetaIndex); GS unchanged.
+ * Lines whose position has no equal-count record among its 8 neighbours are the same in both orders; only the tie groups differ. */
+#define COMPVHIP_KHT_ORDER_REFERENCE 0
+#define COMPVHIP_KHT_ORDER_CANONICAL 1
+/* The knobs of a KHT call.  Zero-initialise and set what is needed: a zero field takes the default -- rho 1, thetaDeg 1, threshold 1, maxLines 0 (every
+ * line), clusterMinDeviation 2.0, clusterMinSize 10, kernelMinHeight 0.002 (so a height of exactly 0 is asked for with a tiny positive value), hostThreads 0
+ * (compvhip_plan_houghkht's default pool; ignored by compvhip_houghkht_ex_u8), order COMPVHIP_KHT_ORDER_REFERENCE. */
+typedef struct compvhip_kht_opts {
+	float rho, thetaDeg;
+	int threshold, maxLines;
+	double clusterMinDeviation;
+	size_t clusterMinSize;
+	double kernelMinHeight;
+	int hostThreads;
+	int order;              /* COMPVHIP_KHT_ORDER_* */
+} compvhip_kht_opts;
+/* compvhip_plan_houghkht / compvhip_houghkht_u8 with the knobs in opts (same buffers, capacity and error contract: COMPVHIP_E_OUT_OF_BOUND when a frame has
+ * more than cap lines, counts[f] / *n tell how many).  opts == NULL or an unknown order: COMPVHIP_E_INVALID_PARAMETER.  In CANONICAL order the vote map
+ * never leaves the device: the peaks of every frame are found and sorted on the GPU and only the lines and their counts are downloaded; the sixth stage
+ * clock (sort + sweep on the host) reads 0 and the GPU peak and sort time is part of the fifth (vote + peaks). */
+COMPVHIP_API int compvhip_plan_houghkht_ex(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_kht_opts* opts,
+                                           compvhip_line* lines, size_t cap, size_t* counts, double* gs);
+COMPVHIP_API int compvhip_houghkht_ex_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, const compvhip_kht_opts* opts,
+                                         compvhip_line* lines, size_t cap, size_t* n, double* gs);
+
 /* Device accumulator of frame f after compvhip_plan_houghsht: uint16 (a cell never exceeds the pixels of a 1-px band),
  * theta-major [T][accPitch] (pitch >= R).  compvhip_plan_acc_export gives the reference's int32 rho-major layout. */
 COMPVHIP_API int compvhip_plan_acc(compvhip_plan* plan, size_t frame, const uint16_t** d_acc, size_t* R, size_t* T, size_t* accPitch);
