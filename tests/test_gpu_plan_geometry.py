@@ -13,6 +13,7 @@ import concurrent.futures as cf
 import numpy as np
 import pytest
 
+from hysteresis_cases import text_frame   # the text-like page, shared with the hysteresis cases
 from oracle_bindings import synth_frame
 from plan_geometries import GEOMETRIES, XCH_GEOMETRY, XCH_MARGIN, XCH_MIN_WAVES, swar_waves
 
@@ -103,34 +104,6 @@ def pad_frames(valid, row_bytes, rng):
 # ---------------------------------------------------------------------------------------------------------------
 # frame content
 # ---------------------------------------------------------------------------------------------------------------
-def text_frame(W, H, seed):
-    """Text-like page: short strokes, diagonals and small glyph boxes in dark ink on a light background, at two or three scales
-    (many small components, many short lines)."""
-    rng = np.random.default_rng(seed)
-    img = np.full((H, W), int(rng.integers(170, 240)), np.uint8)
-    img += rng.integers(0, 6, (H, W), dtype=np.uint8)
-    for scale in (1, 2, 4)[:2 + seed % 2]:
-        n = max(2, W * H // (120 * scale * scale))
-        xs = rng.integers(0, W, n); ys = rng.integers(0, H, n)
-        kinds = rng.integers(0, 4, n); lens = rng.integers(2, 9, n) * scale; inks = rng.integers(0, 100, n)
-        for x, y, k, ln, ink in zip(xs, ys, kinds, lens, inks):
-            t = scale
-            if k == 0:
-                img[y:y + t, x:x + ln] = ink
-            elif k == 1:
-                img[y:y + ln, x:x + t] = ink
-            elif k == 2:
-                img[y:y + ln, x:x + t] = ink; img[y:y + ln, x + ln - t:x + ln] = ink
-                img[y:y + t, x:x + ln] = ink; img[y + ln - t:y + ln, x:x + ln] = ink
-            else:
-                d = np.arange(ln)
-                for o in range(t):
-                    yy, xx = y + d, x + d + o
-                    m = (yy < H) & (xx < W)
-                    img[yy[m], xx[m]] = ink
-    return img
-
-
 def checker_frame(W, H, seed):
     c = 3 + seed % 7
     x = np.arange(W)[None, :] // c
