@@ -41,6 +41,7 @@ EXPORTS = [
     "compvhip_houghkht_kernels_u8", "compvhip_houghkht_stage_ms", "compvhip_convlt1_8u16s16s", "compvhip_convlt1_16s16s16s",
     "compvhip_plan_pipeline_ex", "compvhip_plan_houghkht", "compvhip_plan_houghkht_stage_ms", "compvhip_houghkht_link_u8",
     "compvhip_houghkht_dims", "compvhip_host_cpu_budget", "compvhip_plan_houghkht_ex", "compvhip_houghkht_ex_u8",
+    "compvhip_plan_houghsht_segments", "compvhip_houghsht_segments_u8",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -52,6 +53,14 @@ class Line(C.Structure):
 
 
 LINE_DTYPE = np.dtype([("rho", "<f4"), ("theta", "<f4"), ("strength", "<i4"), ("row", "<i4"), ("col", "<i4")])
+
+
+class Segment(C.Structure):
+    """compvhip_segment (include/compv_hip.h): a piece of an SHT line between the pixels (x0, y0) and (x1, y1)"""
+    _fields_ = [("line", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("support", C.c_int32)]
+
+
+SEGMENT_DTYPE = np.dtype([("line", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("support", "<i4")])
 
 
 class PipelineOpts(C.Structure):
@@ -147,6 +156,8 @@ def load():
     L.compvhip_plan_houghkht_ex.argtypes = [vp, vp, C.POINTER(KhtOpts), vp, sz, vp, vp]
     L.compvhip_houghkht_ex_u8.argtypes = [vp, vp, sz, sz, sz, C.POINTER(KhtOpts), vp, sz, C.POINTER(sz), C.POINTER(C.c_double)]
     L.compvhip_plan_pipeline_ex.argtypes = [vp, vp, C.POINTER(PipelineOpts), vp, vp, sz, vp, vp, C.POINTER(i32)]
+    L.compvhip_plan_houghsht_segments.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, vp, sz, vp, vp]
+    L.compvhip_houghsht_segments_u8.argtypes = [vp, vp, sz, sz, sz, C.c_float, vp, sz, i32, i32, vp, sz, C.POINTER(sz)]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -266,6 +277,19 @@ class Context:
         lines = lines[:n.value]
         return (lines, acc) if want_acc else lines
 
+    def houghsht_segments(self, edges, lines, theta_deg=1.0, min_length=1, max_gap=0, cap=1 << 12):
+        """compvhip_houghsht_segments_u8: the segments (SEGMENT_DTYPE array) of caller-held SHT lines (a LINE_DTYPE array, e.g. what houghsht()
+        returned for the same edge map and theta_deg; only row / col are read) -- where along each line its edge pixels are."""
+        H, W = edges.shape
+        lines = np.ascontiguousarray(lines, LINE_DTYPE)
+        segs = np.zeros(max(cap, 1), SEGMENT_DTYPE)
+        n = C.c_size_t(0)
+        rc = self.lib.compvhip_houghsht_segments_u8(self.h, _ptr(edges), W, H, edges.strides[0], theta_deg, _ptr(lines), len(lines), min_length, max_gap,
+                                                    _ptr(segs), cap, C.byref(n))
+        if rc == E_OUT_OF_BOUND and n.value > cap:
+            return self.houghsht_segments(edges, lines, theta_deg, min_length, max_gap, cap=n.value)
+        self._chk(rc)
+        return segs[:n.value]
 
     def houghkht(self, edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, order="reference"):
         """Returns (lines, GS); lines['row'] / ['col'] hold the rho / theta indices.  order: "reference" (compvhip_houghkht_u8: the reference's tie
@@ -350,6 +374,12 @@ class Plan:
 
     def houghsht(self, d_edges, threshold, max_lines, d_lines, line_cap, d_counts, stream=0):
         self.ctx._chk(self.lib.compvhip_plan_houghsht(self.h, d_edges, threshold, max_lines, d_lines, line_cap, d_counts, stream))
+
+    def houghsht_segments(self, d_edges, d_lines, d_counts, line_cap, max_lines, min_length, max_gap, d_segs, seg_cap, d_seg_counts, stream=0):
+        """compvhip_plan_houghsht_segments: segments of the device line arrays of houghsht() / pipeline(); d_edges = 0 reads the 1-bit masks of
+        the plan's last Canny.  d_segs: frames * seg_cap Segment records, d_seg_counts: frames int32 (found, before clipping)."""
+        self.ctx._chk(self.lib.compvhip_plan_houghsht_segments(self.h, d_edges or None, d_lines, d_counts, line_cap, max_lines, min_length, max_gap,
+                                                               d_segs, seg_cap, d_seg_counts, stream))
 
     def pipeline(self, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap, d_counts, stream=0):
         self.ctx._chk(self.lib.compvhip_plan_pipeline(self.h, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap,

@@ -114,6 +114,9 @@ struct compvhip_ctx {
 	uint32_t* dHist = nullptr;                             // [256] histogram + 1 result word of compvhip_otsu_u8
 	int32_t* dCounts = nullptr;
 	int32_t* dAccOut = nullptr; size_t dAccOutElems = 0;
+	compvhip_line* dSegLines = nullptr; size_t dSegLinesCap = 0;   // staging of compvhip_houghsht_segments_u8: the caller's lines ...
+	compvhip_segment* dSegs = nullptr; size_t dSegsCap = 0;        // ... and the segments; the count travels through dCounts
+	int32_t* dSegCount = nullptr;
 	KhtScratch kht;                    // KHT scratch of the host entry point (compvhip_houghkht_u8)
 };
 
@@ -173,6 +176,7 @@ struct compvhip_plan {
 	uint8_t* nmsFlags = nullptr;                 // NMS survivors (flag planes)
 	int* blockCounts = nullptr; int lineBlocks = 0;   // NMS survivors per 64 accumulator rows (part of `counters`)
 	void* sortTemp = nullptr; size_t sortTempBytes = 0;
+	int32_t* segPerLine = nullptr; size_t segPerLineCap = 0;   // line segments (sht_segments_kernels.hip): segments per line, then their prefix sums
 	int strengthBits = 16, keyBits = 0;
 	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
 	uint16_t* chunkHist = nullptr; uint32_t* strengthStart = nullptr; int sortChunks = 0; bool deviceSort = false;
@@ -896,6 +900,7 @@ void compvhip_ctx_destroy(compvhip_ctx* ctx)
 	if (ctx->hostPlan) compvhip_plan_destroy(ctx->hostPlan);
 	dfree(ctx, ctx->dPacked); dfree(ctx, ctx->dHist);
 	dfree(ctx, ctx->dIn); dfree(ctx, ctx->dOut); dfree(ctx, ctx->dCounts); dfree(ctx, ctx->dAccOut);
+	dfree(ctx, ctx->dSegLines); dfree(ctx, ctx->dSegs); dfree(ctx, ctx->dSegCount);
 	khtScratchFree(ctx, ctx->kht);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
@@ -1044,7 +1049,7 @@ void compvhip_plan_destroy(compvhip_plan* p)
 	dfree(ctx, p->dKt); dfree(ctx, p->dRowBase); dfree(ctx, p->partLo); dfree(ctx, p->partHi); dfree(ctx, p->colFlag);
 	dfree(ctx, p->sinQ); dfree(ctx, p->cosQ); dfree(ctx, p->edges); dfree(ctx, p->acc);
 	dfree(ctx, p->keysA); dfree(ctx, p->keysB); dfree(ctx, p->valsA); dfree(ctx, p->valsB); dfree(ctx, p->nmsFlags); dfree(ctx, p->chunkHist); dfree(ctx, p->strengthStart);
-	dfree(ctx, p->nmsRange); dfree(ctx, p->reach); dfree(ctx, p->sortTemp);
+	dfree(ctx, p->nmsRange); dfree(ctx, p->reach); dfree(ctx, p->sortTemp); dfree(ctx, p->segPerLine);
 	delete p;
 }
 
@@ -1544,6 +1549,50 @@ int compvhip_plan_edge_counts(compvhip_plan* p, const int32_t** d_edge_counts)
 	return COMPVHIP_OK;
 }
 
+// ---- Hough line segments (sht_segments_kernels.hip; definition in include/compv_hip.h) ---------------------------------------
+// edges / edgeStride: byte maps [frames][H][edgeStride], or nullptr = the plan's bit masks
+static int segmentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap,
+                        int maxLines, int minLength, int maxGap, compvhip_segment* d_segs, size_t segCap, int32_t* d_segCounts, hipStream_t st)
+{
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_lines || !d_counts || !d_segCounts || !lineCap || (segCap && !d_segs)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null line / count / segment buffer");
+	if (minLength < 1 || maxGap < 0) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "segments need minLength >= 1 and maxGap >= 0");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	int rc = ensureSht(p);
+	if (rc) return rc;
+	size_t nLines = std::min(lineCap, p->R * p->T);   // a frame has at most R * T lines
+	if (maxLines > 0) nLines = std::min(nLines, static_cast<size_t>(maxLines));
+	if (nLines > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "line capacity beyond 2^31");
+	if (p->segPerLineCap < nLines * p->frames) {
+		dfree(ctx, p->segPerLine); p->segPerLineCap = 0;
+		HIPCHK(ctx, dmalloc(ctx, &p->segPerLine, nLines * p->frames));
+		p->segPerLineCap = nLines * p->frames;
+	}
+	if (p->timing) timelineClear(p);
+	ShtSegArgs a;
+	a.ebits = p->ebits; a.edges = d_edges; a.bitsFrameStride = p->bitsFrameStride; a.edgeFrameStride = edgeStride * p->H; a.wb = p->wb; a.S = static_cast<int>(edgeStride);
+	a.sinQ = p->sinQ; a.cosQ = p->cosQ; a.lines = d_lines; a.lineCounts = d_counts; a.lineCap = lineCap; a.nLines = static_cast<int>(nLines);
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.R = static_cast<int>(p->R); a.T = static_cast<int>(p->T); a.barrier = static_cast<int>(p->W + p->H);
+	a.minLength = minLength; a.maxGap = maxGap; a.perLine = p->segPerLine; a.segs = d_segs; a.segCap = segCap; a.segCounts = d_segCounts; a.frame0 = 0;
+	const int frames = static_cast<int>(p->frames);
+	{ Stamp s(p, st, "sht_segments_count_kernel"); HIPCHK(ctx, launch_sht_segments(a, frames, 0, st)); }
+	{ Stamp s(p, st, "sht_segments_scan_kernel"); HIPCHK(ctx, launch_sht_segments(a, frames, 1, st)); }
+	if (segCap) { Stamp s(p, st, "sht_segments_write_kernel"); HIPCHK(ctx, launch_sht_segments(a, frames, 2, st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_houghsht_segments(compvhip_plan* p, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap, int maxLines,
+                                    int minLength, int maxGap, compvhip_segment* d_segs, size_t segCap, int32_t* d_segCounts, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	for (const auto& stp : p->steps)
+		if (stp.used) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the lines)");
+	if (!segCap) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "segCap must be > 0");
+	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
+	return segmentsImpl(p, d_edges, p->S, d_lines, d_counts, lineCap, maxLines, minLength, maxGap, d_segs, segCap, d_segCounts, static_cast<hipStream_t>(stream));
+}
+
 // ---- host entry points -------------------------------------------------------------------------------------------
 static int hostPlan(compvhip_ctx* ctx, size_t W, size_t H, float thetaDeg, compvhip_plan** out)
 {
@@ -1812,6 +1861,47 @@ int compvhip_houghsht_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size
 		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	}
 	if (found > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "line buffer too small");
+	return COMPVHIP_OK;
+}
+
+int compvhip_houghsht_segments_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float thetaDeg, const compvhip_line* lines, size_t n,
+                                  int minLength, int maxGap, compvhip_segment* segs, size_t cap, size_t* nSegs)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!edges || !nSegs || (n && !lines) || (cap && !segs) || S < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	if (!(thetaDeg > 0.f) || minLength < 1 || maxGap < 0) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "theta must be > 0, minLength >= 1, maxGap >= 0");
+	if (W < 3 || H < 3 || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
+	*nSegs = 0;
+	size_t R, T;
+	int rc = shtDims(W, H, thetaDeg, &R, &T, nullptr);
+	if (rc) return fail(ctx, rc, "invalid SHT geometry");
+	if (n > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "too many lines");
+	for (size_t i = 0; i < n; ++i)
+		if (lines[i].row < 0 || static_cast<size_t>(lines[i].row) >= R || lines[i].col < 0 || static_cast<size_t>(lines[i].col) >= T)
+			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "a line's (row, col) is not a cell of the R x T accumulator");
+	if (!n) return COMPVHIP_OK;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_plan* p = nullptr;
+	rc = hostPlan(ctx, W, H, thetaDeg, &p);
+	if (rc) return rc;
+	if (ctx->dSegLinesCap < n) { dfree(ctx, ctx->dSegLines); ctx->dSegLinesCap = 0; HIPCHK(ctx, dmalloc(ctx, &ctx->dSegLines, n)); ctx->dSegLinesCap = n; }
+	if (ctx->dSegsCap < cap) { dfree(ctx, ctx->dSegs); ctx->dSegsCap = 0; HIPCHK(ctx, dmalloc(ctx, &ctx->dSegs, cap)); ctx->dSegsCap = cap; }
+	if (!ctx->dCounts) HIPCHK(ctx, dmalloc(ctx, &ctx->dCounts, 1));
+	if (!ctx->dSegCount) HIPCHK(ctx, dmalloc(ctx, &ctx->dSegCount, 1));
+	const int32_t nLines = static_cast<int32_t>(n);
+	HIPCHK(ctx, hipMemcpy2DAsync(ctx->dIn, p->S, edges, S, W, H, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dSegLines, lines, n * sizeof(compvhip_line), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dCounts, &nLines, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // nLines lives on this stack frame; pageable copies may still be staged
+	rc = segmentsImpl(p, ctx->dIn, p->S, ctx->dSegLines, ctx->dCounts, n, 0, minLength, maxGap, ctx->dSegs, cap, ctx->dSegCount, ctx->stream);
+	if (rc) return rc;
+	int32_t found = 0;
+	HIPCHK(ctx, hipMemcpyAsync(&found, ctx->dSegCount, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	*nSegs = static_cast<size_t>(found);
+	const size_t ncopy = std::min(static_cast<size_t>(found), cap);
+	if (ncopy) HIPCHK(ctx, hipMemcpy(segs, ctx->dSegs, ncopy * sizeof(compvhip_segment), hipMemcpyDeviceToHost));
+	if (static_cast<size_t>(found) > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "segment buffer too small");
 	return COMPVHIP_OK;
 }
 

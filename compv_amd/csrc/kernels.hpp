@@ -184,4 +184,27 @@ hipError_t launch_sht_sort_lines(const ShtArgs& a, const ShtSortArgs& q, int fra
 hipError_t sht_sort_pairs(void* temp, size_t& tempBytes, const uint32_t* keysIn, uint32_t* keysOut, const uint32_t* valsIn, uint32_t* valsOut, size_t n,
                           int keyBits, hipStream_t stream);
 
+// ---- Hough SHT line segments (sht_segments_kernels.hip) -------------------------------------------------------
+struct ShtSegArgs {
+	const uint32_t* ebits;    // edge bit masks [frames][H][wb] (read when edges == nullptr)
+	const uint8_t* edges;     // or byte edge maps [frames][H][S], non-zero = edge
+	size_t bitsFrameStride, edgeFrameStride;
+	int wb, S;
+	const int32_t* sinQ;      // [T] the vote's Q16 tables
+	const int32_t* cosQ;
+	const compvhip_line* lines;   // [frames][lineCap]; only row / col are read
+	const int32_t* lineCounts;    // [frames] lines found (may exceed lineCap)
+	size_t lineCap;
+	int nLines;               // lines considered per frame at most: min(lineCap, maxLines if > 0)
+	int W, H, R, T, barrier;
+	int minLength, maxGap;
+	int32_t* perLine;         // [frames][nLines] scratch: segments per line, then their exclusive prefix sums
+	compvhip_segment* segs;   // [frames][segCap]
+	size_t segCap;
+	int32_t* segCounts;       // [frames] segments found (before clipping to segCap)
+	int frame0;               // filled by the launcher
+};
+// phase 0: count the segments of every line; 1: exclusive scan per frame + segCounts; 2: write the segments
+hipError_t launch_sht_segments(const ShtSegArgs& a, int frames, int phase, hipStream_t stream);
+
 } // namespace compvhip

@@ -366,6 +366,45 @@ COMPVHIP_API int compvhip_plan_acc_export(compvhip_plan* plan, size_t frame, int
  * kernel counts them: a compvhip_plan_canny call alone resets them to zero, and before the plan's first SHT the call is refused. */
 COMPVHIP_API int compvhip_plan_edge_counts(compvhip_plan* plan, const int32_t** d_edge_counts);
 
+/* ---- Hough line SEGMENTS: where along an SHT line its edge pixels are ----------------------------------------
+ * The reference stops at infinite lines (toCartesian: two points at x = 0 and x = W).  The pixels of an SHT line are exactly the edge pixels
+ * that voted for its accumulator cell, which gives an integer-only definition (docs/kernels/sht_segments.md):
+ *  1. Support: pixel (x, y) belongs to line (row, col) iff (x * cosQ[col] + y * sinQ[col]) >> 16 == (W + H) - row -- the vote's own expression
+ *     on the plan's Q16 tables, exact for every geometry.  Only row / col of a compvhip_line are read.
+ *  2. Major axis: sinQ[col] >= |cosQ[col]|: x-major (position p = x, N = W, minor coordinate y); otherwise y-major (p = y, N = H, minor x).
+ *     A position holds at most 2 support pixels.
+ *  3. Occupancy: cnt[p] = support pixels at p that are inside the image and edges (non-zero); the sum over p is the line's strength.
+ *  4. Segments: maximal groups of positions with cnt > 0 in which consecutive ones differ by at most maxGap + 1; a group [p0, p1] is a
+ *     segment iff p1 - p0 + 1 >= minLength.
+ *  5. Record: the line's index in the frame's line array, the pixels at p0 and p1 (of two edges at a position: the smaller minor
+ *     coordinate), support = sum of cnt over p0..p1.
+ *  6. Order: by line index, then p0, ascending.  Lines considered per frame: min(d_counts[f], lineCap, maxLines if > 0). */
+typedef struct compvhip_segment {
+	int32_t line;
+	int32_t x0, y0, x1, y1;
+	int32_t support;
+} compvhip_segment;
+
+/* Segments of the lines a compvhip_plan_houghsht / _pipeline call left on the device, for all frames of the plan.  d_edges: the byte edge maps
+ * [frames][H][S] the lines were found on, or NULL = the 1-bit masks of the plan's last Canny / pipeline step (no byte re-read;
+ * COMPVHIP_E_INVALID_PARAMETER when the plan holds none: before its first Canny, or after a compvhip_plan_houghsht on foreign edge maps replaced
+ * them).  d_segs: frames * segCap records; d_segCounts[f]: segments found in frame f BEFORE clipping -- the first min(count, segCap) in the order
+ * above are written, so a clipped result is a prefix of the full one.  Asynchronous on `stream` (the plan's SHT tables and a scratch array of
+ * frames * min(lineCap, maxLines) counters are allocated on first use).  COMPVHIP_E_INVALID_STATE while the plan has asynchronous steps that
+ * were not waited for (a replayed step rewrites d_lines later); COMPVHIP_E_INVALID_PARAMETER for minLength < 1, maxGap < 0, lineCap == 0 or
+ * segCap == 0. */
+COMPVHIP_API int compvhip_plan_houghsht_segments(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts,
+                                                 size_t lineCap, int maxLines, int minLength, int maxGap,
+                                                 compvhip_segment* d_segs, size_t segCap, int32_t* d_segCounts, void* stream);
+
+/* The same for caller-held lines of one HOST edge map (lines of compvhip_houghsht_u8 in either order, or of a plan: only row / col are read;
+ * segs[i].line indexes `lines`).  Synchronous.  *nSegs receives the number of segments found; when it exceeds cap only the first cap are written
+ * and COMPVHIP_E_OUT_OF_BOUND is returned (cap == 0 with segs == NULL asks for the number).  A line whose (row, col) is outside the R x T
+ * accumulator of (W, H, thetaDeg): COMPVHIP_E_INVALID_PARAMETER. */
+COMPVHIP_API int compvhip_houghsht_segments_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float thetaDeg,
+                                               const compvhip_line* lines, size_t n, int minLength, int maxGap,
+                                               compvhip_segment* segs, size_t cap, size_t* nSegs);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel
