@@ -42,6 +42,7 @@ EXPORTS = [
     "compvhip_plan_pipeline_ex", "compvhip_plan_houghkht", "compvhip_plan_houghkht_stage_ms", "compvhip_houghkht_link_u8",
     "compvhip_houghkht_dims", "compvhip_host_cpu_budget", "compvhip_plan_houghkht_ex", "compvhip_houghkht_ex_u8",
     "compvhip_plan_houghsht_segments", "compvhip_houghsht_segments_u8",
+    "compvhip_plan_components", "compvhip_components_u8",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -61,6 +62,14 @@ class Segment(C.Structure):
 
 
 SEGMENT_DTYPE = np.dtype([("line", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("support", "<i4")])
+
+
+class Component(C.Structure):
+    """compvhip_component (include/compv_hip.h): root (x, y), inclusive bounding box, pixel count of a connected component"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("pixels", C.c_int32)]
+
+
+COMP_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("pixels", "<i4")])
 
 
 class PipelineOpts(C.Structure):
@@ -158,6 +167,8 @@ def load():
     L.compvhip_plan_pipeline_ex.argtypes = [vp, vp, C.POINTER(PipelineOpts), vp, vp, sz, vp, vp, C.POINTER(i32)]
     L.compvhip_plan_houghsht_segments.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, vp, sz, vp, vp]
     L.compvhip_houghsht_segments_u8.argtypes = [vp, vp, sz, sz, sz, C.c_float, vp, sz, i32, i32, vp, sz, C.POINTER(sz)]
+    L.compvhip_plan_components.argtypes = [vp, vp, i32, i32, vp, sz, vp, sz, vp, vp]
+    L.compvhip_components_u8.argtypes = [vp, vp, sz, sz, sz, i32, i32, vp, sz, vp, sz, C.POINTER(sz)]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -291,6 +302,20 @@ class Context:
         self._chk(rc)
         return segs[:n.value]
 
+    def components(self, edges, connectivity=8, min_pixels=1, want_labels=True, cap=1 << 12):
+        """compvhip_components_u8: (labels, records) of one edge map -- the int32 label map (None without want_labels) and the COMP_DTYPE
+        array of the components with at least min_pixels pixels, in ascending order of their root's raster index."""
+        H, W = edges.shape
+        labels = np.zeros((H, W), np.int32) if want_labels else None
+        comps = np.zeros(max(cap, 1), COMP_DTYPE)
+        n = C.c_size_t(0)
+        rc = self.lib.compvhip_components_u8(self.h, _ptr(edges), W, H, edges.strides[0], connectivity, min_pixels,
+                                             _ptr(labels) if want_labels else None, W, _ptr(comps), cap, C.byref(n))
+        if rc == E_OUT_OF_BOUND and n.value > cap:
+            return self.components(edges, connectivity, min_pixels, want_labels, cap=n.value)
+        self._chk(rc)
+        return labels, comps[:n.value]
+
     def houghkht(self, edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, order="reference"):
         """Returns (lines, GS); lines['row'] / ['col'] hold the rho / theta indices.  order: "reference" (compvhip_houghkht_u8: the reference's tie
         order) or "canonical" (compvhip_houghkht_ex_u8: count descending, ties by emission key, peaks found and sorted on the GPU)."""
@@ -380,6 +405,13 @@ class Plan:
         the plan's last Canny.  d_segs: frames * seg_cap Segment records, d_seg_counts: frames int32 (found, before clipping)."""
         self.ctx._chk(self.lib.compvhip_plan_houghsht_segments(self.h, d_edges or None, d_lines, d_counts, line_cap, max_lines, min_length, max_gap,
                                                                d_segs, seg_cap, d_seg_counts, stream))
+
+    def components(self, d_edges, connectivity, min_pixels, d_labels, label_stride, d_comps, comp_cap, d_comp_counts, stream=0):
+        """compvhip_plan_components: connected components of every frame; d_edges = 0 reads the 1-bit masks of the plan's last Canny.
+        d_labels: frames * H * label_stride int32 (0: no label map), d_comps: frames * comp_cap Component records (0 with comp_cap 0:
+        counts only), d_comp_counts: frames int32 (found, before clipping)."""
+        self.ctx._chk(self.lib.compvhip_plan_components(self.h, d_edges or None, connectivity, min_pixels, d_labels or None, label_stride,
+                                                        d_comps or None, comp_cap, d_comp_counts, stream))
 
     def pipeline(self, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap, d_counts, stream=0):
         self.ctx._chk(self.lib.compvhip_plan_pipeline(self.h, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap,

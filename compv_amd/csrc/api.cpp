@@ -117,6 +117,9 @@ struct compvhip_ctx {
 	compvhip_line* dSegLines = nullptr; size_t dSegLinesCap = 0;   // staging of compvhip_houghsht_segments_u8: the caller's lines ...
 	compvhip_segment* dSegs = nullptr; size_t dSegsCap = 0;        // ... and the segments; the count travels through dCounts
 	int32_t* dSegCount = nullptr;
+	int32_t* dCompLabels = nullptr; size_t dCompLabelsCap = 0;    // staging of compvhip_components_u8: the label map (W * H) ...
+	compvhip_component* dComps = nullptr; size_t dCompsCap = 0;   // ... the records ...
+	int32_t* dCompCount = nullptr;                                 // ... and their number
 	KhtScratch kht;                    // KHT scratch of the host entry point (compvhip_houghkht_u8)
 };
 
@@ -177,6 +180,9 @@ struct compvhip_plan {
 	int* blockCounts = nullptr; int lineBlocks = 0;   // NMS survivors per 64 accumulator rows (part of `counters`)
 	void* sortTemp = nullptr; size_t sortTempBytes = 0;
 	int32_t* segPerLine = nullptr; size_t segPerLineCap = 0;   // line segments (sht_segments_kernels.hip): segments per line, then their prefix sums
+	// connected components (components_kernels.hip), allocated on first use: survivors per row [frames][H]; the packed copy of a byte edge map
+	// [frames][H][wb]; parent words [frames][H][W] of the calls without a label map (with one, the parent words live in it)
+	int32_t* compRows = nullptr; uint32_t* compBits = nullptr; int32_t* compParent = nullptr;
 	int strengthBits = 16, keyBits = 0;
 	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
 	uint16_t* chunkHist = nullptr; uint32_t* strengthStart = nullptr; int sortChunks = 0; bool deviceSort = false;
@@ -901,6 +907,7 @@ void compvhip_ctx_destroy(compvhip_ctx* ctx)
 	dfree(ctx, ctx->dPacked); dfree(ctx, ctx->dHist);
 	dfree(ctx, ctx->dIn); dfree(ctx, ctx->dOut); dfree(ctx, ctx->dCounts); dfree(ctx, ctx->dAccOut);
 	dfree(ctx, ctx->dSegLines); dfree(ctx, ctx->dSegs); dfree(ctx, ctx->dSegCount);
+	dfree(ctx, ctx->dCompLabels); dfree(ctx, ctx->dComps); dfree(ctx, ctx->dCompCount);
 	khtScratchFree(ctx, ctx->kht);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
@@ -1050,6 +1057,7 @@ void compvhip_plan_destroy(compvhip_plan* p)
 	dfree(ctx, p->sinQ); dfree(ctx, p->cosQ); dfree(ctx, p->edges); dfree(ctx, p->acc);
 	dfree(ctx, p->keysA); dfree(ctx, p->keysB); dfree(ctx, p->valsA); dfree(ctx, p->valsB); dfree(ctx, p->nmsFlags); dfree(ctx, p->chunkHist); dfree(ctx, p->strengthStart);
 	dfree(ctx, p->nmsRange); dfree(ctx, p->reach); dfree(ctx, p->sortTemp); dfree(ctx, p->segPerLine);
+	dfree(ctx, p->compRows); dfree(ctx, p->compBits); dfree(ctx, p->compParent);
 	delete p;
 }
 
@@ -1593,6 +1601,60 @@ int compvhip_plan_houghsht_segments(compvhip_plan* p, const uint8_t* d_edges, co
 	return segmentsImpl(p, d_edges, p->S, d_lines, d_counts, lineCap, maxLines, minLength, maxGap, d_segs, segCap, d_segCounts, static_cast<hipStream_t>(stream));
 }
 
+// ---- connected components (components_kernels.hip; definition in include/compv_hip.h) -----------------------------------------
+// edges / edgeStride: byte maps [frames][H][edgeStride] (packed into the plan's compBits first), or nullptr = the plan's bit masks
+static int componentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, int connectivity, int minPixels, int32_t* d_labels, size_t labelStride,
+                          compvhip_component* d_comps, size_t compCap, int32_t* d_compCounts, hipStream_t st)
+{
+	compvhip_ctx* ctx = p->ctx;
+	if (connectivity != 4 && connectivity != 8) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "connectivity must be 4 or 8");
+	if (minPixels < 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "minPixels must be >= 1");
+	if (!d_compCounts || (compCap && !d_comps)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null count / record buffer");
+	if (d_labels && labelStride < p->W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "labelStride < W");
+	if (p->W * p->H > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "W * H beyond 2^31");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t frames = p->frames;
+	if (!p->compRows) HIPCHK(ctx, dmalloc(ctx, &p->compRows, p->H * frames));
+	if (d_edges && !p->compBits) HIPCHK(ctx, dmalloc(ctx, &p->compBits, p->bitsFrameStride * frames));
+	if (!d_labels && !p->compParent) HIPCHK(ctx, dmalloc(ctx, &p->compParent, p->W * p->H * frames));
+	if (p->timing) timelineClear(p);
+	const int nf = static_cast<int>(frames);
+	if (d_edges) {
+		Stamp s(p, st, "bytes_to_bits_kernel");
+		HIPCHK(ctx, launch_bytes_to_bits(d_edges, static_cast<int>(p->W), static_cast<int>(p->H), static_cast<int>(edgeStride), edgeStride * p->H, p->compBits, p->wb,
+		                                 p->bitsFrameStride, nf, st));
+	}
+	CompArgs a;
+	a.bits = d_edges ? p->compBits : p->ebits; a.bitsFrameStride = p->bitsFrameStride; a.wb = p->wb;
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.words = static_cast<int>((p->W + 31) / 32);
+	a.lastMask = (p->W & 31) ? (1u << (p->W & 31)) - 1u : ~0u;
+	a.conn8 = connectivity == 8; a.minPixels = minPixels;
+	a.parent = d_labels ? d_labels : p->compParent; a.ps = static_cast<int>(d_labels ? labelStride : p->W);
+	a.parentFrameStride = static_cast<size_t>(a.ps) * p->H; a.wantLabels = d_labels != nullptr;
+	a.comps = d_comps; a.compCap = compCap; a.compCounts = d_compCounts; a.rowCounts = p->compRows; a.frame0 = 0;
+	static const char* const names[9] = { "comp_tile_kernel", "comp_border_kernel", "comp_flatten_kernel", "comp_count_kernel", "comp_rows_kernel<false>",
+	                                      "comp_scan_kernel", "comp_rows_kernel<true>", "comp_boxes_kernel", "comp_finish_kernel" };
+	for (int phase = 0; phase < 9; ++phase) {
+		if (phase == 7 && !a.wantLabels && !compCap) continue;   // nothing to label, no box to grow
+		if (phase == 8 && !a.wantLabels) continue;
+		Stamp s(p, st, names[phase]);
+		HIPCHK(ctx, launch_components(a, nf, phase, st));
+	}
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_components(compvhip_plan* p, const uint8_t* d_edges, int connectivity, int minPixels, int32_t* d_labels, size_t labelStride,
+                             compvhip_component* d_comps, size_t compCap, int32_t* d_compCounts, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	for (const auto& stp : p->steps)
+		if (stp.used) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the masks)");
+	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
+	if (labelStride > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "labelStride beyond 2^31");
+	return componentsImpl(p, d_edges, p->S, connectivity, minPixels, d_labels, labelStride, d_comps, compCap, d_compCounts, static_cast<hipStream_t>(stream));
+}
+
 // ---- host entry points -------------------------------------------------------------------------------------------
 static int hostPlan(compvhip_ctx* ctx, size_t W, size_t H, float thetaDeg, compvhip_plan** out)
 {
@@ -1902,6 +1964,35 @@ int compvhip_houghsht_segments_u8(compvhip_ctx* ctx, const uint8_t* edges, size_
 	const size_t ncopy = std::min(static_cast<size_t>(found), cap);
 	if (ncopy) HIPCHK(ctx, hipMemcpy(segs, ctx->dSegs, ncopy * sizeof(compvhip_segment), hipMemcpyDeviceToHost));
 	if (static_cast<size_t>(found) > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "segment buffer too small");
+	return COMPVHIP_OK;
+}
+
+int compvhip_components_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, int connectivity, int minPixels, int32_t* labels, size_t labelStride,
+                           compvhip_component* comps, size_t cap, size_t* nComps)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!edges || !nComps || (cap && !comps) || S < W || (labels && labelStride < W)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	if (W < 3 || H < 3 || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
+	if ((connectivity != 4 && connectivity != 8) || minPixels < 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "connectivity must be 4 or 8, minPixels >= 1");
+	*nComps = 0;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_plan* p = ctx->hostPlan;
+	int rc = hostPlan(ctx, W, H, (p && p->W == W && p->H == H) ? p->thetaDeg : 1.f, &p);   // any theta serves: keep the cached plan when it fits
+	if (rc) return rc;
+	if (labels && ctx->dCompLabelsCap < W * H) { dfree(ctx, ctx->dCompLabels); ctx->dCompLabelsCap = 0; HIPCHK(ctx, dmalloc(ctx, &ctx->dCompLabels, W * H)); ctx->dCompLabelsCap = W * H; }
+	if (ctx->dCompsCap < cap) { dfree(ctx, ctx->dComps); ctx->dCompsCap = 0; HIPCHK(ctx, dmalloc(ctx, &ctx->dComps, cap)); ctx->dCompsCap = cap; }
+	if (!ctx->dCompCount) HIPCHK(ctx, dmalloc(ctx, &ctx->dCompCount, 1));
+	HIPCHK(ctx, hipMemcpy2DAsync(ctx->dIn, p->S, edges, S, W, H, hipMemcpyHostToDevice, ctx->stream));
+	rc = componentsImpl(p, ctx->dIn, p->S, connectivity, minPixels, labels ? ctx->dCompLabels : nullptr, W, cap ? ctx->dComps : nullptr, cap, ctx->dCompCount, ctx->stream);
+	if (rc) return rc;
+	int32_t found = 0;
+	HIPCHK(ctx, hipMemcpyAsync(&found, ctx->dCompCount, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	*nComps = static_cast<size_t>(found);
+	if (labels) HIPCHK(ctx, hipMemcpy2D(labels, labelStride * sizeof(int32_t), ctx->dCompLabels, W * sizeof(int32_t), W * sizeof(int32_t), H, hipMemcpyDeviceToHost));
+	const size_t ncopy = std::min(static_cast<size_t>(found), cap);
+	if (ncopy) HIPCHK(ctx, hipMemcpy(comps, ctx->dComps, ncopy * sizeof(compvhip_component), hipMemcpyDeviceToHost));
+	if (static_cast<size_t>(found) > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "component buffer too small");
 	return COMPVHIP_OK;
 }
 

@@ -207,4 +207,28 @@ struct ShtSegArgs {
 // phase 0: count the segments of every line; 1: exclusive scan per frame + segCounts; 2: write the segments
 hipError_t launch_sht_segments(const ShtSegArgs& a, int frames, int phase, hipStream_t stream);
 
+// ---- connected components of edge maps (components_kernels.hip) -------------------------------------------------
+struct CompArgs {
+	const uint32_t* bits;     // edge bit masks [frames][H][wb]: the plan's own, or the plan's packed copy of a byte map
+	size_t bitsFrameStride;
+	int wb;
+	int W, H;
+	int words;                // mask words of a row that hold columns < W: ceil(W / 32)
+	uint32_t lastMask;        // the bits of word `words - 1` that are columns < W
+	int conn8;                // 8-connectivity (else 4)
+	int minPixels;
+	int32_t* parent;          // [frames][H][ps]: parent words, then labels -- the caller's label map, or the plan's scratch (ps == W)
+	size_t parentFrameStride;
+	int ps;
+	int wantLabels;           // parent is the caller's label map: finish it (ids on every foreground pixel, 0 elsewhere)
+	compvhip_component* comps;    // [frames][compCap]
+	size_t compCap;
+	int32_t* compCounts;      // [frames] survivors (before clipping to compCap)
+	int32_t* rowCounts;       // [frames][H] scratch: survivors whose root lies in a row, then their exclusive prefix sums
+	int frame0;               // filled by the launcher
+};
+// phases 0..8 in launch order: tiles, tile borders, flatten, pixel counts, survivors per row, row scan, ids + records, boxes (+ labels of the
+// non-root pixels), label map roots + background
+hipError_t launch_components(const CompArgs& a, int frames, int phase, hipStream_t stream);
+
 } // namespace compvhip

@@ -405,6 +405,43 @@ COMPVHIP_API int compvhip_houghsht_segments_u8(compvhip_ctx* ctx, const uint8_t*
                                                const compvhip_line* lines, size_t n, int minLength, int maxGap,
                                                compvhip_segment* segs, size_t cap, size_t* nSegs);
 
+/* ---- connected components of an edge map: which pixels belong together, how many, how big, where ---------------
+ * The reference's labeller (core/ccl, PLSL) has a result type of its own; this call has a canonical, integer-only definition instead
+ * (docs/kernels/components.md), so that two correct implementations agree on every byte:
+ *  Inputs: an edge map of W x H pixels (foreground = non-zero byte, or set bit of the plan's masks; bytes or bits at columns >= W are never
+ *     foreground, whatever they hold), connectivity 4 or 8, minPixels >= 1.
+ *  1. Components: the maximal sets of foreground pixels connected through foreground pixels by 8- (or 4-) neighbour steps.
+ *  2. Root of a component: its pixel with the smallest raster index y * W + x (W, not the stride).
+ *  3. Survivors: components with at least minPixels pixels.  The others are dropped: no record, label 0.
+ *  4. Id: survivors are numbered 1, 2, ... in ascending order of their root's raster index.
+ *  5. Label map (optional): int32 [frames][H][labelStride], labelStride >= W; 0 for background and dropped components, otherwise the id.
+ *     Elements at columns >= W are not written.  The label map does not depend on compCap.
+ *  6. Record of component id, stored at index id - 1: the root, the inclusive bounding box, the pixel count.
+ *  7. Counts and capacity: d_compCounts[f] = survivors of frame f BEFORE clipping; the first min(count, compCap) records are written and
+ *     nothing behind them, so a clipped result is a prefix of the full one.  Frames are independent. */
+typedef struct compvhip_component {
+	int32_t x, y;               /* the root */
+	int32_t x0, y0, x1, y1;     /* bounding box, inclusive */
+	int32_t pixels;
+} compvhip_component;
+
+/* Components of all frames of the plan.  d_edges: byte edge maps [frames][H][S], or NULL = the 1-bit masks of the plan's last Canny / pipeline
+ * step (COMPVHIP_E_INVALID_PARAMETER when the plan holds none, COMPVHIP_E_INVALID_STATE while asynchronous steps were not waited for; a byte
+ * map is packed into a mask copy of the call's own and leaves the plan's masks alone).  d_labels == NULL: no label map wanted; d_comps == NULL
+ * with compCap == 0: counts only.  Bad connectivity, minPixels < 1, labelStride < W (with a label map): COMPVHIP_E_INVALID_PARAMETER.
+ * Asynchronous on `stream`.  Scratch is owned by the plan and allocated on first use: frames * H int32, for byte maps a mask copy
+ * (frames * H * wb words, 1/8 of the bytes), and -- only when d_labels == NULL -- one int32 parent word per pixel (frames * W * H * 4 bytes:
+ * 33 MB per 4K frame); with a label map the parent words live in it (labelled in place). */
+COMPVHIP_API int compvhip_plan_components(compvhip_plan* plan, const uint8_t* d_edges, int connectivity, int minPixels,
+                                          int32_t* d_labels, size_t labelStride, compvhip_component* d_comps, size_t compCap,
+                                          int32_t* d_compCounts, void* stream);
+
+/* The same for one HOST edge map (3 <= W, H <= 32767 like every host entry point).  Synchronous.  labels: optional, H rows of labelStride
+ * int32.  *nComps receives the number of survivors; when it exceeds cap only the first cap records are written and COMPVHIP_E_OUT_OF_BOUND
+ * is returned (cap == 0 with comps == NULL asks for the number; the label map is complete either way). */
+COMPVHIP_API int compvhip_components_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, int connectivity, int minPixels,
+                                        int32_t* labels, size_t labelStride, compvhip_component* comps, size_t cap, size_t* nComps);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel
