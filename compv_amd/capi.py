@@ -42,6 +42,7 @@ EXPORTS = [
     "compvhip_plan_pipeline_ex", "compvhip_plan_houghkht", "compvhip_plan_houghkht_stage_ms", "compvhip_houghkht_link_u8",
     "compvhip_houghkht_dims", "compvhip_host_cpu_budget", "compvhip_plan_houghkht_ex", "compvhip_houghkht_ex_u8",
     "compvhip_plan_houghsht_segments", "compvhip_houghsht_segments_u8",
+    "compvhip_plan_houghsht_fit", "compvhip_houghsht_fit_u8",
     "compvhip_plan_components", "compvhip_components_u8",
 ]
 
@@ -62,6 +63,16 @@ class Segment(C.Structure):
 
 
 SEGMENT_DTYPE = np.dtype([("line", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("support", "<i4")])
+
+
+class LineFit(C.Structure):
+    """compvhip_line_fit (include/compv_hip.h): the band's pixel count and moments, the fitted unit normal (nx, ny), rho and mean squared distance"""
+    _fields_ = [("line", C.c_int32), ("pixels", C.c_int32), ("sx", C.c_int64), ("sy", C.c_int64), ("sxx", C.c_int64), ("sxy", C.c_int64), ("syy", C.c_int64),
+                ("nx", C.c_double), ("ny", C.c_double), ("rho", C.c_double), ("rms2", C.c_double)]
+
+
+LINE_FIT_DTYPE = np.dtype([("line", "<i4"), ("pixels", "<i4"), ("sx", "<i8"), ("sy", "<i8"), ("sxx", "<i8"), ("sxy", "<i8"), ("syy", "<i8"),
+                           ("nx", "<f8"), ("ny", "<f8"), ("rho", "<f8"), ("rms2", "<f8")])
 
 
 class Component(C.Structure):
@@ -167,6 +178,8 @@ def load():
     L.compvhip_plan_pipeline_ex.argtypes = [vp, vp, C.POINTER(PipelineOpts), vp, vp, sz, vp, vp, C.POINTER(i32)]
     L.compvhip_plan_houghsht_segments.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, vp, sz, vp, vp]
     L.compvhip_houghsht_segments_u8.argtypes = [vp, vp, sz, sz, sz, C.c_float, vp, sz, i32, i32, vp, sz, C.POINTER(sz)]
+    L.compvhip_plan_houghsht_fit.argtypes = [vp, vp, vp, vp, sz, i32, i32, vp, vp, sz, vp, sz, vp, vp, vp]
+    L.compvhip_houghsht_fit_u8.argtypes = [vp, vp, sz, sz, sz, C.c_float, vp, sz, i32, vp, sz, vp, sz, C.POINTER(sz), vp]
     L.compvhip_plan_components.argtypes = [vp, vp, i32, i32, vp, sz, vp, sz, vp, vp]
     L.compvhip_components_u8.argtypes = [vp, vp, sz, sz, sz, i32, i32, vp, sz, vp, sz, C.POINTER(sz)]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
@@ -302,6 +315,23 @@ class Context:
         self._chk(rc)
         return segs[:n.value]
 
+    def houghsht_fit(self, edges, lines, theta_deg=1.0, half_width=3, segs=None, want_refined=False):
+        """compvhip_houghsht_fit_u8: the least-squares fits (LINE_FIT_DTYPE array) through the edge pixels within half_width rho cells of
+        caller-held SHT lines (a LINE_DTYPE array; only row / col are read) -- one record per line, or per segment of segs (a SEGMENT_DTYPE
+        array of those lines).  want_refined (per line only): returns (fits, lines with the fitted rho / theta)."""
+        H, W = edges.shape
+        lines = np.ascontiguousarray(lines, LINE_DTYPE)
+        if segs is not None:
+            segs = np.ascontiguousarray(segs, SEGMENT_DTYPE)
+        cap = len(lines) if segs is None else len(segs)
+        fits = np.zeros(max(cap, 1), LINE_FIT_DTYPE)
+        refined = np.zeros(max(len(lines), 1), LINE_DTYPE) if want_refined else None
+        n = C.c_size_t(0)
+        self._chk(self.lib.compvhip_houghsht_fit_u8(self.h, _ptr(edges), W, H, edges.strides[0], theta_deg, _ptr(lines), len(lines), half_width,
+                                                    None if segs is None else _ptr(segs), 0 if segs is None else len(segs), _ptr(fits), cap, C.byref(n),
+                                                    _ptr(refined) if want_refined else None))
+        return (fits[:n.value], refined[:len(lines)]) if want_refined else fits[:n.value]
+
     def components(self, edges, connectivity=8, min_pixels=1, want_labels=True, cap=1 << 12):
         """compvhip_components_u8: (labels, records) of one edge map -- the int32 label map (None without want_labels) and the COMP_DTYPE
         array of the components with at least min_pixels pixels, in ascending order of their root's raster index."""
@@ -405,6 +435,14 @@ class Plan:
         the plan's last Canny.  d_segs: frames * seg_cap Segment records, d_seg_counts: frames int32 (found, before clipping)."""
         self.ctx._chk(self.lib.compvhip_plan_houghsht_segments(self.h, d_edges or None, d_lines, d_counts, line_cap, max_lines, min_length, max_gap,
                                                                d_segs, seg_cap, d_seg_counts, stream))
+
+    def houghsht_fit(self, d_edges, d_lines, d_counts, line_cap, max_lines, half_width, d_segs, d_seg_counts, seg_cap, d_fits, fit_cap, d_fit_counts,
+                     d_refined=0, stream=0):
+        """compvhip_plan_houghsht_fit: least-squares fits of the device line arrays of houghsht() / pipeline(), per line (d_segs = 0) or per
+        segment of houghsht_segments(); d_edges = 0 reads the 1-bit masks of the plan's last Canny.  d_fits: frames * fit_cap LineFit
+        records, d_fit_counts: frames int32 (records, before clipping), d_refined: 0 or frames * line_cap Line records."""
+        self.ctx._chk(self.lib.compvhip_plan_houghsht_fit(self.h, d_edges or None, d_lines, d_counts, line_cap, max_lines, half_width, d_segs or None,
+                                                          d_seg_counts or None, seg_cap, d_fits or None, fit_cap, d_fit_counts, d_refined or None, stream))
 
     def components(self, d_edges, connectivity, min_pixels, d_labels, label_stride, d_comps, comp_cap, d_comp_counts, stream=0):
         """compvhip_plan_components: connected components of every frame; d_edges = 0 reads the 1-bit masks of the plan's last Canny.

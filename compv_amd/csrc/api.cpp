@@ -117,6 +117,9 @@ struct compvhip_ctx {
 	compvhip_line* dSegLines = nullptr; size_t dSegLinesCap = 0;   // staging of compvhip_houghsht_segments_u8: the caller's lines ...
 	compvhip_segment* dSegs = nullptr; size_t dSegsCap = 0;        // ... and the segments; the count travels through dCounts
 	int32_t* dSegCount = nullptr;
+	compvhip_line_fit* dFits = nullptr; size_t dFitsCap = 0;       // staging of compvhip_houghsht_fit_u8: the records, their number ...
+	int32_t* dFitCount = nullptr;
+	compvhip_line* dFitRefined = nullptr; size_t dFitRefinedCap = 0;   // ... and the refined lines (lines and segments travel through dSegLines / dSegs)
 	int32_t* dCompLabels = nullptr; size_t dCompLabelsCap = 0;    // staging of compvhip_components_u8: the label map (W * H) ...
 	compvhip_component* dComps = nullptr; size_t dCompsCap = 0;   // ... the records ...
 	int32_t* dCompCount = nullptr;                                 // ... and their number
@@ -907,6 +910,7 @@ void compvhip_ctx_destroy(compvhip_ctx* ctx)
 	dfree(ctx, ctx->dPacked); dfree(ctx, ctx->dHist);
 	dfree(ctx, ctx->dIn); dfree(ctx, ctx->dOut); dfree(ctx, ctx->dCounts); dfree(ctx, ctx->dAccOut);
 	dfree(ctx, ctx->dSegLines); dfree(ctx, ctx->dSegs); dfree(ctx, ctx->dSegCount);
+	dfree(ctx, ctx->dFits); dfree(ctx, ctx->dFitCount); dfree(ctx, ctx->dFitRefined);
 	dfree(ctx, ctx->dCompLabels); dfree(ctx, ctx->dComps); dfree(ctx, ctx->dCompCount);
 	khtScratchFree(ctx, ctx->kht);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1525,7 +1529,7 @@ static int toCartesianImpl(compvhip_plan* p, const compvhip_line* d_lines, const
 	if (rc) return rc;
 	const float widthF = static_cast<float>(p->W), heightF = static_cast<float>(p->H);
 	const float r = std::sqrt((widthF * widthF) + (heightF * heightF)); // houghsht.cxx:570
-	HIPCHK(ctx, launch_sht_cartesian(d_lines, d_counts, lineCap, maxLines, static_cast<int>(p->frames), static_cast<int>(p->T), p->cosT, p->invSinT, widthF, r, d_cart,
+	HIPCHK(ctx, launch_sht_cartesian(d_lines, d_counts, lineCap, maxLines, static_cast<int>(p->frames), static_cast<int>(p->T), p->cosT, p->invSinT, p->thetaStep, widthF, r, d_cart,
 	                                 static_cast<hipStream_t>(stream)));
 	return COMPVHIP_OK;
 }
@@ -1599,6 +1603,51 @@ int compvhip_plan_houghsht_segments(compvhip_plan* p, const uint8_t* d_edges, co
 	if (!segCap) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "segCap must be > 0");
 	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
 	return segmentsImpl(p, d_edges, p->S, d_lines, d_counts, lineCap, maxLines, minLength, maxGap, d_segs, segCap, d_segCounts, static_cast<hipStream_t>(stream));
+}
+
+// ---- Hough line refinement (sht_fit_kernels.hip; definition in include/compv_hip.h) -------------------------------------------
+constexpr size_t kFitMaxSide = 8192;   // the central moments stay below 2^63 up to here
+constexpr int kFitMaxHalfWidth = 8;
+
+// edges / edgeStride: byte maps [frames][H][edgeStride], or nullptr = the plan's bit masks
+static int fitImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap, int maxLines,
+                   int halfWidth, const compvhip_segment* d_segs, const int32_t* d_segCounts, size_t segCap, compvhip_line_fit* d_fits, size_t fitCap,
+                   int32_t* d_fitCounts, compvhip_line* d_refined, hipStream_t st)
+{
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_lines || !d_counts || !d_fitCounts || !lineCap || (fitCap && !d_fits)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null line / count / fit buffer");
+	if (d_segs && (!d_segCounts || d_refined)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "per-segment fits need d_segCounts and take no d_refined");
+	if (halfWidth < 0 || halfWidth > kFitMaxHalfWidth) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "halfWidth must be 0 .. 8");
+	if (std::max(p->W, p->H) > kFitMaxSide) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "line fits need max(W, H) <= 8192 (int64 central moments)");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	int rc = ensureSht(p);
+	if (rc) return rc;
+	size_t nLines = std::min(lineCap, p->R * p->T);   // a frame has at most R * T lines
+	if (maxLines > 0) nLines = std::min(nLines, static_cast<size_t>(maxLines));
+	if (nLines > static_cast<size_t>(INT32_MAX) || (d_segs && segCap > static_cast<size_t>(INT32_MAX)))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "line / segment capacity beyond 2^31");
+	if (p->timing) timelineClear(p);
+	ShtFitArgs a;
+	a.ebits = p->ebits; a.edges = d_edges; a.bitsFrameStride = p->bitsFrameStride; a.edgeFrameStride = edgeStride * p->H; a.wb = p->wb; a.S = static_cast<int>(edgeStride);
+	a.sinQ = p->sinQ; a.cosQ = p->cosQ; a.lines = d_lines; a.lineCounts = d_counts; a.lineCap = lineCap; a.nLines = static_cast<int>(nLines);
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.R = static_cast<int>(p->R); a.T = static_cast<int>(p->T); a.barrier = static_cast<int>(p->W + p->H);
+	a.halfWidth = halfWidth; a.segs = d_segs; a.segCounts = d_segCounts; a.segCap = d_segs ? segCap : 0;
+	a.fits = d_fits; a.fitCap = fitCap; a.fitCounts = d_fitCounts; a.refined = d_refined; a.frame0 = 0;
+	{ Stamp s(p, st, "sht_fit_kernel"); HIPCHK(ctx, launch_sht_fit(a, static_cast<int>(p->frames), st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_houghsht_fit(compvhip_plan* p, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap, int maxLines,
+                               int halfWidth, const compvhip_segment* d_segs, const int32_t* d_segCounts, size_t segCap, compvhip_line_fit* d_fits, size_t fitCap,
+                               int32_t* d_fitCounts, compvhip_line* d_refined, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	for (const auto& stp : p->steps)
+		if (stp.used) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the lines)");
+	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
+	return fitImpl(p, d_edges, p->S, d_lines, d_counts, lineCap, maxLines, halfWidth, d_segs, d_segCounts, segCap, d_fits, fitCap, d_fitCounts, d_refined,
+	               static_cast<hipStream_t>(stream));
 }
 
 // ---- connected components (components_kernels.hip; definition in include/compv_hip.h) -----------------------------------------
@@ -1964,6 +2013,62 @@ int compvhip_houghsht_segments_u8(compvhip_ctx* ctx, const uint8_t* edges, size_
 	const size_t ncopy = std::min(static_cast<size_t>(found), cap);
 	if (ncopy) HIPCHK(ctx, hipMemcpy(segs, ctx->dSegs, ncopy * sizeof(compvhip_segment), hipMemcpyDeviceToHost));
 	if (static_cast<size_t>(found) > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "segment buffer too small");
+	return COMPVHIP_OK;
+}
+
+int compvhip_houghsht_fit_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float thetaDeg, const compvhip_line* lines, size_t n,
+                             int halfWidth, const compvhip_segment* segs, size_t nSegs, compvhip_line_fit* fits, size_t cap, size_t* nFits, compvhip_line* refined)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!edges || !nFits || (n && !lines) || (cap && !fits) || S < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	if (!(thetaDeg > 0.f) || halfWidth < 0 || halfWidth > kFitMaxHalfWidth) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "theta must be > 0, halfWidth 0 .. 8");
+	if (segs && refined) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "refined lines are a per-line result: segs must be NULL");
+	if (W < 3 || H < 3 || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
+	if (std::max(W, H) > kFitMaxSide) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "line fits need max(W, H) <= 8192 (int64 central moments)");
+	*nFits = 0;
+	size_t R, T;
+	int rc = shtDims(W, H, thetaDeg, &R, &T, nullptr);
+	if (rc) return fail(ctx, rc, "invalid SHT geometry");
+	if (n > static_cast<size_t>(INT32_MAX) || (segs && nSegs > static_cast<size_t>(INT32_MAX))) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "too many lines / segments");
+	for (size_t i = 0; i < n; ++i)
+		if (lines[i].row < 0 || static_cast<size_t>(lines[i].row) >= R || lines[i].col < 0 || static_cast<size_t>(lines[i].col) >= T)
+			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "a line's (row, col) is not a cell of the R x T accumulator");
+	if (segs)
+		for (size_t j = 0; j < nSegs; ++j)
+			if (segs[j].line < 0 || static_cast<size_t>(segs[j].line) >= n) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "a segment's line is not one of the n lines");
+	const size_t nRec = segs ? nSegs : n;
+	if (!n || !nRec) return COMPVHIP_OK;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_plan* p = nullptr;
+	rc = hostPlan(ctx, W, H, thetaDeg, &p);
+	if (rc) return rc;
+	if (ctx->dSegLinesCap < n) { dfree(ctx, ctx->dSegLines); ctx->dSegLinesCap = 0; HIPCHK(ctx, dmalloc(ctx, &ctx->dSegLines, n)); ctx->dSegLinesCap = n; }
+	if (segs && ctx->dSegsCap < nSegs) { dfree(ctx, ctx->dSegs); ctx->dSegsCap = 0; HIPCHK(ctx, dmalloc(ctx, &ctx->dSegs, nSegs)); ctx->dSegsCap = nSegs; }
+	if (ctx->dFitsCap < cap) { dfree(ctx, ctx->dFits); ctx->dFitsCap = 0; HIPCHK(ctx, dmalloc(ctx, &ctx->dFits, cap)); ctx->dFitsCap = cap; }
+	if (refined && ctx->dFitRefinedCap < n) { dfree(ctx, ctx->dFitRefined); ctx->dFitRefinedCap = 0; HIPCHK(ctx, dmalloc(ctx, &ctx->dFitRefined, n)); ctx->dFitRefinedCap = n; }
+	if (!ctx->dCounts) HIPCHK(ctx, dmalloc(ctx, &ctx->dCounts, 1));
+	if (!ctx->dSegCount) HIPCHK(ctx, dmalloc(ctx, &ctx->dSegCount, 1));
+	if (!ctx->dFitCount) HIPCHK(ctx, dmalloc(ctx, &ctx->dFitCount, 1));
+	const int32_t nLines = static_cast<int32_t>(n), nS = static_cast<int32_t>(nSegs);
+	HIPCHK(ctx, hipMemcpy2DAsync(ctx->dIn, p->S, edges, S, W, H, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dSegLines, lines, n * sizeof(compvhip_line), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dCounts, &nLines, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+	if (segs) {
+		HIPCHK(ctx, hipMemcpyAsync(ctx->dSegs, segs, nSegs * sizeof(compvhip_segment), hipMemcpyHostToDevice, ctx->stream));
+		HIPCHK(ctx, hipMemcpyAsync(ctx->dSegCount, &nS, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+	}
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the counts live on this stack frame; pageable copies may still be staged
+	rc = fitImpl(p, ctx->dIn, p->S, ctx->dSegLines, ctx->dCounts, n, 0, halfWidth, segs ? ctx->dSegs : nullptr, ctx->dSegCount, nSegs, cap ? ctx->dFits : nullptr, cap,
+	             ctx->dFitCount, refined ? ctx->dFitRefined : nullptr, ctx->stream);
+	if (rc) return rc;
+	int32_t found = 0;
+	HIPCHK(ctx, hipMemcpyAsync(&found, ctx->dFitCount, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	*nFits = static_cast<size_t>(found);
+	const size_t ncopy = std::min(static_cast<size_t>(found), cap);
+	if (ncopy) HIPCHK(ctx, hipMemcpy(fits, ctx->dFits, ncopy * sizeof(compvhip_line_fit), hipMemcpyDeviceToHost));
+	if (refined) HIPCHK(ctx, hipMemcpy(refined, ctx->dFitRefined, n * sizeof(compvhip_line), hipMemcpyDeviceToHost));
+	if (static_cast<size_t>(found) > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "fit buffer too small");
 	return COMPVHIP_OK;
 }
 

@@ -164,8 +164,9 @@ size_t sht_nms_rows(int R);
 int sht_lines_blocks(int R);
 // acc [T][pitch] -> reference layout [R][stride]
 // maxLines > 0: only the first min(count, lineCap, maxLines) lines of a frame are converted (what sht_decode_kernel wrote)
+// a line whose theta is col * thetaStep takes cos / 1 / sin from the tables; any other theta (a refined line) is evaluated on the device
 hipError_t launch_sht_cartesian(const void* lines /*compvhip_line*/, const int* counts, size_t lineCap, int maxLines, int frames, int T, const float* cosT,
-                                const float* invSinT, float widthF, float r, float* out /*[frames][lineCap][4]*/, hipStream_t stream);
+                                const float* invSinT, float thetaStep, float widthF, float r, float* out /*[frames][lineCap][4]*/, hipStream_t stream);
 hipError_t launch_sht_acc_transpose(const uint16_t* accT, int R, int T, int accPitch, int32_t* out, size_t outStride, hipStream_t stream);
 // the line sort sized on the device (sht_sort_kernels.hip): counting sort on the strength, stable ranks from chunks sorted in the LDS
 constexpr int kShtSortChunk = 4096;             // lines per chunk (one workgroup)
@@ -206,6 +207,31 @@ struct ShtSegArgs {
 };
 // phase 0: count the segments of every line; 1: exclusive scan per frame + segCounts; 2: write the segments
 hipError_t launch_sht_segments(const ShtSegArgs& a, int frames, int phase, hipStream_t stream);
+
+// ---- Hough SHT line refinement (sht_fit_kernels.hip) -------------------------------------------------------------
+struct ShtFitArgs {
+	const uint32_t* ebits;    // edge bit masks [frames][H][wb] (read when edges == nullptr)
+	const uint8_t* edges;     // or byte edge maps [frames][H][S], non-zero = edge
+	size_t bitsFrameStride, edgeFrameStride;
+	int wb, S;
+	const int32_t* sinQ;      // [T] the vote's Q16 tables
+	const int32_t* cosQ;
+	const compvhip_line* lines;   // [frames][lineCap]; only row / col are read
+	const int32_t* lineCounts;    // [frames] lines found (may exceed lineCap)
+	size_t lineCap;
+	int nLines;               // lines considered per frame at most: min(lineCap, maxLines if > 0)
+	int W, H, R, T, barrier;
+	int halfWidth;            // 0 .. 8 rho cells either side of the line's
+	const compvhip_segment* segs; // [frames][segCap] per-segment mode (nullptr: one record per line)
+	const int32_t* segCounts;     // [frames] segments found (may exceed segCap)
+	size_t segCap;
+	compvhip_line_fit* fits;  // [frames][fitCap]
+	size_t fitCap;
+	int32_t* fitCounts;       // [frames] records (before clipping to fitCap)
+	compvhip_line* refined;   // [frames][lineCap] the lines with the fitted rho / theta (per-line mode, may be nullptr)
+	int frame0;               // filled by the launcher
+};
+hipError_t launch_sht_fit(const ShtFitArgs& a, int frames, hipStream_t stream);
 
 // ---- connected components of edge maps (components_kernels.hip) -------------------------------------------------
 struct CompArgs {

@@ -405,6 +405,59 @@ COMPVHIP_API int compvhip_houghsht_segments_u8(compvhip_ctx* ctx, const uint8_t*
                                                const compvhip_line* lines, size_t n, int minLength, int maxGap,
                                                compvhip_segment* segs, size_t cap, size_t* nSegs);
 
+/* ---- Hough line REFINEMENT: where the line really is -------------------------------------------------------------
+ * An SHT line is an accumulator cell: rho is an integer and theta a multiple of the theta step.  The fit below is the total-least-squares
+ * line through the edge pixels of a band of rho cells around the cell (docs/kernels/sht_fit.md).  Its integer part has no tolerance; its
+ * binary64 part uses + - * / sqrt only, each rounded once, in the order given, so it is reproducible bit for bit as well.
+ *  Inputs: the edge map (non-zero byte, or set bit of the plan's masks; columns >= W are never edges), the plan's Q16 tables, the line's cell
+ *     (row, col) -- rho_i = (W + H) - row, t = col; the float fields of compvhip_line are not read --, halfWidth b in 0 .. 8, and optionally a
+ *     range [p0, p1] of positions on the line's major axis (rule 2 of the segment definition: x-major iff sinQ[t] >= |cosQ[t]|).
+ *  1. Band: edge pixel (x, y) belongs to the fit iff | ((x * cosQ[t] + y * sinQ[t]) >> 16) - rho_i | <= b (arithmetic shift of the exact sum:
+ *     the vote's own expression) and, with a range, its major coordinate lies in [p0, p1].  b = 0 without a range is the line's support
+ *     (pixels == strength); in general pixels is the sum of the accumulator cells (row - b .. row + b, col), rows clipped to [0, R).
+ *  2. Moments (int64, exact): n, sx = sum x, sy = sum y, sxx = sum x^2, sxy = sum x y, syy = sum y^2.
+ *  3. Central moments (int64, exact): A = n sxx - sx^2, B = n sxy - sx sy, C = n syy - sy^2.  A position holds at most 25 band pixels, so
+ *     for max(W, H) <= 8192 n <= 204 800 and |A|, |B|, |C| <= n^2 * 8191^2 < 2^63.  Larger geometries: COMPVHIP_E_NOT_IMPLEMENTED.
+ *  4. Fit (binary64, no FMA, in this order): a = (double)A, bb = (double)B, c = (double)C; d = a - c; s = sqrt(d * d + 4 * (bb * bb)).
+ *     n < 2 or s == 0: the fit is INVALID and nx = ny = rho = rms2 = 0.  Otherwise: d >= 0: u = -(2 * bb), v = d + s; else u = s - d,
+ *     v = -(2 * bb).  h = sqrt(u * u + v * v); nx = u / h; ny = v / h; when ny < 0, or ny == 0 and nx < 0, both are negated (the Hough
+ *     convention: the normal is (cos theta, sin theta), theta in [0, pi]).  rho = (nx * (double)sx + ny * (double)sy) / (double)n (signed,
+ *     from the image origin, as in toCartesian); rms2 = max(0, (a + c) - s) / (2 * (double)n * (double)n), the mean squared distance.
+ *  5. Record: compvhip_line_fit, 80 bytes without padding.
+ *  6. Per line (d_segs == NULL): record i belongs to line i of the frame's line array; lines considered: min(d_counts[f], lineCap, maxLines
+ *     if > 0).  Per segment (d_segs != NULL): record j belongs to segment j of the first min(d_segCounts[f], segCap) segments, line =
+ *     segs[j].line, range = [x0, x1] on an x-major line and [y0, y1] otherwise (clipped to the image).  A segment whose line is not one of
+ *     the lines considered, or a line whose cell is outside the accumulator, has an empty band (pixels = 0, invalid fit).
+ *     d_fitCounts[f] = records BEFORE clipping; the first min(count, fitCap) are written and nothing behind them.
+ *  7. Refined lines (optional, per-line mode): a copy of the lines considered in which a valid fit replaces rho by (float)rho, theta by
+ *     (float)atan2(ny, nx) and strength by pixels; row / col stay.  theta is the only value of the feature that goes through a libm function. */
+typedef struct compvhip_line_fit {
+	int32_t line, pixels;
+	int64_t sx, sy, sxx, sxy, syy;
+	double  nx, ny, rho, rms2;
+} compvhip_line_fit;
+
+/* Fits of the lines (or of the segments of the lines) a compvhip_plan_houghsht / _pipeline call left on the device, for all frames of the plan.
+ * d_edges: as for compvhip_plan_houghsht_segments (NULL = the plan's masks, with the same state rules and error codes, COMPVHIP_E_INVALID_STATE
+ * while asynchronous steps were not waited for included).  d_segs == NULL: per line; otherwise d_segs / d_segCounts / segCap are what
+ * compvhip_plan_houghsht_segments wrote for the same lines.  d_fits: frames * fitCap records (NULL with fitCap == 0: counts, and refined lines,
+ * only).  d_refined: NULL, or frames * lineCap lines, of which the lines considered are written -- it feeds compvhip_plan_to_cartesian with the
+ * same d_counts and lineCap; COMPVHIP_E_INVALID_PARAMETER in per-segment mode.  halfWidth outside 0 .. 8, lineCap == 0 or a null line / count
+ * buffer: COMPVHIP_E_INVALID_PARAMETER; max(W, H) > 8192: COMPVHIP_E_NOT_IMPLEMENTED.  Asynchronous on `stream`; no scratch beyond the
+ * plan's SHT tables. */
+COMPVHIP_API int compvhip_plan_houghsht_fit(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts,
+                                            size_t lineCap, int maxLines, int halfWidth,
+                                            const compvhip_segment* d_segs, const int32_t* d_segCounts, size_t segCap,
+                                            compvhip_line_fit* d_fits, size_t fitCap, int32_t* d_fitCounts, compvhip_line* d_refined, void* stream);
+
+/* The same for caller-held lines (and, with segs != NULL, nSegs segments of them) of one HOST edge map; lines in either order, only row / col
+ * are read.  Synchronous.  *nFits receives the number of records (n, or nSegs); when it exceeds cap only the first cap are written and
+ * COMPVHIP_E_OUT_OF_BOUND is returned (cap == 0 with fits == NULL asks for the number).  refined: NULL, or n lines (segs must be NULL).  A line
+ * whose (row, col) is outside the R x T accumulator of (W, H, thetaDeg), or a segment whose line is not below n: COMPVHIP_E_INVALID_PARAMETER. */
+COMPVHIP_API int compvhip_houghsht_fit_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float thetaDeg,
+                                          const compvhip_line* lines, size_t n, int halfWidth, const compvhip_segment* segs, size_t nSegs,
+                                          compvhip_line_fit* fits, size_t cap, size_t* nFits, compvhip_line* refined);
+
 /* ---- connected components of an edge map: which pixels belong together, how many, how big, where ---------------
  * The reference's labeller (core/ccl, PLSL) has a result type of its own; this call has a canonical, integer-only definition instead
  * (docs/kernels/components.md), so that two correct implementations agree on every byte:
