@@ -27,6 +27,10 @@ THRESHOLD_COMPARE_TO_GRADIENT, THRESHOLD_PERCENT_OF_MEAN, THRESHOLD_OTSU = 0, 1,
 (FMT_RGBA32, FMT_ARGB32, FMT_BGRA32, FMT_RGB24, FMT_BGR24, FMT_RGB565LE, FMT_RGB565BE, FMT_BGR565LE, FMT_BGR565BE,
  FMT_YUYV422, FMT_UYVY422, FMT_Y) = range(12)
 FMT_BYTES = [4, 4, 4, 3, 3, 2, 2, 2, 2, 2, 2, 1]
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
+STREL_RECT, STREL_DIAMOND, STREL_CROSS = 0, 1, 2
+BORDER_ZERO, BORDER_REPLICATE = 0, 2
+MORPH_KERNEL_AUTO, MORPH_KERNEL_GENERAL, MORPH_KERNEL_SEPARABLE = 0, 1, 2
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -44,6 +48,8 @@ EXPORTS = [
     "compvhip_plan_houghsht_segments", "compvhip_houghsht_segments_u8",
     "compvhip_plan_houghsht_fit", "compvhip_houghsht_fit_u8",
     "compvhip_plan_components", "compvhip_components_u8",
+    "compvhip_threshold_u8", "compvhip_plan_threshold", "compvhip_threshold_adaptive_u8", "compvhip_plan_threshold_adaptive",
+    "compvhip_morph_strel", "compvhip_morph_u8", "compvhip_plan_morph", "compvhip_plan_morph_ex",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -182,6 +188,15 @@ def load():
     L.compvhip_houghsht_fit_u8.argtypes = [vp, vp, sz, sz, sz, C.c_float, vp, sz, i32, vp, sz, vp, sz, C.POINTER(sz), vp]
     L.compvhip_plan_components.argtypes = [vp, vp, i32, i32, vp, sz, vp, sz, vp, vp]
     L.compvhip_components_u8.argtypes = [vp, vp, sz, sz, sz, i32, i32, vp, sz, vp, sz, C.POINTER(sz)]
+    f64 = C.c_double
+    L.compvhip_threshold_u8.argtypes = [vp, vp, sz, sz, sz, f64, vp, sz]
+    L.compvhip_plan_threshold.argtypes = [vp, vp, f64, vp, vp, vp]
+    L.compvhip_threshold_adaptive_u8.argtypes = [vp, vp, sz, sz, sz, sz, f64, f64, i32, vp, sz]
+    L.compvhip_plan_threshold_adaptive.argtypes = [vp, vp, sz, f64, f64, i32, vp, vp]
+    L.compvhip_morph_strel.argtypes = [i32, sz, sz, vp]
+    L.compvhip_morph_u8.argtypes = [vp, vp, sz, sz, sz, vp, sz, sz, i32, i32, vp, sz]
+    L.compvhip_plan_morph.argtypes = [vp, vp, vp, sz, sz, i32, i32, vp, vp]
+    L.compvhip_plan_morph_ex.argtypes = [vp, vp, vp, sz, sz, i32, i32, i32, vp, vp]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -346,6 +361,28 @@ class Context:
         self._chk(rc)
         return labels, comps[:n.value]
 
+    def threshold(self, img, threshold):
+        """compvhip_threshold_u8 (CompVImageThreshold::global): img > round(clip(threshold)) ? 255 : 0."""
+        H, W = img.shape
+        out = np.empty((H, W), np.uint8)
+        self._chk(self.lib.compvhip_threshold_u8(self.h, _ptr(img), W, H, img.strides[0], threshold, _ptr(out), W))
+        return out
+
+    def threshold_adaptive(self, img, block_size, delta, max_val=255.0, invert=False):
+        """compvhip_threshold_adaptive_u8 (CompVImageThreshold::adaptive with the Q16 mean kernel)."""
+        H, W = img.shape
+        out = np.empty((H, W), np.uint8)
+        self._chk(self.lib.compvhip_threshold_adaptive_u8(self.h, _ptr(img), W, H, img.strides[0], block_size, delta, max_val, int(bool(invert)), _ptr(out), W))
+        return out
+
+    def morph(self, img, strel, op, border=BORDER_REPLICATE):
+        """compvhip_morph_u8 (CompVMathMorph::process): strel is a 2-D uint8 array, non-zero = member."""
+        H, W = img.shape
+        strel = np.ascontiguousarray(strel, np.uint8)
+        out = np.empty((H, W), np.uint8)
+        self._chk(self.lib.compvhip_morph_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(strel), strel.shape[1], strel.shape[0], op, border, _ptr(out), W))
+        return out
+
     def houghkht(self, edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, order="reference"):
         """Returns (lines, GS); lines['row'] / ['col'] hold the rho / theta indices.  order: "reference" (compvhip_houghkht_u8: the reference's tie
         order) or "canonical" (compvhip_houghkht_ex_u8: count descending, ties by emission key, peaks found and sorted on the GPU)."""
@@ -450,6 +487,22 @@ class Plan:
         counts only), d_comp_counts: frames int32 (found, before clipping)."""
         self.ctx._chk(self.lib.compvhip_plan_components(self.h, d_edges or None, connectivity, min_pixels, d_labels or None, label_stride,
                                                         d_comps or None, comp_cap, d_comp_counts, stream))
+
+    def threshold(self, d_in, threshold, d_out, d_levels=0, stream=0):
+        """compvhip_plan_threshold: d_levels = 0 cuts every frame at `threshold`, otherwise frame f at d_levels[f] (what otsu() wrote)."""
+        self.ctx._chk(self.lib.compvhip_plan_threshold(self.h, d_in, threshold, d_levels or None, d_out, stream))
+
+    def threshold_adaptive(self, d_in, block_size, delta, max_val, invert, d_out, stream=0):
+        self.ctx._chk(self.lib.compvhip_plan_threshold_adaptive(self.h, d_in, block_size, delta, max_val, int(bool(invert)), d_out, stream))
+
+    def morph(self, d_in, strel, op, border, d_out, kernel=MORPH_KERNEL_AUTO, stream=0):
+        """compvhip_plan_morph (kernel = MORPH_KERNEL_AUTO) / compvhip_plan_morph_ex: strel is a 2-D uint8 HOST array, non-zero = member."""
+        strel = np.ascontiguousarray(strel, np.uint8)
+        sh, sw = strel.shape
+        if kernel == MORPH_KERNEL_AUTO:
+            self.ctx._chk(self.lib.compvhip_plan_morph(self.h, d_in, _ptr(strel), sw, sh, op, border, d_out, stream))
+        else:
+            self.ctx._chk(self.lib.compvhip_plan_morph_ex(self.h, d_in, _ptr(strel), sw, sh, op, border, kernel, d_out, stream))
 
     def pipeline(self, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap, d_counts, stream=0):
         self.ctx._chk(self.lib.compvhip_plan_pipeline(self.h, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap,
@@ -584,6 +637,15 @@ def to_cartesian(W, H, lines, kht=False):
     if rc != OK:
         raise CompvHipError(rc, "invalid toCartesian parameters")
     return out[:n]
+
+
+def morph_strel(kind, w, h):
+    """CompVMathMorph::buildStructuringElement (host arithmetic, no GPU needed): (h, w) uint8, 0xff marks a member."""
+    s = np.zeros((max(h, 0), max(w, 0)), np.uint8)
+    rc = load().compvhip_morph_strel(kind, w, h, _ptr(s) if s.size else None)
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_morph_strel")
+    return s
 
 
 def gauss_kernel_fixedpoint(size, sigma):

@@ -186,6 +186,7 @@ struct compvhip_plan {
 	// connected components (components_kernels.hip), allocated on first use: survivors per row [frames][H]; the packed copy of a byte edge map
 	// [frames][H][wb]; parent words [frames][H][W] of the calls without a label map (with one, the parent words live in it)
 	int32_t* compRows = nullptr; uint32_t* compBits = nullptr; int32_t* compParent = nullptr;
+	uint8_t* morphTmp = nullptr;                 // thresholding / morphology (morph_kernels.hip), allocated on first use: the u8 plane [frames][H][S] between the two basic operations of an OPEN / CLOSE, and the out-of-place target of an in-place adaptive threshold
 	int strengthBits = 16, keyBits = 0;
 	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
 	uint16_t* chunkHist = nullptr; uint32_t* strengthStart = nullptr; int sortChunks = 0; bool deviceSort = false;
@@ -1054,6 +1055,7 @@ void compvhip_plan_destroy(compvhip_plan* p)
 	if (p->hFlags) (void)hipHostFree(p->hFlags);
 	if (p->hRounds) (void)hipHostFree(p->hRounds);
 	dfree(ctx, p->hist); dfree(ctx, p->otsu); dfree(ctx, p->blurTmp); dfree(ctx, p->grayTmp);
+	dfree(ctx, p->morphTmp);
 	for (KhtBatchState* b : p->khtBatch) khtBatchFree(ctx, b);
 	p->khtBatch.clear();
 	dfree(ctx, p->cosT); dfree(ctx, p->invSinT);
@@ -1704,6 +1706,165 @@ int compvhip_plan_components(compvhip_plan* p, const uint8_t* d_edges, int conne
 	return componentsImpl(p, d_edges, p->S, connectivity, minPixels, d_labels, labelStride, d_comps, compCap, d_compCounts, static_cast<hipStream_t>(stream));
 }
 
+// ---- thresholding and morphology (morph_kernels.hip; definitions in include/compv_hip.h) ---------------------------------------------------
+static bool planeOverlap(const compvhip_plan* p, const uint8_t* a, const uint8_t* b)
+{
+	const size_t span = p->S * p->H * p->frames;
+	return (a < b + span) && (b < a + span);
+}
+
+// COMPV_MATH_ROUNDFU_2_NEAREST_INT(COMPV_MATH_CLIP3(0x00, 0xff, v), int) (compv_image_threshold.cxx:133-136,213-220)
+static int roundClipU8(double v) { return static_cast<int>((v > 255.0 ? 255.0 : (v < 0.0 ? 0.0 : v)) + 0.5); }
+
+int compvhip_plan_threshold(compvhip_plan* p, const uint8_t* d_in, double threshold, const int32_t* d_levels, uint8_t* d_out, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	if (!d_levels && !(threshold >= 0.0)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "threshold < 0"); // compv_image_threshold.cxx:120
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	ThreshArgs a;
+	a.in = d_in; a.out = d_out; a.levels = d_levels; a.frameStride = p->S * p->H;
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
+	a.t8 = d_levels ? 0 : roundClipU8(threshold);
+	Stamp s(p, st, "threshold_kernel");
+	HIPCHK(ctx, launch_threshold(a, static_cast<int>(p->frames), st));
+	return COMPVHIP_OK;
+}
+
+static int checkAdaptive(compvhip_ctx* ctx, size_t W, size_t H, size_t blockSize, double delta, double maxVal)
+{
+	if (!(blockSize & 1) || blockSize < 3) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "blockSize must be odd and >= 3"); // compv_image_threshold.cxx:185
+	if (blockSize > 31) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "adaptive threshold supports block sizes 3..31");
+	if (W < blockSize || H < blockSize) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image smaller than the block"); // compv_math_convlt.h:100
+	if (!(maxVal >= 0.0) || delta != delta) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "maxVal < 0"); // compv_image_threshold.cxx:202
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_threshold_adaptive(compvhip_plan* p, const uint8_t* d_in, size_t blockSize, double delta, double maxVal, int invert, uint8_t* d_out, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	int rc = checkAdaptive(ctx, p->W, p->H, blockSize, delta, maxVal);
+	if (rc) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t span = p->S * p->H * p->frames;
+	const bool alias = planeOverlap(p, d_in, d_out);
+	if (alias && d_in != d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output overlap without being the same buffer");
+	if (alias && !p->morphTmp) HIPCHK(ctx, dmalloc(ctx, &p->morphTmp, span)); // a tile reads the halo its neighbours write: in place goes through the plan's plane
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	AdaptArgs a;
+	a.in = d_in; a.out = alias ? p->morphTmp : d_out; a.frameStride = p->S * p->H;
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
+	a.r = static_cast<int>(blockSize >> 1);
+	a.k = static_cast<uint16_t>((1.f / static_cast<float>(blockSize)) * 0xffff);   // CompVKernel::mean (compv_kernel.cxx:16) through fixedPointKernel (compv_math_convlt.h:88)
+	a.delta = roundClipU8(delta); a.maxVal = roundClipU8(maxVal); a.invert = invert != 0;
+	{
+		Stamp s(p, st, "threshold_adaptive_kernel");
+		HIPCHK(ctx, launch_threshold_adaptive(a, static_cast<int>(p->frames), st));
+	}
+	if (alias) {   // rows only up to W: the padding columns of the caller's buffer stay as they are
+		for (size_t f = 0; f < p->frames; ++f)
+			HIPCHK(ctx, hipMemcpy2DAsync(d_out + f * p->S * p->H, p->S, p->morphTmp + f * p->S * p->H, p->S, p->W, p->H, hipMemcpyDeviceToDevice, st));
+	}
+	return COMPVHIP_OK;
+}
+
+// buildStructuringElementGeneric (compv_math_morph.cxx:476-540)
+int compvhip_morph_strel(int type, size_t w, size_t h, uint8_t* strel)
+{
+	if (!strel || !w || !h) return COMPVHIP_E_INVALID_PARAMETER; // :478
+	if (type != COMPVHIP_MORPH_STREL_RECT && type != COMPVHIP_MORPH_STREL_DIAMOND && type != COMPVHIP_MORPH_STREL_CROSS) return COMPVHIP_E_NOT_IMPLEMENTED; // :534
+	if (type == COMPVHIP_MORPH_STREL_DIAMOND && w != h) return COMPVHIP_E_INVALID_PARAMETER;
+	if (type == COMPVHIP_MORPH_STREL_RECT) { memset(strel, 0xff, w * h); return COMPVHIP_OK; }
+	memset(strel, 0, w * h);
+	if (type == COMPVHIP_MORPH_STREL_CROSS) {
+		memset(strel + (h >> 1) * w, 0xff, w);
+		for (size_t j = 0; j < h; ++j) strel[j * w + (w >> 1)] = 0xff;
+		return COMPVHIP_OK;
+	}
+	const size_t c = w >> 1;
+	for (size_t j = 0; j < h; ++j) {   // 1, 3, 5, ... members centred on column w / 2 down to the middle row, then back
+		const size_t half = j <= (h >> 1) ? j : h - 1 - j;
+		memset(strel + j * w + c - half, 0xff, 2 * half + 1);
+	}
+	return COMPVHIP_OK;
+}
+
+// strel -> member masks + the kernel that serves it
+static int morphPrepare(compvhip_ctx* ctx, size_t W, size_t H, const uint8_t* strel, size_t sw, size_t sh, int op, int border, int kernel, MorphArgs* a)
+{
+	if (!strel || !sw || !sh) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null / empty structuring element");
+	if (!(sw & 1) || !(sh & 1) || sw > static_cast<size_t>(kMorphMaxStrel) || sh > static_cast<size_t>(kMorphMaxStrel))
+		return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "structuring elements are odd-sized, 1..31 a side");
+	if (W < sw || H < sh) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image smaller than the structuring element"); // compv_math_morph.cxx:131
+	if (op != COMPVHIP_MORPH_OP_ERODE && op != COMPVHIP_MORPH_OP_DILATE && op != COMPVHIP_MORPH_OP_OPEN && op != COMPVHIP_MORPH_OP_CLOSE)
+		return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "morph op (erode, dilate, open, close)"); // :119
+	if (border != COMPVHIP_BORDER_REPLICATE && border != COMPVHIP_BORDER_ZERO) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "border type (replicate, zero)"); // :571
+	size_t members = 0, cross = 0;
+	for (size_t j = 0; j < sh; ++j) {
+		uint32_t m = 0;
+		for (size_t i = 0; i < sw; ++i) {
+			if (!strel[j * sw + i]) continue;
+			m |= 1u << i; ++members;
+			if (j == (sh >> 1) || i == (sw >> 1)) ++cross;
+		}
+		a->rows[j] = m;
+	}
+	for (size_t j = sh; j < static_cast<size_t>(kMorphMaxStrel); ++j) a->rows[j] = 0;
+	if (!members) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "structuring element is full of zeros"); // :460
+	const bool isRect = members == sw * sh, isCross = !isRect && members == cross && cross == sw + sh - 1;
+	if (kernel == COMPVHIP_MORPH_KERNEL_GENERAL) a->kind = kMorphGeneral;
+	else if (kernel == COMPVHIP_MORPH_KERNEL_AUTO || kernel == COMPVHIP_MORPH_KERNEL_SEPARABLE) {
+		a->kind = isRect ? kMorphRect : (isCross ? kMorphCross : kMorphGeneral);
+		// up to 15 members the member-list kernel is the faster one (3x3: 0.28 ms against 0.35 ms at 4K x 32; docs/kernels/morph.md): the second LDS plane
+		// and barrier of the separable kernel cost more than the taps it saves
+		if (kernel == COMPVHIP_MORPH_KERNEL_AUTO && members <= kMorphGeneralMaxMembers) a->kind = kMorphGeneral;
+		if (kernel == COMPVHIP_MORPH_KERNEL_SEPARABLE && a->kind == kMorphGeneral)
+			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "the separable kernel serves full rectangles and crosses only");
+	}
+	else return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "kernel selector");
+	a->sw = static_cast<int>(sw); a->sh = static_cast<int>(sh); a->replicate = border == COMPVHIP_BORDER_REPLICATE;
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_morph_ex(compvhip_plan* p, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op, int border, int kernel, uint8_t* d_out,
+                           void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	MorphArgs a;
+	int rc = morphPrepare(ctx, p->W, p->H, strel, sw, sh, op, border, kernel, &a);
+	if (rc) return rc;
+	if (planeOverlap(p, d_in, d_out)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap"); // compv_math_morph.cxx:140-145 reallocates
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const bool two = op == COMPVHIP_MORPH_OP_OPEN || op == COMPVHIP_MORPH_OP_CLOSE;
+	if (two && !p->morphTmp) HIPCHK(ctx, dmalloc(ctx, &p->morphTmp, p->S * p->H * p->frames));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	a.frameStride = p->S * p->H; a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
+	const int nf = static_cast<int>(p->frames);
+	static const char* const names[3] = { "morph_general_kernel", "morph_separable_kernel<rect>", "morph_separable_kernel<cross>" };
+	// OPEN = erode then dilate, CLOSE = dilate then erode (compv_math_morph.cxx:104-111): two complete basic operations, borders included
+	a.in = d_in; a.out = two ? p->morphTmp : d_out; a.dilate = op == COMPVHIP_MORPH_OP_DILATE || op == COMPVHIP_MORPH_OP_CLOSE;
+	{ Stamp s(p, st, names[a.kind]); HIPCHK(ctx, launch_morph(a, nf, st)); }
+	if (two) {
+		a.in = p->morphTmp; a.out = d_out; a.dilate = !a.dilate;
+		Stamp s(p, st, names[a.kind]); HIPCHK(ctx, launch_morph(a, nf, st));
+	}
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_morph(compvhip_plan* p, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op, int border, uint8_t* d_out, void* stream)
+{
+	return compvhip_plan_morph_ex(p, d_in, strel, sw, sh, op, border, COMPVHIP_MORPH_KERNEL_AUTO, d_out, stream);
+}
+
 // ---- host entry points -------------------------------------------------------------------------------------------
 static int hostPlan(compvhip_ctx* ctx, size_t W, size_t H, float thetaDeg, compvhip_plan** out)
 {
@@ -2099,6 +2260,54 @@ int compvhip_components_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, si
 	if (ncopy) HIPCHK(ctx, hipMemcpy(comps, ctx->dComps, ncopy * sizeof(compvhip_component), hipMemcpyDeviceToHost));
 	if (static_cast<size_t>(found) > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "component buffer too small");
 	return COMPVHIP_OK;
+}
+
+// thresholding / morphology on one host frame: upload, run the plan call on the cached single-frame plan, download
+static int hostPlaneOp(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint8_t* out, size_t So, const std::function<int(compvhip_plan*)>& run)
+{
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_plan* p = ctx->hostPlan;
+	int rc = hostPlan(ctx, W, H, (p && p->W == W && p->H == H) ? p->thetaDeg : 1.f, &p);   // any theta serves: keep the cached plan when it fits
+	if (rc) return rc;
+	HIPCHK(ctx, hipMemcpy2DAsync(ctx->dIn, p->S, in, S, W, H, hipMemcpyHostToDevice, ctx->stream));
+	rc = run(p);
+	if (rc) return rc;
+	HIPCHK(ctx, hipMemcpy2DAsync(out, So, ctx->dOut, p->S, W, H, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return COMPVHIP_OK;
+}
+
+int compvhip_threshold_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double threshold, uint8_t* out, size_t So)
+{
+	int rc = checkImage(ctx, in, W, H, S, out, So);
+	if (rc) return rc;
+	if (!(threshold >= 0.0)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "threshold < 0"); // compv_image_threshold.cxx:120
+	return hostPlaneOp(ctx, in, W, H, S, out, So, [&](compvhip_plan* p) { return compvhip_plan_threshold(p, ctx->dIn, threshold, nullptr, ctx->dOut, ctx->stream); });
+}
+
+int compvhip_threshold_adaptive_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, size_t blockSize, double delta, double maxVal, int invert,
+                                   uint8_t* out, size_t So)
+{
+	int rc = checkImage(ctx, in, W, H, S, out, So);
+	if (rc) return rc;
+	rc = checkAdaptive(ctx, W, H, blockSize, delta, maxVal);
+	if (rc) return rc;
+	return hostPlaneOp(ctx, in, W, H, S, out, So,
+	                   [&](compvhip_plan* p) { return compvhip_plan_threshold_adaptive(p, ctx->dIn, blockSize, delta, maxVal, invert, ctx->dOut, ctx->stream); });
+}
+
+int compvhip_morph_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint8_t* strel, size_t sw, size_t sh, int op, int border, uint8_t* out,
+                      size_t So)
+{
+	int rc = checkImage(ctx, in, W, H, S, out, So);
+	if (rc) return rc;
+	MorphArgs a;
+	rc = morphPrepare(ctx, W, H, strel, sw, sh, op, border, COMPVHIP_MORPH_KERNEL_AUTO, &a);
+	if (rc) return rc;
+	// the host planes overlap when their byte ranges do (compv_math_morph.cxx:140-145: the reference reallocates; here the caller is told)
+	const uint8_t* inEnd = in + (H - 1) * S + W; const uint8_t* outEnd = out + (H - 1) * So + W;
+	if (in < outEnd && out < inEnd) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap");
+	return hostPlaneOp(ctx, in, W, H, S, out, So, [&](compvhip_plan* p) { return compvhip_plan_morph(p, ctx->dIn, strel, sw, sh, op, border, ctx->dOut, ctx->stream); });
 }
 
 // ---- KHT -----------------------------------------------------------------------------------------------------------------------

@@ -257,4 +257,40 @@ struct CompArgs {
 // non-root pixels), label map roots + background
 hipError_t launch_components(const CompArgs& a, int frames, int phase, hipStream_t stream);
 
+// ---- thresholding and morphology (morph_kernels.hip) --------------------------------------------------------------------------------
+struct ThreshArgs {
+	const uint8_t* in;        // [frames][H][S]; may be `out`
+	uint8_t* out;
+	const int32_t* levels;    // per-frame level (device; clipped to 0..255) or nullptr: t8 for every frame
+	size_t frameStride;
+	int W, H, S;
+	int t8;
+};
+hipError_t launch_threshold(const ThreshArgs& a, int frames, hipStream_t stream);
+struct AdaptArgs {
+	const uint8_t* in;        // [frames][H][S]; must not overlap `out` (a tile reads the halo its neighbours write)
+	uint8_t* out;
+	size_t frameStride;
+	int W, H, S;
+	int r;                    // blockSize / 2: 1..15
+	uint32_t k;               // the Q16 tap of the mean kernel
+	int delta, maxVal, invert;
+};
+hipError_t launch_threshold_adaptive(const AdaptArgs& a, int frames, hipStream_t stream);
+constexpr int kMorphMaxStrel = 31;
+constexpr size_t kMorphGeneralMaxMembers = 15;   // compvhip_plan_morph sends a rectangle / cross of at most this many members to the general kernel
+enum { kMorphGeneral = 0, kMorphRect = 1, kMorphCross = 2 };   // kernel of one basic operation
+struct MorphArgs {
+	const uint8_t* in;        // [frames][H][S]; must not overlap `out`
+	uint8_t* out;
+	size_t frameStride;
+	int W, H, S;
+	int sw, sh;               // odd, 1..31
+	int dilate;               // max (else min)
+	int replicate;            // border cells take in(y, x) (else 0)
+	int kind;                 // kMorphGeneral: rows[] is read; kMorphRect / kMorphCross: sw and sh say it all
+	uint32_t rows[kMorphMaxStrel];   // bit i of rows[j]: (j, i) is a member
+};
+hipError_t launch_morph(const MorphArgs& a, int frames, hipStream_t stream);
+
 } // namespace compvhip

@@ -495,6 +495,83 @@ COMPVHIP_API int compvhip_plan_components(compvhip_plan* plan, const uint8_t* d_
 COMPVHIP_API int compvhip_components_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, int connectivity, int minPixels,
                                         int32_t* labels, size_t labelStride, compvhip_component* comps, size_t cap, size_t* nComps);
 
+/* ---- thresholding and morphology: from a gray frame to text blobs (docs/kernels/morph.md) --------------------------------------
+ * The step between the pre-processing (grayscale, Otsu, blur) and compvhip_plan_components: binarise, close the gaps between glyph strokes,
+ * label.  All arithmetic is integer; every result is defined bit for bit.  The plan forms are asynchronous on `stream` and work on
+ * [frames][H][S] device planes; the host forms are synchronous (3 <= W, H <= 32767 like every host entry point). */
+enum { /* COMPV_MATH_MORPH_OP_TYPE_* (compv_common.h:410-419); the reference compiles its gradient out (compv_math_morph.cxx:112-117) */
+	COMPVHIP_MORPH_OP_ERODE = 0,
+	COMPVHIP_MORPH_OP_DILATE = 1,
+	COMPVHIP_MORPH_OP_OPEN = 2,     /* erode, then dilate */
+	COMPVHIP_MORPH_OP_CLOSE = 3     /* dilate, then erode */
+};
+enum { /* COMPV_MATH_MORPH_STREL_TYPE_* (compv_common.h:402-406) */
+	COMPVHIP_MORPH_STREL_RECT = 0,
+	COMPVHIP_MORPH_STREL_DIAMOND = 1,
+	COMPVHIP_MORPH_STREL_CROSS = 2
+};
+enum { /* COMPV_BORDER_TYPE_* (compv_common.h:306-310); _IGNORE (1) is internal to the reference's threading */
+	COMPVHIP_BORDER_ZERO = 0,
+	COMPVHIP_BORDER_REPLICATE = 2   /* CompVMathMorph::process's default */
+};
+enum { /* kernel of compvhip_plan_morph_ex */
+	COMPVHIP_MORPH_KERNEL_AUTO = 0,      /* what compvhip_plan_morph takes: separable for a full rectangle or a cross of more than 15 members, general otherwise */
+	COMPVHIP_MORPH_KERNEL_GENERAL = 1,   /* the member-list kernel, whatever the shape */
+	COMPVHIP_MORPH_KERNEL_SEPARABLE = 2  /* full rectangles and crosses only (anything else: COMPVHIP_E_INVALID_PARAMETER) */
+};
+
+/* CompVImageThreshold::global (base/image/compv_image_threshold.cxx:118-180, leaf :320-347): out = in > t8 ? 0xff : 0 with
+ * t8 = (uint8_t)(clip(threshold, 0, 255) + 0.5).  threshold < 0: COMPVHIP_E_INVALID_PARAMETER (:120).  in and out may alias. */
+COMPVHIP_API int compvhip_threshold_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double threshold,
+                                       uint8_t* out, size_t So);
+/* The same on `frames` device frames.  d_levels != NULL: frame f is cut at d_levels[f] clipped to 0..255 and `threshold` is ignored --
+ * the array compvhip_plan_otsu writes, so Otsu + binarise is CompVImage::thresholdOtsu(input, t, &output) (compv_image_threshold.cxx:110-113)
+ * without a host round trip.  d_in and d_out may be the same buffer.  Columns >= W of d_out are never written. */
+COMPVHIP_API int compvhip_plan_threshold(compvhip_plan* plan, const uint8_t* d_in, double threshold, const int32_t* d_levels,
+                                         uint8_t* d_out, void* stream);
+
+/* CompVImageThreshold::adaptive (base/image/compv_image_threshold.cxx:183-317) as its single-threaded path computes it:
+ *   k    = (uint16_t)((1.f / (float)blockSize) * 0xffff)                         CompVKernel::mean, base/compv_kernel.cxx:12-25
+ *   mean = compvhip_convlt1_fixedpoint_u8 with blockSize taps k, vertical and horizontal (zero border of blockSize / 2 included)
+ *   d = (int)(clip(delta, 0, 255) + 0.5), m = (uint8_t)(clip(maxVal, 0, 255) + 0.5)
+ *   hit = (in - mean + 255) >= (256 - d)                                         the 768-entry LUT of :222-226,287
+ *   out = (hit != invert) ? m : 0
+ * On the border mean is 0 and the formula decides there as everywhere else.  blockSize even or < 3, W or H < blockSize, maxVal < 0:
+ * COMPVHIP_E_INVALID_PARAMETER; odd blockSize > 31: COMPVHIP_E_NOT_IMPLEMENTED.  in and out may alias. */
+COMPVHIP_API int compvhip_threshold_adaptive_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, size_t blockSize,
+                                                double delta, double maxVal, int invert, uint8_t* out, size_t So);
+/* The same on `frames` device frames, one fused kernel: the mean never reaches memory.  d_in == d_out is served through a plane the plan owns
+ * (allocated on first use) and a device copy; any other overlap: COMPVHIP_E_INVALID_PARAMETER.  Columns >= W of d_out are never written. */
+COMPVHIP_API int compvhip_plan_threshold_adaptive(compvhip_plan* plan, const uint8_t* d_in, size_t blockSize, double delta, double maxVal,
+                                                  int invert, uint8_t* d_out, void* stream);
+
+/* CompVMathMorph::buildStructuringElement (base/math/compv_math_morph.cxx:89-93,476-540): strel = h rows of w bytes, 0xff marks a member.
+ * RECT: all; CROSS: row h / 2 and column w / 2; DIAMOND (w == h, else COMPVHIP_E_INVALID_PARAMETER): 1, 3, 5, ... members centred on column
+ * w / 2 down to the middle row, then back.  w or h == 0: COMPVHIP_E_INVALID_PARAMETER; unknown type: COMPVHIP_E_NOT_IMPLEMENTED.  Host
+ * arithmetic only; no GPU involved. */
+COMPVHIP_API int compvhip_morph_strel(int type, size_t w, size_t h, uint8_t* strel);
+
+/* CompVMathMorph::process (base/math/compv_math_morph.cxx:95-123; basicOper :125-247, borders :542-674, leaf :676-692).
+ * strel: sh rows of sw bytes, non-zero = member; sw, sh odd, 1..31 (even or larger: COMPVHIP_E_NOT_IMPLEMENTED); all zero, W < sw or
+ * H < sh: COMPVHIP_E_INVALID_PARAMETER.  One basic operation, with wd = sw >> 1, hd = sh >> 1, hb = (sh + 1) >> 1:
+ *   interior   wd <= x < W - wd, hd <= y < H - hd:  out(y, x) = OP over the members (j, i) of in(y - hd + j, x - wd + i), OP = min (erode) or
+ *              max (dilate) -- the same offsets for both: dilation does NOT reflect the strel
+ *   borders    afterwards, rows y < hb and y >= H - hb, then columns x < wd and x >= W - wd, take in(y, x) (REPLICATE) or 0 (ZERO).  The
+ *              row border is hb rows, one more than the interior leaves open (addBordersVt, :552): with sh = 3 rows 1 and H - 2 are
+ *              overwritten although they were computed, with sh = 1 the first and last rows are copied.
+ * OPEN / CLOSE are two complete basic operations, borders included.  in and out must not overlap (COMPVHIP_E_INVALID_PARAMETER; the
+ * reference reallocates, :140-145).  Other op / border values: COMPVHIP_E_NOT_IMPLEMENTED. */
+COMPVHIP_API int compvhip_morph_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint8_t* strel, size_t sw,
+                                   size_t sh, int op, int border, uint8_t* out, size_t So);
+/* The same on `frames` device frames (strel is a HOST array).  An OPEN / CLOSE is two launches through a u8 plane [frames][H][S] the plan owns
+ * (allocated on first use).  Columns >= W of d_out are never written. */
+COMPVHIP_API int compvhip_plan_morph(compvhip_plan* plan, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op,
+                                     int border, uint8_t* d_out, void* stream);
+/* compvhip_plan_morph with the kernel named (COMPVHIP_MORPH_KERNEL_*): for measuring one kernel against the other and for testing both on
+ * the same structuring element.  The result does not depend on it. */
+COMPVHIP_API int compvhip_plan_morph_ex(compvhip_plan* plan, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op,
+                                        int border, int kernel, uint8_t* d_out, void* stream);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel
