@@ -31,6 +31,7 @@ MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 STREL_RECT, STREL_DIAMOND, STREL_CROSS = 0, 1, 2
 BORDER_ZERO, BORDER_REPLICATE = 0, 2
 MORPH_KERNEL_AUTO, MORPH_KERNEL_GENERAL, MORPH_KERNEL_SEPARABLE = 0, 1, 2
+CORNER_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("strength", "<i4")])   # compvhip_corner
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -50,6 +51,7 @@ EXPORTS = [
     "compvhip_plan_components", "compvhip_components_u8",
     "compvhip_threshold_u8", "compvhip_plan_threshold", "compvhip_threshold_adaptive_u8", "compvhip_plan_threshold_adaptive",
     "compvhip_morph_strel", "compvhip_morph_u8", "compvhip_plan_morph", "compvhip_plan_morph_ex",
+    "compvhip_plan_fast", "compvhip_fast_u8",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -197,6 +199,8 @@ def load():
     L.compvhip_morph_u8.argtypes = [vp, vp, sz, sz, sz, vp, sz, sz, i32, i32, vp, sz]
     L.compvhip_plan_morph.argtypes = [vp, vp, vp, sz, sz, i32, i32, vp, vp]
     L.compvhip_plan_morph_ex.argtypes = [vp, vp, vp, sz, sz, i32, i32, i32, vp, vp]
+    L.compvhip_plan_fast.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, sz, vp, vp]
+    L.compvhip_fast_u8.argtypes = [vp, vp, sz, sz, sz, i32, i32, i32, i32, vp, sz, vp, sz, C.POINTER(sz)]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -383,6 +387,22 @@ class Context:
         self._chk(self.lib.compvhip_morph_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(strel), strel.shape[1], strel.shape[0], op, border, _ptr(out), W))
         return out
 
+    def fast(self, img, threshold=20, fast_type=9, nonmax=True, max_features=-1, want_scores=False, cap=4096):
+        """compvhip_fast_u8 (CompVCornerDeteFAST::process): -> corners (CORNER_DTYPE, raster order) [, score map].  The call is repeated with a
+        larger buffer when `cap` was too small."""
+        H, W = img.shape
+        scores = np.empty((H, W), np.uint8) if want_scores else None
+        n = C.c_size_t(0)
+        while True:
+            rec = np.zeros(cap, CORNER_DTYPE)
+            rc = self.lib.compvhip_fast_u8(self.h, _ptr(img), W, H, img.strides[0], threshold, fast_type, int(bool(nonmax)), max_features,
+                                           _ptr(scores) if want_scores else None, W, _ptr(rec) if cap else None, cap, C.byref(n))
+            if rc != E_OUT_OF_BOUND:
+                break
+            cap = n.value
+        self._chk(rc)
+        return (rec[:n.value], scores) if want_scores else rec[:n.value]
+
     def houghkht(self, edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, order="reference"):
         """Returns (lines, GS); lines['row'] / ['col'] hold the rho / theta indices.  order: "reference" (compvhip_houghkht_u8: the reference's tie
         order) or "canonical" (compvhip_houghkht_ex_u8: count descending, ties by emission key, peaks found and sorted on the GPU)."""
@@ -503,6 +523,11 @@ class Plan:
             self.ctx._chk(self.lib.compvhip_plan_morph(self.h, d_in, _ptr(strel), sw, sh, op, border, d_out, stream))
         else:
             self.ctx._chk(self.lib.compvhip_plan_morph_ex(self.h, d_in, _ptr(strel), sw, sh, op, border, kernel, d_out, stream))
+
+    def fast(self, d_gray, threshold, fast_type, nonmax, max_features, d_scores, d_corners, corner_cap, d_counts, stream=0):
+        """compvhip_plan_fast: d_scores = 0 for no score map, d_corners = 0 with corner_cap = 0 for counts only."""
+        self.ctx._chk(self.lib.compvhip_plan_fast(self.h, d_gray, threshold, fast_type, int(bool(nonmax)), max_features, d_scores or None,
+                                                  d_corners or None, corner_cap, d_counts, stream))
 
     def pipeline(self, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap, d_counts, stream=0):
         self.ctx._chk(self.lib.compvhip_plan_pipeline(self.h, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap,

@@ -123,6 +123,8 @@ struct compvhip_ctx {
 	int32_t* dCompLabels = nullptr; size_t dCompLabelsCap = 0;    // staging of compvhip_components_u8: the label map (W * H) ...
 	compvhip_component* dComps = nullptr; size_t dCompsCap = 0;   // ... the records ...
 	int32_t* dCompCount = nullptr;                                 // ... and their number
+	compvhip_corner* dFastCorners = nullptr; size_t dFastCornersCap = 0;   // staging of compvhip_fast_u8: the records (the score map travels through dOut) ...
+	int32_t* dFastCount = nullptr;                                         // ... and their number
 	KhtScratch kht;                    // KHT scratch of the host entry point (compvhip_houghkht_u8)
 };
 
@@ -187,6 +189,9 @@ struct compvhip_plan {
 	// [frames][H][wb]; parent words [frames][H][W] of the calls without a label map (with one, the parent words live in it)
 	int32_t* compRows = nullptr; uint32_t* compBits = nullptr; int32_t* compParent = nullptr;
 	uint8_t* morphTmp = nullptr;                 // thresholding / morphology (morph_kernels.hip), allocated on first use: the u8 plane [frames][H][S] between the two basic operations of an OPEN / CLOSE, and the out-of-place target of an in-place adaptive threshold
+	// FAST corners (fast_kernels.hip), allocated on first use: [frames][H] corners per row, [frames][H] their scan, [frames][256] score histogram, [frames] cut
+	// level -- one allocation; and the score map [frames][H][S] of the calls that do not want one
+	int* fastWork = nullptr; uint8_t* fastScores = nullptr;
 	int strengthBits = 16, keyBits = 0;
 	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
 	uint16_t* chunkHist = nullptr; uint32_t* strengthStart = nullptr; int sortChunks = 0; bool deviceSort = false;
@@ -913,6 +918,7 @@ void compvhip_ctx_destroy(compvhip_ctx* ctx)
 	dfree(ctx, ctx->dSegLines); dfree(ctx, ctx->dSegs); dfree(ctx, ctx->dSegCount);
 	dfree(ctx, ctx->dFits); dfree(ctx, ctx->dFitCount); dfree(ctx, ctx->dFitRefined);
 	dfree(ctx, ctx->dCompLabels); dfree(ctx, ctx->dComps); dfree(ctx, ctx->dCompCount);
+	dfree(ctx, ctx->dFastCorners); dfree(ctx, ctx->dFastCount);
 	khtScratchFree(ctx, ctx->kht);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
@@ -1056,6 +1062,7 @@ void compvhip_plan_destroy(compvhip_plan* p)
 	if (p->hRounds) (void)hipHostFree(p->hRounds);
 	dfree(ctx, p->hist); dfree(ctx, p->otsu); dfree(ctx, p->blurTmp); dfree(ctx, p->grayTmp);
 	dfree(ctx, p->morphTmp);
+	dfree(ctx, p->fastWork); dfree(ctx, p->fastScores);
 	for (KhtBatchState* b : p->khtBatch) khtBatchFree(ctx, b);
 	p->khtBatch.clear();
 	dfree(ctx, p->cosT); dfree(ctx, p->invSinT);
@@ -1865,6 +1872,43 @@ int compvhip_plan_morph(compvhip_plan* p, const uint8_t* d_in, const uint8_t* st
 	return compvhip_plan_morph_ex(p, d_in, strel, sw, sh, op, border, COMPVHIP_MORPH_KERNEL_AUTO, d_out, stream);
 }
 
+// ---- FAST corners (fast_kernels.hip; definition in include/compv_hip.h) ------------------------------------------------------------------
+static int checkFast(compvhip_ctx* ctx, size_t W, size_t H, int fastType)
+{
+	if (W < 7 || H < 7) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "FAST needs W, H >= 7 (one interior pixel)");
+	if (fastType != 9 && fastType != 12) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "fastType must be 9 or 12"); // compv_core_feature_fast_dete.cxx:146
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_fast(compvhip_plan* p, const uint8_t* d_gray, int threshold, int fastType, int nonmax, int maxFeatures, uint8_t* d_scores,
+                       compvhip_corner* d_corners, size_t cornerCap, int32_t* d_counts, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_gray || !d_counts || (cornerCap && !d_corners)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame / count / corner pointer");
+	int rc = checkFast(ctx, p->W, p->H, fastType);
+	if (rc) return rc;
+	if ((reinterpret_cast<uintptr_t>(d_gray) & 7) || (reinterpret_cast<uintptr_t>(d_scores) & 7)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames must be 8-byte aligned");
+	if ((reinterpret_cast<uintptr_t>(d_corners) & 3) || (reinterpret_cast<uintptr_t>(d_counts) & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "records and counts must be 4-byte aligned");
+	if (d_scores && planeOverlap(p, d_gray, d_scores)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frame and score map must not overlap");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t F = p->frames, H = p->H, work = F * (2 * H + 257);
+	if (!p->fastWork) HIPCHK(ctx, dmalloc(ctx, &p->fastWork, work));
+	if (!d_scores && !p->fastScores) HIPCHK(ctx, dmalloc(ctx, &p->fastScores, p->S * H * F));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	FastArgs a;
+	a.in = d_gray; a.scores = d_scores ? d_scores : p->fastScores; a.frameStride = p->S * H;
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(H); a.S = static_cast<int>(p->S);
+	a.t = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold); a.N = fastType; a.nonmax = nonmax != 0; a.maxFeatures = maxFeatures;   // :135
+	a.rowCounts = p->fastWork; a.hist = a.rowCounts + F * H; a.minScore = a.hist + F * 256; a.rowOffsets = a.minScore + F;
+	a.corners = d_corners; a.cornerCap = cornerCap; a.counts = d_counts;
+	HIPCHK(ctx, hipMemsetAsync(a.rowCounts, 0, F * (H + 256) * sizeof(int), st));   // the row counts and the histogram are sums
+	{ Stamp s(p, st, "fast_score_kernel"); HIPCHK(ctx, launch_fast(a, static_cast<int>(F), 0, st)); }
+	{ Stamp s(p, st, "fast_list_kernels"); HIPCHK(ctx, launch_fast(a, static_cast<int>(F), 1, st)); }   // cut level, row recount, scan, emit
+	return COMPVHIP_OK;
+}
+
 // ---- host entry points -------------------------------------------------------------------------------------------
 static int hostPlan(compvhip_ctx* ctx, size_t W, size_t H, float thetaDeg, compvhip_plan** out)
 {
@@ -2259,6 +2303,35 @@ int compvhip_components_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, si
 	const size_t ncopy = std::min(static_cast<size_t>(found), cap);
 	if (ncopy) HIPCHK(ctx, hipMemcpy(comps, ctx->dComps, ncopy * sizeof(compvhip_component), hipMemcpyDeviceToHost));
 	if (static_cast<size_t>(found) > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "component buffer too small");
+	return COMPVHIP_OK;
+}
+
+int compvhip_fast_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, int threshold, int fastType, int nonmax, int maxFeatures, uint8_t* scores,
+                     size_t So, compvhip_corner* corners, size_t cap, size_t* n)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!gray || !n || (cap && !corners) || S < W || (scores && So < W)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	*n = 0;
+	int rc = checkFast(ctx, W, H, fastType);
+	if (rc) return rc;
+	if (W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (7..32767)");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_plan* p = ctx->hostPlan;
+	rc = hostPlan(ctx, W, H, (p && p->W == W && p->H == H) ? p->thetaDeg : 1.f, &p);   // any theta serves: keep the cached plan when it fits
+	if (rc) return rc;
+	if (ctx->dFastCornersCap < cap) { dfree(ctx, ctx->dFastCorners); ctx->dFastCornersCap = 0; HIPCHK(ctx, dmalloc(ctx, &ctx->dFastCorners, cap)); ctx->dFastCornersCap = cap; }
+	if (!ctx->dFastCount) HIPCHK(ctx, dmalloc(ctx, &ctx->dFastCount, 1));
+	HIPCHK(ctx, hipMemcpy2DAsync(ctx->dIn, p->S, gray, S, W, H, hipMemcpyHostToDevice, ctx->stream));
+	rc = compvhip_plan_fast(p, ctx->dIn, threshold, fastType, nonmax, maxFeatures, scores ? ctx->dOut : nullptr, cap ? ctx->dFastCorners : nullptr, cap, ctx->dFastCount, ctx->stream);
+	if (rc) return rc;
+	int32_t found = 0;
+	HIPCHK(ctx, hipMemcpyAsync(&found, ctx->dFastCount, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	if (scores) HIPCHK(ctx, hipMemcpy2DAsync(scores, So, ctx->dOut, p->S, W, H, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	*n = static_cast<size_t>(found);
+	const size_t ncopy = std::min(static_cast<size_t>(found), cap);
+	if (ncopy) HIPCHK(ctx, hipMemcpy(corners, ctx->dFastCorners, ncopy * sizeof(compvhip_corner), hipMemcpyDeviceToHost));
+	if (static_cast<size_t>(found) > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "corner buffer too small");
 	return COMPVHIP_OK;
 }
 

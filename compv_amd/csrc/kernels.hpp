@@ -293,4 +293,22 @@ struct MorphArgs {
 };
 hipError_t launch_morph(const MorphArgs& a, int frames, hipStream_t stream);
 
+// ---- FAST corners (fast_kernels.hip) ----------------------------------------------------------------------------------------------------
+struct FastArgs {
+	const uint8_t* in;        // [frames][H][S]
+	uint8_t* scores;          // [frames][H][S]: the caller's map or the plan's; must not overlap `in`
+	size_t frameStride;
+	int W, H, S;
+	int t, N, nonmax;         // t in 0..255, N 9 or 12
+	int maxFeatures;          // > 1: cut at the maxFeatures-th largest strength (hist and minScore are used)
+	int* rowCounts;           // [frames][H] corners per row; ZEROED by the caller before the launch
+	int* rowOffsets;          // [frames][H] their exclusive scan
+	int* hist;                // [frames][256] corners per score; ZEROED by the caller before the launch
+	int* minScore;            // [frames] the smallest score of the list
+	compvhip_corner* corners; size_t cornerCap;   // [frames][cornerCap]
+	int32_t* counts;          // [frames] corners before clipping
+};
+// stage 0: score + NMS (score map, row counts, histogram); stage 1: [cut level -> row recount ->] scan -> emit
+hipError_t launch_fast(const FastArgs& a, int frames, int stage, hipStream_t stream);
+
 } // namespace compvhip

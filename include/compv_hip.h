@@ -572,6 +572,49 @@ COMPVHIP_API int compvhip_plan_morph(compvhip_plan* plan, const uint8_t* d_in, c
 COMPVHIP_API int compvhip_plan_morph_ex(compvhip_plan* plan, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op,
                                         int border, int kernel, uint8_t* d_out, void* stream);
 
+/* ---- FAST corner detection (docs/kernels/fast.md) -------------------------------------------------------------------------------------
+ * CompVCornerDeteFAST (core/features/fast/compv_core_feature_fast_dete.cxx; COMPV_FAST_ID) on device frames: scores, non-maximum
+ * suppression and the corner list, every output defined bit for bit.  For a gray frame I of W x H, threshold t (clipped to 0..255 as the
+ * reference's set() does, :135) and N = 9 or 12 (fastType; anything else: COMPVHIP_E_INVALID_PARAMETER, :146):
+ *  1. Ring: 16 offsets (dx, dy) clockwise from the top (:221-238):
+ *     (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3); p_k = I(x + dx_k, y + dy_k).
+ *  2. Limits b = min(255, I + t), d = max(0, I - t); differences D_k = max(0, d - p_k), B_k = max(0, p_k - b).
+ *  3. Score of an interior pixel (3 <= x < W - 3, 3 <= y < H - 3): the max over the 16 arcs of N consecutive ring positions of the min over the
+ *     arc of D_k, and the same for B_k; the larger of the two.  0 when no arc is entirely darker or entirely brighter.  Every other pixel
+ *     scores 0.  (The early exits of CompVFastDataRow_C, :679-688, :729, :748, are necessary conditions and do not change the value.)
+ *  4. NMS (nonmax != 0; :773-831): a pixel with score s > 0 is dropped when any of its 8 neighbours has a score >= s.  All comparisons use the
+ *     scores before suppression; two equal neighbours both go.
+ *  5. Record {x, y, strength}: strength = score + t - 1 as an exact integer (<= 254; :498,:521).  At t == 0 the reference's own code paths
+ *     disagree (one wraps a byte); the integer formula holds here.
+ *  6. Order: raster (y, then x), the reference's single-threaded order.
+ *  7. maxFeatures > 1 and more corners than that: with s* the maxFeatures-th largest strength of the frame, every corner with strength >= s*
+ *     stays, in raster order -- ties at the cut all stay, so the count may exceed maxFeatures.  (The reference's selectBest,
+ *     compv_common.h:641-656, reads an nth_element pivot the standard leaves unspecified; its result lies between the corners above s* and
+ *     this set.)  maxFeatures <= 1: no cut.
+ *  8. Counts and capacity, as compvhip_plan_components: d_counts[f] = corners of frame f BEFORE clipping to cornerCap; the first
+ *     min(count, cornerCap) records of frame f are written at d_corners + f * cornerCap and nothing behind them, so a clipped result is a
+ *     prefix of the full one.  Frames are independent.
+ *  9. Score map (optional): uint8 [frames][H][S]; the scores after NMS when NMS is on, untouched by the maxFeatures cut; border pixels
+ *     hold 0; columns >= W are never written.
+ * W or H < 7 (no interior pixel): COMPVHIP_E_INVALID_PARAMETER (the reference accepts 4..6, where its row length underflows). */
+typedef struct compvhip_corner {
+	int32_t x, y;
+	int32_t strength;           /* score + t - 1 */
+} compvhip_corner;
+
+/* Corners of all frames of the plan.  d_gray: [frames][H][S]; d_scores: NULL or a score map of the same geometry (8-byte aligned, must not
+ * overlap d_gray); d_corners and d_counts: 4-byte aligned (anything else: COMPVHIP_E_INVALID_PARAMETER); d_corners == NULL with cornerCap == 0: counts only.  Asynchronous on `stream`; results are deterministic run to run.  Scratch
+ * is owned by the plan, allocated on first use and released with it: frames * (2 * H + 257) int32, and -- only when d_scores == NULL -- a score
+ * map of the plan's own. */
+COMPVHIP_API int compvhip_plan_fast(compvhip_plan* plan, const uint8_t* d_gray, int threshold, int fastType, int nonmax, int maxFeatures,
+                                    uint8_t* d_scores, compvhip_corner* d_corners, size_t cornerCap, int32_t* d_counts, void* stream);
+
+/* The same for one HOST frame (7 <= W, H <= 32767).  Synchronous, on the context's cached single-frame plan.  scores: optional, H rows of So
+ * bytes (So >= W).  *n receives the number of corners; when it exceeds cap only the first cap records are written and COMPVHIP_E_OUT_OF_BOUND
+ * is returned (cap == 0 with corners == NULL asks for the number; the score map is complete either way). */
+COMPVHIP_API int compvhip_fast_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, int threshold, int fastType, int nonmax,
+                                  int maxFeatures, uint8_t* scores, size_t So, compvhip_corner* corners, size_t cap, size_t* n);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel

@@ -1,6 +1,7 @@
 // compv_hip_plugin.cxx -- the reference-side binding: CompV C++ classes that implement CompV's own abstract
-// CompVEdgeDete / CompVHough interfaces on top of the C ABI in include/compv_hip.h, and the factory table that
-// re-registers the ids COMPV_CANNY_ID / COMPV_SOBEL_ID / COMPV_SCHARR_ID / COMPV_PREWITT_ID / COMPV_HOUGHSHT_ID / COMPV_HOUGHKHT_ID.
+// CompVEdgeDete / CompVHough / CompVCornerDete interfaces on top of the C ABI in include/compv_hip.h, and the factory table that
+// re-registers the ids COMPV_CANNY_ID / COMPV_SOBEL_ID / COMPV_SCHARR_ID / COMPV_PREWITT_ID / COMPV_HOUGHSHT_ID / COMPV_HOUGHKHT_ID /
+// COMPV_FAST_ID.
 //
 // CompVFeature::addFactory() REPLACES an existing id (base/compv_features.cxx:30-40), so after
 //     CompVInit(); compv_hip_plugin_register();
@@ -76,12 +77,14 @@ private:
 
 // ---- options ---------------------------------------------------------------------------------------------------
 // What a set(id, ptr, size) call may change, as data.  `kind` fixes the value size the reference insists on; a value is accepted when
-// v > 0 (FLT_POS, INT_POS), 0 < v <= hi (FLT_RANGE), v >= 0 (FLT_NONNEG), v in `allowed` (INT_ENUM2), anything (FLT_ANY / INT_ANY / BOOL_ANY).
-enum OptKind { FLT_POS, FLT_RANGE, FLT_NONNEG, FLT_ANY, INT_POS, INT_ANY, INT_ENUM2, BOOL_ANY };
+// v > 0 (FLT_POS, INT_POS), 0 < v <= hi (FLT_RANGE), v >= 0 (FLT_NONNEG), v in `allowed` (INT_ENUM2), anything (FLT_ANY / INT_ANY / BOOL_ANY; BOOL_STORE
+// keeps the value, as an int).
+enum OptKind { FLT_POS, FLT_RANGE, FLT_NONNEG, FLT_ANY, INT_POS, INT_ANY, INT_ENUM2, BOOL_ANY, BOOL_STORE };
 struct Settings { // every tunable of the four detector families; a family only lists the ones it accepts
 	float cannyLow, cannyHigh; int cannyType; int kernelSize;
 	float rho, thetaDeg; int threshold; int maxLines;          // maxLines <= 0: unlimited
 	float clusterMinDeviation; int clusterMinSize; float kernelMinHeight;
+	int fastThreshold, fastType, fastMaxFeatures, fastNonMax;
 };
 struct OptSpec { int id; OptKind kind; size_t offset; float hi; int allowed[2]; };
 #define OPT_AT(member) offsetof(Settings, member)
@@ -94,6 +97,12 @@ static COMPV_ERROR_CODE applyOption(const OptSpec* table, size_t count, Settings
 		if (o.id != id) continue;
 		char* dst = reinterpret_cast<char*>(&st) + o.offset;
 		if (o.kind == BOOL_ANY) return size == sizeof(bool) ? COMPV_ERROR_CODE_S_OK : COMPV_ERROR_CODE_E_INVALID_PARAMETER; // nothing to store
+		if (o.kind == BOOL_STORE) {
+			if (size != sizeof(bool)) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+			const int v = *reinterpret_cast<const bool*>(value) ? 1 : 0;
+			memcpy(dst, &v, sizeof(v));
+			return COMPV_ERROR_CODE_S_OK;
+		}
 		if (o.kind == FLT_POS || o.kind == FLT_RANGE || o.kind == FLT_NONNEG || o.kind == FLT_ANY) {
 			float v;
 			if (size != sizeof(v)) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
@@ -138,6 +147,12 @@ static const OptSpec kKhtOptions[] = {
 	{ COMPV_HOUGHKHT_SET_FLT32_KERNEL_MIN_HEIGTH, FLT_NONNEG, OPT_AT(kernelMinHeight), 0.f, { 0, 0 } },        // 0 keeps every kernel
 	{ COMPV_HOUGHKHT_SET_BOOL_OVERRIDE_INPUT_EDGES, BOOL_ANY, 0, 0.f, { 0, 0 } }, // the HIP path always works on its own copy
 };
+static const OptSpec kFastOptions[] = {   // compv_core_feature_fast_dete.cxx:128-160
+	{ COMPV_FAST_SET_INT_THRESHOLD, INT_ANY, OPT_AT(fastThreshold), 0.f, { 0, 0 } },             // clipped to 0..255 behind the C ABI, as :135
+	{ COMPV_FAST_SET_INT_MAX_FEATURES, INT_ANY, OPT_AT(fastMaxFeatures), 0.f, { 0, 0 } },
+	{ COMPV_FAST_SET_INT_FAST_TYPE, INT_ENUM2, OPT_AT(fastType), 0.f, { COMPV_FAST_TYPE_9, COMPV_FAST_TYPE_12 } },
+	{ COMPV_FAST_SET_BOOL_NON_MAXIMA_SUPP, BOOL_STORE, OPT_AT(fastNonMax), 0.f, { 0, 0 } },
+};
 #define OPT_COUNT(t) (sizeof(t) / sizeof((t)[0]))
 
 static Settings defaults()
@@ -147,6 +162,7 @@ static Settings defaults()
 	s.cannyType = COMPV_CANNY_THRESHOLD_TYPE_COMPARE_TO_GRADIENT; s.kernelSize = 3;
 	s.rho = 1.f; s.thetaDeg = 1.f; s.threshold = 1; s.maxLines = 0;
 	s.clusterMinDeviation = 2.0f; s.clusterMinSize = 10; s.kernelMinHeight = 0.002f; // houghkht.cxx:38-40
+	s.fastThreshold = 20; s.fastType = COMPV_FAST_TYPE_9; s.fastMaxFeatures = 2000; s.fastNonMax = 1; // compv_core_feature_fast_dete.cxx:76-79
 	return s;
 }
 
@@ -398,6 +414,62 @@ private:
 };
 
 // ------------------------------------------------------------------------------------------------------------------
+// FAST corners  (stands in for CompVCornerDeteFAST)
+// ------------------------------------------------------------------------------------------------------------------
+class CompVCornerDeteFastHip : public CompVCornerDete
+{
+public:
+	CompVCornerDeteFastHip() : CompVCornerDete(COMPV_FAST_ID), m_Set(defaults()) { }
+	virtual ~CompVCornerDeteFastHip() { }
+	COMPV_OBJECT_GET_ID(CompVCornerDeteFastHip);
+
+	virtual COMPV_ERROR_CODE set(int id, const void* valuePtr, size_t valueSize) override
+	{
+		return applyOption(kFastOptions, OPT_COUNT(kFastOptions), m_Set, id, valuePtr, valueSize, false, this);
+	}
+
+	// Corners in raster order, the order of the reference on one thread.  With maxFeatures > 1 the list is the canonical cut (every corner at or
+	// above the maxFeatures-th largest strength), of which the reference's selectBest keeps an unspecified subset of the ties.
+	virtual COMPV_ERROR_CODE process(const CompVMatPtr& image, CompVInterestPointVector& interestPoints) override
+	{
+		if (!isGray8(image)) return COMPV_ERROR_CODE_E_INVALID_PARAMETER; // the reference converts packed input to gray first; callers here pass the gray plane
+		compvhip_ctx* ctx = NULL;
+		COMPV_CHECK_CODE_RETURN(m_Ctx.acquire(ctx));
+		interestPoints.clear();
+		if (m_Corners.size() < 4096) m_Corners.resize(4096);
+		const int N = m_Set.fastType == COMPV_FAST_TYPE_12 ? 12 : 9;
+		size_t n = 0;
+		int rc = COMPVHIP_OK;
+		for (int pass = 0; pass < 2; ++pass) {
+			rc = compvhip_fast_u8(ctx, image->ptr<const uint8_t>(), image->cols(), image->rows(), image->stride(), m_Set.fastThreshold, N, m_Set.fastNonMax,
+				m_Set.fastMaxFeatures, NULL, 0, m_Corners.data(), m_Corners.size(), &n);
+			if (rc != COMPVHIP_E_OUT_OF_BOUND) break;
+			m_Corners.resize(n);
+		}
+		if (rc != COMPVHIP_OK) return report(ctx, "compvhip_fast_u8", rc);
+		interestPoints.reserve(n);
+		for (size_t i = 0; i < n; ++i) {
+			interestPoints.push_back(CompVInterestPoint(static_cast<compv_float32_t>(m_Corners[i].x), static_cast<compv_float32_t>(m_Corners[i].y), static_cast<compv_float32_t>(m_Corners[i].strength)));
+		}
+		return COMPV_ERROR_CODE_S_OK;
+	}
+
+	static COMPV_ERROR_CODE newObj(CompVCornerDetePtrPtr dete)
+	{
+		if (!dete) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+		CompVPtr<CompVCornerDeteFastHip*> obj = new CompVCornerDeteFastHip();
+		if (!obj) return COMPV_ERROR_CODE_E_OUT_OF_MEMORY;
+		*dete = *obj;
+		return COMPV_ERROR_CODE_S_OK;
+	}
+
+private:
+	LazyCtx m_Ctx;
+	Settings m_Set;
+	std::vector<compvhip_corner> m_Corners;
+};
+
+// ------------------------------------------------------------------------------------------------------------------
 // factory table (file-static: addFactory stores the POINTER, as core/compv_core.cxx:56-103 relies on for the built-ins)
 // ------------------------------------------------------------------------------------------------------------------
 static const CompVFeatureFactory kHipFactories[] = {
@@ -407,6 +479,7 @@ static const CompVFeatureFactory kHipFactories[] = {
 	{ COMPV_PREWITT_ID, "Prewitt edge detector (HIP/gfx950)", nullptr, nullptr, CompVEdgeDeteBaseHip::newObjOf<COMPV_PREWITT_ID, COMPVHIP_OP_PREWITT>, nullptr, nullptr },
 	{ COMPV_HOUGHSHT_ID, "Hough standard (HIP/gfx950)", nullptr, nullptr, nullptr, CompVHoughShtHip::newObj, nullptr },
 	{ COMPV_HOUGHKHT_ID, "Hough kernel-based (HIP/gfx950)", nullptr, nullptr, nullptr, CompVHoughKhtHip::newObj, nullptr },
+	{ COMPV_FAST_ID, "FAST corner detector (HIP/gfx950)", CompVCornerDeteFastHip::newObj, nullptr, nullptr, nullptr, nullptr },
 };
 
 COMPV_NAMESPACE_END()

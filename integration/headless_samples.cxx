@@ -6,6 +6,7 @@
 // equal strengths is unspecified: unstable std::sort, core/features/hough/compv_core_feature_houghsht.cxx:243-249).
 //
 // usage: headless_samples [W H [frames [cpuThreads]]]      exit code 0 = drop-in parity on every frame
+//        headless_samples --fast-only [W H]                 the FAST corner comparison alone (default 200 x 258), with the median time of five calls each
 // cpuThreads (default 1) is CompVBase::init()'s thread count for the CPU reference run.  The default is the single-threaded
 // path because the reference's multi-threaded gradient is not deterministic: each row band also recomputes |gx|+|gy| for
 // its two overlap rows from gx/gy rows that the neighbouring band may not have written yet
@@ -149,6 +150,39 @@ static COMPV_ERROR_CODE runSamples(size_t W, size_t H, uint32_t seed, Result& r)
 	return COMPV_ERROR_CODE_S_OK;
 }
 
+// FAST corners through the factory (CompVCornerDete::newObj(&dete, COMPV_FAST_ID) + the four set() calls, as the reference's feature samples do) on a
+// 200 x 258 frame with maxFeatures = -1: the point list (x, y, strength) in the order returned.  Blocks with 3-px diagonal stripes and a little noise
+// give corners as well as flat plateaus.
+typedef std::vector<std::tuple<float, float, float> > FastPoints;
+static COMPV_ERROR_CODE runFast(FastPoints& out, double& ms, size_t W = 200, size_t H = 258)
+{
+	CompVMatPtr image;
+	COMPV_CHECK_CODE_RETURN(CompVImage::newObj8u(&image, COMPV_SUBTYPE_PIXELS_Y, W, H));
+	synthFrame(image, 777u);
+	CompVCornerDetePtr dete;
+	COMPV_CHECK_CODE_RETURN(CompVCornerDete::newObj(&dete, COMPV_FAST_ID));
+	COMPV_CHECK_CODE_RETURN(dete->setInt(COMPV_FAST_SET_INT_THRESHOLD, 20));
+	COMPV_CHECK_CODE_RETURN(dete->setInt(COMPV_FAST_SET_INT_FAST_TYPE, COMPV_FAST_TYPE_9));
+	COMPV_CHECK_CODE_RETURN(dete->setInt(COMPV_FAST_SET_INT_MAX_FEATURES, -1));
+	COMPV_CHECK_CODE_RETURN(dete->setBool(COMPV_FAST_SET_BOOL_NON_MAXIMA_SUPP, true));
+	CompVInterestPointVector pts;
+	COMPV_CHECK_CODE_RETURN(dete->process(image, pts));          // the first call allocates (score maps here, context and plan there)
+	double samples[5];          // the median of five further calls
+	for (int i = 0; i < 5; ++i) {
+		const auto t0 = std::chrono::steady_clock::now();
+		COMPV_CHECK_CODE_RETURN(dete->process(image, pts));
+		samples[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	}
+	std::sort(samples, samples + 5);
+	ms = samples[2];
+	out.clear();
+	for (size_t i = 0; i < pts.size(); ++i) out.push_back(std::make_tuple(pts[i].x, pts[i].y, pts[i].strength));
+	int badType = 10;
+	COMPV_CHECK_EXP_RETURN(dete->set(COMPV_FAST_SET_INT_FAST_TYPE, &badType, sizeof(badType)) != COMPV_ERROR_CODE_E_INVALID_PARAMETER, COMPV_ERROR_CODE_E_UNITTEST_FAILED,
+		"a FAST type other than 9 / 12 must give E_INVALID_PARAMETER");
+	return COMPV_ERROR_CODE_S_OK;
+}
+
 // A CONSUMER of the line set: CompVCalibCamera builds its Canny and Hough objects through the same factories
 // (core/calib/compv_core_calib_camera.cxx:1255-1279: SHT, theta = 0.5 deg, maxLines = 60 per pattern line, Canny(1.33, 2.66)) and runs
 // Canny -> SHT -> toCartesian -> line subdivision / grouping -> intersections on a chessboard view (:127-..).  Same application
@@ -277,6 +311,7 @@ static int checkPreproc(size_t W, size_t H, uint32_t seed)
 
 int main(int argc, char** argv)
 {
+	const bool fastOnly = argc > 1 && !strcmp(argv[1], "--fast-only");
 	const size_t W = argc > 2 ? (size_t)atoi(argv[1]) : 1280, H = argc > 2 ? (size_t)atoi(argv[2]) : 720;
 	const int frames = argc > 3 ? atoi(argv[3]) : 2;
 	const int cpuThreads = argc > 4 ? atoi(argv[4]) : 1;
@@ -284,6 +319,18 @@ int main(int argc, char** argv)
 	// CompVInit() of compv_api.h minus GL/camera/drawing (absent on a headless box): base + core
 	if (COMPV_ERROR_CODE_IS_NOK(CompVBase::init(cpuThreads)) || COMPV_ERROR_CODE_IS_NOK(CompVCore::init())) { fprintf(stderr, "CompV init failed\n"); return 2; }
 
+	FastPoints fastCpu, fastHip;
+	double fastCpuMs = 0.0, fastHipMs = 0.0;
+	if (fastOnly) {
+		const size_t fw = argc > 3 ? (size_t)atoi(argv[2]) : 200, fh = argc > 3 ? (size_t)atoi(argv[3]) : 258;
+		if (COMPV_ERROR_CODE_IS_NOK(runFast(fastCpu, fastCpuMs, fw, fh))) { fprintf(stderr, "CPU FAST run failed\n"); return 8; }
+		if (compv_hip_plugin_register() != 0) { fprintf(stderr, "HIP plugin registration failed (no GPU?)\n"); return 4; }
+		if (COMPV_ERROR_CODE_IS_NOK(runFast(fastHip, fastHipMs, fw, fh))) { fprintf(stderr, "HIP FAST run failed\n"); return 9; }
+		printf("fast_corners: %s [%zux%zu, %zu points, HIP %zu | CompV CPU %.2f ms, HIP plugin %.2f ms (incl. H2D/D2H)]\n", (fastCpu == fastHip && !fastCpu.empty()) ? "MATCH" : "DIFF",
+			fw, fh, fastCpu.size(), fastHip.size(), fastCpuMs, fastHipMs);
+		return (fastCpu == fastHip && !fastCpu.empty()) ? 0 : 1;
+	}
+	if (COMPV_ERROR_CODE_IS_NOK(runFast(fastCpu, fastCpuMs))) { fprintf(stderr, "CPU FAST run failed\n"); return 8; }
 	std::vector<Result> cpu(frames), gpu(frames);
 	for (int f = 0; f < frames; ++f) {
 		if (COMPV_ERROR_CODE_IS_NOK(runSamples(W, H, 12345u + f, cpu[f]))) { fprintf(stderr, "CPU run failed\n"); return 3; }
@@ -327,6 +374,9 @@ int main(int argc, char** argv)
 			okE ? "==" : "DIFF", okR ? "==" : "DIFF", calCpu.rawLines, okG ? "==" : "DIFF", calCpu.groupedLines, calCpu.code, calHip.code, calCpu.corners.size() / 2, okC ? "==" : "DIFF");
 		bad += !(okE && okR && okG && okC);
 	}
+	if (COMPV_ERROR_CODE_IS_NOK(runFast(fastHip, fastHipMs))) { fprintf(stderr, "HIP FAST run failed\n"); return 9; }
+	printf("fast_corners: %s [200x258, %zu points, HIP %zu]\n", (fastCpu == fastHip && !fastCpu.empty()) ? "MATCH" : "DIFF", fastCpu.size(), fastHip.size());
+	bad += !(fastCpu == fastHip && !fastCpu.empty());
 	bad += checkPreproc(W, H, 4242u) != 0;
 	printf(bad ? "DROP-IN PARITY FAILED\n" : "DROP-IN PARITY OK\n");
 	return bad ? 1 : 0;
