@@ -32,6 +32,7 @@ STREL_RECT, STREL_DIAMOND, STREL_CROSS = 0, 1, 2
 BORDER_ZERO, BORDER_REPLICATE = 0, 2
 MORPH_KERNEL_AUTO, MORPH_KERNEL_GENERAL, MORPH_KERNEL_SEPARABLE = 0, 1, 2
 CORNER_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("strength", "<i4")])   # compvhip_corner
+MATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imageIdx", "<i4"), ("distance", "<i4")])   # compvhip_match = CompVDMatch
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -52,6 +53,8 @@ EXPORTS = [
     "compvhip_threshold_u8", "compvhip_plan_threshold", "compvhip_threshold_adaptive_u8", "compvhip_plan_threshold_adaptive",
     "compvhip_morph_strel", "compvhip_morph_u8", "compvhip_plan_morph", "compvhip_plan_morph_ex",
     "compvhip_plan_fast", "compvhip_fast_u8",
+    "compvhip_matcher_create", "compvhip_matcher_destroy", "compvhip_matcher_knn", "compvhip_matcher_good", "compvhip_match_hamming_u8",
+    "compvhip_matcher_set_timing", "compvhip_matcher_get_timing",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -107,6 +110,11 @@ def _kht_order(order):
     if order not in KHT_ORDERS:
         raise ValueError("order must be one of %s, not %r" % (sorted(KHT_ORDERS), order))
     return KHT_ORDERS[order]
+
+
+class MatchOpts(C.Structure):
+    """compvhip_match_opts (include/compv_hip.h): ratio <= 0 / maxDistance < 0 / crossCheck == 0 switch a test off"""
+    _fields_ = [("ratio", C.c_double), ("maxDistance", C.c_int), ("crossCheck", C.c_int)]
 
 
 class CompvHipError(RuntimeError):
@@ -201,6 +209,14 @@ def load():
     L.compvhip_plan_morph_ex.argtypes = [vp, vp, vp, sz, sz, i32, i32, i32, vp, vp]
     L.compvhip_plan_fast.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, sz, vp, vp]
     L.compvhip_fast_u8.argtypes = [vp, vp, sz, sz, sz, i32, i32, i32, i32, vp, sz, vp, sz, C.POINTER(sz)]
+    L.compvhip_matcher_create.argtypes = [vp, sz, sz, sz, sz, i32, C.POINTER(vp)]
+    L.compvhip_matcher_destroy.argtypes = [vp]
+    L.compvhip_matcher_destroy.restype = None
+    L.compvhip_matcher_knn.argtypes = [vp, vp, sz, vp, vp, sz, vp, i32, vp, vp]
+    L.compvhip_matcher_good.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, i32, C.POINTER(MatchOpts), vp, sz, vp, vp]
+    L.compvhip_match_hamming_u8.argtypes = [vp, vp, sz, sz, vp, sz, sz, sz, i32, vp, sz, C.POINTER(sz)]
+    L.compvhip_matcher_set_timing.argtypes = [vp, i32]
+    L.compvhip_matcher_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -403,6 +419,21 @@ class Context:
         self._chk(rc)
         return (rec[:n.value], scores) if want_scores else rec[:n.value]
 
+    def match_hamming(self, query, train, knn=2):
+        """compvhip_match_hamming_u8 (CompVMatcherBruteForce::process): query (Q, cols) and train (T, cols) uint8 rows -> (min(knn, T), Q) MATCH_DTYPE
+        records, neighbour r of query q at [r, q], distances ascending.  Among equal distances the records follow the REFERENCE's insertion order
+        (tests/match_model.py: knn_reference; docs/kernels/match.md), not the (distance, train index) order of Matcher.knn: on ties the two calls
+        return different train indices, never different distances."""
+        assert query.dtype == np.uint8 and train.dtype == np.uint8 and query.ndim == 2 and train.ndim == 2 and query.shape[1] == train.shape[1]
+        assert query.strides[1] == 1 and train.strides[1] == 1
+        Q, cols = query.shape
+        T = train.shape[0]
+        out = np.zeros((max(knn, 1), max(Q, 1)), MATCH_DTYPE)
+        rows = C.c_size_t(0)
+        self._chk(self.lib.compvhip_match_hamming_u8(self.h, _ptr(query), Q, query.strides[0], _ptr(train), T, train.strides[0], cols, knn, _ptr(out), out.shape[1],
+                                                     C.byref(rows)))
+        return out[:rows.value, :Q]
+
     def houghkht(self, edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, order="reference"):
         """Returns (lines, GS); lines['row'] / ['col'] hold the rho / theta indices.  order: "reference" (compvhip_houghkht_u8: the reference's tie
         order) or "canonical" (compvhip_houghkht_ex_u8: count descending, ties by emission key, peaks found and sorted on the GPU)."""
@@ -600,6 +631,50 @@ class Plan:
         names = (C.c_char_p * cap)()
         ms = (C.c_float * cap)()
         n = self.lib.compvhip_plan_get_timing(self.h, names, ms, cap)
+        return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
+
+
+class Matcher:
+    """Batched device-resident brute-force Hamming matcher (compvhip_matcher).  Pointers are raw device addresses; 0 stands for NULL."""
+
+    def __init__(self, ctx, desc_bytes, query_cap, train_cap, pairs=1, knn=2):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.compvhip_matcher_create(ctx.h, desc_bytes, query_cap, train_cap, pairs, knn, C.byref(h)))
+        self.h = h
+        self.desc_bytes, self.query_cap, self.train_cap, self.pairs, self.knn_rows = desc_bytes, query_cap, train_cap, pairs, knn
+
+    def close(self):
+        if self.h:
+            self.lib.compvhip_matcher_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def knn(self, d_query, query_stride, d_query_counts, d_train, train_stride, d_train_counts, train_shared, d_matches, stream=0):
+        """compvhip_matcher_knn: d_matches = [pairs][knn][query_cap] MATCH_DTYPE records; d_*_counts = 0: every pair is full."""
+        self.ctx._chk(self.lib.compvhip_matcher_knn(self.h, d_query or None, query_stride, d_query_counts or None, d_train or None, train_stride,
+                                                    d_train_counts or None, int(bool(train_shared)), d_matches or None, stream))
+
+    def good(self, d_matches, d_query, query_stride, d_query_counts, d_train, train_stride, d_train_counts, train_shared, d_good, good_cap, d_good_counts,
+             ratio=0.0, max_distance=-1, cross_check=False, stream=0):
+        """compvhip_matcher_good: the good list of what knn() wrote; d_good = [pairs][good_cap] records (0 with good_cap 0: counts only)."""
+        o = MatchOpts(ratio, max_distance, int(bool(cross_check)))
+        self.ctx._chk(self.lib.compvhip_matcher_good(self.h, d_matches or None, d_query or None, query_stride, d_query_counts or None, d_train or None, train_stride,
+                                                     d_train_counts or None, int(bool(train_shared)), C.byref(o), d_good or None, good_cap, d_good_counts or None, stream))
+
+    def set_timing(self, mode=1):
+        self.ctx._chk(self.lib.compvhip_matcher_set_timing(self.h, int(mode)))
+
+    def get_timing(self, cap=16):
+        names = (C.c_char_p * cap)()
+        ms = (C.c_float * cap)()
+        n = self.lib.compvhip_matcher_get_timing(self.h, names, ms, cap)
         return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
 
 

@@ -129,6 +129,13 @@ struct compvhip_ctx {
 };
 
 struct TimingEntry { const char* name; hipEvent_t a, b; };
+// per-kernel timing of the last call of a plan or a matcher: event pairs around the launches, the events pooled and reused
+struct TimingState {
+	int timing = 0; // plan: 0 off, 1 every kernel, 2 canny_tile + sht_vote, 3 sht_vote only, 4 canny_tile only; matcher: 0 off, 1 every kernel
+	std::vector<hipEvent_t> eventPool;
+	std::vector<TimingEntry> timeline;
+	std::vector<std::string> timingNames; std::vector<float> timingMs;
+};
 
 // one step of the device-resident pipeline: [grayscale ->] Canny -> SHT [-> toCartesian] (compvhip_plan_pipeline{,_async,_ex})
 struct StepParams {
@@ -138,7 +145,7 @@ struct StepParams {
 	uint8_t* d_edges = nullptr; compvhip_line* d_lines = nullptr; size_t lineCap = 0; int32_t* d_counts = nullptr;
 };
 
-struct compvhip_plan {
+struct compvhip_plan : TimingState {
 	compvhip_ctx* ctx = nullptr;
 	size_t W = 0, H = 0, S = 0, frames = 0;
 	float thetaDeg = 1.f;
@@ -208,11 +215,14 @@ struct compvhip_plan {
 	// seq: enqueue order; replay: an EARLIER step of the plan was replayed after this one ran -- its outputs may have been overwritten
 	struct AsyncStep { bool used = false; bool replay = false; uint64_t seq = 0; hipEvent_t done = nullptr; hipStream_t stream = nullptr; StepParams sp; size_t sortN = 0; int rounds = 0; } steps[kAsyncDepth];
 	uint64_t stepSeq = 0;
-	// timing
-	int timing = 0; // 0 off, 1 every kernel, 2 canny_tile + sht_vote, 3 sht_vote only, 4 canny_tile only
-	std::vector<hipEvent_t> eventPool;
-	std::vector<TimingEntry> timeline;
-	std::vector<std::string> timingNames; std::vector<float> timingMs;
+};
+
+// brute-force matcher (match_kernels.hip): every buffer is allocated by compvhip_matcher_create
+struct compvhip_matcher : TimingState {
+	compvhip_ctx* ctx = nullptr;
+	int descDwords = 0, queryCap = 0, trainCap = 0, pairs = 0, knn = 0;
+	uint32_t* partial = nullptr;        // keys of the slice kernel: max of the forward ([pairs][train slices][knn][queryCap]) and the reverse ([pairs][query slices][trainCap]) run
+	compvhip_match* reverse = nullptr;  // [pairs][trainCap]: best query of every train row (cross check)
 };
 
 namespace {
@@ -443,15 +453,17 @@ static bool stampWanted(const compvhip_plan* p, const char* name)
 	return false;
 }
 
-static bool takeEvent(compvhip_plan* p, hipEvent_t* e)
+static bool takeEvent(TimingState* p, hipEvent_t* e)
 {
 	if (!p->eventPool.empty()) { *e = p->eventPool.back(); p->eventPool.pop_back(); return true; }
 	return hipEventCreate(e) == hipSuccess;
 }
 
 struct Stamp {
-	compvhip_plan* p; hipStream_t s; size_t idx; bool on;
-	Stamp(compvhip_plan* plan, hipStream_t stream, const char* name) : p(plan), s(stream), idx(0), on(stampWanted(plan, name))
+	TimingState* p; hipStream_t s; size_t idx; bool on;
+	Stamp(compvhip_plan* plan, hipStream_t stream, const char* name) : Stamp(plan, stream, name, stampWanted(plan, name)) {}
+	Stamp(compvhip_matcher* matcher, hipStream_t stream, const char* name) : Stamp(matcher, stream, name, matcher->timing != 0) {}
+	Stamp(TimingState* state, hipStream_t stream, const char* name, bool wanted) : p(state), s(stream), idx(0), on(wanted)
 	{
 		if (!on) return;
 		TimingEntry t; t.name = name;
@@ -464,13 +476,13 @@ struct Stamp {
 	~Stamp() { if (on) (void)hipEventRecord(p->timeline[idx].b, s); }
 };
 
-void timelineClear(compvhip_plan* p)
+void timelineClear(TimingState* p)
 {
 	for (auto& t : p->timeline) { p->eventPool.push_back(t.a); p->eventPool.push_back(t.b); } // events are reused, not re-created
 	p->timeline.clear();
 }
 
-void timelineCollect(compvhip_plan* p)
+void timelineCollect(TimingState* p)
 {
 	p->timingNames.clear(); p->timingMs.clear();
 	for (auto& t : p->timeline) {
@@ -3133,6 +3145,177 @@ int compvhip_plan_houghkht_stage_ms(compvhip_plan* p, double* ms6, double* wallM
 	if (wallMs) *wallMs = p->khtWallMs;
 	if (threads) *threads = p->khtThreads;
 	return COMPVHIP_OK;
+}
+
+// ---- brute-force Hamming matching (match_kernels.hip; definition in include/compv_hip.h) ---------------------------------------------------
+namespace {
+constexpr size_t kMatchMaxCap = size_t(1) << 22;   // rows per side: keeps every grid dimension and 32-bit row index in range
+
+int checkMatchBuffers(compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const uint8_t* d_train, size_t trainStride)
+{
+	compvhip_ctx* ctx = m->ctx;
+	const size_t bytes = static_cast<size_t>(m->descDwords) * 4;
+	if (!d_query || !d_train) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null descriptor pointer");
+	if (queryStride < bytes || trainStride < bytes || (queryStride & 3) || (trainStride & 3) || queryStride > 65536 || trainStride > 65536)
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descriptor stride below descBytes, above 65536 or no multiple of 4");
+	if ((reinterpret_cast<uintptr_t>(d_query) & 3) || (reinterpret_cast<uintptr_t>(d_train) & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descriptors must be 4-byte aligned");
+	return COMPVHIP_OK;
+}
+
+MatchSliceArgs matchForward(const compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
+                            const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches)
+{
+	MatchSliceArgs a;
+	a.query = d_query; a.train = d_train; a.queryCounts = d_queryCounts; a.trainCounts = d_trainCounts;
+	a.queryCap = m->queryCap; a.trainCap = m->trainCap; a.queryStride = static_cast<int>(queryStride); a.trainStride = static_cast<int>(trainStride);
+	a.queryShared = 0; a.trainShared = trainShared != 0;
+	a.descDwords = m->descDwords; a.knn = m->knn; a.slices = (m->trainCap + kMatchTrainSlice - 1) / kMatchTrainSlice;
+	a.partial = m->partial; a.matches = d_matches;
+	return a;
+}
+} // namespace
+
+int compvhip_matcher_create(compvhip_ctx* ctx, size_t descBytes, size_t queryCap, size_t trainCap, size_t pairs, int knn, compvhip_matcher** out)
+{
+	if (!ctx || !out) return COMPVHIP_E_INVALID_PARAMETER;
+	*out = nullptr;
+	if (descBytes < 4 || descBytes > 4 * static_cast<size_t>(kMatchMaxDwords) || (descBytes & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descBytes must be a multiple of 4 in 4..128");
+	if (knn < 1 || knn > kMatchMaxKnn) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "knn must be in 1..8");
+	if (!queryCap || !trainCap || !pairs || queryCap > kMatchMaxCap || trainCap > kMatchMaxCap || pairs > 65535) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity out of range");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_matcher* m = new (std::nothrow) compvhip_matcher();
+	if (!m) return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "matcher");
+	m->ctx = ctx; m->descDwords = static_cast<int>(descBytes / 4); m->queryCap = static_cast<int>(queryCap); m->trainCap = static_cast<int>(trainCap);
+	m->pairs = static_cast<int>(pairs); m->knn = knn;
+	const size_t tSlices = (trainCap + kMatchTrainSlice - 1) / kMatchTrainSlice, qSlices = (queryCap + kMatchTrainSlice - 1) / kMatchTrainSlice;
+	const size_t words = pairs * std::max(tSlices * static_cast<size_t>(knn) * queryCap, qSlices * trainCap);
+	if (dmalloc(ctx, &m->partial, words) != hipSuccess || dmalloc(ctx, &m->reverse, pairs * trainCap) != hipSuccess) {
+		compvhip_matcher_destroy(m);
+		return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "matcher scratch");
+	}
+	*out = m;
+	return COMPVHIP_OK;
+}
+
+void compvhip_matcher_destroy(compvhip_matcher* m)
+{
+	if (!m) return;
+	compvhip_ctx* ctx = m->ctx;
+	(void)hipSetDevice(ctx->device);
+	timelineClear(m);
+	for (hipEvent_t e : m->eventPool) (void)hipEventDestroy(e);
+	dfree(ctx, m->partial); dfree(ctx, m->reverse);
+	delete m;
+}
+
+int compvhip_matcher_set_timing(compvhip_matcher* m, int enabled)
+{
+	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
+	m->timing = enabled != 0;
+	return COMPVHIP_OK;
+}
+
+int compvhip_matcher_get_timing(compvhip_matcher* m, const char** names, float* ms, int cap)
+{
+	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
+	(void)hipSetDevice(m->ctx->device);
+	if (!m->timeline.empty()) {
+		for (auto& t : m->timeline) (void)hipEventSynchronize(t.b);
+		timelineCollect(m);
+	}
+	const int n = std::min<int>(cap, static_cast<int>(m->timingMs.size()));
+	for (int i = 0; i < n; ++i) { if (names) names[i] = m->timingNames[i].c_str(); if (ms) ms[i] = m->timingMs[i]; }
+	return n;
+}
+
+int compvhip_matcher_knn(compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
+                         const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches, void* stream)
+{
+	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = m->ctx;
+	int rc = checkMatchBuffers(m, d_query, queryStride, d_train, trainStride);
+	if (rc) return rc;
+	if (!d_matches || (reinterpret_cast<uintptr_t>(d_matches) & 15)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records: null or not 16-byte aligned");
+	if ((reinterpret_cast<uintptr_t>(d_queryCounts) & 3) || (reinterpret_cast<uintptr_t>(d_trainCounts) & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "counts must be 4-byte aligned");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (m->timing) timelineClear(m);
+	const MatchSliceArgs a = matchForward(m, d_query, queryStride, d_queryCounts, d_train, trainStride, d_trainCounts, trainShared, d_matches);
+	{ Stamp s(m, st, "match_slice_kernel"); HIPCHK(ctx, launch_match_slices(a, m->pairs, st)); }
+	{ Stamp s(m, st, "match_merge_kernel"); HIPCHK(ctx, launch_match_merge(a, m->pairs, st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_matcher_good(compvhip_matcher* m, const compvhip_match* d_matches, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts,
+                          const uint8_t* d_train, size_t trainStride, const int32_t* d_trainCounts, int trainShared, const compvhip_match_opts* opts,
+                          compvhip_match* d_good, size_t goodCap, int32_t* d_goodCounts, void* stream)
+{
+	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = m->ctx;
+	if (!opts || !d_matches || !d_goodCounts || (goodCap && !d_good)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null options / match / count / good pointer");
+	if (opts->ratio > 0.0 && m->knn < 2) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "the ratio test needs knn >= 2");
+	if ((reinterpret_cast<uintptr_t>(d_matches) & 15) || (reinterpret_cast<uintptr_t>(d_good) & 15)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records must be 16-byte aligned");
+	if ((reinterpret_cast<uintptr_t>(d_queryCounts) & 3) || (reinterpret_cast<uintptr_t>(d_trainCounts) & 3) || (reinterpret_cast<uintptr_t>(d_goodCounts) & 3))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "counts must be 4-byte aligned");
+	if (opts->crossCheck) {
+		int rc = checkMatchBuffers(m, d_query, queryStride, d_train, trainStride);
+		if (rc) return rc;
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (m->timing) timelineClear(m);
+	if (opts->crossCheck) {          // the same kernels with the roles swapped and knn = 1: reverse[pair][t] = the best query of train row t
+		MatchSliceArgs r;
+		r.query = d_train; r.train = d_query; r.queryCounts = d_trainCounts; r.trainCounts = d_queryCounts;
+		r.queryCap = m->trainCap; r.trainCap = m->queryCap; r.queryStride = static_cast<int>(trainStride); r.trainStride = static_cast<int>(queryStride);
+		r.queryShared = trainShared != 0; r.trainShared = 0;
+		r.descDwords = m->descDwords; r.knn = 1; r.slices = (m->queryCap + kMatchTrainSlice - 1) / kMatchTrainSlice;
+		r.partial = m->partial; r.matches = m->reverse;
+		{ Stamp s(m, st, "match_reverse_slice_kernel"); HIPCHK(ctx, launch_match_slices(r, m->pairs, st)); }
+		{ Stamp s(m, st, "match_reverse_merge_kernel"); HIPCHK(ctx, launch_match_merge(r, m->pairs, st)); }
+	}
+	MatchGoodArgs g;
+	g.matches = d_matches; g.reverse = opts->crossCheck ? m->reverse : nullptr; g.queryCounts = d_queryCounts; g.trainCounts = d_trainCounts;
+	g.queryCap = m->queryCap; g.trainCap = m->trainCap; g.trainShared = trainShared != 0; g.knn = m->knn;
+	g.ratio = opts->ratio; g.maxDistance = opts->maxDistance; g.crossCheck = opts->crossCheck != 0;
+	g.good = d_good; g.goodCap = goodCap; g.counts = d_goodCounts;
+	{ Stamp s(m, st, "match_good_kernel"); HIPCHK(ctx, launch_match_good(g, m->pairs, st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_match_hamming_u8(compvhip_ctx* ctx, const uint8_t* query, size_t Q, size_t queryStride, const uint8_t* train, size_t T, size_t trainStride, size_t cols,
+                              int knn, compvhip_match* matches, size_t matchStride, size_t* rows)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!query || !train || !matches || !rows || !Q || !T || queryStride < cols || trainStride < cols || matchStride < Q) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	if (cols < 1 || cols > 4 * static_cast<size_t>(kMatchMaxDwords)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "cols must be in 1..128");
+	*rows = 0;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t S = alignUp(cols, 4);
+	compvhip_matcher* m = nullptr;
+	int rc = compvhip_matcher_create(ctx, S, Q, T, 1, knn, &m);
+	if (rc) return rc;
+	uint8_t* dDesc = nullptr; compvhip_match* dMatches = nullptr;
+	const size_t nRows = std::min<size_t>(static_cast<size_t>(knn), T);
+	do {
+		if (dmalloc(ctx, &dDesc, (Q + T) * S) != hipSuccess || dmalloc(ctx, &dMatches, static_cast<size_t>(knn) * Q) != hipSuccess) { rc = fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "match staging"); break; }
+		hipError_t e = hipMemsetAsync(dDesc, 0, (Q + T) * S, ctx->stream);          // the zero bytes that pad a row to a dword multiple
+		if (e == hipSuccess) e = hipMemcpy2DAsync(dDesc, S, query, queryStride, cols, Q, hipMemcpyHostToDevice, ctx->stream);
+		if (e == hipSuccess) e = hipMemcpy2DAsync(dDesc + Q * S, S, train, trainStride, cols, T, hipMemcpyHostToDevice, ctx->stream);
+		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "descriptor upload", e); break; }
+		// not compvhip_matcher_knn: the reference's order among equal distances is not the (distance, index) order of the device call
+		const MatchSliceArgs a = matchForward(m, dDesc, S, nullptr, dDesc + Q * S, S, nullptr, 0, dMatches);
+		e = launch_match_reference(a, 1, ctx->stream);
+		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "launch_match_reference", e); break; }
+		e = hipMemcpy2DAsync(matches, matchStride * sizeof(compvhip_match), dMatches, Q * sizeof(compvhip_match), Q * sizeof(compvhip_match), nRows, hipMemcpyDeviceToHost, ctx->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "match download", e); break; }
+		*rows = nRows;
+	} while (0);
+	(void)hipStreamSynchronize(ctx->stream);
+	dfree(ctx, dDesc); dfree(ctx, dMatches);
+	compvhip_matcher_destroy(m);
+	return rc;
 }
 
 } // extern "C"

@@ -311,4 +311,36 @@ struct FastArgs {
 // stage 0: score + NMS (score map, row counts, histogram); stage 1: [cut level -> row recount ->] scan -> emit
 hipError_t launch_fast(const FastArgs& a, int frames, int stage, hipStream_t stream);
 
+// ---- brute-force Hamming matching (match_kernels.hip) ------------------------------------------------------------------------------------
+constexpr int kMatchQueryBlock = 256;     // queries of one workgroup of the slice kernel: one per lane
+constexpr int kMatchTrainSlice = 128;     // train rows one workgroup stages in LDS
+constexpr int kMatchMaxKnn = 8;
+constexpr int kMatchMaxDwords = 32;       // 128 descriptor bytes
+struct MatchSliceArgs {
+	const uint8_t* query;     // [pairs][queryCap] rows of queryStride bytes ([queryCap] rows when queryShared)
+	const uint8_t* train;     // the same for the train side
+	const int32_t* queryCounts; const int32_t* trainCounts;   // device counts per pair (one count on a shared side); nullptr: the capacity
+	int queryCap, trainCap, queryStride, trainStride;
+	int queryShared, trainShared;
+	int descDwords;           // 1..32
+	int knn;                  // 1..8
+	int slices;               // (trainCap + kMatchTrainSlice - 1) / kMatchTrainSlice
+	uint32_t* partial;        // [pairs][slices][knn][queryCap] keys: distance << 16 | row within the slice
+	compvhip_match* matches;  // [pairs][knn][queryCap], 16-byte aligned
+};
+hipError_t launch_match_slices(const MatchSliceArgs& a, int pairs, hipStream_t stream);
+hipError_t launch_match_merge(const MatchSliceArgs& a, int pairs, hipStream_t stream);
+// the reference's own order among equal distances (partial is not used, but must be there): one lane per query walks every train row
+hipError_t launch_match_reference(const MatchSliceArgs& a, int pairs, hipStream_t stream);
+struct MatchGoodArgs {
+	const compvhip_match* matches;   // [pairs][knn][queryCap]
+	const compvhip_match* reverse;   // [pairs][trainCap]: the best query of every train row (crossCheck only)
+	const int32_t* queryCounts; const int32_t* trainCounts;
+	int queryCap, trainCap, trainShared, knn;
+	double ratio; int maxDistance, crossCheck;
+	compvhip_match* good; size_t goodCap;   // [pairs][goodCap], 16-byte aligned
+	int32_t* counts;                 // [pairs] good matches before clipping
+};
+hipError_t launch_match_good(const MatchGoodArgs& a, int pairs, hipStream_t stream);
+
 } // namespace compvhip

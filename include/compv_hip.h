@@ -615,6 +615,73 @@ COMPVHIP_API int compvhip_plan_fast(compvhip_plan* plan, const uint8_t* d_gray, 
 COMPVHIP_API int compvhip_fast_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, int threshold, int fastType, int nonmax,
                                   int maxFeatures, uint8_t* scores, size_t So, compvhip_corner* corners, size_t cap, size_t* n);
 
+/* ---- brute-force Hamming matching (docs/kernels/match.md) --------------------------------------------------------------------------
+ * CompVMatcherBruteForce (core/matchers/compv_core_matcher_bruteforce.cxx:81-228; COMPV_BRUTEFORCE_ID) on device descriptors, every output
+ * defined bit for bit.  One pair has Q query rows and T train rows of descBytes bytes:
+ *  1. Distance: d(q, t) = popcount of the XOR of the two rows over their descBytes bytes.  Stride padding is never read.
+ *  2. Neighbours, as compvhip_matcher_knn returns them: the train rows sorted ascending by (d(q, t), t); neighbour r is the r-th of them.
+ *     This is NOT the reference's order among equal distances: its loops (:181-191 for KNN == 2, :215-222) let a displaced entry pass the
+ *     equally distant entries behind it, so its order depends on the arrival sequence (docs/kernels/match.md).  The distances of every
+ *     column agree; only the host form, compvhip_match_hamming_u8, reproduces the reference's train indices on ties.
+ *  3. Record: matches[r][q] = {q, t_r, 0, d(q, t_r)} -- CompVDMatch (compv_common.h:674) -- for r < min(knn, T).  The device form has the fixed
+ *     shape [pairs][knn][queryCap]: rows r >= T hold {q, -1, 0, INT32_MAX}; columns q >= the pair's query count are never written.
+ *  4. Counts: d_queryCounts[p] / d_trainCounts[p] are int32 in device memory and may exceed the capacity (as compvhip_plan_fast's d_counts
+ *     can): min(count, cap) rows are used, a negative count is 0, a NULL pointer means every pair is full.
+ *  5. Good list (samples/object_recognition/main.cxx:183-200): matches[0][q] of the queries that pass every enabled test, in ascending q --
+ *     ratio: (double)d0 < ratio * (double)d1 (one binary64 multiply, one compare; needs knn >= 2; a pair with T < 2 passes none);
+ *     distance: d0 <= maxDistance; cross check: among the pair's queries, q has the smallest (d(q', t0), q') for its best train row t0.
+ *     d_goodCounts[p] = their number BEFORE clipping to goodCap; the first min(count, goodCap) are written and nothing behind them.
+ *     (The sample's loop bound min(rows - 1, cols) drops the last query: its quirk, not reproduced.) */
+typedef struct compvhip_match {
+	int32_t queryIdx, trainIdx, imageIdx, distance;
+} compvhip_match;
+typedef struct compvhip_match_opts {
+	double ratio;               /* <= 0: no ratio test */
+	int maxDistance;            /* < 0: no distance test */
+	int crossCheck;             /* != 0: cross check */
+} compvhip_match_opts;
+typedef struct compvhip_matcher compvhip_matcher;   /* scratch for `pairs` pairs of at most queryCap x trainCap rows; not tied to an image geometry */
+
+/* descBytes: a multiple of 4 in 4..128; knn 1..8; queryCap, trainCap, pairs >= 1 (anything else: COMPVHIP_E_INVALID_PARAMETER).  All scratch
+ * is allocated here -- pairs * max(ceil(trainCap / 128) * knn * queryCap, ceil(queryCap / 128) * trainCap) key words (the forward and the
+ * reverse run share them) and pairs * trainCap records --
+ * and released by compvhip_matcher_destroy: no later call allocates or synchronises.  Destroy a matcher BEFORE its context.  Like a plan, a
+ * matcher is not re-entrant: its calls share the scratch and must be ordered on one stream. */
+COMPVHIP_API int compvhip_matcher_create(compvhip_ctx* ctx, size_t descBytes, size_t queryCap, size_t trainCap, size_t pairs, int knn,
+                                         compvhip_matcher** matcher);
+COMPVHIP_API void compvhip_matcher_destroy(compvhip_matcher* matcher);
+
+/* d_query: [pairs][queryCap] rows of queryStride bytes (descBytes <= queryStride <= 65536, queryStride % 4 == 0, 4-byte aligned); d_train: the same with
+ * trainCap / trainStride, or, with trainShared != 0, ONE train set [trainCap] and ONE train count that serve every pair (one trained object
+ * against many frames).  d_matches: [pairs][knn][queryCap] records, 16-byte aligned.  Asynchronous on `stream`; deterministic run to run. */
+COMPVHIP_API int compvhip_matcher_knn(compvhip_matcher* matcher, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts,
+                                      const uint8_t* d_train, size_t trainStride, const int32_t* d_trainCounts, int trainShared,
+                                      compvhip_match* d_matches, void* stream);
+
+/* The good list of the d_matches a compvhip_matcher_knn call of this matcher wrote for the same descriptors and counts.  The descriptors are
+ * read by the cross check only (it runs the distance kernel with the roles swapped and knn = 1 into the matcher's scratch).  d_good:
+ * [pairs][goodCap] records, 16-byte aligned (NULL with goodCap == 0: counts only); d_goodCounts: [pairs] int32.  opts == NULL, or
+ * ratio > 0 on a matcher with knn < 2: COMPVHIP_E_INVALID_PARAMETER.  Asynchronous on `stream`. */
+COMPVHIP_API int compvhip_matcher_good(compvhip_matcher* matcher, const compvhip_match* d_matches,
+                                       const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts,
+                                       const uint8_t* d_train, size_t trainStride, const int32_t* d_trainCounts, int trainShared,
+                                       const compvhip_match_opts* opts, compvhip_match* d_good, size_t goodCap, int32_t* d_goodCounts, void* stream);
+
+/* CompVMatcherBruteForce::process for one HOST pair: Q query rows and T train rows of `cols` bytes (1..128; rows are padded to a dword multiple
+ * with zero bytes on the way to the device, which cannot change a distance), knn 1..8.  matches: min(knn, T) rows of matchStride records
+ * (matchStride >= Q), the reference's shape (:102); *rows receives min(knn, T).  Among equal distances the records follow the REFERENCE's
+ * insertion order (tests/match_model.py: knn_reference; docs/kernels/match.md), not the (d, t) order of item 2: on ties the train indices of
+ * this call and of compvhip_matcher_knn differ, the distances never do.  Synchronous; one lane per query walks every train row, so this is
+ * the parity path, not the fast one. */
+COMPVHIP_API int compvhip_match_hamming_u8(compvhip_ctx* ctx, const uint8_t* query, size_t Q, size_t queryStride, const uint8_t* train, size_t T,
+                                           size_t trainStride, size_t cols, int knn, compvhip_match* matches, size_t matchStride, size_t* rows);
+
+/* Per-kernel timing of the matcher's last call (HIP events on the call's stream), as compvhip_plan_set_timing / _get_timing: entries
+ * match_slice_kernel, match_merge_kernel [, match_reverse_slice_kernel, match_reverse_merge_kernel], match_good_kernel.  Reading the
+ * timing waits for the events. */
+COMPVHIP_API int compvhip_matcher_set_timing(compvhip_matcher* matcher, int enabled);
+COMPVHIP_API int compvhip_matcher_get_timing(compvhip_matcher* matcher, const char** names, float* ms, int cap);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel

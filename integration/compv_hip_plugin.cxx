@@ -1,7 +1,7 @@
 // compv_hip_plugin.cxx -- the reference-side binding: CompV C++ classes that implement CompV's own abstract
 // CompVEdgeDete / CompVHough / CompVCornerDete interfaces on top of the C ABI in include/compv_hip.h, and the factory table that
 // re-registers the ids COMPV_CANNY_ID / COMPV_SOBEL_ID / COMPV_SCHARR_ID / COMPV_PREWITT_ID / COMPV_HOUGHSHT_ID / COMPV_HOUGHKHT_ID /
-// COMPV_FAST_ID.
+// COMPV_FAST_ID, and a CompVMatcher for COMPV_BRUTEFORCE_ID (CompVMatcher::addFactory replaces by id as well, base/compv_matchers.cxx:44-54).
 //
 // CompVFeature::addFactory() REPLACES an existing id (base/compv_features.cxx:30-40), so after
 //     CompVInit(); compv_hip_plugin_register();
@@ -15,6 +15,7 @@
 // table and applied by one routine, and every computation (toCartesian included) lives behind the C ABI.
 #include <compv/base/compv_base.h>
 #include <compv/base/compv_features.h>
+#include <compv/base/compv_matchers.h>
 #include <compv/base/compv_debug.h>
 #include <compv/base/image/compv_image.h>
 
@@ -470,6 +471,79 @@ private:
 };
 
 // ------------------------------------------------------------------------------------------------------------------
+// Brute-force Hamming matcher  (stands in for CompVMatcherBruteForce, core/matchers/compv_core_matcher_bruteforce.cxx)
+// ------------------------------------------------------------------------------------------------------------------
+class CompVMatcherBruteForceHip : public CompVMatcher
+{
+public:
+	CompVMatcherBruteForceHip() : m_nKNN(2), m_bCrossCheck(false) { }          // the reference's defaults (:21-27)
+	virtual ~CompVMatcherBruteForceHip() { }
+	COMPV_OBJECT_GET_ID(CompVMatcherBruteForceHip);
+
+	// The reference's ids, sizes and ranges (:33-66), with one deviation: KNN above 8 is refused here (the reference takes up to 255).  The cross-check
+	// setting is stored and ignored, as the reference does (:51-61).
+	virtual COMPV_ERROR_CODE set(int id, const void* valuePtr, size_t valueSize) override
+	{
+		if (!valuePtr || !valueSize) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+		switch (id) {
+		case COMPV_BRUTEFORCE_SET_INT_KNN: {
+			if (valueSize != sizeof(int)) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+			const int knn = *reinterpret_cast<const int*>(valuePtr);
+			if (knn < 1 || knn > 8) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+			m_nKNN = knn;
+			return COMPV_ERROR_CODE_S_OK;
+		}
+		case COMPV_BRUTEFORCE_SET_INT_NORM: {
+			if (valueSize != sizeof(int)) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+			return *reinterpret_cast<const int*>(valuePtr) == COMPV_BRUTEFORCE_NORM_HAMMING ? COMPV_ERROR_CODE_S_OK : COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+		}
+		case COMPV_BRUTEFORCE_SET_BOOL_CROSS_CHECK: {
+			if (valueSize != sizeof(bool)) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+			const bool crossCheck = *reinterpret_cast<const bool*>(valuePtr);
+			if (crossCheck && m_nKNN != 1) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+			m_bCrossCheck = crossCheck;
+			return COMPV_ERROR_CODE_S_OK;
+		}
+		default:
+			return CompVCaps::set(id, valuePtr, valueSize);
+		}
+	}
+
+	// The reference's parameter checks (:83-96), its output shape (clip(knn, 1, T) rows of Q records, :102) and its order among equal distances.
+	virtual COMPV_ERROR_CODE process(const CompVMatPtr& queryDescriptions, const CompVMatPtr& trainDescriptions, CompVMatPtrPtr matches) override
+	{
+		if (!matches || !queryDescriptions || queryDescriptions->isEmpty() || !queryDescriptions->isRawTypeMatch<uint8_t>() || !trainDescriptions
+			|| trainDescriptions->isEmpty() || !trainDescriptions->isRawTypeMatch<uint8_t>() || queryDescriptions->cols() != trainDescriptions->cols()
+			|| queryDescriptions->stride() != trainDescriptions->stride()) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+		compvhip_ctx* ctx = NULL;
+		COMPV_CHECK_CODE_RETURN(m_Ctx.acquire(ctx));
+		const size_t Q = queryDescriptions->rows(), T = trainDescriptions->rows();
+		const size_t rows = T < static_cast<size_t>(m_nKNN) ? T : static_cast<size_t>(m_nKNN);
+		COMPV_CHECK_CODE_RETURN((CompVMat::newObjAligned<CompVDMatch, COMPV_MAT_TYPE_STRUCT>(matches, rows, Q)));
+		size_t got = 0;
+		const int rc = compvhip_match_hamming_u8(ctx, queryDescriptions->ptr<const uint8_t>(), Q, queryDescriptions->strideInBytes(), trainDescriptions->ptr<const uint8_t>(), T,
+			trainDescriptions->strideInBytes(), queryDescriptions->cols(), m_nKNN, reinterpret_cast<compvhip_match*>((*matches)->ptr<CompVDMatch>()), (*matches)->stride(), &got);
+		if (rc != COMPVHIP_OK) return report(ctx, "compvhip_match_hamming_u8", rc);
+		return got == rows ? COMPV_ERROR_CODE_S_OK : COMPV_ERROR_CODE_E_INVALID_STATE;
+	}
+
+	static COMPV_ERROR_CODE newObj(CompVMatcherPtrPtr matcher)
+	{
+		if (!matcher) return COMPV_ERROR_CODE_E_INVALID_PARAMETER;
+		CompVPtr<CompVMatcherBruteForceHip*> obj = new CompVMatcherBruteForceHip();
+		if (!obj) return COMPV_ERROR_CODE_E_OUT_OF_MEMORY;
+		*matcher = *obj;
+		return COMPV_ERROR_CODE_S_OK;
+	}
+
+private:
+	LazyCtx m_Ctx;
+	int m_nKNN;
+	bool m_bCrossCheck;
+};
+static_assert(sizeof(compvhip_match) == sizeof(CompVDMatch), "compvhip_match must have CompVDMatch's layout");
+
+// ------------------------------------------------------------------------------------------------------------------
 // factory table (file-static: addFactory stores the POINTER, as core/compv_core.cxx:56-103 relies on for the built-ins)
 // ------------------------------------------------------------------------------------------------------------------
 static const CompVFeatureFactory kHipFactories[] = {
@@ -481,6 +555,7 @@ static const CompVFeatureFactory kHipFactories[] = {
 	{ COMPV_HOUGHKHT_ID, "Hough kernel-based (HIP/gfx950)", nullptr, nullptr, nullptr, CompVHoughKhtHip::newObj, nullptr },
 	{ COMPV_FAST_ID, "FAST corner detector (HIP/gfx950)", CompVCornerDeteFastHip::newObj, nullptr, nullptr, nullptr, nullptr },
 };
+static const CompVMatcherFactory kHipMatcherFactory = { COMPV_BRUTEFORCE_ID, "Brute force matcher (HIP/gfx950)", CompVMatcherBruteForceHip::newObj };
 
 COMPV_NAMESPACE_END()
 
@@ -495,5 +570,6 @@ extern "C" __attribute__((visibility("default"))) int compv_hip_plugin_register(
 	for (size_t i = 0; i < sizeof(kHipFactories) / sizeof(kHipFactories[0]); ++i) {
 		if (COMPV_ERROR_CODE_IS_NOK(CompVFeature::addFactory(&kHipFactories[i]))) return -2;
 	}
+	if (COMPV_ERROR_CODE_IS_NOK(CompVMatcher::addFactory(&kHipMatcherFactory))) return -2;
 	return 0;
 }

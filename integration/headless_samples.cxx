@@ -7,6 +7,7 @@
 //
 // usage: headless_samples [W H [frames [cpuThreads]]]      exit code 0 = drop-in parity on every frame
 //        headless_samples --fast-only [W H]                 the FAST corner comparison alone (default 200 x 258), with the median time of five calls each
+//        headless_samples --match-only [Q T]                the brute-force matcher comparison alone (default 2000 x 2000 rows of 32 bytes, KNN 2), byte for byte
 // cpuThreads (default 1) is CompVBase::init()'s thread count for the CPU reference run.  The default is the single-threaded
 // path because the reference's multi-threaded gradient is not deterministic: each row band also recomputes |gx|+|gy| for
 // its two overlap rows from gx/gy rows that the neighbouring band may not have written yet
@@ -14,6 +15,7 @@
 // result itself occasionally differs from run to run.
 #include <compv/base/compv_base.h>
 #include <compv/base/compv_features.h>
+#include <compv/base/compv_matchers.h>
 #include <compv/base/compv_debug.h>
 #include <compv/base/image/compv_image.h>
 #include <compv/core/compv_core.h>
@@ -183,6 +185,44 @@ static COMPV_ERROR_CODE runFast(FastPoints& out, double& ms, size_t W = 200, siz
 	return COMPV_ERROR_CODE_S_OK;
 }
 
+// The brute-force matcher through the factory (CompVMatcher::newObj(&m, COMPV_BRUTEFORCE_ID), setInt(KNN), process, as samples/object_recognition/main.cxx
+// does) on seeded 32-byte descriptors: half of the query rows are train rows with a few bits flipped, the rest is noise.  The record matrix, row by row.
+static COMPV_ERROR_CODE runMatch(std::vector<int32_t>& out, double& ms, size_t Q, size_t T, int knn)
+{
+	CompVMatPtr query, train, matches;
+	COMPV_CHECK_CODE_RETURN(CompVMat::newObjAligned<uint8_t>(&query, Q, 32));
+	COMPV_CHECK_CODE_RETURN(CompVMat::newObjAligned<uint8_t>(&train, T, 32));
+	uint32_t s = 2463534242u;
+	for (size_t j = 0; j < T; ++j) for (size_t i = 0; i < 32; ++i) { s ^= s << 13; s ^= s >> 17; s ^= s << 5; *train->ptr<uint8_t>(j, i) = (uint8_t)(s >> 11); }
+	for (size_t j = 0; j < Q; ++j) {
+		for (size_t i = 0; i < 32; ++i) { s ^= s << 13; s ^= s >> 17; s ^= s << 5; *query->ptr<uint8_t>(j, i) = (j & 1) ? (uint8_t)(s >> 11) : *train->ptr<const uint8_t>((j * 7) % T, i); }
+		if (!(j & 1)) for (int k = 0; k < (int)(j % 9); ++k) { s ^= s << 13; s ^= s >> 17; s ^= s << 5; *query->ptr<uint8_t>(j, (s >> 8) & 31) ^= (uint8_t)(1u << (s & 7)); }
+	}
+	CompVMatcherPtr matcher;
+	COMPV_CHECK_CODE_RETURN(CompVMatcher::newObj(&matcher, COMPV_BRUTEFORCE_ID));
+	COMPV_CHECK_CODE_RETURN(matcher->setInt(COMPV_BRUTEFORCE_SET_INT_KNN, knn));
+	COMPV_CHECK_CODE_RETURN(matcher->setInt(COMPV_BRUTEFORCE_SET_INT_NORM, COMPV_BRUTEFORCE_NORM_HAMMING));
+	COMPV_CHECK_CODE_RETURN(matcher->process(query, train, &matches));          // the first call allocates
+	double samples[5];
+	for (int i = 0; i < 5; ++i) {
+		const auto t0 = std::chrono::steady_clock::now();
+		COMPV_CHECK_CODE_RETURN(matcher->process(query, train, &matches));
+		samples[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	}
+	std::sort(samples, samples + 5);
+	ms = samples[2];
+	out.clear();
+	out.push_back((int32_t)matches->rows()); out.push_back((int32_t)matches->cols());
+	for (size_t r = 0; r < matches->rows(); ++r) {
+		const int32_t* row = reinterpret_cast<const int32_t*>(matches->ptr<const CompVDMatch>(r));
+		out.insert(out.end(), row, row + 4 * matches->cols());
+	}
+	int badNorm = COMPV_BRUTEFORCE_NORM_L2;
+	COMPV_CHECK_EXP_RETURN(matcher->set(COMPV_BRUTEFORCE_SET_INT_NORM, &badNorm, sizeof(badNorm)) != COMPV_ERROR_CODE_E_INVALID_PARAMETER, COMPV_ERROR_CODE_E_UNITTEST_FAILED,
+		"a norm other than HAMMING must give E_INVALID_PARAMETER");
+	return COMPV_ERROR_CODE_S_OK;
+}
+
 // A CONSUMER of the line set: CompVCalibCamera builds its Canny and Hough objects through the same factories
 // (core/calib/compv_core_calib_camera.cxx:1255-1279: SHT, theta = 0.5 deg, maxLines = 60 per pattern line, Canny(1.33, 2.66)) and runs
 // Canny -> SHT -> toCartesian -> line subdivision / grouping -> intersections on a chessboard view (:127-..).  Same application
@@ -319,6 +359,18 @@ int main(int argc, char** argv)
 	// CompVInit() of compv_api.h minus GL/camera/drawing (absent on a headless box): base + core
 	if (COMPV_ERROR_CODE_IS_NOK(CompVBase::init(cpuThreads)) || COMPV_ERROR_CODE_IS_NOK(CompVCore::init())) { fprintf(stderr, "CompV init failed\n"); return 2; }
 
+	if (argc > 1 && !strcmp(argv[1], "--match-only")) {
+		const size_t mq = argc > 3 ? (size_t)atoi(argv[2]) : 2000, mt = argc > 3 ? (size_t)atoi(argv[3]) : 2000;
+		std::vector<int32_t> cpuM, hipM;
+		double cpuMs = 0.0, hipMs = 0.0;
+		if (!mq || !mt || COMPV_ERROR_CODE_IS_NOK(runMatch(cpuM, cpuMs, mq, mt, 2))) { fprintf(stderr, "CPU matcher run failed\n"); return 8; }
+		if (compv_hip_plugin_register() != 0) { fprintf(stderr, "HIP plugin registration failed (no GPU?)\n"); return 4; }
+		if (COMPV_ERROR_CODE_IS_NOK(runMatch(hipM, hipMs, mq, mt, 2))) { fprintf(stderr, "HIP matcher run failed\n"); return 9; }
+		const bool same = cpuM == hipM && cpuM.size() > 2;
+		printf("bruteforce_matches: %s [%zu x %zu rows of 32 bytes, KNN 2, %zu records | CompV CPU %.2f ms on %d thread(s), HIP plugin %.2f ms (incl. H2D/D2H)]\n", same ? "MATCH" : "DIFF",
+			mq, mt, cpuM.size() / 4, cpuMs, cpuThreads, hipMs);
+		return same ? 0 : 1;
+	}
 	FastPoints fastCpu, fastHip;
 	double fastCpuMs = 0.0, fastHipMs = 0.0;
 	if (fastOnly) {
