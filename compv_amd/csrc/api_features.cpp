@@ -1,0 +1,471 @@
+// api_features.cpp -- plan-level calls of the features built on the Canny / SHT plan: line segments, line fits, connected components,
+// thresholding and morphology, FAST corners, brute-force matching.
+#include "api_internal.hpp"
+
+// ---- Hough line segments (sht_segments_kernels.hip; definition in include/compv_hip.h) ---------------------------------------
+// edges / edgeStride: byte maps [frames][H][edgeStride], or nullptr = the plan's bit masks
+int compvhip_api::segmentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap,
+                               int maxLines, int minLength, int maxGap, compvhip_segment* d_segs, size_t segCap, int32_t* d_segCounts, hipStream_t st)
+{
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_lines || !d_counts || !d_segCounts || !lineCap || (segCap && !d_segs)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null line / count / segment buffer");
+	if (minLength < 1 || maxGap < 0) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "segments need minLength >= 1 and maxGap >= 0");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	int rc = ensureSht(p);
+	if (rc) return rc;
+	size_t nLines = std::min(lineCap, p->R * p->T);   // a frame has at most R * T lines
+	if (maxLines > 0) nLines = std::min(nLines, static_cast<size_t>(maxLines));
+	if (nLines > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "line capacity beyond 2^31");
+	HIPCHK(ctx, p->segPerLine.reserve(ctx, nLines * p->frames));
+	if (p->timing) timelineClear(p);
+	ShtSegArgs a;
+	a.ebits = p->ebits; a.edges = d_edges; a.bitsFrameStride = p->bitsFrameStride; a.edgeFrameStride = edgeStride * p->H; a.wb = p->wb; a.S = static_cast<int>(edgeStride);
+	a.sinQ = p->sinQ; a.cosQ = p->cosQ; a.lines = d_lines; a.lineCounts = d_counts; a.lineCap = lineCap; a.nLines = static_cast<int>(nLines);
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.R = static_cast<int>(p->R); a.T = static_cast<int>(p->T); a.barrier = static_cast<int>(p->W + p->H);
+	a.minLength = minLength; a.maxGap = maxGap; a.perLine = p->segPerLine; a.segs = d_segs; a.segCap = segCap; a.segCounts = d_segCounts; a.frame0 = 0;
+	const int frames = static_cast<int>(p->frames);
+	{ Stamp s(p, st, "sht_segments_count_kernel"); HIPCHK(ctx, launch_sht_segments(a, frames, 0, st)); }
+	{ Stamp s(p, st, "sht_segments_scan_kernel"); HIPCHK(ctx, launch_sht_segments(a, frames, 1, st)); }
+	if (segCap) { Stamp s(p, st, "sht_segments_write_kernel"); HIPCHK(ctx, launch_sht_segments(a, frames, 2, st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_houghsht_segments(compvhip_plan* p, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap, int maxLines,
+                                    int minLength, int maxGap, compvhip_segment* d_segs, size_t segCap, int32_t* d_segCounts, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	for (const auto& stp : p->steps)
+		if (stp.used) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the lines)");
+	if (!segCap) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "segCap must be > 0");
+	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
+	return segmentsImpl(p, d_edges, p->S, d_lines, d_counts, lineCap, maxLines, minLength, maxGap, d_segs, segCap, d_segCounts, static_cast<hipStream_t>(stream));
+}
+
+// ---- Hough line refinement (sht_fit_kernels.hip; definition in include/compv_hip.h) -------------------------------------------
+// edges / edgeStride: byte maps [frames][H][edgeStride], or nullptr = the plan's bit masks
+int compvhip_api::fitImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap, int maxLines,
+                   int halfWidth, const compvhip_segment* d_segs, const int32_t* d_segCounts, size_t segCap, compvhip_line_fit* d_fits, size_t fitCap,
+                   int32_t* d_fitCounts, compvhip_line* d_refined, hipStream_t st)
+{
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_lines || !d_counts || !d_fitCounts || !lineCap || (fitCap && !d_fits)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null line / count / fit buffer");
+	if (d_segs && (!d_segCounts || d_refined)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "per-segment fits need d_segCounts and take no d_refined");
+	if (halfWidth < 0 || halfWidth > kFitMaxHalfWidth) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "halfWidth must be 0 .. 8");
+	if (std::max(p->W, p->H) > kFitMaxSide) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "line fits need max(W, H) <= 8192 (int64 central moments)");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	int rc = ensureSht(p);
+	if (rc) return rc;
+	size_t nLines = std::min(lineCap, p->R * p->T);   // a frame has at most R * T lines
+	if (maxLines > 0) nLines = std::min(nLines, static_cast<size_t>(maxLines));
+	if (nLines > static_cast<size_t>(INT32_MAX) || (d_segs && segCap > static_cast<size_t>(INT32_MAX)))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "line / segment capacity beyond 2^31");
+	if (p->timing) timelineClear(p);
+	ShtFitArgs a;
+	a.ebits = p->ebits; a.edges = d_edges; a.bitsFrameStride = p->bitsFrameStride; a.edgeFrameStride = edgeStride * p->H; a.wb = p->wb; a.S = static_cast<int>(edgeStride);
+	a.sinQ = p->sinQ; a.cosQ = p->cosQ; a.lines = d_lines; a.lineCounts = d_counts; a.lineCap = lineCap; a.nLines = static_cast<int>(nLines);
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.R = static_cast<int>(p->R); a.T = static_cast<int>(p->T); a.barrier = static_cast<int>(p->W + p->H);
+	a.halfWidth = halfWidth; a.segs = d_segs; a.segCounts = d_segCounts; a.segCap = d_segs ? segCap : 0;
+	a.fits = d_fits; a.fitCap = fitCap; a.fitCounts = d_fitCounts; a.refined = d_refined; a.frame0 = 0;
+	{ Stamp s(p, st, "sht_fit_kernel"); HIPCHK(ctx, launch_sht_fit(a, static_cast<int>(p->frames), st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_houghsht_fit(compvhip_plan* p, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap, int maxLines,
+                               int halfWidth, const compvhip_segment* d_segs, const int32_t* d_segCounts, size_t segCap, compvhip_line_fit* d_fits, size_t fitCap,
+                               int32_t* d_fitCounts, compvhip_line* d_refined, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	for (const auto& stp : p->steps)
+		if (stp.used) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the lines)");
+	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
+	return fitImpl(p, d_edges, p->S, d_lines, d_counts, lineCap, maxLines, halfWidth, d_segs, d_segCounts, segCap, d_fits, fitCap, d_fitCounts, d_refined,
+	               static_cast<hipStream_t>(stream));
+}
+
+// ---- connected components (components_kernels.hip; definition in include/compv_hip.h) -----------------------------------------
+// edges / edgeStride: byte maps [frames][H][edgeStride] (packed into the plan's compBits first), or nullptr = the plan's bit masks
+int compvhip_api::componentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, int connectivity, int minPixels, int32_t* d_labels, size_t labelStride,
+                          compvhip_component* d_comps, size_t compCap, int32_t* d_compCounts, hipStream_t st)
+{
+	compvhip_ctx* ctx = p->ctx;
+	if (connectivity != 4 && connectivity != 8) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "connectivity must be 4 or 8");
+	if (minPixels < 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "minPixels must be >= 1");
+	if (!d_compCounts || (compCap && !d_comps)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null count / record buffer");
+	if (d_labels && labelStride < p->W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "labelStride < W");
+	if (p->W * p->H > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "W * H beyond 2^31");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t frames = p->frames;
+	if (!p->compRows) HIPCHK(ctx, dmalloc(ctx, &p->compRows, p->H * frames));
+	if (d_edges && !p->compBits) HIPCHK(ctx, dmalloc(ctx, &p->compBits, p->bitsFrameStride * frames));
+	if (!d_labels && !p->compParent) HIPCHK(ctx, dmalloc(ctx, &p->compParent, p->W * p->H * frames));
+	if (p->timing) timelineClear(p);
+	const int nf = static_cast<int>(frames);
+	if (d_edges) {
+		Stamp s(p, st, "bytes_to_bits_kernel");
+		HIPCHK(ctx, launch_bytes_to_bits(d_edges, static_cast<int>(p->W), static_cast<int>(p->H), static_cast<int>(edgeStride), edgeStride * p->H, p->compBits, p->wb,
+		                                 p->bitsFrameStride, nf, st));
+	}
+	CompArgs a;
+	a.bits = d_edges ? p->compBits : p->ebits; a.bitsFrameStride = p->bitsFrameStride; a.wb = p->wb;
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.words = static_cast<int>((p->W + 31) / 32);
+	a.lastMask = (p->W & 31) ? (1u << (p->W & 31)) - 1u : ~0u;
+	a.conn8 = connectivity == 8; a.minPixels = minPixels;
+	a.parent = d_labels ? d_labels : p->compParent; a.ps = static_cast<int>(d_labels ? labelStride : p->W);
+	a.parentFrameStride = static_cast<size_t>(a.ps) * p->H; a.wantLabels = d_labels != nullptr;
+	a.comps = d_comps; a.compCap = compCap; a.compCounts = d_compCounts; a.rowCounts = p->compRows; a.frame0 = 0;
+	static const char* const names[9] = { "comp_tile_kernel", "comp_border_kernel", "comp_flatten_kernel", "comp_count_kernel", "comp_rows_kernel<false>",
+	                                      "comp_scan_kernel", "comp_rows_kernel<true>", "comp_boxes_kernel", "comp_finish_kernel" };
+	for (int phase = 0; phase < 9; ++phase) {
+		if (phase == 7 && !a.wantLabels && !compCap) continue;   // nothing to label, no box to grow
+		if (phase == 8 && !a.wantLabels) continue;
+		Stamp s(p, st, names[phase]);
+		HIPCHK(ctx, launch_components(a, nf, phase, st));
+	}
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_components(compvhip_plan* p, const uint8_t* d_edges, int connectivity, int minPixels, int32_t* d_labels, size_t labelStride,
+                             compvhip_component* d_comps, size_t compCap, int32_t* d_compCounts, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	for (const auto& stp : p->steps)
+		if (stp.used) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the masks)");
+	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
+	if (labelStride > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "labelStride beyond 2^31");
+	return componentsImpl(p, d_edges, p->S, connectivity, minPixels, d_labels, labelStride, d_comps, compCap, d_compCounts, static_cast<hipStream_t>(stream));
+}
+
+// ---- thresholding and morphology (morph_kernels.hip; definitions in include/compv_hip.h) ---------------------------------------------------
+static bool planeOverlap(const compvhip_plan* p, const uint8_t* a, const uint8_t* b)
+{
+	const size_t span = p->S * p->H * p->frames;
+	return (a < b + span) && (b < a + span);
+}
+
+// COMPV_MATH_ROUNDFU_2_NEAREST_INT(COMPV_MATH_CLIP3(0x00, 0xff, v), int) (compv_image_threshold.cxx:133-136,213-220)
+static int roundClipU8(double v) { return static_cast<int>((v > 255.0 ? 255.0 : (v < 0.0 ? 0.0 : v)) + 0.5); }
+
+int compvhip_plan_threshold(compvhip_plan* p, const uint8_t* d_in, double threshold, const int32_t* d_levels, uint8_t* d_out, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	if (!d_levels && !(threshold >= 0.0)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "threshold < 0"); // compv_image_threshold.cxx:120
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	ThreshArgs a;
+	a.in = d_in; a.out = d_out; a.levels = d_levels; a.frameStride = p->S * p->H;
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
+	a.t8 = d_levels ? 0 : roundClipU8(threshold);
+	Stamp s(p, st, "threshold_kernel");
+	HIPCHK(ctx, launch_threshold(a, static_cast<int>(p->frames), st));
+	return COMPVHIP_OK;
+}
+
+int compvhip_api::checkAdaptive(compvhip_ctx* ctx, size_t W, size_t H, size_t blockSize, double delta, double maxVal)
+{
+	if (!(blockSize & 1) || blockSize < 3) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "blockSize must be odd and >= 3"); // compv_image_threshold.cxx:185
+	if (blockSize > 31) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "adaptive threshold supports block sizes 3..31");
+	if (W < blockSize || H < blockSize) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image smaller than the block"); // compv_math_convlt.h:100
+	if (!(maxVal >= 0.0) || delta != delta) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "maxVal < 0"); // compv_image_threshold.cxx:202
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_threshold_adaptive(compvhip_plan* p, const uint8_t* d_in, size_t blockSize, double delta, double maxVal, int invert, uint8_t* d_out, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	int rc = checkAdaptive(ctx, p->W, p->H, blockSize, delta, maxVal);
+	if (rc) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t span = p->S * p->H * p->frames;
+	const bool alias = planeOverlap(p, d_in, d_out);
+	if (alias && d_in != d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output overlap without being the same buffer");
+	if (alias && !p->morphTmp) HIPCHK(ctx, dmalloc(ctx, &p->morphTmp, span)); // a tile reads the halo its neighbours write: in place goes through the plan's plane
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	AdaptArgs a;
+	a.in = d_in; a.out = alias ? p->morphTmp : d_out; a.frameStride = p->S * p->H;
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
+	a.r = static_cast<int>(blockSize >> 1);
+	a.k = static_cast<uint16_t>((1.f / static_cast<float>(blockSize)) * 0xffff);   // CompVKernel::mean (compv_kernel.cxx:16) through fixedPointKernel (compv_math_convlt.h:88)
+	a.delta = roundClipU8(delta); a.maxVal = roundClipU8(maxVal); a.invert = invert != 0;
+	{
+		Stamp s(p, st, "threshold_adaptive_kernel");
+		HIPCHK(ctx, launch_threshold_adaptive(a, static_cast<int>(p->frames), st));
+	}
+	if (alias) {   // rows only up to W: the padding columns of the caller's buffer stay as they are
+		for (size_t f = 0; f < p->frames; ++f)
+			HIPCHK(ctx, hipMemcpy2DAsync(d_out + f * p->S * p->H, p->S, p->morphTmp + f * p->S * p->H, p->S, p->W, p->H, hipMemcpyDeviceToDevice, st));
+	}
+	return COMPVHIP_OK;
+}
+
+// buildStructuringElementGeneric (compv_math_morph.cxx:476-540)
+int compvhip_morph_strel(int type, size_t w, size_t h, uint8_t* strel)
+{
+	if (!strel || !w || !h) return COMPVHIP_E_INVALID_PARAMETER; // :478
+	if (type != COMPVHIP_MORPH_STREL_RECT && type != COMPVHIP_MORPH_STREL_DIAMOND && type != COMPVHIP_MORPH_STREL_CROSS) return COMPVHIP_E_NOT_IMPLEMENTED; // :534
+	if (type == COMPVHIP_MORPH_STREL_DIAMOND && w != h) return COMPVHIP_E_INVALID_PARAMETER;
+	if (type == COMPVHIP_MORPH_STREL_RECT) { memset(strel, 0xff, w * h); return COMPVHIP_OK; }
+	memset(strel, 0, w * h);
+	if (type == COMPVHIP_MORPH_STREL_CROSS) {
+		memset(strel + (h >> 1) * w, 0xff, w);
+		for (size_t j = 0; j < h; ++j) strel[j * w + (w >> 1)] = 0xff;
+		return COMPVHIP_OK;
+	}
+	const size_t c = w >> 1;
+	for (size_t j = 0; j < h; ++j) {   // 1, 3, 5, ... members centred on column w / 2 down to the middle row, then back
+		const size_t half = j <= (h >> 1) ? j : h - 1 - j;
+		memset(strel + j * w + c - half, 0xff, 2 * half + 1);
+	}
+	return COMPVHIP_OK;
+}
+
+// strel -> member masks + the kernel that serves it
+int compvhip_api::morphPrepare(compvhip_ctx* ctx, size_t W, size_t H, const uint8_t* strel, size_t sw, size_t sh, int op, int border, int kernel, MorphArgs* a)
+{
+	if (!strel || !sw || !sh) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null / empty structuring element");
+	if (!(sw & 1) || !(sh & 1) || sw > static_cast<size_t>(kMorphMaxStrel) || sh > static_cast<size_t>(kMorphMaxStrel))
+		return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "structuring elements are odd-sized, 1..31 a side");
+	if (W < sw || H < sh) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image smaller than the structuring element"); // compv_math_morph.cxx:131
+	if (op != COMPVHIP_MORPH_OP_ERODE && op != COMPVHIP_MORPH_OP_DILATE && op != COMPVHIP_MORPH_OP_OPEN && op != COMPVHIP_MORPH_OP_CLOSE)
+		return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "morph op (erode, dilate, open, close)"); // :119
+	if (border != COMPVHIP_BORDER_REPLICATE && border != COMPVHIP_BORDER_ZERO) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "border type (replicate, zero)"); // :571
+	size_t members = 0, cross = 0;
+	for (size_t j = 0; j < sh; ++j) {
+		uint32_t m = 0;
+		for (size_t i = 0; i < sw; ++i) {
+			if (!strel[j * sw + i]) continue;
+			m |= 1u << i; ++members;
+			if (j == (sh >> 1) || i == (sw >> 1)) ++cross;
+		}
+		a->rows[j] = m;
+	}
+	for (size_t j = sh; j < static_cast<size_t>(kMorphMaxStrel); ++j) a->rows[j] = 0;
+	if (!members) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "structuring element is full of zeros"); // :460
+	const bool isRect = members == sw * sh, isCross = !isRect && members == cross && cross == sw + sh - 1;
+	if (kernel == COMPVHIP_MORPH_KERNEL_GENERAL) a->kind = kMorphGeneral;
+	else if (kernel == COMPVHIP_MORPH_KERNEL_AUTO || kernel == COMPVHIP_MORPH_KERNEL_SEPARABLE) {
+		a->kind = isRect ? kMorphRect : (isCross ? kMorphCross : kMorphGeneral);
+		// up to 15 members the member-list kernel is the faster one (3x3: 0.28 ms against 0.35 ms at 4K x 32; docs/kernels/morph.md): the second LDS plane
+		// and barrier of the separable kernel cost more than the taps it saves
+		if (kernel == COMPVHIP_MORPH_KERNEL_AUTO && members <= kMorphGeneralMaxMembers) a->kind = kMorphGeneral;
+		if (kernel == COMPVHIP_MORPH_KERNEL_SEPARABLE && a->kind == kMorphGeneral)
+			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "the separable kernel serves full rectangles and crosses only");
+	}
+	else return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "kernel selector");
+	a->sw = static_cast<int>(sw); a->sh = static_cast<int>(sh); a->replicate = border == COMPVHIP_BORDER_REPLICATE;
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_morph_ex(compvhip_plan* p, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op, int border, int kernel, uint8_t* d_out,
+                           void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	MorphArgs a;
+	int rc = morphPrepare(ctx, p->W, p->H, strel, sw, sh, op, border, kernel, &a);
+	if (rc) return rc;
+	if (planeOverlap(p, d_in, d_out)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap"); // compv_math_morph.cxx:140-145 reallocates
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const bool two = op == COMPVHIP_MORPH_OP_OPEN || op == COMPVHIP_MORPH_OP_CLOSE;
+	if (two && !p->morphTmp) HIPCHK(ctx, dmalloc(ctx, &p->morphTmp, p->S * p->H * p->frames));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	a.frameStride = p->S * p->H; a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
+	const int nf = static_cast<int>(p->frames);
+	static const char* const names[3] = { "morph_general_kernel", "morph_separable_kernel<rect>", "morph_separable_kernel<cross>" };
+	// OPEN = erode then dilate, CLOSE = dilate then erode (compv_math_morph.cxx:104-111): two complete basic operations, borders included
+	a.in = d_in; a.out = two ? p->morphTmp : d_out; a.dilate = op == COMPVHIP_MORPH_OP_DILATE || op == COMPVHIP_MORPH_OP_CLOSE;
+	{ Stamp s(p, st, names[a.kind]); HIPCHK(ctx, launch_morph(a, nf, st)); }
+	if (two) {
+		a.in = p->morphTmp; a.out = d_out; a.dilate = !a.dilate;
+		Stamp s(p, st, names[a.kind]); HIPCHK(ctx, launch_morph(a, nf, st));
+	}
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_morph(compvhip_plan* p, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op, int border, uint8_t* d_out, void* stream)
+{
+	return compvhip_plan_morph_ex(p, d_in, strel, sw, sh, op, border, COMPVHIP_MORPH_KERNEL_AUTO, d_out, stream);
+}
+
+// ---- FAST corners (fast_kernels.hip; definition in include/compv_hip.h) ------------------------------------------------------------------
+int compvhip_api::checkFast(compvhip_ctx* ctx, size_t W, size_t H, int fastType)
+{
+	if (W < 7 || H < 7) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "FAST needs W, H >= 7 (one interior pixel)");
+	if (fastType != 9 && fastType != 12) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "fastType must be 9 or 12"); // compv_core_feature_fast_dete.cxx:146
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_fast(compvhip_plan* p, const uint8_t* d_gray, int threshold, int fastType, int nonmax, int maxFeatures, uint8_t* d_scores,
+                       compvhip_corner* d_corners, size_t cornerCap, int32_t* d_counts, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_gray || !d_counts || (cornerCap && !d_corners)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame / count / corner pointer");
+	int rc = checkFast(ctx, p->W, p->H, fastType);
+	if (rc) return rc;
+	if ((reinterpret_cast<uintptr_t>(d_gray) & 7) || (reinterpret_cast<uintptr_t>(d_scores) & 7)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames must be 8-byte aligned");
+	if ((reinterpret_cast<uintptr_t>(d_corners) & 3) || (reinterpret_cast<uintptr_t>(d_counts) & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "records and counts must be 4-byte aligned");
+	if (d_scores && planeOverlap(p, d_gray, d_scores)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frame and score map must not overlap");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t F = p->frames, H = p->H, work = F * (2 * H + 257);
+	if (!p->fastWork) HIPCHK(ctx, dmalloc(ctx, &p->fastWork, work));
+	if (!d_scores && !p->fastScores) HIPCHK(ctx, dmalloc(ctx, &p->fastScores, p->S * H * F));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	FastArgs a;
+	a.in = d_gray; a.scores = d_scores ? d_scores : p->fastScores; a.frameStride = p->S * H;
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(H); a.S = static_cast<int>(p->S);
+	a.t = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold); a.N = fastType; a.nonmax = nonmax != 0; a.maxFeatures = maxFeatures;   // :135
+	a.rowCounts = p->fastWork; a.hist = a.rowCounts + F * H; a.minScore = a.hist + F * 256; a.rowOffsets = a.minScore + F;
+	a.corners = d_corners; a.cornerCap = cornerCap; a.counts = d_counts;
+	HIPCHK(ctx, hipMemsetAsync(a.rowCounts, 0, F * (H + 256) * sizeof(int), st));   // the row counts and the histogram are sums
+	{ Stamp s(p, st, "fast_score_kernel"); HIPCHK(ctx, launch_fast(a, static_cast<int>(F), 0, st)); }
+	{ Stamp s(p, st, "fast_list_kernels"); HIPCHK(ctx, launch_fast(a, static_cast<int>(F), 1, st)); }   // cut level, row recount, scan, emit
+	return COMPVHIP_OK;
+}
+
+// ---- brute-force Hamming matching (match_kernels.hip; definition in include/compv_hip.h) ---------------------------------------------------
+namespace {
+constexpr size_t kMatchMaxCap = size_t(1) << 22;   // rows per side: keeps every grid dimension and 32-bit row index in range
+
+int checkMatchBuffers(compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const uint8_t* d_train, size_t trainStride)
+{
+	compvhip_ctx* ctx = m->ctx;
+	const size_t bytes = static_cast<size_t>(m->descDwords) * 4;
+	if (!d_query || !d_train) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null descriptor pointer");
+	if (queryStride < bytes || trainStride < bytes || (queryStride & 3) || (trainStride & 3) || queryStride > 65536 || trainStride > 65536)
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descriptor stride below descBytes, above 65536 or no multiple of 4");
+	if ((reinterpret_cast<uintptr_t>(d_query) & 3) || (reinterpret_cast<uintptr_t>(d_train) & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descriptors must be 4-byte aligned");
+	return COMPVHIP_OK;
+}
+} // namespace
+
+MatchSliceArgs compvhip_api::matchForward(const compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
+                            const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches)
+{
+	MatchSliceArgs a;
+	a.query = d_query; a.train = d_train; a.queryCounts = d_queryCounts; a.trainCounts = d_trainCounts;
+	a.queryCap = m->queryCap; a.trainCap = m->trainCap; a.queryStride = static_cast<int>(queryStride); a.trainStride = static_cast<int>(trainStride);
+	a.queryShared = 0; a.trainShared = trainShared != 0;
+	a.descDwords = m->descDwords; a.knn = m->knn; a.slices = (m->trainCap + kMatchTrainSlice - 1) / kMatchTrainSlice;
+	a.partial = m->partial; a.matches = d_matches;
+	return a;
+}
+
+int compvhip_matcher_create(compvhip_ctx* ctx, size_t descBytes, size_t queryCap, size_t trainCap, size_t pairs, int knn, compvhip_matcher** out)
+{
+	if (!ctx || !out) return COMPVHIP_E_INVALID_PARAMETER;
+	*out = nullptr;
+	if (descBytes < 4 || descBytes > 4 * static_cast<size_t>(kMatchMaxDwords) || (descBytes & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descBytes must be a multiple of 4 in 4..128");
+	if (knn < 1 || knn > kMatchMaxKnn) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "knn must be in 1..8");
+	if (!queryCap || !trainCap || !pairs || queryCap > kMatchMaxCap || trainCap > kMatchMaxCap || pairs > 65535) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity out of range");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_matcher* m = new (std::nothrow) compvhip_matcher();
+	if (!m) return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "matcher");
+	m->ctx = ctx; m->descDwords = static_cast<int>(descBytes / 4); m->queryCap = static_cast<int>(queryCap); m->trainCap = static_cast<int>(trainCap);
+	m->pairs = static_cast<int>(pairs); m->knn = knn;
+	const size_t tSlices = (trainCap + kMatchTrainSlice - 1) / kMatchTrainSlice, qSlices = (queryCap + kMatchTrainSlice - 1) / kMatchTrainSlice;
+	const size_t words = pairs * std::max(tSlices * static_cast<size_t>(knn) * queryCap, qSlices * trainCap);
+	if (dmalloc(ctx, &m->partial, words) != hipSuccess || dmalloc(ctx, &m->reverse, pairs * trainCap) != hipSuccess) {
+		compvhip_matcher_destroy(m);
+		return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "matcher scratch");
+	}
+	*out = m;
+	return COMPVHIP_OK;
+}
+
+void compvhip_matcher_destroy(compvhip_matcher* m)
+{
+	if (!m) return;
+	compvhip_ctx* ctx = m->ctx;
+	(void)hipSetDevice(ctx->device);
+	timelineClear(m);
+	for (hipEvent_t e : m->eventPool) (void)hipEventDestroy(e);
+	dfree(ctx, m->partial); dfree(ctx, m->reverse);
+	delete m;
+}
+
+int compvhip_matcher_set_timing(compvhip_matcher* m, int enabled)
+{
+	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
+	m->timing = enabled != 0;
+	return COMPVHIP_OK;
+}
+
+int compvhip_matcher_get_timing(compvhip_matcher* m, const char** names, float* ms, int cap)
+{
+	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
+	(void)hipSetDevice(m->ctx->device);
+	if (!m->timeline.empty()) {
+		for (auto& t : m->timeline) (void)hipEventSynchronize(t.b);
+		timelineCollect(m);
+	}
+	const int n = std::min<int>(cap, static_cast<int>(m->timingMs.size()));
+	for (int i = 0; i < n; ++i) { if (names) names[i] = m->timingNames[i].c_str(); if (ms) ms[i] = m->timingMs[i]; }
+	return n;
+}
+
+int compvhip_matcher_knn(compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
+                         const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches, void* stream)
+{
+	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = m->ctx;
+	int rc = checkMatchBuffers(m, d_query, queryStride, d_train, trainStride);
+	if (rc) return rc;
+	if (!d_matches || (reinterpret_cast<uintptr_t>(d_matches) & 15)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records: null or not 16-byte aligned");
+	if ((reinterpret_cast<uintptr_t>(d_queryCounts) & 3) || (reinterpret_cast<uintptr_t>(d_trainCounts) & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "counts must be 4-byte aligned");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (m->timing) timelineClear(m);
+	const MatchSliceArgs a = matchForward(m, d_query, queryStride, d_queryCounts, d_train, trainStride, d_trainCounts, trainShared, d_matches);
+	{ Stamp s(m, st, "match_slice_kernel"); HIPCHK(ctx, launch_match_slices(a, m->pairs, st)); }
+	{ Stamp s(m, st, "match_merge_kernel"); HIPCHK(ctx, launch_match_merge(a, m->pairs, st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_matcher_good(compvhip_matcher* m, const compvhip_match* d_matches, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts,
+                          const uint8_t* d_train, size_t trainStride, const int32_t* d_trainCounts, int trainShared, const compvhip_match_opts* opts,
+                          compvhip_match* d_good, size_t goodCap, int32_t* d_goodCounts, void* stream)
+{
+	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = m->ctx;
+	if (!opts || !d_matches || !d_goodCounts || (goodCap && !d_good)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null options / match / count / good pointer");
+	if (opts->ratio > 0.0 && m->knn < 2) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "the ratio test needs knn >= 2");
+	if ((reinterpret_cast<uintptr_t>(d_matches) & 15) || (reinterpret_cast<uintptr_t>(d_good) & 15)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records must be 16-byte aligned");
+	if ((reinterpret_cast<uintptr_t>(d_queryCounts) & 3) || (reinterpret_cast<uintptr_t>(d_trainCounts) & 3) || (reinterpret_cast<uintptr_t>(d_goodCounts) & 3))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "counts must be 4-byte aligned");
+	if (opts->crossCheck) {
+		int rc = checkMatchBuffers(m, d_query, queryStride, d_train, trainStride);
+		if (rc) return rc;
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (m->timing) timelineClear(m);
+	if (opts->crossCheck) {          // the same kernels with the roles swapped and knn = 1: reverse[pair][t] = the best query of train row t
+		MatchSliceArgs r;
+		r.query = d_train; r.train = d_query; r.queryCounts = d_trainCounts; r.trainCounts = d_queryCounts;
+		r.queryCap = m->trainCap; r.trainCap = m->queryCap; r.queryStride = static_cast<int>(trainStride); r.trainStride = static_cast<int>(queryStride);
+		r.queryShared = trainShared != 0; r.trainShared = 0;
+		r.descDwords = m->descDwords; r.knn = 1; r.slices = (m->queryCap + kMatchTrainSlice - 1) / kMatchTrainSlice;
+		r.partial = m->partial; r.matches = m->reverse;
+		{ Stamp s(m, st, "match_reverse_slice_kernel"); HIPCHK(ctx, launch_match_slices(r, m->pairs, st)); }
+		{ Stamp s(m, st, "match_reverse_merge_kernel"); HIPCHK(ctx, launch_match_merge(r, m->pairs, st)); }
+	}
+	MatchGoodArgs g;
+	g.matches = d_matches; g.reverse = opts->crossCheck ? m->reverse : nullptr; g.queryCounts = d_queryCounts; g.trainCounts = d_trainCounts;
+	g.queryCap = m->queryCap; g.trainCap = m->trainCap; g.trainShared = trainShared != 0; g.knn = m->knn;
+	g.ratio = opts->ratio; g.maxDistance = opts->maxDistance; g.crossCheck = opts->crossCheck != 0;
+	g.good = d_good; g.goodCap = goodCap; g.counts = d_goodCounts;
+	{ Stamp s(m, st, "match_good_kernel"); HIPCHK(ctx, launch_match_good(g, m->pairs, st)); }
+	return COMPVHIP_OK;
+}

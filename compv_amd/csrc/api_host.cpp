@@ -1,0 +1,484 @@
+// api_host.cpp -- the host-pointer (`*_u8`) entry points: one frame in host memory in, results in host memory out, synchronous
+// (KHT: api_kht.cpp).  They run the plan-level calls on a single-frame plan and staging buffers cached in the context.
+#include "api_internal.hpp"
+
+// ---- host entry points -------------------------------------------------------------------------------------------
+namespace {
+constexpr float kAnyTheta = 0.f;   // hostPlan: any theta serves, keep the cached plan when it fits
+
+// the single-frame plan cached for the host entry points (rebuilt for another size, or another theta when the call's result depends on it), dIn / dOut sized for it
+int hostPlan(compvhip_ctx* ctx, size_t W, size_t H, float thetaDeg, compvhip_plan** out)
+{
+	const size_t S = alignUp(W, 64);
+	compvhip_plan* p = ctx->hostPlan;
+	if (p && (p->W != W || p->H != H || (thetaDeg != kAnyTheta && p->thetaDeg != thetaDeg))) { compvhip_plan_destroy(p); ctx->hostPlan = p = nullptr; }
+	if (!p) {
+		int rc = compvhip_plan_create(ctx, W, H, S, 1, thetaDeg != kAnyTheta ? thetaDeg : 1.f, &p);
+		if (rc) return rc;
+		ctx->hostPlan = p;
+	}
+	HIPCHK(ctx, ctx->dIn.reserve(ctx, S * H));
+	HIPCHK(ctx, ctx->dOut.reserve(ctx, S * H));
+	*out = p;
+	return COMPVHIP_OK;
+}
+
+// H rows of rowBytes bytes between a host plane (stride S) and device staging (stride Sd), on the context's stream
+hipError_t upload(compvhip_ctx* ctx, void* dst, size_t Sd, const void* src, size_t S, size_t rowBytes, size_t H) { return hipMemcpy2DAsync(dst, Sd, src, S, rowBytes, H, hipMemcpyHostToDevice, ctx->stream); }
+hipError_t download(compvhip_ctx* ctx, void* dst, size_t S, const void* src, size_t Sd, size_t rowBytes, size_t H) { return hipMemcpy2DAsync(dst, S, src, Sd, rowBytes, H, hipMemcpyDeviceToHost, ctx->stream); }
+
+// The frame of the host calls on the cached plan: select the device, get the plan (thetaDeg or kAnyTheta), upload the plane into dIn, run; with `out`, download
+// dOut into it and wait for the stream (without, `run` ends in a synchronisation of its own: takeList).
+template <typename Run>   // int run(compvhip_plan*)
+int hostPlaneOp(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, float thetaDeg, uint8_t* out, size_t So, const Run& run)
+{
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_plan* p = nullptr;
+	int rc = hostPlan(ctx, W, H, thetaDeg, &p);
+	if (rc) return rc;
+	HIPCHK(ctx, upload(ctx, ctx->dIn, p->S, in, S, W, H));
+	rc = run(p);
+	if (rc) (void)hipStreamSynchronize(ctx->stream);   // a failed call leaves no copy from the caller's plane in flight
+	if (rc || !out) return rc;
+	HIPCHK(ctx, download(ctx, out, So, ctx->dOut, p->S, W, H));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return COMPVHIP_OK;
+}
+
+// The caller's lines with their number into dSegLines / dCounts and, with segs, its segments into dSegs / dSegCount (dSegCount is the caller's to allocate).
+int stageLists(compvhip_ctx* ctx, const compvhip_line* lines, size_t n, const compvhip_segment* segs, size_t nSegs)
+{
+	HIPCHK(ctx, ctx->dSegLines.reserve(ctx, n));
+	if (segs) HIPCHK(ctx, ctx->dSegs.reserve(ctx, nSegs));
+	HIPCHK(ctx, ctx->dCounts.reserve(ctx, 1));
+	const int32_t nLines = static_cast<int32_t>(n), nS = static_cast<int32_t>(nSegs);
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dSegLines, lines, n * sizeof(compvhip_line), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dCounts, &nLines, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+	if (segs) {
+		HIPCHK(ctx, hipMemcpyAsync(ctx->dSegs, segs, nSegs * sizeof(compvhip_segment), hipMemcpyHostToDevice, ctx->stream));
+		HIPCHK(ctx, hipMemcpyAsync(ctx->dSegCount, &nS, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+	}
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the counts live on this stack frame; pageable copies may still be staged
+	return COMPVHIP_OK;
+}
+
+// Waits for the stream, stores the int32 record count in *n and copies the first min(count, cap) records; COMPVHIP_E_OUT_OF_BOUND (`what`) when they did not all fit.
+template <typename T>
+int takeList(compvhip_ctx* ctx, const int32_t* dCount, const T* dRecs, T* recs, size_t cap, size_t* n, const char* what)
+{
+	int32_t found = 0;
+	HIPCHK(ctx, hipMemcpyAsync(&found, dCount, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	*n = static_cast<size_t>(found);
+	const size_t ncopy = std::min(*n, cap);
+	if (ncopy) HIPCHK(ctx, hipMemcpy(recs, dRecs, ncopy * sizeof(T), hipMemcpyDeviceToHost));
+	if (*n > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, what);
+	return COMPVHIP_OK;
+}
+
+int checkImage(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const void* out, size_t So)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!in || !out || S < W || So < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image or stride < width");
+	if (W < 3 || H < 3 || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
+	return COMPVHIP_OK;
+}
+} // namespace
+
+int compvhip_canny_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, float tLow, float tHigh, int ksize, int type,
+                      uint8_t* out, size_t So)
+{
+	int rc = checkImage(ctx, in, W, H, S, out, So);
+	if (rc) return rc;
+	int lo, hi;
+	rc = validateCannyParams(ctx, tLow, tHigh, ksize, type, &lo, &hi);
+	if (rc) return rc;
+	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p) { return compvhip_plan_canny(p, ctx->dIn, tLow, tHigh, ksize, type, ctx->dOut, ctx->stream); });
+}
+
+int compvhip_edge_dete_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, int op, uint8_t* out, size_t So)
+{
+	int rc = checkImage(ctx, in, W, H, S, out, So);
+	if (rc) return rc;
+	if (op != COMPVHIP_OP_SOBEL && op != COMPVHIP_OP_SCHARR && op != COMPVHIP_OP_PREWITT)
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "invalid detector id"); // edge_dete.cxx:246
+	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p) -> int {
+		EdgeDeteArgs a;
+		a.in = ctx->dIn; a.out = ctx->dOut; a.gmax = p->sums;
+		a.inFrameStride = p->S * H; a.outFrameStride = p->S * H;
+		a.W = static_cast<int>(W); a.H = static_cast<int>(H); a.S = static_cast<int>(p->S); a.So = static_cast<int>(p->S);
+		a.tilesX = p->tilesX; a.tilesY = p->tilesY;
+		HIPCHK(ctx, launch_edge_dete(a, op, 1, ctx->stream));
+		return COMPVHIP_OK;
+	});
+}
+
+int compvhip_gauss_kernel_fixedpoint(size_t size, float sigma, uint16_t* kernel)
+{
+	// compv_math_gauss.h:24-55 with T = float (note the float/double mix), then compv_math_convlt.h:88
+	if (!kernel || !(size & 1) || size > 255 || !(sigma > 0.f)) return COMPVHIP_E_INVALID_PARAMETER;
+	float f[255];
+	const size_t half = size >> 1;
+	const float sigma2_times2 = static_cast<float>(2 * (sigma * sigma));
+	const float a = static_cast<float>(1 / std::sqrt(3.14159265358979323846 * sigma2_times2));
+	float sum = a;
+	f[half] = a;
+	for (size_t x = 1; x <= half; ++x) {
+		const float k = static_cast<float>(a * std::exp(-static_cast<double>((x * x) / sigma2_times2)));
+		f[x + half] = k; f[half - x] = k;
+		sum += (k + k);
+	}
+	sum = 1 / sum;
+	for (size_t x = 0; x < size; ++x) { f[x] *= sum; kernel[x] = static_cast<uint16_t>(f[x] * 0xffff); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_convlt1_fixedpoint_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint16_t* vtKern, const uint16_t* hzKern,
+                                   size_t kernSize, uint8_t* out, size_t So)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!in || !out || S < W || So < W || !W || !H || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image, stride < width or size out of range");
+	int rc = checkFxpKernel(ctx, W, H, vtKern, hzKern, kernSize);
+	if (rc) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t Sd = alignUp(W, 64), bytes = Sd * H;
+	HIPCHK(ctx, ctx->dIn.reserve(ctx, bytes));
+	HIPCHK(ctx, ctx->dOut.reserve(ctx, bytes));
+	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
+	// dIn -> dOut with the fused kernel (no intermediate: the two staging buffers never alias)
+	HIPCHK(ctx, launch_convlt_fxp(ctx->dIn, nullptr, ctx->dOut, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), bytes, 1, vtKern, hzKern,
+	                              static_cast<int>(kernSize), ctx->stream));
+	HIPCHK(ctx, download(ctx, out, So, ctx->dOut, Sd, W, H));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return COMPVHIP_OK;
+}
+
+// CompVMathConvlt::convlt1<uint8_t | int16_t, int16_t, int16_t> (compv_math_convlt.h:26-28,37-39,98-292): the separable integer correlation the
+// gradient is made of, stand-alone.  The device buffers are private to the call (the operator is not on the per-frame hot path: there it is
+// fused into the tile kernels); S, So in elements.
+static int convlt1I16(compvhip_ctx* ctx, const void* in, bool inIsU8, size_t W, size_t H, size_t S, const int16_t* vtKern, const int16_t* hzKern, size_t kernSize,
+                      int16_t* out, size_t So)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!in || !out || !vtKern || !hzKern || S < W || So < W || !(kernSize & 1) || W < kernSize || H < kernSize)
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "convolution: null pointer, stride < width, even kernel size or image smaller than the kernel"); // compv_math_convlt.h:100
+	if (kernSize > static_cast<size_t>(kFxpMaxTaps)) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "integer convolution supports kernel sizes 1..15");
+	if (W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t es = inIsU8 ? 1 : 2;
+	const size_t Sd = alignUp(W, 64);
+	uint8_t* dIn = nullptr; int16_t* dTmp = nullptr; int16_t* dOut = nullptr;
+	int rc = COMPVHIP_OK;
+	do {
+		if (dmalloc(ctx, &dIn, Sd * H * es) != hipSuccess || dmalloc(ctx, &dTmp, Sd * H) != hipSuccess || dmalloc(ctx, &dOut, Sd * H) != hipSuccess) { rc = fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "convolution buffers"); break; }
+		hipError_t e = hipMemcpy2DAsync(dIn, Sd * es, in, S * es, W * es, H, hipMemcpyHostToDevice, ctx->stream);
+		if (e == hipSuccess) e = launch_convlt_i16(dIn, inIsU8, dTmp, dOut, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), static_cast<int>(Sd), vtKern, hzKern,
+		                                           static_cast<int>(kernSize), ctx->stream);
+		if (e == hipSuccess) e = hipMemcpy2DAsync(out, So * 2, dOut, Sd * 2, W * 2, H, hipMemcpyDeviceToHost, ctx->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+		if (e != hipSuccess) rc = fail(ctx, COMPVHIP_E_HIP, "integer convolution", e);
+	} while (0);
+	dfree(ctx, dIn); dfree(ctx, dTmp); dfree(ctx, dOut);
+	return rc;
+}
+
+int compvhip_convlt1_8u16s16s(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const int16_t* vtKern, const int16_t* hzKern, size_t kernSize,
+                              int16_t* out, size_t So)
+{
+	return convlt1I16(ctx, in, true, W, H, S, vtKern, hzKern, kernSize, out, So);
+}
+
+int compvhip_convlt1_16s16s16s(compvhip_ctx* ctx, const int16_t* in, size_t W, size_t H, size_t S, const int16_t* vtKern, const int16_t* hzKern, size_t kernSize,
+                               int16_t* out, size_t So)
+{
+	return convlt1I16(ctx, in, false, W, H, S, vtKern, hzKern, kernSize, out, So);
+}
+
+int compvhip_grayscale_u8(compvhip_ctx* ctx, const uint8_t* in, int pixfmt, size_t W, size_t H, size_t S, uint8_t* out, size_t So)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!in || !out || S < W || So < W || !W || !H || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image, stride < width or size out of range");
+	const int bpp = pixfmtBytes(pixfmt);
+	if (!bpp) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "pixel format without a grayscale conversion"); // conv_to_grayscale.cxx:86-88
+	if ((pixfmt == COMPVHIP_FMT_YUYV422 || pixfmt == COMPVHIP_FMT_UYVY422) && (W & 1)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "packed 4:2:2 needs an even width");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t Sd = alignUp(W, 64);
+	HIPCHK(ctx, ctx->dPacked.reserve(ctx, Sd * H * bpp));
+	HIPCHK(ctx, ctx->dOut.reserve(ctx, Sd * H));
+	HIPCHK(ctx, upload(ctx, ctx->dPacked, Sd * bpp, in, S * bpp, W * bpp, H));
+	GrayArgs a;
+	a.in = ctx->dPacked; a.out = ctx->dOut; a.W = static_cast<int>(W); a.H = static_cast<int>(H); a.S = static_cast<int>(Sd); a.So = static_cast<int>(Sd);
+	HIPCHK(ctx, launch_gray(a, pixfmt, 1, ctx->stream));
+	HIPCHK(ctx, download(ctx, out, So, ctx->dOut, Sd, W, H));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return COMPVHIP_OK;
+}
+
+int compvhip_otsu_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double* threshold)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!in || !threshold || S < W || !W || !H || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image, stride < width or size out of range"); // threshold.cxx:54
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t Sd = alignUp(W, 64);
+	const size_t bytes = Sd * H;
+	HIPCHK(ctx, ctx->dIn.reserve(ctx, bytes));
+	HIPCHK(ctx, ctx->dHist.reserve(ctx, static_cast<size_t>(256) * kOtsuMaxChunks + 1));
+	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
+	int32_t* dT = reinterpret_cast<int32_t*>(ctx->dHist + static_cast<size_t>(256) * kOtsuMaxChunks);
+	HIPCHK(ctx, launch_otsu(ctx->dIn, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), bytes, 1, 0.5f, 1.f, ctx->dHist, dT, nullptr, ctx->stream));
+	int32_t t = 0;
+	HIPCHK(ctx, hipMemcpyAsync(&t, dT, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	*threshold = static_cast<double>(t);
+	return COMPVHIP_OK;
+}
+
+// CompVHoughSht::process ends with std::sort(lines, strength >) and keeps the first maxLines (houghsht.cxx:241-249).  std::sort is
+// unstable, but deterministic for one libstdc++ and one input order, and the input order is nms_apply's emission order: accumulator
+// rows ascending, columns ascending (:546-562; per-thread vectors are concatenated in row order, :228-234).  Re-creating that order
+// and calling the same std::sort gives the reference's list element by element -- callers such as CompVCalibCamera (line grouping,
+// core/calib/compv_core_calib_camera.cxx:200-) depend on the order inside equal-strength groups.  The permutation only depends on
+// the strengths, so it is computed on (strength, index) pairs.
+static void referenceLineOrder(const std::vector<uint32_t>& keys, const std::vector<uint32_t>& cells, uint32_t strengthMask, size_t T, long long barrier, float thetaStep,
+                               std::vector<compvhip_line>& lines)
+{
+	// keys / cells arrive in emission order (ascending cell): exactly the array the reference sorts
+	const size_t n = keys.size();
+	struct Item { int32_t strength; uint32_t idx; };
+	std::vector<Item> items(n);
+	for (size_t i = 0; i < n; ++i) { items[i].strength = static_cast<int32_t>(keys[i] & strengthMask); items[i].idx = static_cast<uint32_t>(i); }
+	std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.strength > b.strength; });
+	lines.resize(n);
+	for (size_t i = 0; i < n; ++i) {
+		const uint32_t cell = cells[items[i].idx];
+		const uint32_t row = cell / static_cast<uint32_t>(T), col = cell - row * static_cast<uint32_t>(T);
+		compvhip_line& l = lines[i];
+		l.rho = static_cast<float>(barrier - static_cast<long long>(row));   // houghsht.cxx:661
+		l.theta = static_cast<float>(col) * thetaStep;                       // houghsht.cxx:662 (one rounded f32 product: -ffp-contract=off)
+		l.strength = items[i].strength; l.row = static_cast<int32_t>(row); l.col = static_cast<int32_t>(col);
+	}
+}
+
+int compvhip_houghsht_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float rho, float thetaDeg, int threshold, int maxLines,
+                         compvhip_line* lines, size_t cap, size_t* n, int32_t* acc, size_t accStride)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!edges || !n || (cap && !lines) || S < W || !W || !H) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument"); // houghsht.cxx:98
+	if (rho != 1.f) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "SHT requires rho == 1 (use KHT for fractional rho)"); // :306-316
+	if (!(thetaDeg > 0.f) || threshold <= 0) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "theta and threshold must be > 0");
+	if (W < 3 || H < 3 || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
+	*n = 0;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_plan* p = nullptr;
+	int rc = hostPlan(ctx, W, H, thetaDeg, &p);
+	if (rc) return rc;
+	rc = ensureSht(p);
+	if (rc) return rc;
+	if (acc && accStride < p->T) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "accStride < theta bins");
+	HIPCHK(ctx, upload(ctx, ctx->dIn, p->S, edges, S, W, H));
+	HIPCHK(ctx, ctx->dCounts.reserve(ctx, 1));
+	// ALL candidate lines of the frame come back as (strength, cell) pairs in emission order -- the sort and the decode kernel are skipped:
+	// the order the reference returns them in, and which equal-strength lines survive maxLines, is decided by its unstable std::sort
+	int32_t count = 0;
+	for (int attempt = 0; attempt < 2; ++attempt) {
+		rc = planShtImpl(p, ctx->dIn, threshold, 0, nullptr, 0, ctx->dCounts, ctx->stream, true, true);
+		if (rc) return rc;
+		HIPCHK(ctx, hipMemcpyAsync(&count, ctx->dCounts, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+		if (static_cast<size_t>(count) <= p->lineCap) break;
+		// more candidate lines than the device key buffer holds: grow it and redo the line stage
+		rc = ensureLineCap(p, static_cast<size_t>(count));
+		if (rc) return rc;
+	}
+	std::vector<uint32_t> hk(static_cast<size_t>(count)), hv(static_cast<size_t>(count));
+	if (count) {
+		HIPCHK(ctx, hipMemcpyAsync(hk.data(), p->keysA, hk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		HIPCHK(ctx, hipMemcpyAsync(hv.data(), p->valsA, hv.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	std::vector<compvhip_line> all;
+	referenceLineOrder(hk, hv, (1u << p->strengthBits) - 1u, p->T, static_cast<long long>(p->W + p->H), p->thetaStep, all);
+	size_t found = all.size();
+	if (maxLines > 0 && found > static_cast<size_t>(maxLines)) found = static_cast<size_t>(maxLines);
+	*n = found;
+	const size_t ncopy = std::min(found, cap);
+	if (ncopy) memcpy(lines, all.data(), ncopy * sizeof(compvhip_line));
+	if (acc) {
+		HIPCHK(ctx, ctx->dAccOut.reserve(ctx, p->R * p->T));
+		HIPCHK(ctx, launch_sht_acc_transpose(p->acc, static_cast<int>(p->R), static_cast<int>(p->T), p->accPitch, ctx->dAccOut, p->T, ctx->stream));
+		HIPCHK(ctx, download(ctx, acc, accStride * sizeof(int32_t), ctx->dAccOut, p->T * sizeof(int32_t), p->T * sizeof(int32_t), p->R));
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	if (found > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "line buffer too small");
+	return COMPVHIP_OK;
+}
+
+int compvhip_houghsht_segments_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float thetaDeg, const compvhip_line* lines, size_t n,
+                                  int minLength, int maxGap, compvhip_segment* segs, size_t cap, size_t* nSegs)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!edges || !nSegs || (n && !lines) || (cap && !segs) || S < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	if (!(thetaDeg > 0.f) || minLength < 1 || maxGap < 0) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "theta must be > 0, minLength >= 1, maxGap >= 0");
+	if (W < 3 || H < 3 || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
+	*nSegs = 0;
+	size_t R, T;
+	int rc = shtDims(W, H, thetaDeg, &R, &T, nullptr);
+	if (rc) return fail(ctx, rc, "invalid SHT geometry");
+	if (n > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "too many lines");
+	for (size_t i = 0; i < n; ++i)
+		if (lines[i].row < 0 || static_cast<size_t>(lines[i].row) >= R || lines[i].col < 0 || static_cast<size_t>(lines[i].col) >= T)
+			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "a line's (row, col) is not a cell of the R x T accumulator");
+	if (!n) return COMPVHIP_OK;
+	return hostPlaneOp(ctx, edges, W, H, S, thetaDeg, nullptr, 0, [&](compvhip_plan* p) -> int {
+		HIPCHK(ctx, ctx->dSegs.reserve(ctx, cap));
+		HIPCHK(ctx, ctx->dSegCount.reserve(ctx, 1));
+		int rc = stageLists(ctx, lines, n, nullptr, 0);
+		if (rc) return rc;
+		rc = segmentsImpl(p, ctx->dIn, p->S, ctx->dSegLines, ctx->dCounts, n, 0, minLength, maxGap, ctx->dSegs, cap, ctx->dSegCount, ctx->stream);
+		if (rc) return rc;
+		return takeList(ctx, ctx->dSegCount.ptr, ctx->dSegs.ptr, segs, cap, nSegs, "segment buffer too small");
+	});
+}
+
+int compvhip_houghsht_fit_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, float thetaDeg, const compvhip_line* lines, size_t n,
+                             int halfWidth, const compvhip_segment* segs, size_t nSegs, compvhip_line_fit* fits, size_t cap, size_t* nFits, compvhip_line* refined)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!edges || !nFits || (n && !lines) || (cap && !fits) || S < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	if (!(thetaDeg > 0.f) || halfWidth < 0 || halfWidth > kFitMaxHalfWidth) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "theta must be > 0, halfWidth 0 .. 8");
+	if (segs && refined) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "refined lines are a per-line result: segs must be NULL");
+	if (W < 3 || H < 3 || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
+	if (std::max(W, H) > kFitMaxSide) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "line fits need max(W, H) <= 8192 (int64 central moments)");
+	*nFits = 0;
+	size_t R, T;
+	int rc = shtDims(W, H, thetaDeg, &R, &T, nullptr);
+	if (rc) return fail(ctx, rc, "invalid SHT geometry");
+	if (n > static_cast<size_t>(INT32_MAX) || (segs && nSegs > static_cast<size_t>(INT32_MAX))) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "too many lines / segments");
+	for (size_t i = 0; i < n; ++i)
+		if (lines[i].row < 0 || static_cast<size_t>(lines[i].row) >= R || lines[i].col < 0 || static_cast<size_t>(lines[i].col) >= T)
+			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "a line's (row, col) is not a cell of the R x T accumulator");
+	if (segs)
+		for (size_t j = 0; j < nSegs; ++j)
+			if (segs[j].line < 0 || static_cast<size_t>(segs[j].line) >= n) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "a segment's line is not one of the n lines");
+	const size_t nRec = segs ? nSegs : n;
+	if (!n || !nRec) return COMPVHIP_OK;
+	return hostPlaneOp(ctx, edges, W, H, S, thetaDeg, nullptr, 0, [&](compvhip_plan* p) -> int {
+		HIPCHK(ctx, ctx->dFits.reserve(ctx, cap));
+		if (refined) HIPCHK(ctx, ctx->dFitRefined.reserve(ctx, n));
+		HIPCHK(ctx, ctx->dSegCount.reserve(ctx, 1));
+		HIPCHK(ctx, ctx->dFitCount.reserve(ctx, 1));
+		int rc = stageLists(ctx, lines, n, segs, nSegs);
+		if (rc) return rc;
+		rc = fitImpl(p, ctx->dIn, p->S, ctx->dSegLines, ctx->dCounts, n, 0, halfWidth, segs ? ctx->dSegs.ptr : nullptr, ctx->dSegCount, nSegs, cap ? ctx->dFits.ptr : nullptr, cap,
+		             ctx->dFitCount, refined ? ctx->dFitRefined.ptr : nullptr, ctx->stream);
+		if (rc) return rc;
+		if (refined) HIPCHK(ctx, hipMemcpyAsync(refined, ctx->dFitRefined, n * sizeof(compvhip_line), hipMemcpyDeviceToHost, ctx->stream));
+		return takeList(ctx, ctx->dFitCount.ptr, ctx->dFits.ptr, fits, cap, nFits, "fit buffer too small");
+	});
+}
+
+int compvhip_components_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, int connectivity, int minPixels, int32_t* labels, size_t labelStride,
+                           compvhip_component* comps, size_t cap, size_t* nComps)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!edges || !nComps || (cap && !comps) || S < W || (labels && labelStride < W)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	if (W < 3 || H < 3 || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
+	if ((connectivity != 4 && connectivity != 8) || minPixels < 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "connectivity must be 4 or 8, minPixels >= 1");
+	*nComps = 0;
+	return hostPlaneOp(ctx, edges, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p) -> int {
+		if (labels) HIPCHK(ctx, ctx->dCompLabels.reserve(ctx, W * H));
+		HIPCHK(ctx, ctx->dComps.reserve(ctx, cap));
+		HIPCHK(ctx, ctx->dCompCount.reserve(ctx, 1));
+		int rc = componentsImpl(p, ctx->dIn, p->S, connectivity, minPixels, labels ? ctx->dCompLabels.ptr : nullptr, W, cap ? ctx->dComps.ptr : nullptr, cap, ctx->dCompCount, ctx->stream);
+		if (rc) return rc;
+		if (labels) HIPCHK(ctx, download(ctx, labels, labelStride * sizeof(int32_t), ctx->dCompLabels, W * sizeof(int32_t), W * sizeof(int32_t), H));
+		return takeList(ctx, ctx->dCompCount.ptr, ctx->dComps.ptr, comps, cap, nComps, "component buffer too small");
+	});
+}
+
+int compvhip_fast_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, int threshold, int fastType, int nonmax, int maxFeatures, uint8_t* scores,
+                     size_t So, compvhip_corner* corners, size_t cap, size_t* n)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!gray || !n || (cap && !corners) || S < W || (scores && So < W)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	*n = 0;
+	int rc = checkFast(ctx, W, H, fastType);
+	if (rc) return rc;
+	if (W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (7..32767)");
+	return hostPlaneOp(ctx, gray, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p) -> int {
+		HIPCHK(ctx, ctx->dFastCorners.reserve(ctx, cap));
+		HIPCHK(ctx, ctx->dFastCount.reserve(ctx, 1));
+		int rc = compvhip_plan_fast(p, ctx->dIn, threshold, fastType, nonmax, maxFeatures, scores ? ctx->dOut.ptr : nullptr, cap ? ctx->dFastCorners.ptr : nullptr, cap, ctx->dFastCount, ctx->stream);
+		if (rc) return rc;
+		if (scores) HIPCHK(ctx, download(ctx, scores, So, ctx->dOut, p->S, W, H));
+		return takeList(ctx, ctx->dFastCount.ptr, ctx->dFastCorners.ptr, corners, cap, n, "corner buffer too small");
+	});
+}
+
+int compvhip_threshold_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double threshold, uint8_t* out, size_t So)
+{
+	int rc = checkImage(ctx, in, W, H, S, out, So);
+	if (rc) return rc;
+	if (!(threshold >= 0.0)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "threshold < 0"); // compv_image_threshold.cxx:120
+	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p) { return compvhip_plan_threshold(p, ctx->dIn, threshold, nullptr, ctx->dOut, ctx->stream); });
+}
+
+int compvhip_threshold_adaptive_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, size_t blockSize, double delta, double maxVal, int invert,
+                                   uint8_t* out, size_t So)
+{
+	int rc = checkImage(ctx, in, W, H, S, out, So);
+	if (rc) return rc;
+	rc = checkAdaptive(ctx, W, H, blockSize, delta, maxVal);
+	if (rc) return rc;
+	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So,
+	                   [&](compvhip_plan* p) { return compvhip_plan_threshold_adaptive(p, ctx->dIn, blockSize, delta, maxVal, invert, ctx->dOut, ctx->stream); });
+}
+
+int compvhip_morph_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint8_t* strel, size_t sw, size_t sh, int op, int border, uint8_t* out,
+                      size_t So)
+{
+	int rc = checkImage(ctx, in, W, H, S, out, So);
+	if (rc) return rc;
+	MorphArgs a;
+	rc = morphPrepare(ctx, W, H, strel, sw, sh, op, border, COMPVHIP_MORPH_KERNEL_AUTO, &a);
+	if (rc) return rc;
+	// the host planes overlap when their byte ranges do (compv_math_morph.cxx:140-145: the reference reallocates; here the caller is told)
+	const uint8_t* inEnd = in + (H - 1) * S + W; const uint8_t* outEnd = out + (H - 1) * So + W;
+	if (in < outEnd && out < inEnd) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap");
+	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p) { return compvhip_plan_morph(p, ctx->dIn, strel, sw, sh, op, border, ctx->dOut, ctx->stream); });
+}
+
+int compvhip_match_hamming_u8(compvhip_ctx* ctx, const uint8_t* query, size_t Q, size_t queryStride, const uint8_t* train, size_t T, size_t trainStride, size_t cols,
+                              int knn, compvhip_match* matches, size_t matchStride, size_t* rows)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!query || !train || !matches || !rows || !Q || !T || queryStride < cols || trainStride < cols || matchStride < Q) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	if (cols < 1 || cols > 4 * static_cast<size_t>(kMatchMaxDwords)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "cols must be in 1..128");
+	*rows = 0;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t S = alignUp(cols, 4);
+	compvhip_matcher* m = nullptr;
+	int rc = compvhip_matcher_create(ctx, S, Q, T, 1, knn, &m);
+	if (rc) return rc;
+	uint8_t* dDesc = nullptr; compvhip_match* dMatches = nullptr;
+	const size_t nRows = std::min<size_t>(static_cast<size_t>(knn), T);
+	do {
+		if (dmalloc(ctx, &dDesc, (Q + T) * S) != hipSuccess || dmalloc(ctx, &dMatches, static_cast<size_t>(knn) * Q) != hipSuccess) { rc = fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "match staging"); break; }
+		hipError_t e = hipMemsetAsync(dDesc, 0, (Q + T) * S, ctx->stream);          // the zero bytes that pad a row to a dword multiple
+		if (e == hipSuccess) e = hipMemcpy2DAsync(dDesc, S, query, queryStride, cols, Q, hipMemcpyHostToDevice, ctx->stream);
+		if (e == hipSuccess) e = hipMemcpy2DAsync(dDesc + Q * S, S, train, trainStride, cols, T, hipMemcpyHostToDevice, ctx->stream);
+		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "descriptor upload", e); break; }
+		// not compvhip_matcher_knn: the reference's order among equal distances is not the (distance, index) order of the device call
+		const MatchSliceArgs a = matchForward(m, dDesc, S, nullptr, dDesc + Q * S, S, nullptr, 0, dMatches);
+		e = launch_match_reference(a, 1, ctx->stream);
+		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "launch_match_reference", e); break; }
+		e = hipMemcpy2DAsync(matches, matchStride * sizeof(compvhip_match), dMatches, Q * sizeof(compvhip_match), Q * sizeof(compvhip_match), nRows, hipMemcpyDeviceToHost, ctx->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "match download", e); break; }
+		*rows = nRows;
+	} while (0);
+	(void)hipStreamSynchronize(ctx->stream);
+	dfree(ctx, dDesc); dfree(ctx, dMatches);
+	compvhip_matcher_destroy(m);
+	return rc;
+}

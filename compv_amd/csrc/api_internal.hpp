@@ -1,0 +1,361 @@
+// api_internal.hpp -- what the translation units of the C ABI's host side (api*.cpp) share: the structs behind the opaque handles, error and
+// allocation helpers, per-kernel timing, and the few functions that are called across files (namespace compvhip_api: not exported).
+#pragma once
+#include "../../include/compv_hip.h"
+#include "kernels.hpp"
+#include "kht.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+using namespace compvhip;
+
+namespace compvhip_api {
+void countLive(compvhip_ctx* ctx, long delta);   // ctx->live += delta (defined below compvhip_ctx)
+
+template <typename T>
+hipError_t dmalloc(compvhip_ctx* ctx, T** p, size_t count)
+{
+	*p = nullptr;
+	if (!count) return hipSuccess;
+	hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
+	if (e == hipSuccess && ctx) countLive(ctx, 1);
+	return e;
+}
+template <typename T>
+void dfree(compvhip_ctx* ctx, T*& p)
+{
+	if (p) { (void)hipFree(p); if (ctx) countLive(ctx, -1); p = nullptr; }
+}
+
+// Growable device memory: a pointer and its capacity in elements, one hipMalloc through dmalloc / dfree (ctx->live counts it once).  A request that fits
+// reuses the buffer; after a failed allocation it is {nullptr, 0}, so a later, smaller request allocates again instead of trusting a stale capacity.
+template <typename T>
+struct DevBuf {
+	T* ptr = nullptr; size_t cap = 0;
+	operator T*() const { return ptr; }
+	hipError_t reserve(compvhip_ctx* ctx, size_t n)   // room for n elements: exactly n when it has to allocate
+	{
+		if (cap >= n) return hipSuccess;
+		release(ctx);
+		const hipError_t e = dmalloc(ctx, &ptr, n);
+		if (e == hipSuccess) cap = n;
+		return e;
+	}
+	// n + 25 % + 1024 when it has to allocate (frames of a stream resemble each other: no reallocation for a slightly denser one)
+	hipError_t grow(compvhip_ctx* ctx, size_t n) { return cap >= n ? hipSuccess : reserve(ctx, n + n / 4 + 1024); }
+	void release(compvhip_ctx* ctx) { dfree(ctx, ptr); cap = 0; }
+};
+// the same for pinned host memory (not counted in ctx->live)
+template <typename T>
+struct PinBuf {
+	T* ptr = nullptr; size_t cap = 0;
+	operator T*() const { return ptr; }
+	hipError_t reserve(size_t n)
+	{
+		if (cap >= n) return hipSuccess;
+		release();
+		const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T));
+		if (e == hipSuccess) cap = n; else ptr = nullptr;
+		return e;
+	}
+	hipError_t grow(size_t n) { return cap >= n ? hipSuccess : reserve(n + n / 4 + 1024); }
+	void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; cap = 0; }
+};
+} // namespace compvhip_api
+using namespace compvhip_api;   // (this header serves the api*.cpp files only)
+
+constexpr int kMaxRounds = 4096;       // hysteresis round flag slots (a multiple of 4); a frame that needs more rounds reuses them (enqueueResolve)
+constexpr int kSpecRounds = 3;         // rounds enqueued speculatively between two convergence checks
+constexpr size_t kMinLineCap = 1u << 16;  // per-frame line-key slots: max(caller's lineCap, 65536), clamped to R*T (include/compv_hip.h, compvhip_plan_houghsht)
+constexpr int kAsyncDepth = 4;            // outstanding compvhip_plan_pipeline_async steps per plan
+constexpr size_t kMaxTimeline = 4096;     // timing entries kept while nobody reads them (asynchronous steps)
+
+// device tables of the canonical KHT path's line fields (khtCanonTables), built once per geometry
+struct KhtCanonTabs {
+	float* rho = nullptr; float* theta = nullptr;
+	size_t W = 0, H = 0; double dRho = 0.0, dTheta = 0.0;
+};
+
+// Device + host scratch of ONE KHT frame in flight: the context owns one for its host entry point, a plan one per worker thread of
+// compvhip_plan_houghkht (every worker has its own HIP stream; nothing in here is shared between threads).
+struct KhtScratch {
+	hipStream_t stream = nullptr; bool ownStream = false;
+	DevBuf<int32_t> counts; DevBuf<KhtVoteParams> params; DevBuf<KhtCell> cells; DevBuf<int> cellCount;
+	DevBuf<KhtPoint> pts;
+	DevBuf<KhtSpan> spans, scratch; DevBuf<KhtSubdivFrame> stack; DevBuf<KhtKernel> kernelsDev;   // one slot per possible cluster, all four
+	DevBuf<KhtStringDesc> strings; DevBuf<uint32_t> counts32;                                      // one per string (counts32: + 2)
+	KhtBitPlane plane;                                         // the linker's working copy (zero border, destroyed by the walk)
+	PinBuf<KhtPoint> linked;                                   // points of the strings, string after string: PINNED host memory, written by the linker, uploaded without staging
+	KhtPeaksWork peaks;                                        // sort records, visited map, axes of the peak stage
+	std::vector<KhtCell> cellsHost;                            // the vote cells of the frame, downloaded
+	KhtCanonTabs tabs; DevBuf<KhtLine> canonLines; DevBuf<int32_t> canonCount;   // canonical order: the frame's sorted lines, their count
+	double stageMs[6] = {};   // link, subdivide (GPU), statistics (GPU), prune + Gmin, vote + peaks (GPU), sort + sweep of the last call
+	std::string err;
+};
+
+struct KhtBatchFrame {      // host state of one frame of the batch; persists from call to call (vectors keep their capacity)
+	KhtBitPlane plane; size_t most = 0, ptsOff = 0, nPts = 0;
+	std::vector<KhtRange> strings; size_t slotBase = 0, slots = 0;
+	uint32_t nClusters = 0;
+	std::vector<KhtKernel> kernels; double hmax = 0.0, GS = 1.0; bool haveGS = false;
+	std::vector<KhtVoteParams> params; size_t paramsBase = 0;
+	std::vector<KhtCell> cells; size_t cellOff = 0; int cellCount = 0;
+	KhtPeaksWork peaks; std::vector<KhtLine> out;
+	double ms[6] = {};
+	int code = COMPVHIP_OK; std::string err;
+};
+struct KhtBatchState {
+	hipStream_t stream = nullptr;
+	DevBuf<uint32_t> dBits; PinBuf<uint32_t> hostBits;                                 // [frames of a group][wpr * H]: device / pinned
+	std::vector<hipEvent_t> ready;                                                     // frame f's bit plane has arrived
+	PinBuf<KhtPoint> linked; DevBuf<KhtPoint> pts;                                     // points of every frame's strings: pinned arena (the linkers write it) / device
+	DevBuf<KhtStringDesc> strings; DevBuf<uint32_t> counts32; PinBuf<KhtStringDesc> stringsHost;
+	DevBuf<uint32_t> totals;                                                           // device [kKhtBatch + 1]: clusters per frame, truncation flag
+	DevBuf<KhtSpan> spans, scratch; DevBuf<KhtSubdivFrame> stack; DevBuf<KhtKernel> kernelsDev;
+	PinBuf<KhtKernel> kernelsHost;
+	DevBuf<int32_t> counts;
+	DevBuf<KhtVoteParams> params; PinBuf<KhtVoteParams> paramsHost;
+	DevBuf<KhtCell> cells; DevBuf<int> cellCount; PinBuf<KhtCell> cellsHost;
+	KhtCanonTabs tabs; DevBuf<KhtLine> canonLines; DevBuf<int32_t> canonCounts;        // canonical order: [frames][cap] sorted lines, [kKhtBatch] counts (device)
+	PinBuf<KhtLine> canonLinesHost;
+	std::vector<KhtBatchFrame> frames;
+	hipEvent_t syncEv = nullptr;   // blocking-sync event: a controller that waits for a GPU stage SLEEPS (hipStreamSynchronize spins on a CPU of the quota the workers need)
+	double stageMs[6] = {};   // of the groups this state handled in the current call
+};
+
+struct compvhip_ctx {
+	int device = 0;
+	std::string err;
+	std::atomic<long> live{0};   // hipMalloc / hipFree balance; KHT workers of a plan allocate from their own threads
+	hipStream_t stream = nullptr;      // stream of the host entry points
+	compvhip_plan* hostPlan = nullptr; // single-frame plan cached for the host entry points
+	DevBuf<uint8_t> dIn, dOut;         // device staging of the host entry points (bytes)
+	DevBuf<uint8_t> dPacked;           // packed-pixel staging of compvhip_grayscale_u8
+	DevBuf<uint32_t> dHist;            // [256] histogram + 1 result word of compvhip_otsu_u8
+	DevBuf<int32_t> dCounts, dAccOut;
+	DevBuf<compvhip_line> dSegLines;   // staging of compvhip_houghsht_segments_u8: the caller's lines ...
+	DevBuf<compvhip_segment> dSegs;    // ... and the segments; the count travels through dCounts
+	DevBuf<int32_t> dSegCount;
+	DevBuf<compvhip_line_fit> dFits;   // staging of compvhip_houghsht_fit_u8: the records, their number ...
+	DevBuf<int32_t> dFitCount;
+	DevBuf<compvhip_line> dFitRefined; // ... and the refined lines (lines and segments travel through dSegLines / dSegs)
+	DevBuf<int32_t> dCompLabels;       // staging of compvhip_components_u8: the label map (W * H) ...
+	DevBuf<compvhip_component> dComps; // ... the records ...
+	DevBuf<int32_t> dCompCount;        // ... and their number
+	DevBuf<compvhip_corner> dFastCorners;   // staging of compvhip_fast_u8: the records (the score map travels through dOut) ...
+	DevBuf<int32_t> dFastCount;             // ... and their number
+	KhtScratch kht;                    // KHT scratch of the host entry point (compvhip_houghkht_u8)
+};
+
+struct TimingEntry { const char* name; hipEvent_t a, b; };
+// per-kernel timing of the last call of a plan or a matcher: event pairs around the launches, the events pooled and reused
+struct TimingState {
+	int timing = 0; // plan: 0 off, 1 every kernel, 2 canny_tile + sht_vote, 3 sht_vote only, 4 canny_tile only; matcher: 0 off, 1 every kernel
+	std::vector<hipEvent_t> eventPool;
+	std::vector<TimingEntry> timeline;
+	std::vector<std::string> timingNames; std::vector<float> timingMs;
+};
+
+// one step of the device-resident pipeline: [grayscale ->] Canny -> SHT [-> toCartesian] (compvhip_plan_pipeline{,_async,_ex})
+struct StepParams {
+	const uint8_t* d_in = nullptr; float tLow = 0.f, tHigh = 0.f; int threshold = 0, maxLines = 0;
+	int ksize = 3, thresholdType = COMPVHIP_CANNY_THRESHOLD_COMPARE_TO_GRADIENT, pixfmt = COMPVHIP_FMT_Y;
+	uint8_t* d_gray = nullptr; int32_t* d_otsu = nullptr; float* d_cart = nullptr;
+	uint8_t* d_edges = nullptr; compvhip_line* d_lines = nullptr; size_t lineCap = 0; int32_t* d_counts = nullptr;
+};
+
+struct compvhip_plan : TimingState {
+	compvhip_ctx* ctx = nullptr;
+	size_t W = 0, H = 0, S = 0, frames = 0;
+	float thetaDeg = 1.f;
+	// canny
+	int tilesX = 0, tilesY = 0, wb = 0;
+	size_t bitsFrameStride = 0;
+	uint32_t* ebits = nullptr; uint32_t* ubits = nullptr;
+	int* counters = nullptr;  // ONE device allocation zeroed by ONE memset per step: [edgeCounts frames][lineCounts frames][tileCounts frames*tiles][blockCounts frames*lineBlocks][frameTotals frames*kFrameSlot][lineTotal kFrameSlot][flags kMaxRounds]
+	size_t nCounts = 0;       // ints in front of the flags
+	int* flags = nullptr; int* hFlags = nullptr; // device (inside counters) / pinned host (kAsyncDepth + 1 slots)
+	int* frameTotals = nullptr; unsigned int* lineTotal = nullptr; // device (inside counters): NMS survivors per frame (one per 128-byte line) / key slots in use
+	unsigned int* hTotals = nullptr;             // pinned host (behind hFlags): lineTotal of the synchronous call (slot 0) and of the asynchronous steps (1 + ticket)
+	// The line sort covers the key slots that exist.  A synchronous step reads their number before it enqueues the sort; an asynchronous step cannot, so it
+	// sorts a range predicted from the totals of the plan's last steps (0 = none seen yet: the whole capacity) -- compvhip_plan_wait compares with the step's
+	// real total and replays the step when the prediction was too small.
+	unsigned int recentTotals[8] = {}; int recentN = 0;
+	// speculative hysteresis rounds of a step: what the plan's last 8 asynchronous steps needed (the first round that changed nothing, inclusive), at least 2, at
+	// most kSpecRounds; a step that needs more is replayed by compvhip_plan_wait and teaches the plan
+	int specRounds = kSpecRounds; unsigned char recentRounds[8] = {}; int recentRoundsN = 0;
+	int* hRoundsDev = nullptr; int* stepHostSlot = nullptr;   // hRounds as the device sees it / the slot of the asynchronous step being enqueued (nullptr otherwise)
+	int* hRounds = nullptr;                      // pinned host, per ticket: [0] the step's line total (the last int of its counter slot ... see runStepAsync), [kFrameSlot .. +3] its first 4 round flags
+	int roundsUsed = 0;
+	int maxRounds = kMaxRounds; // flag slots in use (COMPVHIP_RESOLVE_WRAP lowers it: tests of the slot reuse)
+	bool countersFresh = false; // the step's memset already zeroed the edge/line counts (no second fill in front of the SHT stage)
+	int2* thrDev = nullptr; unsigned int* sums = nullptr;
+	uint8_t* dirty = nullptr;  // per-workgroup change flags of the resolve rounds
+	uint8_t* patchOut = nullptr; uint8_t* copyBack = nullptr; // byte map the tile kernel writes and the resolve rounds patch / in-place target of the last Canny call
+	uint8_t* grayTmp = nullptr; // luma plane of a packed-input step when the caller does not want it (compvhip_plan_pipeline_ex)
+	uint8_t* tmpOut = nullptr; // aliasing (in == out) scratch: a tile may still read the row halo a neighbour has overwritten
+	bool bitsValid = false;
+	// sht
+	bool shtReady = false;
+	size_t R = 0, T = 0; float thetaStep = 0.f; int accPitch = 0;
+	uint8_t* blurTmp = nullptr;                       // u8 intermediate of the fixed-point convolution
+	uint32_t* hist = nullptr; int32_t* otsu = nullptr; // pre-processing scratch: partial histograms, [frames] Otsu level
+	float* cosT = nullptr; float* invSinT = nullptr; // toCartesian tables: cosf(theta_col), 1/sinf(theta_col)
+	int32_t* sinQ = nullptr; int32_t* cosQ = nullptr;
+	uint32_t* edges = nullptr; size_t edgeCap = 0; int* edgeCounts = nullptr;
+	uint16_t* acc = nullptr; size_t accFrameStride = 0;
+	uint32_t* keysA = nullptr; uint32_t* keysB = nullptr; uint32_t* valsA = nullptr; uint32_t* valsB = nullptr; size_t lineCap = 0; int* lineCounts = nullptr;
+	int2* reach = nullptr;                       // [T] accumulator rows the windows of a theta cover
+	int2* nmsRange = nullptr;                    // [column groups of the NMS] accumulator rows the windows can reach
+	uint8_t* nmsFlags = nullptr;                 // NMS survivors (flag planes)
+	int* blockCounts = nullptr; int lineBlocks = 0;   // NMS survivors per 64 accumulator rows (part of `counters`)
+	void* sortTemp = nullptr; size_t sortTempBytes = 0;
+	DevBuf<int32_t> segPerLine;   // line segments (sht_segments_kernels.hip): segments per line, then their prefix sums
+	// connected components (components_kernels.hip), allocated on first use: survivors per row [frames][H]; the packed copy of a byte edge map
+	// [frames][H][wb]; parent words [frames][H][W] of the calls without a label map (with one, the parent words live in it)
+	int32_t* compRows = nullptr; uint32_t* compBits = nullptr; int32_t* compParent = nullptr;
+	uint8_t* morphTmp = nullptr;                 // thresholding / morphology (morph_kernels.hip), allocated on first use: the u8 plane [frames][H][S] between the two basic operations of an OPEN / CLOSE, and the out-of-place target of an in-place adaptive threshold
+	// FAST corners (fast_kernels.hip), allocated on first use: [frames][H] corners per row, [frames][H] their scan, [frames][256] score histogram, [frames] cut
+	// level -- one allocation; and the score map [frames][H][S] of the calls that do not want one
+	int* fastWork = nullptr; uint8_t* fastScores = nullptr;
+	int strengthBits = 16, keyBits = 0;
+	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
+	uint16_t* chunkHist = nullptr; uint32_t* strengthStart = nullptr; int sortChunks = 0; bool deviceSort = false;
+	// voting over image tiles (planned at plan creation: the per-tile edge counters live in `counters`)
+	bool voteTiles = false;                      // the tile grid exists
+	ShtTileArgs vt = {};                         // geometry + device tables
+	std::vector<int32_t> vtKt, vtRowBase;        // host copies of the [tiles][T] tables
+	int32_t* dKt = nullptr; int32_t* dRowBase = nullptr; uint8_t* partLo = nullptr; uint8_t* partHi = nullptr; uint8_t* colFlag = nullptr; int* tileCounts = nullptr;
+	// batched KHT (compvhip_plan_houghkht): one scratch set + stream per worker thread, stage clocks of the last call
+	std::vector<KhtBatchState*> khtBatch;        // device / pinned buffers and per-frame host state of the batched call: one per group of frames in flight
+	std::vector<std::unique_ptr<KhtPeaksWork>> khtWork;   // sort + sweep workspace (axes, 1.6 MB visited map at 4K) of WORKER w: it stays in that core's cache from frame to frame
+	double khtStageMs[6] = {}; double khtWallMs = 0.0; int khtThreads = 0;
+	// asynchronous steps (compvhip_plan_pipeline_async / compvhip_plan_wait)
+	// seq: enqueue order; replay: an EARLIER step of the plan was replayed after this one ran -- its outputs may have been overwritten
+	struct AsyncStep { bool used = false; bool replay = false; uint64_t seq = 0; hipEvent_t done = nullptr; hipStream_t stream = nullptr; StepParams sp; size_t sortN = 0; int rounds = 0; } steps[kAsyncDepth];
+	uint64_t stepSeq = 0;
+};
+
+// brute-force matcher (match_kernels.hip): every buffer is allocated by compvhip_matcher_create
+struct compvhip_matcher : TimingState {
+	compvhip_ctx* ctx = nullptr;
+	int descDwords = 0, queryCap = 0, trainCap = 0, pairs = 0, knn = 0;
+	uint32_t* partial = nullptr;        // keys of the slice kernel: max of the forward ([pairs][train slices][knn][queryCap]) and the reverse ([pairs][query slices][trainCap]) run
+	compvhip_match* reverse = nullptr;  // [pairs][trainCap]: best query of every train row (cross check)
+};
+namespace compvhip_api {
+
+inline void countLive(compvhip_ctx* ctx, long delta) { ctx->live += delta; }
+
+inline int fail(compvhip_ctx* ctx, int code, const char* what, hipError_t e = hipSuccess)
+{
+	if (ctx) {
+		ctx->err = what ? what : "";
+		if (e != hipSuccess) { ctx->err += ": "; ctx->err += hipGetErrorString(e); }
+	}
+	return code;
+}
+
+#define HIPCHK(ctx, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail((ctx), COMPVHIP_E_HIP, #call, e__); } while (0)
+
+inline size_t alignUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// timing mode 1 = every kernel; 2 = only the two kernels bench.py prices against the roofline (an event pair costs a few
+// microseconds of stream time, ~0.1 ms per step when wrapped around all ~13 launches of the pipeline)
+inline bool stampWanted(const compvhip_plan* p, const char* name)
+{
+	if (p->timing == 1) return true;
+	if (p->timing == 2) return !strcmp(name, "canny_tile_kernel") || !strcmp(name, "sht_vote_kernel");
+	if (p->timing == 3) return !strcmp(name, "sht_vote_kernel");
+	if (p->timing == 4) return !strcmp(name, "canny_tile_kernel");
+	return false;
+}
+
+inline bool takeEvent(TimingState* p, hipEvent_t* e)
+{
+	if (!p->eventPool.empty()) { *e = p->eventPool.back(); p->eventPool.pop_back(); return true; }
+	return hipEventCreate(e) == hipSuccess;
+}
+
+struct Stamp {
+	TimingState* p; hipStream_t s; size_t idx; bool on;
+	Stamp(compvhip_plan* plan, hipStream_t stream, const char* name) : Stamp(plan, stream, name, stampWanted(plan, name)) {}
+	Stamp(compvhip_matcher* matcher, hipStream_t stream, const char* name) : Stamp(matcher, stream, name, matcher->timing != 0) {}
+	Stamp(TimingState* state, hipStream_t stream, const char* name, bool wanted) : p(state), s(stream), idx(0), on(wanted)
+	{
+		if (!on) return;
+		TimingEntry t; t.name = name;
+		if (!takeEvent(p, &t.a)) { on = false; return; }
+		if (!takeEvent(p, &t.b)) { p->eventPool.push_back(t.a); on = false; return; }
+		(void)hipEventRecord(t.a, s);
+		p->timeline.push_back(t);
+		idx = p->timeline.size() - 1;
+	}
+	~Stamp() { if (on) (void)hipEventRecord(p->timeline[idx].b, s); }
+};
+
+inline void timelineClear(TimingState* p)
+{
+	for (auto& t : p->timeline) { p->eventPool.push_back(t.a); p->eventPool.push_back(t.b); } // events are reused, not re-created
+	p->timeline.clear();
+}
+
+inline void timelineCollect(TimingState* p)
+{
+	p->timingNames.clear(); p->timingMs.clear();
+	for (auto& t : p->timeline) {
+		float ms = 0.f;
+		if (hipEventElapsedTime(&ms, t.a, t.b) != hipSuccess) ms = -1.f;
+		p->timingNames.push_back(t.name); p->timingMs.push_back(ms);
+	}
+	timelineClear(p);
+}
+
+// ---- functions called across files ----
+// api.cpp
+int shtDims(size_t W, size_t H, float thetaDeg, size_t* R, size_t* T, float* step);
+int ensureSht(compvhip_plan* p);
+int ensureLineCap(compvhip_plan* p, size_t cap);
+int validateCannyParams(compvhip_ctx* ctx, float tLow, float tHigh, int ksize, int type, int* lo, int* hi);
+int pixfmtBytes(int fmt);
+int checkFxpKernel(compvhip_ctx* ctx, size_t W, size_t H, const uint16_t* vt, const uint16_t* hz, size_t k);
+// How many key slots the line sort covers (the reference sorts lines.size() elements, houghsht.cxx:241-249):
+//   kSortAll   the whole capacity, unused slots zeroed by sht_lines_kernel -- the stream-ordered entry point, which may not wait for the device;
+//   kSortExact the slots in use, read back behind sht_lines_kernel (one stream synchronisation) -- the synchronous step, which ends in one anyway;
+//   otherwise  that many slots (a prediction: the asynchronous step; the caller checks it against the real total later).
+constexpr size_t kSortAll = ~static_cast<size_t>(0), kSortExact = kSortAll - 1;
+int planShtImpl(compvhip_plan* p, const uint8_t* d_edges, int threshold, int maxLines, compvhip_line* d_lines, size_t lineCap, int32_t* d_counts,
+                hipStream_t st, bool clearTimeline, bool pairsOnly = false, size_t sortN = kSortAll);
+// api_features.cpp
+constexpr size_t kFitMaxSide = 8192;   // the central moments stay below 2^63 up to here
+constexpr int kFitMaxHalfWidth = 8;
+int segmentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap,
+                 int maxLines, int minLength, int maxGap, compvhip_segment* d_segs, size_t segCap, int32_t* d_segCounts, hipStream_t st);
+int fitImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap, int maxLines,
+            int halfWidth, const compvhip_segment* d_segs, const int32_t* d_segCounts, size_t segCap, compvhip_line_fit* d_fits, size_t fitCap,
+            int32_t* d_fitCounts, compvhip_line* d_refined, hipStream_t st);
+int componentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, int connectivity, int minPixels, int32_t* d_labels, size_t labelStride,
+                   compvhip_component* d_comps, size_t compCap, int32_t* d_compCounts, hipStream_t st);
+int checkAdaptive(compvhip_ctx* ctx, size_t W, size_t H, size_t blockSize, double delta, double maxVal);
+int morphPrepare(compvhip_ctx* ctx, size_t W, size_t H, const uint8_t* strel, size_t sw, size_t sh, int op, int border, int kernel, MorphArgs* a);
+int checkFast(compvhip_ctx* ctx, size_t W, size_t H, int fastType);
+MatchSliceArgs matchForward(const compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
+                            const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches);
+// api_kht.cpp
+size_t hostCpuBudget();
+void khtScratchFree(compvhip_ctx* ctx, KhtScratch& k);
+void khtBatchFree(compvhip_ctx* ctx, KhtBatchState* b);
+} // namespace compvhip_api

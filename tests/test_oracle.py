@@ -145,7 +145,7 @@ def _pack_lines(rho, theta, strength):
 
 def test_sht_tie_order_runtime_is_the_fixtures_runtime():
     """The order of equal-strength lines is "what this C++ runtime's std::sort does", in the reference and in compvhip_houghsht_u8 /
-    compvhip_houghkht_u8 that reproduce it (api.cpp referenceLineOrder, kht_host.cpp khtPeaks).  The fixtures record the libstdc++ they
+    compvhip_houghkht_u8 that reproduce it (api_host.cpp referenceLineOrder, kht_host.cpp khtPeaks).  The fixtures record the libstdc++ they
     were generated with; on another runtime they would have to be regenerated (with the reference rebuilt against it): fail loudly."""
     from oracle_bindings import libstdcxx_version
     want = _sht_order_golden()["_runtime"]["libstdcxx"]
