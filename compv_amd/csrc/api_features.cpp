@@ -2,6 +2,15 @@
 // thresholding and morphology, FAST corners, brute-force matching.
 #include "api_internal.hpp"
 
+// what the segment and the fit kernels read alike: the edge pixels, the vote's tables, the lines
+static void fillLineSet(ShtLineSetArgs& a, const compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, const compvhip_line* d_lines, const int32_t* d_counts,
+                        size_t lineCap, size_t nLines)
+{
+	a.ebits = p->ebits; a.edges = d_edges; a.bitsFrameStride = p->bitsFrameStride; a.edgeFrameStride = edgeStride * p->H; a.wb = p->wb; a.S = static_cast<int>(edgeStride);
+	a.sinQ = p->sinQ; a.cosQ = p->cosQ; a.lines = d_lines; a.lineCounts = d_counts; a.lineCap = lineCap; a.nLines = static_cast<int>(nLines);
+	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.R = static_cast<int>(p->R); a.T = static_cast<int>(p->T); a.barrier = static_cast<int>(p->W + p->H);
+}
+
 // ---- Hough line segments (sht_segments_kernels.hip; definition in include/compv_hip.h) ---------------------------------------
 // edges / edgeStride: byte maps [frames][H][edgeStride], or nullptr = the plan's bit masks
 int compvhip_api::segmentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap,
@@ -19,9 +28,7 @@ int compvhip_api::segmentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t 
 	HIPCHK(ctx, p->segPerLine.reserve(ctx, nLines * p->frames));
 	if (p->timing) timelineClear(p);
 	ShtSegArgs a;
-	a.ebits = p->ebits; a.edges = d_edges; a.bitsFrameStride = p->bitsFrameStride; a.edgeFrameStride = edgeStride * p->H; a.wb = p->wb; a.S = static_cast<int>(edgeStride);
-	a.sinQ = p->sinQ; a.cosQ = p->cosQ; a.lines = d_lines; a.lineCounts = d_counts; a.lineCap = lineCap; a.nLines = static_cast<int>(nLines);
-	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.R = static_cast<int>(p->R); a.T = static_cast<int>(p->T); a.barrier = static_cast<int>(p->W + p->H);
+	fillLineSet(a, p, d_edges, edgeStride, d_lines, d_counts, lineCap, nLines);
 	a.minLength = minLength; a.maxGap = maxGap; a.perLine = p->segPerLine; a.segs = d_segs; a.segCap = segCap; a.segCounts = d_segCounts; a.frame0 = 0;
 	const int frames = static_cast<int>(p->frames);
 	{ Stamp s(p, st, "sht_segments_count_kernel"); HIPCHK(ctx, launch_sht_segments(a, frames, 0, st)); }
@@ -62,9 +69,7 @@ int compvhip_api::fitImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeS
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "line / segment capacity beyond 2^31");
 	if (p->timing) timelineClear(p);
 	ShtFitArgs a;
-	a.ebits = p->ebits; a.edges = d_edges; a.bitsFrameStride = p->bitsFrameStride; a.edgeFrameStride = edgeStride * p->H; a.wb = p->wb; a.S = static_cast<int>(edgeStride);
-	a.sinQ = p->sinQ; a.cosQ = p->cosQ; a.lines = d_lines; a.lineCounts = d_counts; a.lineCap = lineCap; a.nLines = static_cast<int>(nLines);
-	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.R = static_cast<int>(p->R); a.T = static_cast<int>(p->T); a.barrier = static_cast<int>(p->W + p->H);
+	fillLineSet(a, p, d_edges, edgeStride, d_lines, d_counts, lineCap, nLines);
 	a.halfWidth = halfWidth; a.segs = d_segs; a.segCounts = d_segCounts; a.segCap = d_segs ? segCap : 0;
 	a.fits = d_fits; a.fitCap = fitCap; a.fitCounts = d_fitCounts; a.refined = d_refined; a.frame0 = 0;
 	{ Stamp s(p, st, "sht_fit_kernel"); HIPCHK(ctx, launch_sht_fit(a, static_cast<int>(p->frames), st)); }

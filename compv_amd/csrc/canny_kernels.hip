@@ -16,8 +16,7 @@
 //   (register-resident column sweeps); repeated (device flags, no data-dependent host work) until no band changes.  The
 //   fixed point "all pixels with g_nms > tLow 8-connected to a pixel with g_nms > tHigh" is unique, hence
 //   bit-exact whatever the propagation order (the reference's own multithreaded bands race the same way).
-#include "stencil.hpp"
-#include "kernels.hpp"
+#include "device.hpp"
 
 #include <cstdlib>
 #include <cstring>

@@ -41,8 +41,7 @@
 // 240 = 15 half-words) but own no pixels.  Every input byte is fetched once per tile (+ 4/64 row halo, + 16/240 column halo).
 // 4 pixels per lane: <= 64 VGPRs and 4.9 KB of LDS per wave put 8 waves on every SIMD (one wave issues an instruction only every
 // ~8.7 cycles whatever its type, so the issue rate of a SIMD is resident waves / 8.7 until a pipe saturates).
-#include "stencil.hpp"
-#include "kernels.hpp"
+#include "device.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -78,12 +77,6 @@ constexpr int kLdsBytes = kXch + 2 * 256 + 8;          // 4936 B per wave: 32 wa
 constexpr uint32_t kBias1k = 0x04000400u;    // +1024 per half: gx, gy
 constexpr uint32_t kBias2k = 0x08000800u;    // +2048 per half: g' = g + 2048 (and "2 * bias" of the absolute value)
 
-__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b)
-{
-	uint32_t d;
-	asm("v_pk_max_u16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-	return d;
-}
 __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) // (mask & a) | (~mask & b)
 {
 	uint32_t d;
@@ -97,10 +90,6 @@ __device__ __forceinline__ uint32_t twice(uint32_t x)
 	asm("v_add_u32 %0, %1, %1" : "=v"(d) : "v"(x));
 	return d;
 }
-// three-operand forms (one instruction each; the constants ride in SGPRs -- VOP3 takes no literal on gfx9)
-__device__ __forceinline__ uint32_t lshl1_add(uint32_t a, uint32_t b) { uint32_t d; asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }   // 2a + b
-__device__ __forceinline__ uint32_t xad(uint32_t a, uint32_t sk, uint32_t c) { uint32_t d; asm("v_xad_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(sk), "v"(c)); return d; }   // (a ^ k) + c
-__device__ __forceinline__ uint32_t add3(uint32_t a, uint32_t b, uint32_t sk) { uint32_t d; asm("v_add3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(sk)); return d; }
 // nibble -> four bytes {0, 0xff}
 __device__ __forceinline__ uint32_t nibble_bytes(uint32_t nib)
 {
@@ -218,12 +207,12 @@ __global__ __launch_bounds__(WAVES * 64, (KS == 3 ? 8 : 7)) void canny_swar_tile
 	// 5x5, per input row and pixel pair: H1 + 1024 = (I[x-2] + 2 I[x-1]) + 1023 - (2 I[x+1] + I[x+2]) + 1 and H2 = (I[x-2] + I[x+2]) + 4 (I[x-1] + I[x] + I[x+1]) + 2 I[x]
 	// from the five pairs at distances -2 .. +2 (every sum stays below 2^16: no carry between the halves)
 	auto hz5 = [&](uint32_t m2, uint32_t m1, uint32_t c0, uint32_t p1, uint32_t p2, uint32_t& H1, uint32_t& H2) {
-		const uint32_t pl = lshl1_add(m1, m2);                 // I[x-2] + 2 I[x-1]      (<= 765)
-		const uint32_t pr = lshl1_add(p1, p2);                 // I[x+2] + 2 I[x+1]
+		const uint32_t pl = lshl_add<1>(m1, m2);                 // I[x-2] + 2 I[x-1]      (<= 765)
+		const uint32_t pr = lshl_add<1>(p1, p2);                 // I[x+2] + 2 I[x+1]
 		H1 = add3(pl, pr ^ 0x03ff03ffu, k1);                    // pl + (1023 - pr) + 1
 		const uint32_t t = (m1 + p1) + c0;
 		uint32_t u; asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(u) : "v"(t), "v"(m2 + p2));   // 4 t + I[x-2] + I[x+2]
-		H2 = lshl1_add(c0, u);
+		H2 = lshl_add<1>(c0, u);
 	};
 
 	// input rows are fetched TWO steps ahead (two register sets that alternate: the row loop is unrolled by four).  With one row in flight per
@@ -312,12 +301,12 @@ __global__ __launch_bounds__(WAVES * 64, (KS == 3 ? 8 : 7)) void canny_swar_tile
 				// gx + 16384 = (1, 4, 6, 4, 1) . (H1 + 1024) down rows yin - 4 .. yin;  gy + 16383 = (H2[yin-4] + 2 H2[yin-3]) + 16383 - (2 H2[yin-1] + H2[yin])
 				const uint32_t t = (h1[s3][k] + h1[s1][k]) + h1[s2][k];
 				uint32_t u; asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(u) : "v"(t), "v"(h1[s4][k] + n1[k]));
-				const uint32_t gxb = lshl1_add(h1[s2][k], u);
-				const uint32_t ptop = lshl1_add(h2[s3][k], h2[s4][k]), pbot = lshl1_add(h2[s1][k], n2[k]);
+				const uint32_t gxb = lshl_add<1>(h1[s2][k], u);
+				const uint32_t ptop = lshl_add<1>(h2[s3][k], h2[s4][k]), pbot = lshl_add<1>(h2[s1][k], n2[k]);
 				const uint32_t gyb = xad(pbot, k3fff, ptop);
 				h1[s4][k] = n1[k]; h2[s4][k] = n2[k];
-				const uint32_t mx = pk_max_u16(gxb, 0x80008000u - gxb);    // |gx| + 16384
-				const uint32_t my = pk_max_u16(gyb, 0x7ffe7ffeu - gyb);    // |gy| + 16383
+				const uint32_t mx = v_pk_max_u16(gxb, 0x80008000u - gxb);    // |gx| + 16384
+				const uint32_t my = v_pk_max_u16(gyb, 0x7ffe7ffeu - gyb);    // |gy| + 16383
 				gq[k] = add3(mx, my, k1);                                  // g + 32768
 				aux[k] = bfi(kFlagPk, gxb ^ gyb, mx);                      // bits 0..13 |gx|, bit 14 = ((gx ^ gy) < 0), gy = 0 reading as negative (see below)
 			}
@@ -327,15 +316,15 @@ __global__ __launch_bounds__(WAVES * 64, (KS == 3 ? 8 : 7)) void canny_swar_tile
 #pragma unroll
 		for (int k = 0; k < 2; ++k) {
 			const uint32_t Lk = L[k], Rk = L[k + 1], Ck = A[k];
-			const uint32_t hyN = lshl1_add(Ck, Lk + Rk);               // I[x-1] + 2 I[x] + I[x+1]           (<= 1020)
+			const uint32_t hyN = lshl_add<1>(Ck, Lk + Rk);               // I[x-1] + 2 I[x] + I[x+1]           (<= 1020)
 			const uint32_t d = xad(Lk, k255, Rk);                      // I[x+1] - I[x-1] + 255    ((L ^ 0xff) = 255 - L per half)
 			const uint32_t gxb = add3(P[k], d, k4);                    // gx + 1024                (P carries 3 x 255)
-			P[k] = lshl1_add(d, dprev[k]);
+			P[k] = lshl_add<1>(d, dprev[k]);
 			dprev[k] = d;
 			const uint32_t gyb = xad(hyTop[k], k3ff, hyN);             // gy + 1023                ((t ^ 0x3ff) = 1023 - t: t <= 1020)
 			hyTop[k] = hyN;
-			const uint32_t mx = pk_max_u16(gxb, kBias2k - gxb);        // |gx| + 1024
-			const uint32_t my = pk_max_u16(gyb, 0x07fe07feu - gyb);    // |gy| + 1023
+			const uint32_t mx = v_pk_max_u16(gxb, kBias2k - gxb);        // |gx| + 1024
+			const uint32_t my = v_pk_max_u16(gyb, 0x07fe07feu - gyb);    // |gy| + 1023
 			gq[k] = add3(mx, my, k1);                                  // g + 2048
 			// bit 10 of gxb ^ gyb = sign(gx) != sign(gy), except that gy = 0 reads as negative: a pixel with gy = 0 is in the horizontal class
 			// (or has g = 0) and the sign only selects between the two diagonals

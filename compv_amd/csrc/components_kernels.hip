@@ -24,7 +24,8 @@
 //                  only where the box read back is still too small
 //  9 comp_finish   label map only: root words := id, background := 0
 // Without a label map 8 only runs when records are wanted and 9 never.
-#include "kernels.hpp"
+#include "device.hpp"
+#include "frame_slices.hpp"
 
 namespace compvhip {
 
@@ -73,25 +74,6 @@ __device__ __forceinline__ void comp_union(const CompArgs& a, int32_t* P, int x,
 		if (old == x) return;                                // x was still a root: linked
 		x = old;                                             // somebody linked x meanwhile: its word is min(old, y) now, unite the other two
 	}
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
-__device__ __forceinline__ int wave_min(int v)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-	return v;
-}
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-	return v;
 }
 
 // the run of ones of m that starts at its lowest set bit: length
@@ -362,7 +344,7 @@ __global__ __launch_bounds__(kCompThreads) void comp_rows_kernel(CompArgs a)
 		if (!WRITE) { base += c; continue; }
 		int incl = c;
 #pragma unroll
-		for (int o = 1; o < 64; o <<= 1) {
+		for (int o = 1; o < 64; o <<= 1) {   // wave_incl_scan, written out
 			const int t = __shfl_up(incl, o);
 			if (lane >= o) incl += t;
 		}
@@ -392,33 +374,10 @@ __global__ __launch_bounds__(kCompThreads) void comp_rows_kernel(CompArgs a)
 constexpr int kScanThreads = 1024;
 __global__ __launch_bounds__(kScanThreads) void comp_scan_kernel(CompArgs a)
 {
-	__shared__ int waveSum[kScanThreads / 64];
-	__shared__ int carryS;
 	const int f = a.frame0 + blockIdx.x;
-	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	int32_t* v = a.rowCounts + (size_t)f * a.H;
-	if (tid == 0) carryS = 0;
-	__syncthreads();
-	for (int b = 0; b < a.H; b += kScanThreads) {
-		const int i = b + tid;
-		const int x = i < a.H ? v[i] : 0;
-		int incl = x;
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) {
-			const int t = __shfl_up(incl, o);
-			if (lane >= o) incl += t;
-		}
-		if (lane == 63) waveSum[wv] = incl;
-		__syncthreads();
-		int before = 0;
-		for (int k = 0; k < wv; ++k) before += waveSum[k];
-		const int carry = carryS;
-		if (i < a.H) v[i] = carry + before + incl - x;
-		__syncthreads();
-		if (tid == kScanThreads - 1) carryS = carry + before + incl;
-		__syncthreads();
-	}
-	if (tid == 0) a.compCounts[f] = carryS;
+	const int32_t total = block_excl_scan<kScanThreads>(v, v, a.H);
+	if (threadIdx.x == 0) a.compCounts[f] = total;
 }
 
 // ---- 8: labels of the non-root pixels, bounding boxes ---------------------------------------------------------------------------------
@@ -491,21 +450,16 @@ __global__ __launch_bounds__(kCompThreads) void comp_finish_kernel(CompArgs a)
 	if (v < 0) *q = -(v + 1);
 }
 
+// the frame index rides in grid dimension frameDim
 template <typename K>
-hipError_t launch_sliced(K kernel, dim3 grid, int frameDim, int frames, const CompArgs& args, int threads, hipStream_t stream)
+hipError_t launch_sliced(K kernel, dim3 grid, int frameDim, int frames, CompArgs a, int threads, hipStream_t stream)
 {
-	// the frame index rides in one grid dimension (<= 65535 in y / z): larger batches go in slices
-	for (int f0 = 0; f0 < frames; f0 += 65535) {
-		CompArgs a = args;
+	return for_frame_slices(frames, [&](int f0, int nf) {
 		a.frame0 = f0;
-		const unsigned nf = (unsigned)(frames - f0 < 65535 ? frames - f0 : 65535);
-		dim3 g = grid;
-		if (frameDim == 0) g.x = nf; else if (frameDim == 1) g.y = nf; else g.z = nf;
-		hipLaunchKernelGGL(kernel, g, dim3((unsigned)threads), 0, stream, a);
-		const hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	return hipSuccess;
+		(frameDim == 0 ? grid.x : frameDim == 1 ? grid.y : grid.z) = (unsigned)nf;
+		hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), 0, stream, a);
+		return hipGetLastError();
+	});
 }
 
 } // namespace

@@ -22,37 +22,16 @@
 //   fast_rows_kernel<0> per row: corners at or above that score                                }
 //   fast_scan_kernel    per frame: exclusive scan of the row counts, the frame's count
 //   fast_rows_kernel<1> per row with corners: walk the score map row in x order, write the records at their final index
-#include "kernels.hpp"
-
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "device.hpp"
 
 namespace compvhip {
 
 namespace {
 
-// ---- byte lanes through the packed 16-bit ALU (as morph_kernels.hip) -------------------------------------------------------------------
-// Four pixels of a dword are split into even and odd bytes, each zero-extended to a 16-bit half; v_pk_min_u16 / v_pk_max_u16 then work on two
-// pixels per instruction.  Sums and differences of such halves stay within 16 bits here (<= 510, >= 0), so plain 32-bit add / sub serve.
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-constexpr uint32_t kLo = 0x00ff00ffu;
-
-__device__ __forceinline__ uint32_t pkmin(uint32_t a, uint32_t b)
-{
-	return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
-__device__ __forceinline__ uint32_t pkmax(uint32_t a, uint32_t b)
-{
-	return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
+// Byte lanes through the packed 16-bit ALU (device.hpp).  Sums and differences of the 16-bit halves stay within 16 bits here (<= 510, >= 0), so
+// plain 32-bit add / sub serve.
 // 0xff in the low byte of every half that is not zero (halves <= 255)
 __device__ __forceinline__ uint32_t nzMask(uint32_t h) { return (((h + kLo) >> 8) & 0x00010001u) * 0xffu; }
-
-__device__ __forceinline__ void storeRow4(uint8_t* dst, int gx, int W, uint32_t v)
-{
-	if (gx + 4 <= W) *reinterpret_cast<uint32_t*>(dst + gx) = v;
-	else for (int b = 0; b < 4 && gx + b < W; ++b) dst[gx + b] = static_cast<uint8_t>(v >> (8 * b));
-}
 
 // ---- tile geometry ---------------------------------------------------------------------------------------------------------------------------
 // One workgroup = one 128 x 32 tile of the output.  Scores are needed for the tile and the 1-pixel ring around it (NMS), in whole dwords: 34 rows
@@ -76,14 +55,14 @@ __device__ __forceinline__ uint32_t arcMax(const uint32_t (&v)[16])
 {
 	uint32_t m2[16], m4[16], m8[16];
 #pragma unroll
-	for (int k = 0; k < 16; ++k) m2[k] = pkmin(v[k], v[(k + 1) & 15]);
+	for (int k = 0; k < 16; ++k) m2[k] = pk_min_u16(v[k], v[(k + 1) & 15]);
 #pragma unroll
-	for (int k = 0; k < 16; ++k) m4[k] = pkmin(m2[k], m2[(k + 2) & 15]);
+	for (int k = 0; k < 16; ++k) m4[k] = pk_min_u16(m2[k], m2[(k + 2) & 15]);
 #pragma unroll
-	for (int k = 0; k < 16; ++k) m8[k] = pkmin(m4[k], m4[(k + 4) & 15]);
+	for (int k = 0; k < 16; ++k) m8[k] = pk_min_u16(m4[k], m4[(k + 4) & 15]);
 	uint32_t best = 0;
 #pragma unroll
-	for (int k = 0; k < 16; ++k) best = pkmax(best, pkmin(m8[k], N == 9 ? v[(k + 8) & 15] : m4[(k + 8) & 15]));   // positions k .. k + 8 / k .. k + 11
+	for (int k = 0; k < 16; ++k) best = pk_max_u16(best, pk_min_u16(m8[k], N == 9 ? v[(k + 8) & 15] : m4[(k + 8) & 15]));   // positions k .. k + 8 / k .. k + 11
 	return best;
 }
 
@@ -95,24 +74,24 @@ __device__ __forceinline__ uint32_t score4(const uint32_t* sRaw, int r, int w, u
 	constexpr int kDy[16] = { -3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3 };
 	const uint32_t c = sRaw[r * kRawPitch + w];
 	const uint32_t cE = c & kLo, cO = (c >> 8) & kLo;
-	const uint32_t bE = pkmin(cE + t2, kLo), bO = pkmin(cO + t2, kLo);          // min(255, I + t)
-	const uint32_t dE = pkmax(cE, t2) - t2, dO = pkmax(cO, t2) - t2;            // max(0, I - t)
+	const uint32_t bE = pk_min_u16(cE + t2, kLo), bO = pk_min_u16(cO + t2, kLo);          // min(255, I + t)
+	const uint32_t dE = pk_max_u16(cE, t2) - t2, dO = pk_max_u16(cO, t2) - t2;            // max(0, I - t)
 	uint32_t DE[16], DO[16], BE[16], BO[16];
 	auto ring = [&](int k) {
 		const uint32_t p = shifted4(sRaw + (r + kDy[k]) * kRawPitch, w, kDx[k]);
 		const uint32_t pE = p & kLo, pO = (p >> 8) & kLo;
-		DE[k] = dE - pkmin(pE, dE); DO[k] = dO - pkmin(pO, dO);                 // max(0, d - p)
-		BE[k] = pkmax(pE, bE) - bE; BO[k] = pkmax(pO, bO) - bO;                 // max(0, p - b)
+		DE[k] = dE - pk_min_u16(pE, dE); DO[k] = dO - pk_min_u16(pO, dO);                 // max(0, d - p)
+		BE[k] = pk_max_u16(pE, bE) - bE; BO[k] = pk_max_u16(pO, bO) - bO;                 // max(0, p - b)
 	};
 	// An arc of 9 or more holds one position of every opposite pair: no darker (brighter) pixel in {0, 8} or in {4, 12} rules a darker (brighter) arc
 	// out.  Most pixels of a natural image end here.
 	ring(0); ring(8); ring(4); ring(12);
-	const uint32_t maybe = pkmin(pkmax(DE[0], DE[8]), pkmax(DE[4], DE[12])) | pkmin(pkmax(DO[0], DO[8]), pkmax(DO[4], DO[12])) |
-	                       pkmin(pkmax(BE[0], BE[8]), pkmax(BE[4], BE[12])) | pkmin(pkmax(BO[0], BO[8]), pkmax(BO[4], BO[12]));
+	const uint32_t maybe = pk_min_u16(pk_max_u16(DE[0], DE[8]), pk_max_u16(DE[4], DE[12])) | pk_min_u16(pk_max_u16(DO[0], DO[8]), pk_max_u16(DO[4], DO[12])) |
+	                       pk_min_u16(pk_max_u16(BE[0], BE[8]), pk_max_u16(BE[4], BE[12])) | pk_min_u16(pk_max_u16(BO[0], BO[8]), pk_max_u16(BO[4], BO[12]));
 	if (!maybe) return 0u;
 #pragma unroll
 	for (int k = 0; k < 16; ++k) if (k & 3) ring(k);
-	const uint32_t e = pkmax(arcMax<N>(DE), arcMax<N>(BE)), o = pkmax(arcMax<N>(DO), arcMax<N>(BO));
+	const uint32_t e = pk_max_u16(arcMax<N>(DE), arcMax<N>(BE)), o = pk_max_u16(arcMax<N>(DO), arcMax<N>(BO));
 	return e | (o << 8);
 }
 
@@ -162,12 +141,12 @@ __global__ __launch_bounds__(256) void fast_score_kernel(FastArgs a)
 		if (NMS && s) {
 			// largest of the 8 neighbours, then keep where s > it: a neighbour >= s suppresses, so two equal neighbours both go
 			uint32_t mE = 0, mO = 0;
-			auto add = [&](uint32_t w) { mE = pkmax(mE, w & kLo); mO = pkmax(mO, (w >> 8) & kLo); };
+			auto add = [&](uint32_t w) { mE = pk_max_u16(mE, w & kLo); mO = pk_max_u16(mO, (w >> 8) & kLo); };
 			add(shifted4(row - kScorePitch, g + 1, -1)); add(row[g + 1 - kScorePitch]); add(shifted4(row - kScorePitch, g + 1, 1));
 			add(shifted4(row, g + 1, -1)); add(shifted4(row, g + 1, 1));
 			add(shifted4(row + kScorePitch, g + 1, -1)); add(row[g + 1 + kScorePitch]); add(shifted4(row + kScorePitch, g + 1, 1));
 			const uint32_t sE = s & kLo, sO = (s >> 8) & kLo;
-			s &= nzMask(pkmax(sE, mE) - mE) | (nzMask(pkmax(sO, mO) - mO) << 8);
+			s &= nzMask(pk_max_u16(sE, mE) - mE) | (nzMask(pk_max_u16(sO, mO) - mO) << 8);
 		}
 		const int gy = ty0 + r, gx = tx0 + 4 * g;
 		if (gy < a.H) storeRow4(dst + static_cast<size_t>(gy) * a.S, gx, a.W, s);
@@ -178,7 +157,7 @@ __global__ __launch_bounds__(256) void fast_score_kernel(FastArgs a)
 				if (v) atomicAdd(&sHist[v], 1);
 			}
 		}
-		for (int d = 16; d; d >>= 1) n += __shfl_xor(n, d);          // stays inside the half wave
+		for (int d = 16; d; d >>= 1) n += __shfl_xor(n, d);          // stays inside the half wave (wave_sum over 32 lanes)
 		if (g == 0 && n) atomicAdd(a.rowCounts + static_cast<size_t>(frame) * a.H + gy, n);          // n > 0 implies gy < H: rows outside the plane score 0
 	}
 	if (a.hist) {
@@ -204,6 +183,8 @@ __global__ __launch_bounds__(256) void fast_cut_kernel(FastArgs a)
 }
 
 // per frame: exclusive scan of the row counts -> row offsets; the total -> counts[frame]
+// (Its own algorithm, not block_excl_scan: a thread sums its share of the rows, one scan round over the 256 sums.  block_excl_scan's nine rounds
+// for 2160 rows measured 3.5 us slower per launch, docs/experiments.md.)
 __global__ __launch_bounds__(256) void fast_scan_kernel(FastArgs a)
 {
 	__shared__ int sPart[256];
@@ -255,7 +236,7 @@ __global__ __launch_bounds__(256) void fast_rows_kernel(FastArgs a)
 			const int v = (w[b >> 2] >> (8 * (b & 3))) & 0xff;
 			if (x + b < a.W && v >= level) { keep |= 1u << b; ++n; }          // level >= 1: zero scores never pass
 		}
-		int incl = n;          // inclusive prefix sum over the wave
+		int incl = n;          // inclusive prefix sum over the wave (wave_incl_scan, written out)
 		for (int d = 1; d < 64; d <<= 1) {
 			const int v = __shfl_up(incl, d);
 			if (lane >= d) incl += v;

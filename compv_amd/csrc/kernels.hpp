@@ -185,8 +185,10 @@ hipError_t launch_sht_sort_lines(const ShtArgs& a, const ShtSortArgs& q, int fra
 hipError_t sht_sort_pairs(void* temp, size_t& tempBytes, const uint32_t* keysIn, uint32_t* keysOut, const uint32_t* valsIn, uint32_t* valsOut, size_t n,
                           int keyBits, hipStream_t stream);
 
-// ---- Hough SHT line segments (sht_segments_kernels.hip) -------------------------------------------------------
-struct ShtSegArgs {
+// ---- Hough SHT line segments and line refinement (sht_segments_kernels.hip, sht_fit_kernels.hip) ----------------------------------
+// what both walks read: the edge pixels, the vote's tables and the lines (24 trailing bytes of ints: the structs derived from it keep the layout
+// they had with these fields written out)
+struct ShtLineSetArgs {
 	const uint32_t* ebits;    // edge bit masks [frames][H][wb] (read when edges == nullptr)
 	const uint8_t* edges;     // or byte edge maps [frames][H][S], non-zero = edge
 	size_t bitsFrameStride, edgeFrameStride;
@@ -198,6 +200,8 @@ struct ShtSegArgs {
 	size_t lineCap;
 	int nLines;               // lines considered per frame at most: min(lineCap, maxLines if > 0)
 	int W, H, R, T, barrier;
+};
+struct ShtSegArgs : ShtLineSetArgs {
 	int minLength, maxGap;
 	int32_t* perLine;         // [frames][nLines] scratch: segments per line, then their exclusive prefix sums
 	compvhip_segment* segs;   // [frames][segCap]
@@ -208,19 +212,7 @@ struct ShtSegArgs {
 // phase 0: count the segments of every line; 1: exclusive scan per frame + segCounts; 2: write the segments
 hipError_t launch_sht_segments(const ShtSegArgs& a, int frames, int phase, hipStream_t stream);
 
-// ---- Hough SHT line refinement (sht_fit_kernels.hip) -------------------------------------------------------------
-struct ShtFitArgs {
-	const uint32_t* ebits;    // edge bit masks [frames][H][wb] (read when edges == nullptr)
-	const uint8_t* edges;     // or byte edge maps [frames][H][S], non-zero = edge
-	size_t bitsFrameStride, edgeFrameStride;
-	int wb, S;
-	const int32_t* sinQ;      // [T] the vote's Q16 tables
-	const int32_t* cosQ;
-	const compvhip_line* lines;   // [frames][lineCap]; only row / col are read
-	const int32_t* lineCounts;    // [frames] lines found (may exceed lineCap)
-	size_t lineCap;
-	int nLines;               // lines considered per frame at most: min(lineCap, maxLines if > 0)
-	int W, H, R, T, barrier;
+struct ShtFitArgs : ShtLineSetArgs {
 	int halfWidth;            // 0 .. 8 rho cells either side of the line's
 	const compvhip_segment* segs; // [frames][segCap] per-segment mode (nullptr: one record per line)
 	const int32_t* segCounts;     // [frames] segments found (may exceed segCap)
@@ -231,6 +223,7 @@ struct ShtFitArgs {
 	compvhip_line* refined;   // [frames][lineCap] the lines with the fitted rho / theta (per-line mode, may be nullptr)
 	int frame0;               // filled by the launcher
 };
+static_assert(sizeof(ShtLineSetArgs) == 104 && sizeof(ShtSegArgs) == 152 && sizeof(ShtFitArgs) == 176, "kernel argument layout");
 hipError_t launch_sht_fit(const ShtFitArgs& a, int frames, hipStream_t stream);
 
 // ---- connected components of edge maps (components_kernels.hip) -------------------------------------------------

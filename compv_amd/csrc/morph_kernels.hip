@@ -9,38 +9,19 @@
 // Integer arithmetic only.  Frames are a grid dimension (blockIdx.z); frame bases are 8-byte aligned and S % 8 == 0 (plan contract), so
 // every row starts on a dword.  Columns >= W are read (they only ever feed border cells, whose value does not depend on them) and
 // never written.
-#include "kernels.hpp"
-
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "device.hpp"
 
 namespace compvhip {
 
-// ---- byte lanes through the packed 16-bit ALU ----------------------------------------------------------------------------------------
-// The ISA has no byte-wise min / max.  A dword of four pixels is split once into its even and odd bytes, each zero-extended to a 16-bit
-// half (E = b0 | b2 << 16, O = b1 | b3 << 16); v_pk_min_u16 / v_pk_max_u16 then work on two pixels per instruction.
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-constexpr uint32_t kLo = 0x00ff00ffu;
-
+// byte lanes through the packed 16-bit ALU (device.hpp)
 template <bool MAX>
-__device__ __forceinline__ uint32_t pk(uint32_t a, uint32_t b)
-{
-	const u16x2 x = __builtin_bit_cast(u16x2, a), y = __builtin_bit_cast(u16x2, b);
-	return __builtin_bit_cast(uint32_t, MAX ? __builtin_elementwise_max(x, y) : __builtin_elementwise_min(x, y));
-}
+__device__ __forceinline__ uint32_t pk(uint32_t a, uint32_t b) { return MAX ? pk_max_u16(a, b) : pk_min_u16(a, b); }
 template <bool MAX>
 struct Acc {   // running min / max of four pixels in split form
 	uint32_t e = MAX ? 0u : kLo, o = MAX ? 0u : kLo;
 	__device__ __forceinline__ void add(uint32_t w) { e = pk<MAX>(e, w & kLo); o = pk<MAX>(o, (w >> 8) & kLo); }
 	__device__ __forceinline__ uint32_t packed() const { return e | (o << 8); }
 };
-
-// rows of a tile are stored only for columns < W: whole dwords where they fit, single bytes at the ragged end
-__device__ __forceinline__ void storeRow4(uint8_t* dst, int gx, int W, uint32_t v)
-{
-	if (gx + 4 <= W) *reinterpret_cast<uint32_t*>(dst + gx) = v;
-	else for (int b = 0; b < 4 && gx + b < W; ++b) dst[gx + b] = static_cast<uint8_t>(v >> (8 * b));
-}
 
 // ---- global threshold ----------------------------------------------------------------------------------------------------------------
 // one thread = 8 adjacent pixels of one row.  x > t per 16-bit half: (x + (255 - t)) carries into bit 8 exactly when x > t.

@@ -20,7 +20,8 @@
 // the walk's loads that is noise, so no DPP form was written).  Lane 0 computes the central moments in int64 and the closed-form 2 x 2 eigen
 // step in binary64 -- + - * / sqrt only, every operation rounded once (-ffp-contract=off), in the order of the definition -- and writes the
 // 80-byte record.  One record per line or segment at a known index: no atomics, no second pass, no scan.
-#include "kernels.hpp"
+#include "device.hpp"
+#include "frame_slices.hpp"
 
 namespace compvhip {
 
@@ -29,20 +30,13 @@ namespace {
 constexpr int kFitWaves = 4;      // waves (= records) per workgroup; the waves never synchronise
 static_assert(sizeof(compvhip_line_fit) == 80, "compvhip_line_fit has no padding");
 
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
-
 template <bool BITS>
 __global__ __launch_bounds__(kFitWaves * 64) void sht_fit_kernel(ShtFitArgs a)
 {
 	const int lane = threadIdx.x & 63;
 	const int ri = blockIdx.x * kFitWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const int f = a.frame0 + blockIdx.y;
-	const int nl = min(max(a.lineCounts[f], 0), a.nLines);
+	const int nl = min(max(a.lineCounts[f], 0), a.nLines);   // line_count, written out
 	const int nRec = a.segs ? (int)min((size_t)max(a.segCounts[f], 0), a.segCap) : nl;
 	if (ri == 0 && lane == 0) a.fitCounts[f] = nRec;
 	if (ri >= nRec) return;
@@ -102,7 +96,7 @@ __global__ __launch_bounds__(kFitWaves * 64) void sht_fit_kernel(ShtFitArgs a)
 			else {
 				for (int m = mlo; m <= mhi; ++m, d += cm) {
 					if ((unsigned long long)d >= (unsigned long long)span) continue;
-					bool e;
+					bool e;      // line_edge<BITS>, written out: with BITS only x-major lines get here
 					if (BITS) e = (a.ebits[frameBase + (size_t)m * a.wb + (p >> 5)] >> (p & 31)) & 1u;      // x-major: pixel (p, m)
 					else e = (xMajor ? a.edges[frameBase + (size_t)m * a.S + p] : a.edges[frameBase + (size_t)p * a.S + m]) != 0;
 					if (e) { ++np; s1 += m; s2 += m * m; }
@@ -154,18 +148,15 @@ hipError_t launch_sht_fit(const ShtFitArgs& args, int frames, hipStream_t stream
 {
 	const size_t recs = args.segs ? args.segCap : (size_t)args.nLines;
 	const dim3 grid((unsigned)((recs + kFitWaves - 1) / kFitWaves > 0 ? (recs + kFitWaves - 1) / kFitWaves : 1), 1);
-	// the frame index rides in blockIdx.y (<= 65535): larger batches go in slices
-	for (int f0 = 0; f0 < frames; f0 += 65535) {
+	// the frame index rides in blockIdx.y
+	return for_frame_slices(frames, [&](int f0, int nf) {
 		ShtFitArgs a = args;
 		a.frame0 = f0;
-		const int nf = frames - f0 < 65535 ? frames - f0 : 65535;
 		const dim3 g(grid.x, (unsigned)nf);
 		if (a.edges) hipLaunchKernelGGL(sht_fit_kernel<false>, g, dim3(kFitWaves * 64), 0, stream, a);
 		else hipLaunchKernelGGL(sht_fit_kernel<true>, g, dim3(kFitWaves * 64), 0, stream, a);
-		const hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	return hipSuccess;
+		return hipGetLastError();
+	});
 }
 
 } // namespace compvhip

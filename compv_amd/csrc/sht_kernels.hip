@@ -258,7 +258,7 @@ __global__ __launch_bounds__(kLnRows) void sht_lines_kernel(ShtArgs a)
 	}
 	uint32_t incl = cnt;
 #pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
+	for (int o = 1; o < 64; o <<= 1) {   // wave_incl_scan, written out
 		const uint32_t n = __shfl_up(incl, o);
 		if (lane >= o) incl += n;
 	}
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(kLnRows) void sht_lines_kernel(ShtArgs a)
 		grand += (g < a.frames) ? c : 0u;
 	}
 #pragma unroll
-	for (int o = 32; o > 0; o >>= 1) { first += __shfl_xor(first, o); count += __shfl_xor(count, o); fbase += __shfl_xor(fbase, o); grand += __shfl_xor(grand, o); }
+	for (int o = 32; o > 0; o >>= 1) { first += __shfl_xor(first, o); count += __shfl_xor(count, o); fbase += __shfl_xor(fbase, o); grand += __shfl_xor(grand, o); }   // four wave_sum's, interleaved
 	uint32_t* __restrict__ keys = a.lineKeys + (size_t)fbase;
 	uint32_t* __restrict__ vals = a.lineVals + (size_t)fbase;
 	// 3. the survivors in (row, column) order: key = frameTag | strength, value = cell (row * T + col), put in place in the LDS and stored
@@ -362,18 +362,18 @@ __global__ __launch_bounds__(kLnRows) void sht_lines_kernel(ShtArgs a)
 	}
 }
 
-struct LineOut { float rho; float theta; int32_t strength; int32_t row; int32_t col; };
+static_assert(sizeof(compvhip_line) == 20, "compvhip_line has no padding");
 
 // After the global descending sort the lines of frame f start at sum_{g<f} min(count_g, lineCap).
 __global__ __launch_bounds__(256) void sht_decode_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, const int* __restrict__ counts, size_t lineCap,
-                                                         int T, int barrier, float thetaStep, int maxLines, int strengthBits, LineOut* __restrict__ lines, size_t outCap)
+                                                         int T, int barrier, float thetaStep, int maxLines, int strengthBits, compvhip_line* __restrict__ lines, size_t outCap)
 {
 	const int frame = blockIdx.y;
 	// the frame's offset: thread g adds the count of frame g (one thread walking the earlier frames' counts exposed a memory latency per
 	// frame: 10 us for the last frames of a batch of 32)
 	__shared__ unsigned long long s_part[4];
 	unsigned long long before = 0;
-	for (int g = threadIdx.x; g < frame; g += 256) {
+	for (int g = threadIdx.x; g < frame; g += 256) {   // dense_frame_base<256>, written out
 		const size_t cg = (size_t)max(counts[g], 0);
 		before += cg < lineCap ? cg : lineCap;
 	}
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void sht_decode_kernel(const uint32_t* __restr
 	const uint32_t k = keys[off + i];
 	const uint32_t cell = vals[off + i];
 	const int row = (int)(cell / (uint32_t)T), col = (int)(cell - (uint32_t)row * (uint32_t)T);
-	LineOut o;
+	compvhip_line o;
 	o.rho = (float)(barrier - row);              // static_cast<float>(barrier - row), houghsht.cxx:661
 	o.theta = __fmul_rn((float)col, thetaStep);  // col * theta (f32), houghsht.cxx:662
 	o.strength = (int32_t)(k & ((1u << strengthBits) - 1u));
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(256) void sht_decode_kernel(const uint32_t* __restr
 // CompVHoughSht::toCartesian (houghsht.cxx:566-589) on the device line arrays.  cos(theta) and 1/sin(theta) come from HOST
 // tables indexed by the line's theta column (libm cosf/sinf, as the reference; device trig would not be bit-identical);
 // the kernel only multiplies and subtracts, with single correctly-rounded operations.
-__global__ __launch_bounds__(256) void sht_cartesian_kernel(const LineOut* __restrict__ lines, const int* __restrict__ counts, size_t lineCap, int maxLines, int T,
+__global__ __launch_bounds__(256) void sht_cartesian_kernel(const compvhip_line* __restrict__ lines, const int* __restrict__ counts, size_t lineCap, int maxLines, int T,
                                                             const float* __restrict__ cosT, const float* __restrict__ invSinT, float thetaStep, float widthF, float r,
                                                             float4* __restrict__ out)
 {
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void sht_cartesian_kernel(const LineOut* __res
 	if (n > lineCap) n = lineCap;
 	if (maxLines > 0 && n > (size_t)maxLines) n = (size_t)maxLines;   // counts[] holds the uncut line count: the decode stage wrote min(count, lineCap, maxLines) slots
 	if (i >= n) return;
-	const LineOut l = lines[(size_t)frame * lineCap + i];
+	const compvhip_line l = lines[(size_t)frame * lineCap + i];
 	float4 o;
 	if (l.theta == 0.f) o = make_float4(l.rho, r, l.rho, -r); // perfect vertical line
 	else if (l.col < 0 || l.col >= T) o = make_float4(0.f, 0.f, 0.f, 0.f);   // not a line of this plan (foreign / uninitialised slot): no table entry to read
@@ -487,7 +487,7 @@ hipError_t launch_sht_decode(const uint32_t* keys, const uint32_t* vals, const i
 	if (n == 0) return hipSuccess;
 	dim3 grid((unsigned)((n + 255) / 256), frames);
 	hipLaunchKernelGGL(sht_decode_kernel, grid, dim3(256), 0, stream, keys, vals, counts, lineCap, T, barrier, thetaStep, maxLines, strengthBits,
-	                   reinterpret_cast<LineOut*>(lines), outCap);
+	                   reinterpret_cast<compvhip_line*>(lines), outCap);
 	return hipGetLastError();
 }
 
@@ -497,7 +497,7 @@ hipError_t launch_sht_cartesian(const void* lines, const int* counts, size_t lin
 	if (!lineCap) return hipSuccess;
 	const size_t span = (maxLines > 0 && (size_t)maxLines < lineCap) ? (size_t)maxLines : lineCap;
 	dim3 grid((unsigned)((span + 255) / 256), frames);
-	hipLaunchKernelGGL(sht_cartesian_kernel, grid, dim3(256), 0, stream, reinterpret_cast<const LineOut*>(lines), counts, lineCap, maxLines, T, cosT, invSinT, thetaStep, widthF, r,
+	hipLaunchKernelGGL(sht_cartesian_kernel, grid, dim3(256), 0, stream, reinterpret_cast<const compvhip_line*>(lines), counts, lineCap, maxLines, T, cosT, invSinT, thetaStep, widthF, r,
 	                   reinterpret_cast<float4*>(out));
 	return hipGetLastError();
 }

@@ -24,7 +24,8 @@
 // kernel and what bounds it on frames whose lines are mostly vertical.  Neither a transposed copy of the masks (an extra pass over every
 // frame for the few hundred lines that use it) nor an LDS-staged band (a y-major line is one pixel wide: staging does not create reuse inside
 // one wave) was tried; lines of neighbouring waves share those cache lines in the L2 when they are close in rho.
-#include "kernels.hpp"
+#include "device.hpp"
+#include "frame_slices.hpp"
 
 namespace compvhip {
 
@@ -32,13 +33,6 @@ namespace {
 
 constexpr int kSegWaves = 4;      // waves (= lines) per workgroup; the waves never synchronise
 constexpr int kScanThreads = 1024;
-
-template <bool BITS>
-__device__ __forceinline__ bool seg_edge(const ShtSegArgs& a, size_t frameBase, int x, int y)
-{
-	if (BITS) return (a.ebits[frameBase + (size_t)y * a.wb + (x >> 5)] >> (x & 31)) & 1u;
-	return a.edges[frameBase + (size_t)y * a.S + x] != 0;
-}
 
 // WRITE = false: perLine[frame][line] = number of segments of the line.  WRITE = true: perLine holds the exclusive prefix sums; the segments
 // are written at perLine[frame][line] + k while that is below segCap.
@@ -49,8 +43,7 @@ __global__ __launch_bounds__(kSegWaves * 64) void sht_segments_kernel(ShtSegArgs
 	const int li = blockIdx.x * kSegWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const int f = a.frame0 + blockIdx.y;
 	if (li >= a.nLines) return;
-	const int n = min(max(a.lineCounts[f], 0), a.nLines);
-	if (li >= n) return;
+	if (li >= line_count(a, f)) return;
 	int32_t* slot = a.perLine + (size_t)f * a.nLines + li;
 	const compvhip_line* ln = a.lines + (size_t)f * a.lineCap + li;
 	const int row = __builtin_amdgcn_readfirstlane(ln->row), col = __builtin_amdgcn_readfirstlane(ln->col);
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(kSegWaves * 64) void sht_segments_kernel(ShtSegArgs
 			for (int k = 0; k < 4; ++k, d += cm) {
 				const int m = est - 1 + k;
 				if ((unsigned long long)d < 65536ull && (unsigned)m < (unsigned)Nm) {
-					if (xMajor ? seg_edge<BITS>(a, frameBase, p, m) : seg_edge<BITS>(a, frameBase, m, p)) {
+					if (xMajor ? line_edge<BITS>(a, frameBase, p, m) : line_edge<BITS>(a, frameBase, m, p)) {
 						if (!cnt) mf = m;
 						++cnt;
 					}
@@ -137,34 +130,10 @@ __global__ __launch_bounds__(kSegWaves * 64) void sht_segments_kernel(ShtSegArgs
 // exclusive prefix sum of a frame's per-line segment counts, in place; segCounts[frame] = their total
 __global__ __launch_bounds__(kScanThreads) void sht_segments_scan_kernel(ShtSegArgs a)
 {
-	__shared__ int waveSum[kScanThreads / 64];
-	__shared__ int carryS;
 	const int f = a.frame0 + blockIdx.x;
-	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	const int n = min(max(a.lineCounts[f], 0), a.nLines);
 	int32_t* v = a.perLine + (size_t)f * a.nLines;
-	if (tid == 0) carryS = 0;
-	__syncthreads();
-	for (int b = 0; b < n; b += kScanThreads) {
-		const int i = b + tid;
-		const int x = i < n ? v[i] : 0;
-		int incl = x;
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) {
-			const int y = __shfl_up(incl, o);
-			if (lane >= o) incl += y;
-		}
-		if (lane == 63) waveSum[wv] = incl;
-		__syncthreads();
-		int before = 0;
-		for (int k = 0; k < wv; ++k) before += waveSum[k];
-		const int carry = carryS;
-		if (i < n) v[i] = carry + before + incl - x;
-		__syncthreads();
-		if (tid == kScanThreads - 1) carryS = carry + before + incl;
-		__syncthreads();
-	}
-	if (tid == 0) a.segCounts[f] = carryS;
+	const int32_t total = block_excl_scan<kScanThreads>(v, v, line_count(a, f));
+	if (threadIdx.x == 0) a.segCounts[f] = total;
 }
 
 template <bool WRITE>
@@ -179,21 +148,18 @@ void launch_walk(const ShtSegArgs& a, int frames, hipStream_t stream)
 
 hipError_t launch_sht_segments(const ShtSegArgs& args, int frames, int phase, hipStream_t stream)
 {
-	// the frame index rides in blockIdx.y (<= 65535): larger batches go in slices
-	for (int f0 = 0; f0 < frames; f0 += 65535) {
+	// the frame index rides in blockIdx.y
+	return for_frame_slices(frames, [&](int f0, int nf) {
 		ShtSegArgs a = args;
 		a.frame0 = f0;
-		const int nf = frames - f0 < 65535 ? frames - f0 : 65535;
 		if (phase == 1) {
 			hipLaunchKernelGGL(sht_segments_scan_kernel, dim3((unsigned)nf), dim3(kScanThreads), 0, stream, a);
 		}
 		else if (a.nLines > 0) {
 			if (phase == 0) launch_walk<false>(a, nf, stream); else launch_walk<true>(a, nf, stream);
 		}
-		const hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	return hipSuccess;
+		return hipGetLastError();
+	});
 }
 
 } // namespace compvhip

@@ -15,7 +15,7 @@
 //   3. sht_place_lines_kernel  one thread per line: slot = start[strength] + lines of that strength in the frame's earlier chunks + rank; the slot's
 //                              compvhip_line is written directly (rho, theta, strength, row, col: what sht_decode_kernel did behind the library sort)
 // Larger strengths (max(W, H) > 4095) or line capacities beyond 32 chunks per frame keep the library sort (sht_kernels.hip).
-#include "kernels.hpp"
+#include "device.hpp"
 
 #include <type_traits>
 
@@ -27,27 +27,6 @@ constexpr int kChunk = kShtSortChunk;        // lines per chunk
 constexpr int kSortThreads = 1024;
 constexpr int kBins = 1 << kShtSortMaxStrengthBits;   // 8192 strengths
 static_assert(kChunk == 4096 && kBins == 8192, "key layout: 13 bits of inverted strength above 12 bits of chunk position");
-
-struct LineOut { float rho; float theta; int32_t strength; int32_t row; int32_t col; };
-
-// lines of the earlier frames (clamped to lineCap): where frame `frame` starts in the dense key array.  Every thread of the block gets the sum.
-template <int THREADS>
-__device__ __forceinline__ size_t frame_base(const int* __restrict__ counts, int frame, size_t lineCap, unsigned long long* s_part)
-{
-	unsigned long long before = 0;
-	for (int g = threadIdx.x; g < frame; g += THREADS) {
-		const size_t cg = (size_t)max(counts[g], 0);
-		before += cg < lineCap ? cg : lineCap;
-	}
-#pragma unroll
-	for (int d = 32; d > 0; d >>= 1) before += __shfl_xor(before, d);
-	if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = before;
-	__syncthreads();
-	unsigned long long sum = 0;
-#pragma unroll
-	for (int w = 0; w < THREADS / 64; ++w) sum += s_part[w];
-	return (size_t)sum;
-}
 
 } // namespace
 
@@ -63,7 +42,7 @@ __global__ __launch_bounds__(kSortThreads) void sht_chunk_sort_kernel(ShtArgs a,
 	const size_t c0 = (size_t)chunk * kChunk;
 	if (c0 >= nf) return;   // uniform: a chunk without lines
 	const int m = (int)min((size_t)kChunk, nf - c0);
-	const size_t base = frame_base<kSortThreads>(a.lineCounts, frame, a.lineCap, s_part) + c0;
+	const size_t base = dense_frame_base<kSortThreads>(a.lineCounts, frame, a.lineCap, s_part) + c0;
 	const uint32_t mask = (1u << a.strengthBits) - 1u;
 	const uint32_t* __restrict__ kin = a.lineKeys + base;
 	const uint32_t* __restrict__ vin = a.lineVals + base;
@@ -111,12 +90,7 @@ __global__ __launch_bounds__(kSortThreads) void sht_chunk_sort_kernel(ShtArgs a,
 		__syncthreads();
 		// exclusive scan of the 1024 counts, one per thread (unused entries of a pass with fewer digits are zero)
 		const uint32_t c = s_cnt[t];
-		uint32_t incl = c;
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) {
-			const uint32_t n = __shfl_up(incl, o);
-			if (lane >= o) incl += n;
-		}
+		const uint32_t incl = wave_incl_scan(c, lane);   // (the block part: block_excl_scan's, with predicated unrolled wave sums)
 		if (lane == 63) s_wsum[wave] = incl;
 		__syncthreads();
 		uint32_t before = 0;
@@ -207,7 +181,7 @@ __global__ __launch_bounds__(kSortThreads) void sht_strength_scan_kernel(ShtArgs
 	uint32_t incl = sum;
 	const int lane = t & 63, wave = t >> 6;
 #pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
+	for (int o = 1; o < 64; o <<= 1) {   // wave_incl_scan, written out
 		const uint32_t n = __shfl_up(incl, o);
 		if (lane >= o) incl += n;
 	}
@@ -223,14 +197,14 @@ __global__ __launch_bounds__(kSortThreads) void sht_strength_scan_kernel(ShtArgs
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sht_place_lines_kernel(ShtArgs a, ShtSortArgs q, float thetaStep, int maxLines, LineOut* __restrict__ lines, size_t outCap)
+__global__ __launch_bounds__(256) void sht_place_lines_kernel(ShtArgs a, ShtSortArgs q, float thetaStep, int maxLines, compvhip_line* __restrict__ lines, size_t outCap)
 {
 	__shared__ unsigned long long s_part[4];
 	const int frame = blockIdx.y;
 	const size_t nf = min((size_t)max(a.lineCounts[frame], 0), a.lineCap);
 	const size_t i0 = (size_t)blockIdx.x * 256;
 	if (i0 >= nf) return;   // uniform
-	const size_t base = frame_base<256>(a.lineCounts, frame, a.lineCap, s_part);
+	const size_t base = dense_frame_base<256>(a.lineCounts, frame, a.lineCap, s_part);
 	const size_t i = i0 + threadIdx.x;
 	if (i >= nf) return;
 	size_t limit = nf;      // slots of the frame that are written: min(lines, lineCap, maxLines, outCap)
@@ -253,7 +227,7 @@ __global__ __launch_bounds__(256) void sht_place_lines_kernel(ShtArgs a, ShtSort
 	if (pos >= limit) return;
 	const uint32_t cell = q.sortedVals[base + i];
 	const int row = (int)(cell / (uint32_t)a.T), col = (int)(cell - (uint32_t)row * (uint32_t)a.T);
-	LineOut o;
+	compvhip_line o;
 	o.rho = (float)(a.barrier - row);            // static_cast<float>(barrier - row), houghsht.cxx:661
 	o.theta = __fmul_rn((float)col, thetaStep);  // col * theta (f32), houghsht.cxx:662
 	o.strength = (int32_t)(((1u << a.strengthBits) - 1u) - inv);
@@ -268,7 +242,7 @@ hipError_t launch_sht_sort_lines(const ShtArgs& a, const ShtSortArgs& q, int fra
 	hipLaunchKernelGGL(sht_chunk_sort_kernel, dim3((unsigned)q.chunks, (unsigned)frames), dim3(kSortThreads), 0, stream, a, q);
 	hipLaunchKernelGGL(sht_strength_scan_kernel, dim3((unsigned)frames), dim3(kSortThreads), 0, stream, a, q);
 	hipLaunchKernelGGL(sht_place_lines_kernel, dim3((unsigned)(q.chunks * (kChunk / 256)), (unsigned)frames), dim3(256), 0, stream, a, q, thetaStep, maxLines,
-	                   reinterpret_cast<LineOut*>(lines), outCap);
+	                   reinterpret_cast<compvhip_line*>(lines), outCap);
 	return hipGetLastError();
 }
 

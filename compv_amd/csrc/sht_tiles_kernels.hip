@@ -20,7 +20,7 @@
 // Exactness: rho = (x cosQ + y sinQ) >> 16 with x = x0 + lx, y = y0 + ly.  With C = x0 cosQ + y0 sinQ = Chi * 65536 + Clo
 // (Clo in [0, 65536)): rho = Chi + q, q = (lx cosQ + ly sinQ + Clo) >> 16, and the accumulator row barrier - rho =
 // rowBase + w with w = qmax - q = (K - lx cosQ - ly sinQ) >> 16, K = qmax * 65536 + 65535 - Clo (host tables, int64 there).
-#include "kernels.hpp"
+#include "device.hpp"
 
 namespace compvhip {
 
@@ -70,13 +70,8 @@ __global__ __launch_bounds__(kTcThreads) void sht_compact_tiles_kernel(ShtArgs a
 		if (!(i < nwords && w0 + c < a.wb)) wv[k] = 0u;
 		cnt += __popc(wv[k]);
 	}
-	int incl = cnt;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		const int n = __shfl_up(incl, o);
-		if (lane >= o) incl += n;
-	}
+	const int incl = wave_incl_scan(cnt, lane);
 	if (lane == 63) s_wave[wave] = incl;
 	__syncthreads();
 	int wbase = 0, total = 0;

@@ -19,8 +19,7 @@
 //    (tools/microbench/cvt_pk_u8_test.hip: the conversion alone would round 0.999 up to 1).
 //  * gmax == 0 (single-thread branch, edge_dete.cxx:199): scale = inf -> NaN/INT_MIN -> every output byte 0.
 //  * |gx| + |gy| <= 2 * 16 * 255 = 8160 for the widest operator (Scharr): the reference's saturating add never saturates.
-#include "stencil.hpp"
-#include "kernels.hpp"
+#include "device.hpp"
 
 #include <type_traits>
 
@@ -33,11 +32,6 @@ constexpr int kEdCols = 256;      // columns per wave tile
 constexpr int kEdRows = 62;       // rows per wave tile (+ 2 = a multiple of kEdAhead)
 constexpr int kEdAhead = 4;       // input rows in flight per wave
 
-__device__ __forceinline__ uint32_t ed_pk_max_u16(uint32_t a, uint32_t b) { uint32_t d; asm("v_pk_max_u16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
-__device__ __forceinline__ uint32_t ed_lshl_add(uint32_t a, uint32_t b) { uint32_t d; asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }    // 2a + b
-__device__ __forceinline__ uint32_t ed_lshl3_add(uint32_t a, uint32_t b) { uint32_t d; asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }   // 8a + b
-__device__ __forceinline__ uint32_t ed_xad(uint32_t a, uint32_t sk, uint32_t c) { uint32_t d; asm("v_xad_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(sk), "v"(c)); return d; }   // (a ^ k) + c
-__device__ __forceinline__ uint32_t ed_add3s(uint32_t a, uint32_t b, uint32_t sk) { uint32_t d; asm("v_add3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(sk)); return d; }
 // float(half h of x) * scale, floored -- the integer part of the reference's product
 template <int HALF> __device__ __forceinline__ float ed_scaled(uint32_t x, float scale)
 {
@@ -139,31 +133,31 @@ __global__ __launch_bounds__(64, 8) void edge_dete_kernel(EdgeDeteArgs a)
 			const uint32_t Lk = L[k], Rk = L[k + 1], Ck = Ak[k];
 			const uint32_t s = Lk + Rk;
 			uint32_t hyN, gxb;
-			const uint32_t d = ed_xad(Lk, k255, Rk);                   // R - L + 255
+			const uint32_t d = xad(Lk, k255, Rk);                   // R - L + 255
 			if (A == 1 && B == 2) {                                    // Sobel
-				hyN = ed_lshl_add(Ck, s);
-				gxb = ed_add3s(P[k], d, kFixP);
-				P[k] = ed_lshl_add(d, dprev[k]);
+				hyN = lshl_add<1>(Ck, s);
+				gxb = add3(P[k], d, kFixP);
+				P[k] = lshl_add<1>(d, dprev[k]);
 				dprev[k] = d;
 			}
 			else if (A == 1) {                                         // Prewitt
 				hyN = s + Ck;
-				gxb = ed_add3s(P[k], d, kFixP);
+				gxb = add3(P[k], d, kFixP);
 				P[k] = dprev[k] + d;
 				dprev[k] = d;
 			}
 			else {                                                     // Scharr: 3, 10, 3 (dprev holds 3 d[y-1])
-				hyN = ed_lshl_add(s, s) + ed_lshl3_add(Ck, Ck + Ck);
-				const uint32_t d3 = ed_lshl_add(d, d);
-				gxb = ed_add3s(P[k], d3, kFixP);
-				P[k] = dprev[k] + ed_lshl3_add(d, d + d);
+				hyN = lshl_add<1>(s, s) + lshl_add<3>(Ck, Ck + Ck);
+				const uint32_t d3 = lshl_add<1>(d, d);
+				gxb = add3(P[k], d3, kFixP);
+				P[k] = dprev[k] + lshl_add<3>(d, d + d);
 				dprev[k] = d3;
 			}
-			const uint32_t gyb = ed_xad(hyTop[k], kKY, hyN);           // hy[y+1] - hy[y-1] + KY
+			const uint32_t gyb = xad(hyTop[k], kKY, hyN);           // hy[y+1] - hy[y-1] + KY
 			hyTop[k] = hyN;
-			const uint32_t mx = ed_pk_max_u16(gxb, 2u * BX * 0x00010001u - gxb);     // |gx| + BX
-			const uint32_t my = ed_pk_max_u16(gyb, 2u * KY * 0x00010001u - gyb);     // |gy| + KY
-			gq[k] = ed_add3s(mx, my, kNegBias);                        // |gx| + |gy| (each half >= its bias: no borrow between the halves)
+			const uint32_t mx = v_pk_max_u16(gxb, 2u * BX * 0x00010001u - gxb);     // |gx| + BX
+			const uint32_t my = v_pk_max_u16(gyb, 2u * KY * 0x00010001u - gyb);     // |gy| + KY
+			gq[k] = add3(mx, my, kNegBias);                        // |gx| + |gy| (each half >= its bias: no borrow between the halves)
 		}
 		if (it < 2 || it >= kEdRows + 2) return;   // (the unrolled loop runs a few steps past the tile)
 		const int yc = y0 + it - 2;
@@ -173,8 +167,8 @@ __global__ __launch_bounds__(64, 8) void edge_dete_kernel(EdgeDeteArgs a)
 			gq[0] &= okm[0] & rowm; gq[1] &= okm[1] & rowm;
 		}
 		if (!SCALE) {
-			vmax[0] = ed_pk_max_u16(vmax[0], gq[0]);
-			vmax[1] = ed_pk_max_u16(vmax[1], gq[1]);
+			vmax[0] = v_pk_max_u16(vmax[0], gq[0]);
+			vmax[1] = v_pk_max_u16(vmax[1], gq[1]);
 		}
 		else {
 			if (yc >= H) return;   // uniform

@@ -130,6 +130,71 @@ def test_segments_geometry_sweep(hip_ctx, oracle, W, H, S, F, theta):
         plan.close()
 
 
+def test_more_lines_than_one_scan_round(hip_ctx, oracle):
+    """More than 1024 lines per frame: the per-frame scan of the segment counts runs a second round and carries the first round's total
+    into it (1025 lines: a second round of one element).  The plan reads only row / col of the lines, so they are made up: cells that
+    cycle over every theta column and over the accumulator rows -- all of them in the first frame, those the image can reach in the second,
+    which so holds more segments per line -- and the frame's strongest cell as its last line (so that the second round of either frame has
+    segments to place).  segCap lies below the second frame's total and above where the first frame's second round starts."""
+    from compv_amd import capi
+    W, H, S, F, theta = 96, 64, 96, 2, 1.0
+    line_cap, n_lines = 1300, (1300, 1025)
+    rng = np.random.default_rng(964)
+    imgs = rng.integers(0, 96, (F, H, W), dtype=np.uint8)                # noise ...
+    for f in range(F):                                                   # ... plus strokes
+        imgs[f, 10 + 7 * f, 5:90] = 255
+        imgs[f, 3:60, 40 + 11 * f] = 255
+        i = np.arange(56)
+        imgs[f, 4 + i, 20 + i + 5 * f] = 255
+        imgs[f, 60 - i, 8 + i] = 255
+    R, T, _ = oracle.sht_dims(W, H, theta)
+    sinQ, cosQ = tables(oracle, W, H, theta)
+    barrier = W + H
+    rows = [np.arange(R), np.arange(max(0, barrier - 116), min(R, barrier + 97))]     # rho = barrier - row between -96 and 115: what 96 x 64 pixels vote for
+    A = Arena()
+    d_in = A.new(F * H * S, imgs)
+    d_e = A.new(F * H * S)
+    d_sc = A.new(F * 4)
+    plan = capi.Plan(hip_ctx, W, H, S, F, theta)
+    try:
+        plan.canny(ptr(d_in), T_LOW, T_HIGH, ptr(d_e))
+        A.check("canny")
+        edges = frames_view(d_e, F, H, S, W).copy()          # bit-exact against the oracle in tests/test_gpu_plan_geometry.py
+        A.keep(d_e, d_e.cpu().numpy())
+        lines = []
+        host_lines = np.full((F, line_cap * LINE_BYTES), SENTINEL, np.uint8)
+        for f in range(F):
+            k = np.arange(n_lines[f])
+            ln = np.zeros(n_lines[f], capi.LINE_DTYPE)
+            ln["row"] = rows[f][(k * 7 + 3 * f) % len(rows[f])]
+            ln["col"] = (k * 11 + f) % T
+            acc = oracle.sht_acc(np.ascontiguousarray(edges[f]), theta)
+            ln["row"][-1], ln["col"][-1] = np.unravel_index(int(acc.argmax()), acc.shape)
+            lines.append(ln)
+            host_lines[f, :n_lines[f] * LINE_BYTES] = np.frombuffer(ln.tobytes(), np.uint8)
+        d_lines = A.new(F * line_cap * LINE_BYTES, host_lines)
+        d_counts = A.new(F * 4, np.array(n_lines, np.int32).view(np.uint8))
+        A.keep(d_lines, host_lines); A.keep(d_counts, d_counts.cpu().numpy())
+        params = [(1, 0), (5, 2)]
+        exp = model_frames(edges, sinQ, cosQ, lines, params)
+        for p in params:
+            # segments behind line 1024 of both frames: the carry is what places them
+            assert all((e["line"] >= 1024).any() for e in exp[p]), p
+            seg_cap = len(exp[p][1]) - 3
+            assert seg_cap > int(np.searchsorted(exp[p][0]["line"], 1024)), (p, seg_cap)     # ... and the first frame's are among the records written
+            d_segs = A.new(F * seg_cap * SEG_BYTES)
+            got = {}
+            for how, de in (("masks", 0), ("bytes", ptr(d_e))):
+                A.refill(d_segs); A.refill(d_sc)
+                plan.houghsht_segments(de, ptr(d_lines), ptr(d_counts), line_cap, 0, p[0], p[1], ptr(d_segs), seg_cap, ptr(d_sc))
+                A.check("segments %s %s" % (how, p))
+                assert_segments(d_segs, d_sc, F, seg_cap, exp[p], "segments %s %s" % (how, p))
+                got[how] = d_segs.cpu().numpy().tobytes()
+            assert got["masks"] == got["bytes"], p
+    finally:
+        plan.close()
+
+
 def _drawn_wide_map(W, H, seed, density):
     """Sparse noise plus a few long drawn lines (horizontal, vertical, two diagonals)."""
     rng = np.random.default_rng(seed)
