@@ -32,6 +32,7 @@ STREL_RECT, STREL_DIAMOND, STREL_CROSS = 0, 1, 2
 BORDER_ZERO, BORDER_REPLICATE = 0, 2
 MORPH_KERNEL_AUTO, MORPH_KERNEL_GENERAL, MORPH_KERNEL_SEPARABLE = 0, 1, 2
 CORNER_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("strength", "<i4")])   # compvhip_corner
+KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("strength", "<f4"), ("orient", "<f4"), ("level", "<i4"), ("size", "<f4")])   # compvhip_keypoint = CompVInterestPoint
 MATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imageIdx", "<i4"), ("distance", "<i4")])   # compvhip_match = CompVDMatch
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
@@ -53,6 +54,7 @@ EXPORTS = [
     "compvhip_threshold_u8", "compvhip_plan_threshold", "compvhip_threshold_adaptive_u8", "compvhip_plan_threshold_adaptive",
     "compvhip_morph_strel", "compvhip_morph_u8", "compvhip_plan_morph", "compvhip_plan_morph_ex",
     "compvhip_plan_fast", "compvhip_fast_u8",
+    "compvhip_plan_orb_keypoints", "compvhip_plan_orb_describe", "compvhip_orb_u8",
     "compvhip_matcher_create", "compvhip_matcher_destroy", "compvhip_matcher_knn", "compvhip_matcher_good", "compvhip_match_hamming_u8",
     "compvhip_matcher_set_timing", "compvhip_matcher_get_timing",
 ]
@@ -110,6 +112,11 @@ def _kht_order(order):
     if order not in KHT_ORDERS:
         raise ValueError("order must be one of %s, not %r" % (sorted(KHT_ORDERS), order))
     return KHT_ORDERS[order]
+
+
+class Keypoint(C.Structure):
+    """compvhip_keypoint (include/compv_hip.h): CompVInterestPoint's layout, 24 bytes"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("strength", C.c_float), ("orient", C.c_float), ("level", C.c_int32), ("size", C.c_float)]
 
 
 class MatchOpts(C.Structure):
@@ -209,6 +216,9 @@ def load():
     L.compvhip_plan_morph_ex.argtypes = [vp, vp, vp, sz, sz, i32, i32, i32, vp, vp]
     L.compvhip_plan_fast.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, sz, vp, vp]
     L.compvhip_fast_u8.argtypes = [vp, vp, sz, sz, sz, i32, i32, i32, i32, vp, sz, vp, sz, C.POINTER(sz)]
+    L.compvhip_plan_orb_keypoints.argtypes = [vp, vp, vp, sz, vp, i32, C.c_float, vp, sz, vp, vp, vp]
+    L.compvhip_plan_orb_describe.argtypes = [vp, vp, vp, sz, vp, C.c_float, i32, vp, sz, vp]
+    L.compvhip_orb_u8.argtypes = [vp, vp, sz, sz, sz, vp, sz, i32, C.c_float, vp, vp, sz, C.POINTER(sz)]
     L.compvhip_matcher_create.argtypes = [vp, sz, sz, sz, sz, i32, C.POINTER(vp)]
     L.compvhip_matcher_destroy.argtypes = [vp]
     L.compvhip_matcher_destroy.restype = None
@@ -419,6 +429,19 @@ class Context:
         self._chk(rc)
         return (rec[:n.value], scores) if want_scores else rec[:n.value]
 
+    def orb(self, img, corners, level=0, scale=1.0):
+        """compvhip_orb_u8: corners (CORNER_DTYPE, e.g. fast()'s) of one pyramid level -> (keypoints KEYPOINT_DTYPE, descriptors (n, 32) uint8): the corners
+        18 pixels from every border, in their order, with the intensity-centroid orientation, and their rotated BRIEF-256/31 rows."""
+        H, W = img.shape
+        corners = np.ascontiguousarray(corners, CORNER_DTYPE)
+        n = len(corners)
+        keys = np.zeros(n, KEYPOINT_DTYPE)
+        desc = np.zeros((n, 32), np.uint8)
+        kept = C.c_size_t(0)
+        self._chk(self.lib.compvhip_orb_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(corners) if n else None, n, level, scale, _ptr(keys) if n else None,
+                                           _ptr(desc) if n else None, 32, C.byref(kept)))
+        return keys[:kept.value], desc[:kept.value]
+
     def match_hamming(self, query, train, knn=2):
         """compvhip_match_hamming_u8 (CompVMatcherBruteForce::process): query (Q, cols) and train (T, cols) uint8 rows -> (min(knn, T), Q) MATCH_DTYPE
         records, neighbour r of query q at [r, q], distances ascending.  Among equal distances the records follow the REFERENCE's insertion order
@@ -559,6 +582,16 @@ class Plan:
         """compvhip_plan_fast: d_scores = 0 for no score map, d_corners = 0 with corner_cap = 0 for counts only."""
         self.ctx._chk(self.lib.compvhip_plan_fast(self.h, d_gray, threshold, fast_type, int(bool(nonmax)), max_features, d_scores or None,
                                                   d_corners or None, corner_cap, d_counts, stream))
+
+    def orb_keypoints(self, d_gray, d_corners, corner_cap, d_corner_counts, level, scale, d_keypoints, key_cap, d_key_counts, d_moments=0, stream=0):
+        """compvhip_plan_orb_keypoints: d_corners / d_corner_counts as fast() wrote them; d_moments = 0 or [frames][key_cap][2] int32 = {m01, m10}."""
+        self.ctx._chk(self.lib.compvhip_plan_orb_keypoints(self.h, d_gray, d_corners or None, corner_cap, d_corner_counts or None, level, scale, d_keypoints or None,
+                                                           key_cap, d_key_counts or None, d_moments or None, stream))
+
+    def orb_describe(self, d_gray, d_keypoints, key_cap, d_key_counts, scale, d_desc, desc_stride=32, blur=True, stream=0):
+        """compvhip_plan_orb_describe: 32-byte rows at d_desc + (f * key_cap + q) * desc_stride; blur=False takes d_gray as already blurred."""
+        self.ctx._chk(self.lib.compvhip_plan_orb_describe(self.h, d_gray, d_keypoints or None, key_cap, d_key_counts or None, scale, int(bool(blur)), d_desc or None,
+                                                          desc_stride, stream))
 
     def pipeline(self, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap, d_counts, stream=0):
         self.ctx._chk(self.lib.compvhip_plan_pipeline(self.h, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap,

@@ -451,6 +451,7 @@ void compvhip_ctx_destroy(compvhip_ctx* ctx)
 	ctx->dPacked.release(ctx); ctx->dHist.release(ctx); ctx->dIn.release(ctx); ctx->dOut.release(ctx); ctx->dCounts.release(ctx); ctx->dAccOut.release(ctx);
 	ctx->dSegLines.release(ctx); ctx->dSegs.release(ctx); ctx->dSegCount.release(ctx); ctx->dFits.release(ctx); ctx->dFitCount.release(ctx); ctx->dFitRefined.release(ctx);
 	ctx->dCompLabels.release(ctx); ctx->dComps.release(ctx); ctx->dCompCount.release(ctx); ctx->dFastCorners.release(ctx); ctx->dFastCount.release(ctx);
+	ctx->dOrbKeys.release(ctx); ctx->dOrbCount.release(ctx); ctx->dOrbDesc.release(ctx);
 	khtScratchFree(ctx, ctx->kht);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
@@ -595,6 +596,7 @@ void compvhip_plan_destroy(compvhip_plan* p)
 	dfree(ctx, p->hist); dfree(ctx, p->otsu); dfree(ctx, p->blurTmp); dfree(ctx, p->grayTmp);
 	dfree(ctx, p->morphTmp);
 	dfree(ctx, p->fastWork); dfree(ctx, p->fastScores);
+	p->orbIndex.release(ctx); dfree(ctx, p->orbBlur);
 	for (KhtBatchState* b : p->khtBatch) khtBatchFree(ctx, b);
 	p->khtBatch.clear();
 	dfree(ctx, p->cosT); dfree(ctx, p->invSinT);

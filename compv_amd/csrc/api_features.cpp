@@ -1,5 +1,5 @@
 // api_features.cpp -- plan-level calls of the features built on the Canny / SHT plan: line segments, line fits, connected components,
-// thresholding and morphology, FAST corners, brute-force matching.
+// thresholding and morphology, FAST corners, ORB keypoints and descriptors, brute-force matching.
 #include "api_internal.hpp"
 
 // what the segment and the fit kernels read alike: the edge pixels, the vote's tables, the lines
@@ -336,6 +336,75 @@ int compvhip_plan_fast(compvhip_plan* p, const uint8_t* d_gray, int threshold, i
 	HIPCHK(ctx, hipMemsetAsync(a.rowCounts, 0, F * (H + 256) * sizeof(int), st));   // the row counts and the histogram are sums
 	{ Stamp s(p, st, "fast_score_kernel"); HIPCHK(ctx, launch_fast(a, static_cast<int>(F), 0, st)); }
 	{ Stamp s(p, st, "fast_list_kernels"); HIPCHK(ctx, launch_fast(a, static_cast<int>(F), 1, st)); }   // cut level, row recount, scan, emit
+	return COMPVHIP_OK;
+}
+
+// ---- ORB keypoints and descriptors (orb_kernels.hip; definition in include/compv_hip.h) -------------------------------------------------------
+int compvhip_api::checkOrb(compvhip_ctx* ctx, size_t W, size_t H, float scale)
+{
+	if (W < 2 * kOrbBorder + 1 || H < 2 * kOrbBorder + 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "ORB needs W, H >= 37 (one position 18 pixels from every border)");
+	if (!(scale > 0.f)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "scale must be > 0");
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_orb_keypoints(compvhip_plan* p, const uint8_t* d_gray, const compvhip_corner* d_corners, size_t cornerCap, const int32_t* d_cornerCounts, int level,
+                                float scale, compvhip_keypoint* d_keypoints, size_t keyCap, int32_t* d_keyCounts, int32_t* d_moments, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_gray || !d_corners || !d_cornerCounts || !d_keyCounts || (keyCap && !d_keypoints)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame / corner / count / keypoint pointer");
+	int rc = checkOrb(ctx, p->W, p->H, scale);
+	if (rc) return rc;
+	if (cornerCap > static_cast<size_t>(INT32_MAX) || keyCap > static_cast<size_t>(INT32_MAX) || p->frames > 65535) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity beyond 2^31 or more than 65535 frames");
+	if ((reinterpret_cast<uintptr_t>(d_corners) & 3) || (reinterpret_cast<uintptr_t>(d_cornerCounts) & 3) || (reinterpret_cast<uintptr_t>(d_keypoints) & 3) ||
+	    (reinterpret_cast<uintptr_t>(d_keyCounts) & 3) || (reinterpret_cast<uintptr_t>(d_moments) & 3) || (reinterpret_cast<uintptr_t>(d_gray) & 3))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames, records, counts and moments must be 4-byte aligned");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int frames = static_cast<int>(p->frames);
+	HIPCHK(ctx, p->orbIndex.reserve(ctx, p->frames * keyCap));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	OrbKeyArgs a;
+	a.gray = d_gray; a.frameStride = p->S * p->H; a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
+	a.corners = d_corners; a.cornerCap = cornerCap; a.cornerCounts = d_cornerCounts; a.level = level; a.scale = scale;
+	a.index = p->orbIndex; a.keys = d_keypoints; a.keyCap = keyCap; a.keyCounts = d_keyCounts; a.moments = d_moments;
+	{ Stamp s(p, st, "orb_select_kernel"); HIPCHK(ctx, launch_orb_select(a, frames, st)); }
+	if (keyCap) { Stamp s(p, st, "orb_orient_kernel"); HIPCHK(ctx, launch_orb_orient(a, frames, st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_orb_describe(compvhip_plan* p, const uint8_t* d_gray, const compvhip_keypoint* d_keypoints, size_t keyCap, const int32_t* d_keyCounts, float scale,
+                               int blur, uint8_t* d_desc, size_t descStride, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_gray || !d_keypoints || !d_keyCounts || !d_desc || !keyCap) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame / keypoint / count / descriptor pointer or keyCap == 0");
+	int rc = checkOrb(ctx, p->W, p->H, scale);
+	if (rc) return rc;
+	if (descStride < 32 || (descStride & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descStride below 32 or no multiple of 4");
+	if (keyCap > static_cast<size_t>(INT32_MAX) || p->frames > 65535) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity beyond 2^31 or more than 65535 frames");
+	if ((reinterpret_cast<uintptr_t>(d_gray) & 3) || (reinterpret_cast<uintptr_t>(d_keypoints) & 3) || (reinterpret_cast<uintptr_t>(d_keyCounts) & 3) || (reinterpret_cast<uintptr_t>(d_desc) & 3))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames, records, counts and descriptors must be 4-byte aligned");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int frames = static_cast<int>(p->frames);
+	if (!p->orbKernReady) {
+		if (compvhip_gauss_kernel_fixedpoint(5, 2.0f, p->orbKern) != COMPVHIP_OK) return fail(ctx, COMPVHIP_E_INVALID_STATE, "Gaussian kernel");   // compv_core_feature_orb_desc.cxx:119-120
+		const char* e = getenv("COMPVHIP_ORB_BRIEF");   // lab knob (tools/orb_bench.py): "lds" / "global" name the byte-read variant of orb_brief_kernel
+		p->orbBriefLds = e ? !strcmp(e, "lds") : kOrbBriefLdsDefault;
+		p->orbKernReady = true;
+	}
+	if (blur && !p->orbBlur) HIPCHK(ctx, dmalloc(ctx, &p->orbBlur, p->S * p->H * p->frames));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	if (blur) {   // out of place: the fused kernel, no intermediate
+		Stamp s(p, st, "convlt_fxp_kernels");
+		HIPCHK(ctx, launch_convlt_fxp(d_gray, nullptr, p->orbBlur, static_cast<int>(p->W), static_cast<int>(p->H), static_cast<int>(p->S), p->S * p->H, frames, p->orbKern,
+		                              p->orbKern, 5, st));
+	}
+	OrbDescArgs a;
+	a.blurred = blur ? p->orbBlur : d_gray; a.frameStride = p->S * p->H; a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
+	a.keys = d_keypoints; a.keyCap = keyCap; a.keyCounts = d_keyCounts; a.scale = scale; a.desc = d_desc; a.descStride = descStride;
+	{ Stamp s(p, st, "orb_brief_kernel"); HIPCHK(ctx, launch_orb_brief(a, frames, p->orbBriefLds, st)); }
 	return COMPVHIP_OK;
 }
 

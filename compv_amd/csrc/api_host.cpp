@@ -415,6 +415,38 @@ int compvhip_fast_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H,
 	});
 }
 
+int compvhip_orb_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_corner* corners, size_t n, int level, float scale,
+                    compvhip_keypoint* keypoints, uint8_t* desc, size_t descStride, size_t* kept)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!gray || !kept || S < W || (n && (!corners || !keypoints || !desc))) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	*kept = 0;
+	int rc = checkOrb(ctx, W, H, scale);
+	if (rc) return rc;
+	if (W > 32767 || H > 32767 || n > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (37..32767) or n beyond 2^31");
+	if (descStride < 32 || (descStride & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descStride below 32 or no multiple of 4");
+	if (!n) return COMPVHIP_OK;
+	return hostPlaneOp(ctx, gray, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p) -> int {
+		HIPCHK(ctx, ctx->dFastCorners.reserve(ctx, n));
+		HIPCHK(ctx, ctx->dFastCount.reserve(ctx, 1));
+		HIPCHK(ctx, ctx->dOrbKeys.reserve(ctx, n));
+		HIPCHK(ctx, ctx->dOrbCount.reserve(ctx, 1));
+		HIPCHK(ctx, ctx->dOrbDesc.reserve(ctx, n * 32));
+		const int32_t count = static_cast<int32_t>(n);
+		HIPCHK(ctx, hipMemcpyAsync(ctx->dFastCorners, corners, n * sizeof(compvhip_corner), hipMemcpyHostToDevice, ctx->stream));
+		HIPCHK(ctx, hipMemcpyAsync(ctx->dFastCount, &count, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the count lives on this stack frame; pageable copies may still be staged
+		int rc = compvhip_plan_orb_keypoints(p, ctx->dIn, ctx->dFastCorners, n, ctx->dFastCount, level, scale, ctx->dOrbKeys, n, ctx->dOrbCount, nullptr, ctx->stream);
+		if (rc) return rc;
+		rc = compvhip_plan_orb_describe(p, ctx->dIn, ctx->dOrbKeys, n, ctx->dOrbCount, scale, 1, ctx->dOrbDesc, 32, ctx->stream);
+		if (rc) return rc;
+		rc = takeList(ctx, ctx->dOrbCount.ptr, ctx->dOrbKeys.ptr, keypoints, n, kept, "keypoint buffer too small");
+		if (rc || !*kept) return rc;
+		HIPCHK(ctx, hipMemcpy2D(desc, descStride, ctx->dOrbDesc, 32, 32, *kept, hipMemcpyDeviceToHost));
+		return COMPVHIP_OK;
+	});
+}
+
 int compvhip_threshold_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double threshold, uint8_t* out, size_t So)
 {
 	int rc = checkImage(ctx, in, W, H, S, out, So);

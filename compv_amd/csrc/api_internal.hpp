@@ -157,6 +157,9 @@ struct compvhip_ctx {
 	DevBuf<int32_t> dCompCount;        // ... and their number
 	DevBuf<compvhip_corner> dFastCorners;   // staging of compvhip_fast_u8: the records (the score map travels through dOut) ...
 	DevBuf<int32_t> dFastCount;             // ... and their number
+	DevBuf<compvhip_keypoint> dOrbKeys;     // staging of compvhip_orb_u8 (the corners and their number travel through dFastCorners / dFastCount): the records ...
+	DevBuf<int32_t> dOrbCount;              // ... their number ...
+	DevBuf<uint8_t> dOrbDesc;               // ... and the descriptor rows
 	KhtScratch kht;                    // KHT scratch of the host entry point (compvhip_houghkht_u8)
 };
 
@@ -231,6 +234,9 @@ struct compvhip_plan : TimingState {
 	// FAST corners (fast_kernels.hip), allocated on first use: [frames][H] corners per row, [frames][H] their scan, [frames][256] score histogram, [frames] cut
 	// level -- one allocation; and the score map [frames][H][S] of the calls that do not want one
 	int* fastWork = nullptr; uint8_t* fastScores = nullptr;
+	// ORB (orb_kernels.hip), allocated on first use: [frames][keyCap] source indices of the surviving corners (grows with the largest keyCap seen); the blurred
+	// batch [frames][H][S] of the describe calls with blur != 0; the Q16 Gaussian (5, 2.0f), computed once; which byte-read variant of orb_brief_kernel runs
+	DevBuf<int32_t> orbIndex; uint8_t* orbBlur = nullptr; uint16_t orbKern[5] = {}; bool orbKernReady = false; bool orbBriefLds = false;
 	int strengthBits = 16, keyBits = 0;
 	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
 	uint16_t* chunkHist = nullptr; uint32_t* strengthStart = nullptr; int sortChunks = 0; bool deviceSort = false;
@@ -352,6 +358,7 @@ int componentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeStride, 
 int checkAdaptive(compvhip_ctx* ctx, size_t W, size_t H, size_t blockSize, double delta, double maxVal);
 int morphPrepare(compvhip_ctx* ctx, size_t W, size_t H, const uint8_t* strel, size_t sw, size_t sh, int op, int border, int kernel, MorphArgs* a);
 int checkFast(compvhip_ctx* ctx, size_t W, size_t H, int fastType);
+int checkOrb(compvhip_ctx* ctx, size_t W, size_t H, float scale);
 MatchSliceArgs matchForward(const compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
                             const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches);
 // api_kht.cpp

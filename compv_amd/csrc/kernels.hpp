@@ -336,4 +336,35 @@ struct MatchGoodArgs {
 };
 hipError_t launch_match_good(const MatchGoodArgs& a, int pairs, hipStream_t stream);
 
+// ---- ORB: keypoint orientation and rotated BRIEF (orb_kernels.hip) -------------------------------------------------------------------------
+// the byte-read variant of orb_brief_kernel that ships: at 32 x 4K with 2000 keypoints a frame the two measured alike (0.0678 ms with the LDS patch, 0.0680 ms
+// with bytes from global memory; docs/kernels/orb.md), so the first one built stays
+constexpr bool kOrbBriefLdsDefault = true;
+constexpr int kOrbBorder = 18;            // (31 + 5) >> 1: a keypoint lies this far from every border; a rotated pattern point reaches no further
+struct OrbKeyArgs {
+	const uint8_t* gray;      // [frames][H][S], the unblurred plane
+	size_t frameStride;
+	int W, H, S;
+	const compvhip_corner* corners; size_t cornerCap;   // [frames][cornerCap]
+	const int32_t* cornerCounts;                        // [frames] corners found (may exceed cornerCap, may be negative)
+	int level; float scale;
+	int32_t* index;           // [frames][keyCap] scratch: source index of the q-th survivor
+	compvhip_keypoint* keys; size_t keyCap;             // [frames][keyCap]
+	int32_t* keyCounts;       // [frames] survivors before clipping to keyCap
+	int32_t* moments;         // nullptr or [frames][keyCap][2] = {m01, m10}
+};
+hipError_t launch_orb_select(const OrbKeyArgs& a, int frames, hipStream_t stream);
+hipError_t launch_orb_orient(const OrbKeyArgs& a, int frames, hipStream_t stream);
+struct OrbDescArgs {
+	const uint8_t* blurred;   // [frames][H][S], 4-byte aligned, S % 4 == 0
+	size_t frameStride;
+	int W, H, S;
+	const compvhip_keypoint* keys; size_t keyCap;
+	const int32_t* keyCounts;
+	float scale;
+	uint8_t* desc; size_t descStride;                   // row q of frame f at desc + (f * keyCap + q) * descStride; 4-byte aligned, descStride % 4 == 0
+};
+// lds: the tests read a patch staged in the LDS (else their bytes from global memory); the result does not depend on it
+hipError_t launch_orb_brief(const OrbDescArgs& a, int frames, bool lds, hipStream_t stream);
+
 } // namespace compvhip

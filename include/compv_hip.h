@@ -682,6 +682,67 @@ COMPVHIP_API int compvhip_match_hamming_u8(compvhip_ctx* ctx, const uint8_t* que
 COMPVHIP_API int compvhip_matcher_set_timing(compvhip_matcher* matcher, int enabled);
 COMPVHIP_API int compvhip_matcher_get_timing(compvhip_matcher* matcher, const char** names, float* ms, int cap);
 
+/* ---- ORB: keypoint orientation and rotated-BRIEF descriptors (docs/kernels/orb.md) ------------------------------------------------------
+ * The intensity-centroid orientation of CompVCornerDeteORB::processLevelAt (core/features/orb/compv_core_feature_orb_dete.cxx:281-358) and the
+ * BRIEF-256/31 of CompVCornerDescORB (compv_core_feature_orb_desc.cxx:206-319) for ONE pyramid level: a plan is the level's geometry, the calls
+ * take the level's number and scale factor.  (No pyramid here: it only adds planes and plans.)  Every output is defined bit for bit.
+ * Keypoints, from a corner list {x, y, strength} of a gray frame I of W x H:
+ *  1. Border erase (eraseTooCloseToBorder, compv_common.h:657): with b = 18 = (31 + 5) >> 1, a corner with x < b, x + b >= W, y < b or
+ *     y + b >= H is dropped; the survivors keep their order.
+ *  2. Moments (CompVPatch::moments0110, base/compv_patch.cxx:106-165, radius 15): m10 = sum i * I(x + i, y + j), m01 = sum j * I(x + i, y + j) over
+ *     j = -15 .. 15, i = -dX[|j|] .. dX[|j|], dX[k] = (int)sqrt(225 - k * k) (row |j| = 15: the centre column only); exact int32, on the
+ *     UNBLURRED plane.
+ *  3. Orientation: rad = (float)atan2((double)m01, (double)m10); orient = rad * k180OverPi, a float32 product with
+ *     k180OverPi = 180.f / 3.1415926535897932384626433f evaluated in float32 (base/math/compv_math.cxx:27,31); orient += 360.f when orient < 0.
+ *     The reference calls std::atan2(float, float), whose last bit depends on the libm; the binary64 call rounded once is the canonical value.
+ *  4. Record: x, y = (float) of the corner's integers, multiplied by sfi = 1.f / scale when level != 0 (:351-354); strength = (float) of the
+ *     corner's; level = the argument; size = 31 / scale (float32).
+ *  5. Counts and capacity, as compvhip_plan_fast: d_keyCounts[f] = survivors of frame f BEFORE clipping to keyCap; the first min(count, keyCap)
+ *     records are written at d_keypoints + f * keyCap and nothing behind them.  d_cornerCounts[f] may exceed cornerCap (min is used); a
+ *     negative count is 0.
+ * Descriptors, 32 bytes per keypoint, row q of frame f at d_desc + (f * keyCap + q) * descStride:
+ *  1. Blur: CompVMathConvlt::convlt1FixedPoint with CompVMathGauss::kernelDim1FixedPoint(5, 2.0f) on both axes (zero output border of 2), into a
+ *     plane of the plan's own: d_gray is never modified (the reference blurs its pyramid in place).  blur == 0: d_gray IS the blurred plane.
+ *  2. Centre: fx = x * scale (float32), xi = (int)((double)fx + 0.5); the same for y (:279-288).
+ *  3. Angle: a = orient * kPiOver180 (float32, kPiOver180 = 3.1415926535897932384626433f / 180.f); fcos = (float)cos((double)a),
+ *     fsin = (float)sin((double)a) -- canonical as in 3. above (the reference: std::cos / std::sin of a float).
+ *  4. Test i of the 256, pattern points (AX, AY), (BX, BY) -- the published rBRIEF pattern of the ORB method, coordinates in -13 .. 12 -- as the
+ *     reference's AVX2 leaf computes it: xf = AX * fcos - AY * fsin, yf = AX * fsin + AY * fcos (two float32 products, one float32 sum, no
+ *     FMA); x = rint(xf), y = rint(yf), ties to even; a = blurred(xi + x, yi + y), b likewise from (BX, BY); bit i % 8 of byte i / 8 is a < b.
+ *  5. A keypoint with xi < 18, xi + 18 >= W, yi < 18 or yi + 18 >= H gets 32 zero bytes IN ITS OWN ROW.  (The reference tests radius 15 and does
+ *     not advance its output pointer for such a point, which shifts every later row.  18 is what the detector guarantees and what a rotated
+ *     (+-13, +-13) reaches: 13 * sqrt(2) = 18.38 rounds to 18.)
+ *  6. Rows q >= min(d_keyCounts[f], keyCap) are never written.
+ * W or H < 37: COMPVHIP_E_INVALID_PARAMETER (no admissible position). */
+typedef struct compvhip_keypoint {   /* CompVInterestPoint (compv_common.h:629), 24 bytes */
+	float x, y;
+	float strength;
+	float orient;               /* degrees, [0, 360] */
+	int32_t level;
+	float size;
+} compvhip_keypoint;
+
+/* Keypoints of all frames of the plan from the corner lists compvhip_plan_fast wrote (d_corners: [frames][cornerCap], d_cornerCounts: [frames],
+ * device).  d_gray: [frames][H][S], 4-byte aligned; d_keypoints: [frames][keyCap] (NULL with keyCap == 0: counts only); d_moments: NULL or
+ * [frames][keyCap][2] int32 = {m01, m10}; records, counts and moments 4-byte aligned; scale > 0 (anything else: COMPVHIP_E_INVALID_PARAMETER).
+ * Asynchronous on `stream`, no atomic, deterministic.  Scratch is owned by the plan, allocated on first use (and again for a larger keyCap) and
+ * released with it: frames * keyCap int32. */
+COMPVHIP_API int compvhip_plan_orb_keypoints(compvhip_plan* plan, const uint8_t* d_gray, const compvhip_corner* d_corners, size_t cornerCap,
+                                             const int32_t* d_cornerCounts, int level, float scale, compvhip_keypoint* d_keypoints, size_t keyCap,
+                                             int32_t* d_keyCounts, int32_t* d_moments, void* stream);
+
+/* Descriptors of the keypoints (compvhip_plan_orb_keypoints' or the caller's own) with the level's `scale`.  descStride >= 32 and a multiple of 4,
+ * d_desc 4-byte aligned, keyCap > 0 (anything else: COMPVHIP_E_INVALID_PARAMETER).  With descStride == 32, d_desc / d_keyCounts are what
+ * compvhip_matcher_knn takes as d_query / d_queryCounts.  Asynchronous on `stream`.  Scratch, allocated on first use with blur != 0: one blurred
+ * batch [frames][H][S]. */
+COMPVHIP_API int compvhip_plan_orb_describe(compvhip_plan* plan, const uint8_t* d_gray, const compvhip_keypoint* d_keypoints, size_t keyCap,
+                                            const int32_t* d_keyCounts, float scale, int blur, uint8_t* d_desc, size_t descStride, void* stream);
+
+/* Both for one HOST frame (37 <= W, H <= 32767) and n host corners: keypoints and desc have room for n records / n rows of descStride bytes;
+ * *kept receives the number of keypoints (<= n).  Synchronous, on the context's cached single-frame plan. */
+COMPVHIP_API int compvhip_orb_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_corner* corners, size_t n,
+                                 int level, float scale, compvhip_keypoint* keypoints, uint8_t* desc, size_t descStride, size_t* kept);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel

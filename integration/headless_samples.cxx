@@ -8,6 +8,8 @@
 // usage: headless_samples [W H [frames [cpuThreads]]]      exit code 0 = drop-in parity on every frame
 //        headless_samples --fast-only [W H]                 the FAST corner comparison alone (default 200 x 258), with the median time of five calls each
 //        headless_samples --match-only [Q T]                the brute-force matcher comparison alone (default 2000 x 2000 rows of 32 bytes, KNN 2), byte for byte
+//        headless_samples --orb-only [W H N]                the reference's ORB orientation and description of about N keypoints of one level, timed on the CPU alone
+//                                                           (default 3840 x 2160, 2000): what compvhip_plan_orb_keypoints / _describe replace; no GPU is touched
 // cpuThreads (default 1) is CompVBase::init()'s thread count for the CPU reference run.  The default is the single-threaded
 // path because the reference's multi-threaded gradient is not deterministic: each row band also recomputes |gx|+|gy| for
 // its two overlap rows from gx/gy rows that the neighbouring band may not have written yet
@@ -17,6 +19,7 @@
 #include <compv/base/compv_features.h>
 #include <compv/base/compv_matchers.h>
 #include <compv/base/compv_debug.h>
+#include <compv/base/compv_patch.h>
 #include <compv/base/image/compv_image.h>
 #include <compv/core/compv_core.h>
 #include <compv/core/calib/compv_core_calib_camera.h>
@@ -223,6 +226,52 @@ static COMPV_ERROR_CODE runMatch(std::vector<int32_t>& out, double& ms, size_t Q
 	return COMPV_ERROR_CODE_S_OK;
 }
 
+// The reference's ORB stages that follow the corner detector, for one pyramid level: an ORB detector (one level, maxFeatures = N) finds the points and owns the
+// pyramid; then, median of five calls each, (a) CompVPatch::moments0110 + atan2 + the degree conversion for every point, as processLevelAt does
+// (compv_core_feature_orb_dete.cxx:331-355), and (b) CompVCornerDescORB::process: the fixed-point blur of the level and the 256 tests per point.
+static COMPV_ERROR_CODE runOrbReference(size_t W, size_t H, int N, size_t& points, double& orientMs, double& describeMs)
+{
+	CompVMatPtr image;
+	COMPV_CHECK_CODE_RETURN(CompVImage::newObj8u(&image, COMPV_SUBTYPE_PIXELS_Y, W, H));
+	synthFrame(image, 777u);
+	CompVCornerDetePtr dete;
+	COMPV_CHECK_CODE_RETURN(CompVCornerDete::newObj(&dete, COMPV_ORB_ID));
+	COMPV_CHECK_CODE_RETURN(dete->setInt(COMPV_ORB_SET_INT_PYRAMID_LEVELS, 1));
+	COMPV_CHECK_CODE_RETURN(dete->setInt(COMPV_ORB_SET_INT_MAX_FEATURES, N));
+	CompVInterestPointVector pts;
+	COMPV_CHECK_CODE_RETURN(dete->process(image, pts));
+	points = pts.size();
+	CompVPatchPtr patch;
+	COMPV_CHECK_CODE_RETURN(CompVPatch::newObj(&patch, 31));
+	double samples[5];
+	float sink = 0.f;
+	for (int i = 0; i < 5; ++i) {
+		const auto t0 = std::chrono::steady_clock::now();
+		for (size_t k = 0; k < pts.size(); ++k) {
+			int m01 = 0, m10 = 0;
+			COMPV_CHECK_CODE_RETURN(patch->moments0110(image->ptr<const uint8_t>(), (int)pts[k].x, (int)pts[k].y, W, H, image->stride(), &m01, &m10));
+			float orient = COMPV_MATH_RADIAN_TO_DEGREE_FLOAT(COMPV_MATH_ATAN2(static_cast<float>(m01), static_cast<float>(m10)));
+			if (orient < 0) orient += 360;
+			sink += orient;
+		}
+		samples[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	}
+	std::sort(samples, samples + 5);
+	orientMs = samples[2];
+	CompVCornerDescPtr desc;
+	COMPV_CHECK_CODE_RETURN(CompVCornerDesc::newObj(&desc, COMPV_ORB_ID, dete));
+	CompVMatPtr rows;
+	COMPV_CHECK_CODE_RETURN(desc->process(image, pts, &rows));          // the first call allocates; every call blurs the detector's level plane (in place) and describes
+	for (int i = 0; i < 5; ++i) {
+		const auto t0 = std::chrono::steady_clock::now();
+		COMPV_CHECK_CODE_RETURN(desc->process(image, pts, &rows));
+		samples[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	}
+	std::sort(samples, samples + 5);
+	describeMs = samples[2];
+	return sink == sink ? COMPV_ERROR_CODE_S_OK : COMPV_ERROR_CODE_E_UNITTEST_FAILED;
+}
+
 // A CONSUMER of the line set: CompVCalibCamera builds its Canny and Hough objects through the same factories
 // (core/calib/compv_core_calib_camera.cxx:1255-1279: SHT, theta = 0.5 deg, maxLines = 60 per pattern line, Canny(1.33, 2.66)) and runs
 // Canny -> SHT -> toCartesian -> line subdivision / grouping -> intersections on a chessboard view (:127-..).  Same application
@@ -354,7 +403,7 @@ int main(int argc, char** argv)
 	const bool fastOnly = argc > 1 && !strcmp(argv[1], "--fast-only");
 	const size_t W = argc > 2 ? (size_t)atoi(argv[1]) : 1280, H = argc > 2 ? (size_t)atoi(argv[2]) : 720;
 	const int frames = argc > 3 ? atoi(argv[3]) : 2;
-	const int cpuThreads = argc > 4 ? atoi(argv[4]) : 1;
+	const int cpuThreads = (argc > 4 && strncmp(argv[1], "--", 2)) ? atoi(argv[4]) : 1;          // (the arguments of a --mode are its own)
 	CompVDebugMgr::setLevel(COMPV_DEBUG_LEVEL_ERROR);
 	// CompVInit() of compv_api.h minus GL/camera/drawing (absent on a headless box): base + core
 	if (COMPV_ERROR_CODE_IS_NOK(CompVBase::init(cpuThreads)) || COMPV_ERROR_CODE_IS_NOK(CompVCore::init())) { fprintf(stderr, "CompV init failed\n"); return 2; }
@@ -370,6 +419,15 @@ int main(int argc, char** argv)
 		printf("bruteforce_matches: %s [%zu x %zu rows of 32 bytes, KNN 2, %zu records | CompV CPU %.2f ms on %d thread(s), HIP plugin %.2f ms (incl. H2D/D2H)]\n", same ? "MATCH" : "DIFF",
 			mq, mt, cpuM.size() / 4, cpuMs, cpuThreads, hipMs);
 		return same ? 0 : 1;
+	}
+	if (argc > 1 && !strcmp(argv[1], "--orb-only")) {
+		const size_t ow = argc > 4 ? (size_t)atoi(argv[2]) : 3840, oh = argc > 4 ? (size_t)atoi(argv[3]) : 2160;
+		const int on = argc > 4 ? atoi(argv[4]) : 2000;
+		size_t points = 0;
+		double orientMs = 0.0, describeMs = 0.0;
+		if (ow < 37 || oh < 37 || on < 1 || COMPV_ERROR_CODE_IS_NOK(runOrbReference(ow, oh, on, points, orientMs, describeMs))) { fprintf(stderr, "CPU ORB run failed\n"); return 8; }
+		printf("orb_reference: [%zux%zu, %zu points | moments + orientation %.3f ms, blur + describe %.3f ms, CompV CPU on %d thread(s)]\n", ow, oh, points, orientMs, describeMs, cpuThreads);
+		return 0;
 	}
 	FastPoints fastCpu, fastHip;
 	double fastCpuMs = 0.0, fastHipMs = 0.0;
