@@ -389,7 +389,7 @@ int compvhip_plan_orb_describe(compvhip_plan* p, const uint8_t* d_gray, const co
 	const int frames = static_cast<int>(p->frames);
 	if (!p->orbKernReady) {
 		if (compvhip_gauss_kernel_fixedpoint(5, 2.0f, p->orbKern) != COMPVHIP_OK) return fail(ctx, COMPVHIP_E_INVALID_STATE, "Gaussian kernel");   // compv_core_feature_orb_desc.cxx:119-120
-		const char* e = getenv("COMPVHIP_ORB_BRIEF");   // lab knob (tools/orb_bench.py): "lds" / "global" name the byte-read variant of orb_brief_kernel
+		const char* e = getenv("COMPVHIP_ORB_BRIEF");   // lab knob (tools/orb_bench.py, tests): "lds" / "global" name the byte-read variant of orb_brief_kernel
 		p->orbBriefLds = e ? !strcmp(e, "lds") : kOrbBriefLdsDefault;
 		p->orbKernReady = true;
 	}
@@ -404,7 +404,7 @@ int compvhip_plan_orb_describe(compvhip_plan* p, const uint8_t* d_gray, const co
 	OrbDescArgs a;
 	a.blurred = blur ? p->orbBlur : d_gray; a.frameStride = p->S * p->H; a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
 	a.keys = d_keypoints; a.keyCap = keyCap; a.keyCounts = d_keyCounts; a.scale = scale; a.desc = d_desc; a.descStride = descStride;
-	{ Stamp s(p, st, "orb_brief_kernel"); HIPCHK(ctx, launch_orb_brief(a, frames, p->orbBriefLds, st)); }
+	{ Stamp s(p, st, p->orbBriefLds ? "orb_brief_kernel" : "orb_brief_kernel_global"); HIPCHK(ctx, launch_orb_brief(a, frames, p->orbBriefLds, st)); }
 	return COMPVHIP_OK;
 }
 

@@ -10,7 +10,8 @@ slices of a pair; the good kernel walks a pair's queries 256 at a time, four wav
   query caps  1, 63, 64, 65 (a wave and its neighbours), 255, 256, 257 (block - 1, block, block + 1)
   train caps  1, 2, 3 (fewer rows than neighbours asked for), 127, 128, 129 (slice - 1, slice, slice + 1), 257 (2 slices + 1)
   knn         1, 2, 3, 8 (the kernels keep lists of 1, 2, 4, 8), with knn > T
-  descBytes   4, 32, 36, 128 (register widths 1, 8, 16 -- nine dwords padded --, 32), stride > descBytes
+  descBytes   4, 32, 36, 128 (register widths 1, 8, 16 -- nine dwords padded --, 32), stride > descBytes; the widths in between (8, 12, 16, 24, 64 bytes:
+              registers 2, 4 padded from three, 4, 8 padded from six, 16) on a reduced grid
 The device call returns the canonical (distance, train index) order; the host form returns the reference's own order among equal distances
 (match_model.knn_reference) and is held against the records of the compiled reference in tests/golden/golden_match.json directly."""
 import hashlib
@@ -162,6 +163,47 @@ def test_caps_sweep(hip_ctx, desc_bytes, stride):
             finally:
                 rig.close()
     assert {k for k, _ in seen} == set(KNN) and any(over for _, over in seen)
+
+
+@pytest.mark.parametrize("desc_bytes,stride", [(8, 12), (12, 16), (16, 20), (24, 28), (64, 68)], ids=lambda v: str(v))
+def test_caps_sweep_remaining_widths(hip_ctx, desc_bytes, stride):
+    """the register widths test_caps_sweep leaves out -- match_slice_kernel<2, *>, <4, *> padded from three dwords and unpadded, <8, *> padded
+    from six, <16, *> unpadded -- on a reduced grid (a single query, a wave + 1, a block + 1; fewer train rows than neighbours, a slice + 1,
+    two slices + 1), knn cycling so that every width meets every knn"""
+    i = desc_bytes // 4
+    seen = set()
+    for qcap in (1, 65, BLOCK + 1):
+        for tcap in (3, SLICE + 1, 2 * SLICE + 1):
+            knn = KNN[i % 4]
+            i += 1
+            seen.add(knn)
+            query = np.concatenate([descriptors("uniform", 1, qcap, desc_bytes, stride, i), descriptors("ties", 1, qcap, desc_bytes, stride, i + 1)])
+            train = np.concatenate([descriptors("uniform", 1, tcap, desc_bytes, stride + 4, i + 2), descriptors("ties", 1, tcap, desc_bytes, stride + 4, i + 3)])
+            rig = Rig(hip_ctx, desc_bytes, qcap, tcap, 2, knn, query, train)
+            try:
+                rig.knn_run()
+                rig.knn_check("B %d Q %d T %d knn %d" % (desc_bytes, qcap, tcap, knn))
+            finally:
+                rig.close()
+    assert seen == set(KNN)
+
+
+@pytest.mark.parametrize("cols", [33, 64, 100, 128])
+def test_host_form_wide_descriptors_keep_the_reference_order(hip_ctx, cols):
+    """compvhip_match_hamming_u8 above 32 bytes: match_reference_kernel<16, *> (33 and 64 bytes: nine dwords padded, sixteen) and <32, *> (100
+    and 128 bytes: 25 dwords padded, 32), every list length, on tie-heavy rows -- the order among equal distances is what this kernel exists for"""
+    Q, T = BLOCK + 1, SLICE + 1
+    seed = {33: 11000, 64: 3000, 100: 5000, 128: 2000}[cols]          # seeds at which the two orders differ in what the lists keep (most do not show it)
+    q, t = mm.content("ties", Q, cols, 300 + cols + seed), mm.content("ties", T, cols, 400 + cols + seed)
+    D = mm.distances(q, t)
+    differs = False
+    for knn in KNN:
+        exp = mm.knn_reference(q, t, knn, D)
+        got = hip_ctx.match_hamming(q, t, knn)
+        assert got.shape == (knn, Q)
+        assert got.tobytes() == exp.tobytes(), (cols, knn)
+        differs = differs or mm.knn(q, t, knn, D).tobytes() != exp.tobytes()
+    assert differs          # the content tells the reference's order from the (distance, train index) order
 
 
 @pytest.mark.parametrize("tcap", [1, 2, 3])

@@ -213,8 +213,18 @@ def test_orb_geometry_sweep(hip_ctx, geom):
         rig.close()
 
 
-def test_single_admissible_position_reads_the_zero_blur_border(hip_ctx):
-    """37 x 37: the only keypoint is (18, 18); turned by 45 degrees its pattern reaches row and column 0 of the blurred plane, which the blur leaves zero"""
+def brief_timing(rig, brief_name):
+    """brief_name: None, or the timing entry the plan's next describe call has to stamp for its orb_brief_kernel variant (checked by brief_stamped)"""
+    if brief_name is not None:
+        rig.plan.set_timing(1)
+
+
+def brief_stamped(rig, brief_name, blur=True):
+    if brief_name is not None:
+        assert [n for n, _ in rig.plan.get_timing()] == (["convlt_fxp_kernels"] if blur else []) + [brief_name]
+
+
+def single_admissible_position_case(hip_ctx, brief_name=None):
     AX, AY, BX, BY = om.pattern()
     c, s, _ = om.canonical_cos_sin(np.array([45.0], np.float32))
     reach = [np.rint(P * c - Q * s) for P, Q in ((AX, AY), (BX, BY))] + [np.rint(P * s + Q * c) for P, Q in ((AX, AY), (BX, BY))]
@@ -229,7 +239,9 @@ def test_single_admissible_position_reads_the_zero_blur_border(hip_ctx):
         host[:] = keys
         rig.d_keys.copy_(rig.ar.torch.from_numpy(u8(host)))
         rig.d_kcounts.copy_(rig.ar.torch.from_numpy(u8(np.array([8, 5], np.int32))))
+        brief_timing(rig, brief_name)
         rig.describe(1.0)
+        brief_stamped(rig, brief_name)
         rows = rig.check_desc("fixed orientations", [keys, keys[:5]], 1.0, W + H)
         assert (rows[0, 0, :32] == rows[0, 7, :32]).all() and rows[0, 0, :32].any()          # 0 and 360 degrees
         assert (rows[0, 1, :32] != rows[0, 0, :32]).any()
@@ -237,9 +249,12 @@ def test_single_admissible_position_reads_the_zero_blur_border(hip_ctx):
         rig.close()
 
 
-def test_describe_callers_keypoints(hip_ctx):
-    """fixed orientations and 360.0, non-integer coordinates at scale 0.83, points inside the 18-pixel margin or holding no number (a zero row each, in
-    place), a count above keyCap; blur = 0 on a pre-blurred plane equals blur = 1 on the raw one; a non-default stream"""
+def test_single_admissible_position_reads_the_zero_blur_border(hip_ctx):
+    """37 x 37: the only keypoint is (18, 18); turned by 45 degrees its pattern reaches row and column 0 of the blurred plane, which the blur leaves zero"""
+    single_admissible_position_case(hip_ctx)
+
+
+def callers_keypoints_case(hip_ctx, brief_name=None):
     import torch
     geom = GEOMETRIES[2]
     W, H, S, F = geom
@@ -266,8 +281,10 @@ def test_describe_callers_keypoints(hip_ctx):
         used = [host[f, :min(max(int(counts[f]), 0), cap)] for f in range(F)]
         st = torch.cuda.Stream()
         st.wait_stream(torch.cuda.current_stream())
+        brief_timing(rig, brief_name)
         rig.describe(SCALE1, stream=st.cuda_stream)
         st.synchronize()
+        brief_stamped(rig, brief_name)
         rows = rig.check_desc("caller's keypoints", used, SCALE1, seed)
         zero = (9, 10, 12, 13, 14)
         assert not rows[0, zero, :32].any() and rows[0, [q for q in range(cap) if q not in zero], :32].any(axis=1).all()
@@ -276,9 +293,63 @@ def test_describe_callers_keypoints(hip_ctx):
         rig.ar.keep(d_pre, pre)
         rig.ar.refill(rig.d_desc)
         rig.describe(SCALE1, blur=False, d_gray=d_pre)
+        brief_stamped(rig, brief_name, blur=False)
         assert (rig.check_desc("pre-blurred", used, SCALE1, seed) == rows).all()
     finally:
         rig.close()
+
+
+def test_describe_callers_keypoints(hip_ctx):
+    """fixed orientations and 360.0, non-integer coordinates at scale 0.83, points inside the 18-pixel margin or holding no number (a zero row each, in
+    place), a count above keyCap; blur = 0 on a pre-blurred plane equals blur = 1 on the raw one; a non-default stream"""
+    callers_keypoints_case(hip_ctx)
+
+
+# ---- orb_brief_kernel<false>: COMPVHIP_ORB_BRIEF=global (read when a plan first describes) makes the tests' bytes come straight from the blurred plane
+GLOBAL_NAME = "orb_brief_kernel_global"
+
+
+@pytest.mark.parametrize("geom", (GEOMETRIES[0], GEOMETRIES[2], GEOMETRIES[3]), ids=GID)
+def test_global_byte_variant_geometries(hip_ctx, monkeypatch, geom):
+    """keypoints and descriptor rows of level 0 and level 1 as in test_orb_geometry_sweep, the rows made by the global-byte variant"""
+    monkeypatch.setenv("COMPVHIP_ORB_BRIEF", "global")
+    W, H, S, F = geom
+    seed = W + H
+    rig = Rig(hip_ctx, geom, seed, 260, desc_stride=48 if W == 131 else 32)
+    try:
+        for level, scale in ((0, 1.0), (1, SCALE1)):
+            exp = rig.expected(level, scale)
+            rig.plan.set_timing(0)
+            rig.keypoints(level, scale)
+            rig.check_keypoints("level %d" % level, exp)
+            brief_timing(rig, GLOBAL_NAME)
+            rig.describe(scale)
+            brief_stamped(rig, GLOBAL_NAME)
+            rig.check_desc("level %d, global bytes" % level, [k for k, _ in exp], scale, seed)
+            rig.refill()
+    finally:
+        rig.close()
+
+
+def test_global_byte_variant_reads_the_zero_blur_border(hip_ctx, monkeypatch):
+    """the single position of 37 x 37 at fixed orientations: this variant reads row and column 0 of the blurred plane straight from memory"""
+    monkeypatch.setenv("COMPVHIP_ORB_BRIEF", "global")
+    single_admissible_position_case(hip_ctx, GLOBAL_NAME)
+
+
+def test_global_byte_variant_on_callers_keypoints(hip_ctx, monkeypatch):
+    """NaN, inf and in-margin points: in this variant the `inside` flag alone keeps the loads in the plane"""
+    monkeypatch.setenv("COMPVHIP_ORB_BRIEF", "global")
+    callers_keypoints_case(hip_ctx, GLOBAL_NAME)
+
+
+@pytest.mark.parametrize("value", [None, "lds"], ids=["unset", "lds"])
+def test_the_default_variant_keeps_its_timing_name(hip_ctx, monkeypatch, value):
+    if value is None:
+        monkeypatch.delenv("COMPVHIP_ORB_BRIEF", raising=False)
+    else:
+        monkeypatch.setenv("COMPVHIP_ORB_BRIEF", value)
+    single_admissible_position_case(hip_ctx, "orb_brief_kernel")
 
 
 def test_streams_scratch_and_timing(hip_ctx):

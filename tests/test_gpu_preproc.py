@@ -44,6 +44,56 @@ def test_grayscale_errors(hip_ctx):
     assert e.value.code == capi.E_NOT_IMPLEMENTED              # conv_to_grayscale.cxx:86-88
 
 
+@pytest.mark.parametrize("fmt", range(len(FMT_NAMES)), ids=FMT_NAMES)
+@pytest.mark.parametrize("W,H,S,F", [(34, 5, 48, 3), (642, 31, 704, 2), (2050, 9, 2056, 2)])          # the last: one group past a workgroup's 2048 columns
+def test_plan_grayscale_batch_matches_oracle(hip_ctx, oracle, fmt, W, H, S, F):
+    """gray_kernel<FMT> with blockIdx.z > 0: every format through Plan.grayscale on packed frames [F][H][S * bpp] that differ from one another
+    (a wrong frame offset shows), between guards, random bytes in the padding samples; the input comes back unchanged"""
+    from compv_amd import capi
+    from test_gpu_plan_geometry import Arena, assert_maps, frames_view, pad_frames, ptr
+    bpp = oracle.fmt_bytes(fmt)
+    assert bpp == capi.FMT_BYTES[fmt]
+    rng = np.random.default_rng(1000 * fmt + W)
+    valid = rng.integers(0, 256, (F, H, W * bpp), dtype=np.uint8)
+    host = pad_frames(valid, S * bpp, rng)
+    exp = [oracle.grayscale(host[f], fmt, W) for f in range(F)]
+    assert all((exp[f] != exp[0]).any() for f in range(1, F))
+    A = Arena()
+    d_in = A.new(host.size, host)
+    A.keep(d_in, host)
+    d_gray = A.new(F * H * S)
+    plan = capi.Plan(hip_ctx, W, H, S, F)
+    try:
+        plan.grayscale(ptr(d_in), fmt, ptr(d_gray))
+        A.check("grayscale %s" % FMT_NAMES[fmt])
+        assert_maps(frames_view(d_gray, F, H, S, W), exp, "grayscale %s" % FMT_NAMES[fmt])
+        if fmt == capi.FMT_Y:
+            d_alias = A.new(host.size, host)
+            plan.grayscale(ptr(d_alias), fmt, ptr(d_alias))
+            A.check("grayscale Y in place")
+            assert_maps(frames_view(d_alias, F, H, S, W), exp, "grayscale Y in place")
+    finally:
+        plan.close()
+
+
+def test_plan_grayscale_refusals_write_nothing(hip_ctx):
+    from compv_amd import capi
+    from test_gpu_plan_geometry import Arena, SENTINEL, ptr
+    W, H, S, F = 33, 4, 40, 2
+    A = Arena()
+    d_in, d_gray = A.new(F * H * S * 4), A.new(F * H * S)
+    plan = capi.Plan(hip_ctx, W, H, S, F)
+    try:
+        for fmt, code in ((capi.FMT_YUYV422, capi.E_INVALID_PARAMETER), (capi.FMT_UYVY422, capi.E_INVALID_PARAMETER), (99, capi.E_NOT_IMPLEMENTED)):
+            with pytest.raises(capi.CompvHipError) as e:
+                plan.grayscale(ptr(d_in), fmt, ptr(d_gray))          # packed 4:2:2 on an odd width; a format without a conversion
+            assert e.value.code == code, fmt
+        A.check("refused grayscale")
+        assert (d_gray.cpu().numpy() == SENTINEL).all() and (d_in.cpu().numpy() == SENTINEL).all()
+    finally:
+        plan.close()
+
+
 @pytest.mark.parametrize("W,H,seed", [(20, 20, 1), (333, 77, 2), (641, 480, 3), (1282, 720, 4), (1920, 1080, 5), (3840, 2160, 6)])
 def test_otsu_matches_oracle(hip_ctx, oracle, W, H, seed):
     rng = np.random.default_rng(seed)
