@@ -57,6 +57,8 @@ EXPORTS = [
     "compvhip_plan_orb_keypoints", "compvhip_plan_orb_describe", "compvhip_orb_u8",
     "compvhip_matcher_create", "compvhip_matcher_destroy", "compvhip_matcher_knn", "compvhip_matcher_good", "compvhip_match_hamming_u8",
     "compvhip_matcher_set_timing", "compvhip_matcher_get_timing",
+    "compvhip_orbpyr_create", "compvhip_orbpyr_destroy", "compvhip_orbpyr_geometry", "compvhip_orbpyr_plane", "compvhip_orbpyr_detect", "compvhip_orbpyr_describe",
+    "compvhip_plan_scale", "compvhip_scale_u8", "compvhip_orb_pyramid_u8", "compvhip_orbpyr_set_timing", "compvhip_orbpyr_get_timing",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -122,6 +124,14 @@ class Keypoint(C.Structure):
 class MatchOpts(C.Structure):
     """compvhip_match_opts (include/compv_hip.h): ratio <= 0 / maxDistance < 0 / crossCheck == 0 switch a test off"""
     _fields_ = [("ratio", C.c_double), ("maxDistance", C.c_int), ("crossCheck", C.c_int)]
+
+
+class OrbPyramidOpts(C.Structure):
+    """compvhip_orbpyr_opts (include/compv_hip.h); the defaults are CompVCornerDeteORB's"""
+    _fields_ = [("levels", C.c_int), ("scaleFactor", C.c_float), ("threshold", C.c_int), ("fastType", C.c_int), ("nonmax", C.c_int), ("maxFeatures", C.c_int)]
+
+    def __init__(self, levels=8, scale_factor=0.83, threshold=20, fast_type=9, nonmax=True, max_features=2000):
+        super().__init__(levels, scale_factor, threshold, fast_type, int(bool(nonmax)), max_features)
 
 
 class CompvHipError(RuntimeError):
@@ -227,6 +237,18 @@ def load():
     L.compvhip_match_hamming_u8.argtypes = [vp, vp, sz, sz, vp, sz, sz, sz, i32, vp, sz, C.POINTER(sz)]
     L.compvhip_matcher_set_timing.argtypes = [vp, i32]
     L.compvhip_matcher_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
+    L.compvhip_orbpyr_create.argtypes = [vp, sz, sz, sz, sz, C.POINTER(OrbPyramidOpts), sz, C.POINTER(vp)]
+    L.compvhip_orbpyr_destroy.argtypes = [vp]
+    L.compvhip_orbpyr_destroy.restype = None
+    L.compvhip_orbpyr_geometry.argtypes = [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_float), C.POINTER(i32)]
+    L.compvhip_orbpyr_plane.argtypes = [vp, i32, i32, C.POINTER(vp)]
+    L.compvhip_orbpyr_detect.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
+    L.compvhip_orbpyr_describe.argtypes = [vp, vp, i32, vp, sz, vp, vp, sz, vp]
+    L.compvhip_plan_scale.argtypes = [vp, vp, vp, sz, sz, sz, vp]
+    L.compvhip_scale_u8.argtypes = [vp, vp, sz, sz, sz, vp, sz, sz, sz]
+    L.compvhip_orb_pyramid_u8.argtypes = [vp, vp, sz, sz, sz, C.POINTER(OrbPyramidOpts), vp, vp, sz, sz, C.POINTER(sz)]
+    L.compvhip_orbpyr_set_timing.argtypes = [vp, i32]
+    L.compvhip_orbpyr_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -442,6 +464,29 @@ class Context:
                                            _ptr(desc) if n else None, 32, C.byref(kept)))
         return keys[:kept.value], desc[:kept.value]
 
+    def scale(self, img, out_w, out_h):
+        """compvhip_scale_u8 (CompVImage::scale, bilinear): -> the (out_h, out_w) plane"""
+        H, W = img.shape
+        out = np.empty((out_h, out_w), np.uint8)
+        self._chk(self.lib.compvhip_scale_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(out), out_w, out_h, out_w))
+        return out
+
+    def orb_pyramid(self, img, opts=None, cap=4096):
+        """compvhip_orb_pyramid_u8 (CompVCornerDeteORB::process + CompVCornerDescORB::process): -> (keypoints KEYPOINT_DTYPE in level order, descriptors
+        (n, 32) uint8).  opts: OrbPyramidOpts or None for the defaults.  The call is repeated with a larger buffer when `cap` was too small."""
+        H, W = img.shape
+        n = C.c_size_t(0)
+        while True:
+            keys = np.zeros(cap, KEYPOINT_DTYPE)
+            desc = np.zeros((cap, 32), np.uint8)
+            rc = self.lib.compvhip_orb_pyramid_u8(self.h, _ptr(img), W, H, img.strides[0], C.byref(opts) if opts is not None else None, _ptr(keys) if cap else None,
+                                                  _ptr(desc) if cap else None, 32, cap, C.byref(n))
+            if rc != E_OUT_OF_BOUND:
+                break
+            cap = n.value
+        self._chk(rc)
+        return keys[:n.value], desc[:n.value]
+
     def match_hamming(self, query, train, knn=2):
         """compvhip_match_hamming_u8 (CompVMatcherBruteForce::process): query (Q, cols) and train (T, cols) uint8 rows -> (min(knn, T), Q) MATCH_DTYPE
         records, neighbour r of query q at [r, q], distances ascending.  Among equal distances the records follow the REFERENCE's insertion order
@@ -593,6 +638,10 @@ class Plan:
         self.ctx._chk(self.lib.compvhip_plan_orb_describe(self.h, d_gray, d_keypoints or None, key_cap, d_key_counts or None, scale, int(bool(blur)), d_desc or None,
                                                           desc_stride, stream))
 
+    def scale(self, d_in, d_out, out_w, out_h, out_stride, stream=0):
+        """compvhip_plan_scale: the plan's frames [frames][H][S] -> d_out [frames][out_h][out_stride], bilinear"""
+        self.ctx._chk(self.lib.compvhip_plan_scale(self.h, d_in or None, d_out or None, out_w, out_h, out_stride, stream))
+
     def pipeline(self, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap, d_counts, stream=0):
         self.ctx._chk(self.lib.compvhip_plan_pipeline(self.h, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap,
                                                       d_counts, stream))
@@ -708,6 +757,61 @@ class Matcher:
         names = (C.c_char_p * cap)()
         ms = (C.c_float * cap)()
         n = self.lib.compvhip_matcher_get_timing(self.h, names, ms, cap)
+        return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
+
+
+class OrbPyramid:
+    """Batched device-resident ORB scale pyramid (compvhip_orbpyr): multi-level detect and describe.  Pointers are raw device addresses; 0 stands for NULL."""
+
+    def __init__(self, ctx, W, H, S, frames, opts=None, corner_cap=4096):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.opts = opts if opts is not None else OrbPyramidOpts()
+        h = C.c_void_p()
+        ctx._chk(self.lib.compvhip_orbpyr_create(ctx.h, W, H, S, frames, C.byref(self.opts), corner_cap, C.byref(h)))
+        self.h = h
+        self.W, self.H, self.S, self.frames, self.levels, self.corner_cap = W, H, S, frames, self.opts.levels, corner_cap
+
+    def close(self):
+        if self.h:
+            self.lib.compvhip_orbpyr_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def geometry(self, level):
+        """-> (W, H, S, scale, quota) of a level; S == 0: the level is empty"""
+        W, H, S, sf, q = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_float(), C.c_int()
+        self.ctx._chk(self.lib.compvhip_orbpyr_geometry(self.h, level, C.byref(W), C.byref(H), C.byref(S), C.byref(sf), C.byref(q)))
+        return W.value, H.value, S.value, np.float32(sf.value), q.value
+
+    def plane(self, level, blurred=False):
+        """device address of the level's plane [frames][H_l][S_l] as the last call built it"""
+        p = C.c_void_p()
+        self.ctx._chk(self.lib.compvhip_orbpyr_plane(self.h, level, int(bool(blurred)), C.byref(p)))
+        return p.value
+
+    def detect(self, d_gray, d_keypoints, key_cap, d_key_counts, d_level_counts=0, d_level_corners=0, stream=0):
+        """compvhip_orbpyr_detect: d_keypoints [frames][key_cap] KEYPOINT_DTYPE in level order, d_key_counts [frames]; optional [frames][levels] int32 arrays"""
+        self.ctx._chk(self.lib.compvhip_orbpyr_detect(self.h, d_gray or None, d_keypoints or None, key_cap, d_key_counts or None, d_level_counts or None,
+                                                      d_level_corners or None, stream))
+
+    def describe(self, d_gray, d_keypoints, key_cap, d_key_counts, d_desc, desc_stride=32, reuse_planes=False, stream=0):
+        """compvhip_orbpyr_describe: every keypoint on the plane of its own level; reuse_planes: the planes of the preceding detect() on the same d_gray"""
+        self.ctx._chk(self.lib.compvhip_orbpyr_describe(self.h, d_gray or None, int(bool(reuse_planes)), d_keypoints or None, key_cap, d_key_counts or None,
+                                                        d_desc or None, desc_stride, stream))
+
+    def set_timing(self, mode=1):
+        self.ctx._chk(self.lib.compvhip_orbpyr_set_timing(self.h, int(mode)))
+
+    def get_timing(self, cap=128):
+        names = (C.c_char_p * cap)()
+        ms = (C.c_float * cap)()
+        n = self.lib.compvhip_orbpyr_get_timing(self.h, names, ms, cap)
         return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
 
 

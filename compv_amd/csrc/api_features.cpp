@@ -1,5 +1,5 @@
 // api_features.cpp -- plan-level calls of the features built on the Canny / SHT plan: line segments, line fits, connected components,
-// thresholding and morphology, FAST corners, ORB keypoints and descriptors, brute-force matching.
+// thresholding and morphology, FAST corners, ORB keypoints and descriptors, bilinear scale and the ORB pyramid, brute-force matching.
 #include "api_internal.hpp"
 
 // what the segment and the fit kernels read alike: the edge pixels, the vote's tables, the lines
@@ -405,6 +405,260 @@ int compvhip_plan_orb_describe(compvhip_plan* p, const uint8_t* d_gray, const co
 	a.blurred = blur ? p->orbBlur : d_gray; a.frameStride = p->S * p->H; a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
 	a.keys = d_keypoints; a.keyCap = keyCap; a.keyCounts = d_keyCounts; a.scale = scale; a.desc = d_desc; a.descStride = descStride;
 	{ Stamp s(p, st, p->orbBriefLds ? "orb_brief_kernel" : "orb_brief_kernel_global"); HIPCHK(ctx, launch_orb_brief(a, frames, p->orbBriefLds, st)); }
+	return COMPVHIP_OK;
+}
+
+// ---- bilinear scale and the ORB pyramid (scale_kernels.hip, orb_kernels.hip; definition in include/compv_hip.h) ---------------------------------------
+int compvhip_api::scaleImpl(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout,
+                            hipStream_t st)
+{
+	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	if (!Wout || !Hout || Wout > 32767 || Hout > 32767 || W > 32767 || H > 32767 || Sout < Wout || Sout > static_cast<size_t>(INT32_MAX) || frames > 65535)
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "scale: a size of 0 or beyond 32767, Sout < Wout, or more than 65535 frames");
+	const size_t inSpan = S * H * frames, outSpan = Sout * Hout * frames;
+	if (d_in < d_out + outSpan && d_out < d_in + inSpan) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap");
+	ScaleArgs a;
+	a.in = d_in; a.frameStride = S * H; a.W = static_cast<int>(W); a.H = static_cast<int>(H); a.S = static_cast<int>(S); a.levels = 1;
+	ScaleLevel& L = a.lv[0];
+	L.out = d_out; L.frameStride = Sout * Hout; L.W = static_cast<int>(Wout); L.H = static_cast<int>(Hout); L.S = static_cast<int>(Sout);
+	if (!scale_level_init(L, a.W, a.H)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "scale ratio outside (0, 256)");   // compv_image_scale_bilinear.cxx:175
+	HIPCHK(ctx, launch_scale_bilinear(a, static_cast<int>(frames), st));
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_scale(compvhip_plan* p, const uint8_t* d_in, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	Stamp s(p, st, "scale_bilinear_kernel");
+	return scaleImpl(ctx, d_in, p->W, p->H, p->S, p->frames, d_out, Wout, Hout, Sout, st);
+}
+
+int compvhip_orbpyr_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size_t frames, const compvhip_orbpyr_opts* opts, size_t cornerCap, compvhip_orbpyr** out)
+{
+	if (!ctx || !out) return COMPVHIP_E_INVALID_PARAMETER;
+	*out = nullptr;
+	if (!opts) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null options");
+	if (opts->levels < 1 || opts->levels > kPyrMaxLevels || !(opts->scaleFactor > 0.f && opts->scaleFactor < 1.f))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "levels must be 1 .. 16 and 0 < scaleFactor < 1");
+	int rc = checkOrb(ctx, W, H, 1.f);
+	if (!rc) rc = checkFast(ctx, W, H, opts->fastType);
+	if (rc) return rc;
+	if (W > 32767 || H > 32767 || S < W || (S & 7) || !frames || frames > 65535 || !cornerCap || cornerCap > static_cast<size_t>(INT32_MAX))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "pyramid: size beyond 32767, S < W or no multiple of 8, frames outside 1 .. 65535, or cornerCap outside 1 .. 2^31");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	compvhip_orbpyr* y = new (std::nothrow) compvhip_orbpyr();
+	if (!y) return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "pyramid");
+	y->ctx = ctx; y->W = W; y->H = H; y->S = S; y->frames = frames; y->cornerCap = cornerCap; y->opts = *opts;
+	// compv_image_scale_pyramid.cxx:39-44,166 and compv_core_feature_orb_dete.cxx:319-321, operation by operation in float32
+	float sf = 1.f, sfs = 1.f, f = opts->scaleFactor;
+	for (int l = 1; l < opts->levels; ++l, f *= opts->scaleFactor) sfs += f;
+	f = opts->scaleFactor;
+	size_t planeBytes = 0;
+	for (int l = 0; l < opts->levels; ++l) {
+		compvhip_orbpyr::Level& L = y->lv[l];
+		if (l) { sf = f; f *= opts->scaleFactor; }
+		L.sf = sf;
+		L.W = l ? static_cast<size_t>(static_cast<float>(W) * sf) : W; L.H = l ? static_cast<size_t>(static_cast<float>(H) * sf) : H;
+		if (opts->maxFeatures > 0) {
+			const float nf = (static_cast<float>(opts->maxFeatures) / sfs) * sf;
+			L.quota = std::max(10, static_cast<int32_t>(static_cast<double>(nf) + 0.5));
+		}
+		if (L.W < 2 * kOrbBorder + 1 || L.H < 2 * kOrbBorder + 1) continue;          // empty: S stays 0
+		L.S = l ? alignUp(L.W, 8) : S;
+		y->active = l + 1;
+		if (l) planeBytes += alignUp(L.S * L.H * frames, 256);
+	}
+	if (compvhip_gauss_kernel_fixedpoint(5, 2.0f, y->kern) != COMPVHIP_OK) { delete y; return fail(ctx, COMPVHIP_E_INVALID_STATE, "Gaussian kernel"); }   // compv_core_feature_orb_desc.cxx:119-120
+	const char* e = getenv("COMPVHIP_ORB_BRIEF");   // the lab knob of compvhip_plan_orb_describe
+	if (e) y->briefLds = !strcmp(e, "lds");
+	const size_t L = static_cast<size_t>(opts->levels);
+	if (dmalloc(ctx, &y->planes, planeBytes) != hipSuccess || dmalloc(ctx, &y->corners, frames * cornerCap) != hipSuccess ||
+	    dmalloc(ctx, &y->fastWork, frames * (2 * H + 257)) != hipSuccess || dmalloc(ctx, &y->fastScores, S * H * frames) != hipSuccess ||
+	    dmalloc(ctx, &y->counts, (3 * L + 1) * frames) != hipSuccess) {
+		compvhip_orbpyr_destroy(y);
+		return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "pyramid planes / scratch");
+	}
+	size_t off = 0;
+	for (int l = 1; l < y->active; ++l) { y->lv[l].plane = y->planes + off; off += alignUp(y->lv[l].S * y->lv[l].H * frames, 256); }
+	*out = y;
+	return COMPVHIP_OK;
+}
+
+void compvhip_orbpyr_destroy(compvhip_orbpyr* y)
+{
+	if (!y) return;
+	compvhip_ctx* ctx = y->ctx;
+	(void)hipSetDevice(ctx->device);
+	timelineClear(y);
+	for (hipEvent_t e : y->eventPool) (void)hipEventDestroy(e);
+	dfree(ctx, y->planes); dfree(ctx, y->blurredAll); dfree(ctx, y->corners); dfree(ctx, y->fastWork); dfree(ctx, y->fastScores); dfree(ctx, y->counts);
+	y->index.release(ctx);
+	delete y;
+}
+
+int compvhip_orbpyr_set_timing(compvhip_orbpyr* y, int enabled)
+{
+	if (!y) return COMPVHIP_E_INVALID_PARAMETER;
+	y->timing = enabled != 0;
+	return COMPVHIP_OK;
+}
+
+int compvhip_orbpyr_get_timing(compvhip_orbpyr* y, const char** names, float* ms, int cap)
+{
+	if (!y) return COMPVHIP_E_INVALID_PARAMETER;
+	(void)hipSetDevice(y->ctx->device);
+	if (!y->timeline.empty()) {
+		for (auto& t : y->timeline) (void)hipEventSynchronize(t.b);
+		timelineCollect(y);
+	}
+	const int n = std::min<int>(cap, static_cast<int>(y->timingMs.size()));
+	for (int i = 0; i < n; ++i) { if (names) names[i] = y->timingNames[i].c_str(); if (ms) ms[i] = y->timingMs[i]; }
+	return n;
+}
+
+int compvhip_orbpyr_geometry(const compvhip_orbpyr* y, int level, size_t* W, size_t* H, size_t* S, float* scale, int* quota)
+{
+	if (!y) return COMPVHIP_E_INVALID_PARAMETER;
+	if (level < 0 || level >= y->opts.levels) return fail(y->ctx, COMPVHIP_E_INVALID_PARAMETER, "level outside 0 .. levels - 1");
+	const compvhip_orbpyr::Level& L = y->lv[level];
+	if (W) *W = L.W;
+	if (H) *H = L.H;
+	if (S) *S = L.S;
+	if (scale) *scale = L.sf;
+	if (quota) *quota = L.quota;
+	return COMPVHIP_OK;
+}
+
+int compvhip_orbpyr_plane(compvhip_orbpyr* y, int level, int blurred, const uint8_t** d_plane)
+{
+	if (!y || !d_plane) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = y->ctx;
+	if (level < 0 || level >= y->opts.levels || level >= y->active) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "level outside 0 .. levels - 1, or an empty level");
+	if (blurred ? !y->blurredOf : !y->planesOf) return fail(ctx, COMPVHIP_E_INVALID_STATE, "no call has built this plane yet");
+	*d_plane = blurred ? y->lv[level].blurred : (level ? y->lv[level].plane : y->planesOf);
+	return COMPVHIP_OK;
+}
+
+namespace {
+int checkPyrFrame(compvhip_orbpyr* y, const uint8_t* d_gray)
+{
+	if (!d_gray) return fail(y->ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	if (reinterpret_cast<uintptr_t>(d_gray) & 7) return fail(y->ctx, COMPVHIP_E_INVALID_PARAMETER, "frames must be 8-byte aligned");
+	return COMPVHIP_OK;
+}
+
+// levels 1 .. active - 1 of every frame from d_gray: one launch
+int pyrScale(compvhip_orbpyr* y, const uint8_t* d_gray, hipStream_t st)
+{
+	compvhip_ctx* ctx = y->ctx;
+	y->planesOf = d_gray;
+	if (y->active < 2) return COMPVHIP_OK;
+	ScaleArgs a;
+	a.in = d_gray; a.frameStride = y->S * y->H; a.W = static_cast<int>(y->W); a.H = static_cast<int>(y->H); a.S = static_cast<int>(y->S); a.levels = y->active - 1;
+	for (int l = 1; l < y->active; ++l) {
+		const compvhip_orbpyr::Level& src = y->lv[l];
+		ScaleLevel& L = a.lv[l - 1];
+		L.out = src.plane; L.frameStride = src.S * src.H; L.W = static_cast<int>(src.W); L.H = static_cast<int>(src.H); L.S = static_cast<int>(src.S);
+		if (!scale_level_init(L, a.W, a.H)) return fail(ctx, COMPVHIP_E_INVALID_STATE, "pyramid level ratio");   // 37 <= W_l <= W <= 32767: cannot happen
+	}
+	Stamp s(y, st, "scale_bilinear_kernel");
+	HIPCHK(ctx, launch_scale_bilinear(a, static_cast<int>(y->frames), st));
+	return COMPVHIP_OK;
+}
+} // namespace
+
+int compvhip_orbpyr_detect(compvhip_orbpyr* y, const uint8_t* d_gray, compvhip_keypoint* d_keypoints, size_t keyCap, int32_t* d_keyCounts, int32_t* d_levelCounts,
+                           int32_t* d_levelCorners, void* stream)
+{
+	if (!y) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = y->ctx;
+	int rc = checkPyrFrame(y, d_gray);
+	if (rc) return rc;
+	if (!d_keyCounts || (keyCap && !d_keypoints) || keyCap > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null count / keypoint pointer or keyCap beyond 2^31");
+	if ((reinterpret_cast<uintptr_t>(d_keypoints) & 3) || (reinterpret_cast<uintptr_t>(d_keyCounts) & 3) || (reinterpret_cast<uintptr_t>(d_levelCounts) & 3) ||
+	    (reinterpret_cast<uintptr_t>(d_levelCorners) & 3))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "records and counts must be 4-byte aligned");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, y->index.reserve(ctx, y->frames * keyCap));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (y->timing) timelineClear(y);
+	const size_t F = y->frames, NL = static_cast<size_t>(y->opts.levels);
+	const int frames = static_cast<int>(F);
+	int32_t* lvCorners = y->counts; int32_t* lvKeys = lvCorners + NL * F; int32_t* totals = lvKeys + NL * F;
+	HIPCHK(ctx, hipMemsetAsync(totals, 0, F * sizeof(int32_t), st));          // nothing in front of level 0
+	rc = pyrScale(y, d_gray, st);
+	if (rc) return rc;
+	const int t = y->opts.threshold;
+	for (int l = 0; l < y->active; ++l) {
+		const compvhip_orbpyr::Level& L = y->lv[l];
+		const uint8_t* plane = l ? L.plane : d_gray;
+		FastArgs a;
+		a.in = plane; a.scores = y->fastScores; a.frameStride = L.S * L.H;
+		a.W = static_cast<int>(L.W); a.H = static_cast<int>(L.H); a.S = static_cast<int>(L.S);
+		a.t = t < 0 ? 0 : (t > 255 ? 255 : t); a.N = y->opts.fastType; a.nonmax = y->opts.nonmax != 0; a.maxFeatures = y->opts.maxFeatures > 0 ? L.quota : -1;
+		a.rowCounts = y->fastWork; a.hist = a.rowCounts + F * L.H; a.minScore = a.hist + F * 256; a.rowOffsets = a.minScore + F;
+		a.corners = y->corners; a.cornerCap = y->cornerCap; a.counts = lvCorners + l * F;
+		HIPCHK(ctx, hipMemsetAsync(a.rowCounts, 0, F * (L.H + 256) * sizeof(int), st));   // the row counts and the histogram are sums
+		{ Stamp s(y, st, "fast_score_kernel"); HIPCHK(ctx, launch_fast(a, frames, 0, st)); }
+		{ Stamp s(y, st, "fast_list_kernels"); HIPCHK(ctx, launch_fast(a, frames, 1, st)); }
+		OrbKeyArgs k;
+		k.gray = plane; k.frameStride = L.S * L.H; k.W = a.W; k.H = a.H; k.S = a.S;
+		k.corners = y->corners; k.cornerCap = y->cornerCap; k.cornerCounts = a.counts; k.level = l; k.scale = L.sf;
+		k.index = y->index; k.keys = d_keypoints; k.keyCap = keyCap; k.keyCounts = lvKeys + l * F; k.moments = nullptr;
+		k.keyBase = totals + l * F; k.keyTotal = totals + (l + 1) * F;
+		{ Stamp s(y, st, "orb_select_kernel"); HIPCHK(ctx, launch_orb_select(k, frames, st)); }
+		if (keyCap) { Stamp s(y, st, "orb_orient_kernel"); HIPCHK(ctx, launch_orb_orient(k, frames, st)); }
+	}
+	OrbPyrCountArgs c;
+	c.totals = totals + static_cast<size_t>(y->active) * F; c.lvKeys = lvKeys; c.lvCorners = lvCorners; c.active = y->active; c.levels = y->opts.levels; c.frames = frames;
+	c.keyCounts = d_keyCounts; c.levelCounts = d_levelCounts; c.levelCorners = d_levelCorners;
+	{ Stamp s(y, st, "orb_pyramid_counts_kernel"); HIPCHK(ctx, launch_orb_pyramid_counts(c, st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_orbpyr_describe(compvhip_orbpyr* y, const uint8_t* d_gray, int reusePlanes, const compvhip_keypoint* d_keypoints, size_t keyCap, const int32_t* d_keyCounts,
+                             uint8_t* d_desc, size_t descStride, void* stream)
+{
+	if (!y) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = y->ctx;
+	int rc = checkPyrFrame(y, d_gray);
+	if (rc) return rc;
+	if (!d_keypoints || !d_keyCounts || !d_desc || !keyCap || keyCap > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null keypoint / count / descriptor pointer, keyCap == 0 or beyond 2^31");
+	if (descStride < 32 || (descStride & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descStride below 32 or no multiple of 4");
+	if ((reinterpret_cast<uintptr_t>(d_keypoints) & 3) || (reinterpret_cast<uintptr_t>(d_keyCounts) & 3) || (reinterpret_cast<uintptr_t>(d_desc) & 3))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "records, counts and descriptors must be 4-byte aligned");
+	if (reusePlanes && y->planesOf != d_gray) return fail(ctx, COMPVHIP_E_INVALID_STATE, "reusePlanes: no planes of a compvhip_orbpyr_detect call on this d_gray");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t F = y->frames;
+	const int frames = static_cast<int>(F);
+	if (!y->blurredAll) {
+		size_t bytes = 0;
+		for (int l = 0; l < y->active; ++l) bytes += alignUp(y->lv[l].S * y->lv[l].H * F, 256);
+		HIPCHK(ctx, dmalloc(ctx, &y->blurredAll, bytes));
+		size_t off = 0;
+		for (int l = 0; l < y->active; ++l) { y->lv[l].blurred = y->blurredAll + off; off += alignUp(y->lv[l].S * y->lv[l].H * F, 256); }
+	}
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (y->timing) timelineClear(y);
+	if (!reusePlanes) { rc = pyrScale(y, d_gray, st); if (rc) return rc; }
+	OrbPyrDescArgs a;
+	a.levels = y->opts.levels;
+	for (int l = 0; l < kPyrMaxLevels; ++l) {
+		const compvhip_orbpyr::Level& L = y->lv[l];
+		OrbLevelPlane& P = a.lv[l];
+		P.blurred = l < y->active ? L.blurred : nullptr; P.frameStride = L.S * L.H; P.W = static_cast<int>(L.W); P.H = static_cast<int>(L.H); P.S = static_cast<int>(L.S);
+		P.scale = L.sf;
+		if (l >= y->active) continue;
+		Stamp s(y, st, "convlt_fxp_kernels");          // out of place: the fused kernel, no intermediate
+		HIPCHK(ctx, launch_convlt_fxp(l ? L.plane : d_gray, nullptr, L.blurred, P.W, P.H, P.S, P.frameStride, frames, y->kern, y->kern, 5, st));
+	}
+	y->blurredOf = d_gray;
+	a.keys = d_keypoints; a.keyCap = keyCap; a.keyCounts = d_keyCounts; a.desc = d_desc; a.descStride = descStride;
+	{ Stamp s(y, st, y->briefLds ? "orb_brief_pyramid_kernel" : "orb_brief_pyramid_kernel_global"); HIPCHK(ctx, launch_orb_brief_pyramid(a, frames, y->briefLds, st)); }
 	return COMPVHIP_OK;
 }
 

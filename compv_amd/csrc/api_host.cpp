@@ -447,6 +447,62 @@ int compvhip_orb_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, 
 	});
 }
 
+int compvhip_scale_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint8_t* out, size_t Wout, size_t Hout, size_t Sout)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!in || !out || S < W || Sout < Wout) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image or stride < width");
+	if (!W || !H || !Wout || !Hout || W > 32767 || H > 32767 || Wout > 32767 || Hout > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (1..32767)");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t Sd = alignUp(W, 64), Sod = alignUp(Wout, 64);          // no plan: a scale has no minimum size
+	HIPCHK(ctx, ctx->dIn.reserve(ctx, Sd * H));
+	HIPCHK(ctx, ctx->dOut.reserve(ctx, Sod * Hout));
+	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
+	int rc = scaleImpl(ctx, ctx->dIn, W, H, Sd, 1, ctx->dOut, Wout, Hout, Sod, ctx->stream);
+	if (!rc) HIPCHK(ctx, download(ctx, out, Sout, ctx->dOut, Sod, Wout, Hout));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return rc;
+}
+
+int compvhip_orb_pyramid_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_orbpyr_opts* opts, compvhip_keypoint* keypoints,
+                            uint8_t* desc, size_t descStride, size_t cap, size_t* n)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!gray || !n || S < W || (cap && (!keypoints || !desc))) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	*n = 0;
+	if (descStride < 32 || (descStride & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descStride below 32 or no multiple of 4");
+	if (W > 32767 || H > 32767 || cap > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (37..32767) or cap beyond 2^31");
+	const compvhip_orbpyr_opts defaults = { 8, 0.83f, 20, 9, 1, 2000 };
+	if (!opts) opts = &defaults;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t Sd = alignUp(W, 64);
+	// with NMS no two corners are neighbours: every second pixel of every second row at most
+	const size_t cornerCap = opts->nonmax ? ((W + 1) / 2) * ((H + 1) / 2) : W * H;
+	compvhip_orbpyr* y = nullptr;
+	int rc = compvhip_orbpyr_create(ctx, W, H, Sd, 1, opts, cornerCap, &y);
+	if (rc) return rc;
+	do {
+		hipError_t e = ctx->dIn.reserve(ctx, Sd * H);
+		if (e == hipSuccess) e = ctx->dOrbKeys.reserve(ctx, cap);
+		if (e == hipSuccess) e = ctx->dOrbCount.reserve(ctx, 1);
+		if (e == hipSuccess) e = ctx->dOrbDesc.reserve(ctx, cap * 32);
+		if (e == hipSuccess) e = upload(ctx, ctx->dIn, Sd, gray, S, W, H);
+		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "pyramid staging", e); break; }
+		rc = compvhip_orbpyr_detect(y, ctx->dIn, cap ? ctx->dOrbKeys.ptr : nullptr, cap, ctx->dOrbCount, nullptr, nullptr, ctx->stream);
+		if (rc) break;
+		if (cap) rc = compvhip_orbpyr_describe(y, ctx->dIn, 1, ctx->dOrbKeys, cap, ctx->dOrbCount, ctx->dOrbDesc, 32, ctx->stream);
+		if (rc) break;
+		rc = takeList(ctx, ctx->dOrbCount.ptr, ctx->dOrbKeys.ptr, keypoints, cap, n, "keypoint buffer too small");
+		const size_t rows = std::min(*n, cap);
+		if ((rc == COMPVHIP_OK || rc == COMPVHIP_E_OUT_OF_BOUND) && rows && hipMemcpy2D(desc, descStride, ctx->dOrbDesc, 32, 32, rows, hipMemcpyDeviceToHost) != hipSuccess)
+			rc = fail(ctx, COMPVHIP_E_HIP, "descriptor download");
+	} while (0);
+	(void)hipStreamSynchronize(ctx->stream);
+	const std::string err = ctx->err;
+	compvhip_orbpyr_destroy(y);
+	ctx->err = err;
+	return rc;
+}
+
 int compvhip_threshold_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double threshold, uint8_t* out, size_t So)
 {
 	int rc = checkImage(ctx, in, W, H, S, out, So);

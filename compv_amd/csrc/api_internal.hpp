@@ -262,6 +262,24 @@ struct compvhip_matcher : TimingState {
 	uint32_t* partial = nullptr;        // keys of the slice kernel: max of the forward ([pairs][train slices][knn][queryCap]) and the reverse ([pairs][query slices][trainCap]) run
 	compvhip_match* reverse = nullptr;  // [pairs][trainCap]: best query of every train row (cross check)
 };
+// ORB pyramid (scale_kernels.hip, fast_kernels.hip, orb_kernels.hip): the levels' geometry and the scratch they share.  `active` levels (a prefix: the sizes
+// only shrink) are at least 37 x 37; the others are empty.
+struct compvhip_orbpyr : TimingState {
+	compvhip_ctx* ctx = nullptr;
+	size_t W = 0, H = 0, S = 0, frames = 0, cornerCap = 0;
+	compvhip_orbpyr_opts opts = {};
+	int active = 0;
+	struct Level { size_t W = 0, H = 0, S = 0; float sf = 0.f; int quota = 0; uint8_t* plane = nullptr; uint8_t* blurred = nullptr; } lv[kPyrMaxLevels];
+	uint8_t* planes = nullptr;          // levels 1 .. active - 1, [frames][H_l][S_l] each, one allocation
+	uint8_t* blurredAll = nullptr;      // levels 0 .. active - 1 blurred, one allocation (first describe)
+	compvhip_corner* corners = nullptr; // [frames][cornerCap], one level at a time
+	int* fastWork = nullptr; uint8_t* fastScores = nullptr;   // as compvhip_plan's, sized for level 0
+	DevBuf<int32_t> index;              // [frames][keyCap] source indices of a level's survivors
+	int32_t* counts = nullptr;          // [levels][frames] FAST counts, [levels][frames] survivors, [levels + 1][frames] running totals (row 0 stays 0)
+	const uint8_t* planesOf = nullptr;  // the d_gray the level planes were scaled from (nullptr: none yet)
+	const uint8_t* blurredOf = nullptr; // the same for the blurred planes
+	uint16_t kern[5] = {}; bool briefLds = kOrbBriefLdsDefault;
+};
 namespace compvhip_api {
 
 inline void countLive(compvhip_ctx* ctx, long delta) { ctx->live += delta; }
@@ -300,6 +318,7 @@ struct Stamp {
 	TimingState* p; hipStream_t s; size_t idx; bool on;
 	Stamp(compvhip_plan* plan, hipStream_t stream, const char* name) : Stamp(plan, stream, name, stampWanted(plan, name)) {}
 	Stamp(compvhip_matcher* matcher, hipStream_t stream, const char* name) : Stamp(matcher, stream, name, matcher->timing != 0) {}
+	Stamp(compvhip_orbpyr* pyramid, hipStream_t stream, const char* name) : Stamp(pyramid, stream, name, pyramid->timing != 0) {}
 	Stamp(TimingState* state, hipStream_t stream, const char* name, bool wanted) : p(state), s(stream), idx(0), on(wanted)
 	{
 		if (!on) return;
@@ -359,6 +378,7 @@ int checkAdaptive(compvhip_ctx* ctx, size_t W, size_t H, size_t blockSize, doubl
 int morphPrepare(compvhip_ctx* ctx, size_t W, size_t H, const uint8_t* strel, size_t sw, size_t sh, int op, int border, int kernel, MorphArgs* a);
 int checkFast(compvhip_ctx* ctx, size_t W, size_t H, int fastType);
 int checkOrb(compvhip_ctx* ctx, size_t W, size_t H, float scale);
+int scaleImpl(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, hipStream_t st);
 MatchSliceArgs matchForward(const compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
                             const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches);
 // api_kht.cpp

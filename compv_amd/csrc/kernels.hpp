@@ -352,6 +352,9 @@ struct OrbKeyArgs {
 	compvhip_keypoint* keys; size_t keyCap;             // [frames][keyCap]
 	int32_t* keyCounts;       // [frames] survivors before clipping to keyCap
 	int32_t* moments;         // nullptr or [frames][keyCap][2] = {m01, m10}
+	// one level of a pyramid (nullptr: a list of its own, as above): the frame's records go behind the keyBase[f] records of the levels before, while they
+	// fit in keyCap; keyTotal[f] = keyBase[f] + keyCounts[f].  index stays level-local.
+	const int32_t* keyBase = nullptr; int32_t* keyTotal = nullptr;
 };
 hipError_t launch_orb_select(const OrbKeyArgs& a, int frames, hipStream_t stream);
 hipError_t launch_orb_orient(const OrbKeyArgs& a, int frames, hipStream_t stream);
@@ -366,5 +369,54 @@ struct OrbDescArgs {
 };
 // lds: the tests read a patch staged in the LDS (else their bytes from global memory); the result does not depend on it
 hipError_t launch_orb_brief(const OrbDescArgs& a, int frames, bool lds, hipStream_t stream);
+
+// ---- ORB pyramid (orb_kernels.hip, scale_kernels.hip) ------------------------------------------------------------------------------------------
+constexpr int kPyrMaxLevels = 16;
+struct OrbLevelPlane {
+	const uint8_t* blurred;   // [frames][H][S] of the level, or nullptr: an empty level (its keypoints get zero rows)
+	size_t frameStride;
+	int W, H, S;
+	float scale;
+};
+struct OrbPyrDescArgs {     // one launch over the concatenated list: every keypoint is described on the plane of its own `level`
+	OrbLevelPlane lv[kPyrMaxLevels];
+	int levels;               // a keypoint's level outside 0 .. levels - 1: a zero row
+	const compvhip_keypoint* keys; size_t keyCap;
+	const int32_t* keyCounts;
+	uint8_t* desc; size_t descStride;
+};
+hipError_t launch_orb_brief_pyramid(const OrbPyrDescArgs& a, int frames, bool lds, hipStream_t stream);
+struct OrbPyrCountArgs {    // per-level counts [levels][frames] of the pyramid's own -> the caller's [frames][levels] arrays and totals
+	const int32_t* totals;    // [frames] keypoints of the frame over all levels
+	const int32_t* lvKeys;    // [active][frames] survivors per level
+	const int32_t* lvCorners; // [active][frames] FAST counts per level
+	int active, levels, frames;
+	int32_t* keyCounts;       // [frames]
+	int32_t* levelCounts;     // nullptr or [frames][levels]
+	int32_t* levelCorners;    // nullptr or [frames][levels]
+};
+hipError_t launch_orb_pyramid_counts(const OrbPyrCountArgs& a, hipStream_t stream);
+
+// CompVImageScaleBilinear (compv_image_scale_bilinear.cxx:48-88): one source batch, up to 16 destinations (the levels of a pyramid), one launch
+struct ScaleLevel {
+	uint8_t* out;             // [frames][H][S]
+	size_t frameStride;
+	int W, H, S;
+	uint32_t sx, sy;          // (int)(((float)Win / (float)W) * 256.f), the same for y
+	int copy;                 // the destination has the source's size: a copy, not the arithmetic
+	int dwords;               // out, S and frameStride are multiples of 4: full groups of 4 pixels go out as one dword
+	int tilesX;               // ceil(W / 256)
+	int blockEnd;             // workgroups of the levels up to this one
+};
+struct ScaleArgs {
+	const uint8_t* in;        // [frames][H][S]
+	size_t frameStride;
+	int W, H, S;
+	int levels;
+	ScaleLevel lv[kPyrMaxLevels];
+};
+// fills sx, sy, copy, dwords, tilesX of `lv` from the two sizes; false: a ratio outside (0, 256) or a size of 0
+bool scale_level_init(ScaleLevel& lv, int Win, int Hin);
+hipError_t launch_scale_bilinear(ScaleArgs& a, int frames, hipStream_t stream);   // fills blockEnd
 
 } // namespace compvhip

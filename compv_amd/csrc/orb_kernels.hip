@@ -12,6 +12,9 @@
 //                       little-endian 64-bit word of the descriptor.  <true>: the 37 x 37 blurred patch is staged in the LDS by coalesced dword
 //                       loads (10 dwords cover a row from the dword boundary at or below xi - 18) and the tests read bytes from there;
 //                       <false>: the tests read their bytes from global memory.  Lanes 0 and 1 store the row, 16 bytes each.
+//   orb_brief_pyramid_kernel   the same wave over the concatenated list of a pyramid: plane, size, stride and scale come from a level table in the
+//                       argument block, chosen by the keypoint's own `level`.  orb_select_kernel / orb_orient_kernel take an optional per-frame
+//                       offset from device memory (keyBase), so the levels' lists are written one behind the other without a host round trip.
 // No atomic anywhere: every slot is decided by a rank, every word by a ballot.
 #include "device.hpp"
 
@@ -75,6 +78,7 @@ __global__ __launch_bounds__(256) void orb_select_kernel(OrbKeyArgs a)
 	const int n = usedCount(a.cornerCounts, f, a.cornerCap);
 	const compvhip_corner* __restrict__ in = a.corners + static_cast<size_t>(f) * a.cornerCap;
 	int32_t* __restrict__ out = a.index + static_cast<size_t>(f) * a.keyCap;
+	const long long before0 = a.keyBase ? a.keyBase[f] : 0;          // records of the pyramid levels before this one
 	long long base = 0;
 	for (int c0 = 0; c0 < n; c0 += 256) {          // n is workgroup-uniform
 		const int c = c0 + tid;
@@ -92,16 +96,21 @@ __global__ __launch_bounds__(256) void orb_select_kernel(OrbKeyArgs a)
 #pragma unroll
 		for (int w = 0; w < 4; ++w) { if (w < wave) off += sWave[w]; total += sWave[w]; }
 		const long long idx = base + off + before;
-		if (ok && idx < static_cast<long long>(a.keyCap)) out[idx] = c;
+		if (ok && before0 + idx < static_cast<long long>(a.keyCap)) out[idx] = c;
 		base += total;
 	}
-	if (tid == 0) a.keyCounts[f] = static_cast<int32_t>(base);
+	if (tid == 0) {
+		a.keyCounts[f] = static_cast<int32_t>(base);
+		if (a.keyTotal) a.keyTotal[f] = static_cast<int32_t>(before0 + base);
+	}
 }
 
 __global__ __launch_bounds__(256) void orb_orient_kernel(OrbKeyArgs a)
 {
 	const int f = blockIdx.y, lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (q >= usedCount(a.keyCounts, f, a.keyCap)) return;          // wave-uniform; no barrier in this kernel
+	const long long place = (a.keyBase ? a.keyBase[f] : 0) + static_cast<long long>(q);          // behind the levels before
+	if (place >= static_cast<long long>(a.keyCap)) return;
 	const compvhip_corner c = a.corners[static_cast<size_t>(f) * a.cornerCap + a.index[static_cast<size_t>(f) * a.keyCap + q]];
 	const uint8_t* __restrict__ centre = a.gray + static_cast<size_t>(f) * a.frameStride + static_cast<size_t>(c.y) * a.S + c.x;   // 18 pixels inside: orb_select_kernel
 	const int half = lane >> 5, col = lane & 31;
@@ -125,7 +134,7 @@ __global__ __launch_bounds__(256) void orb_orient_kernel(OrbKeyArgs a)
 	if (a.level != 0) { const float sfi = 1.f / a.scale; x = __fmul_rn(x, sfi); y = __fmul_rn(y, sfi); }
 	compvhip_keypoint k;
 	k.x = x; k.y = y; k.strength = static_cast<float>(c.strength); k.orient = orient; k.level = a.level; k.size = 31.f / a.scale;
-	const size_t slot = static_cast<size_t>(f) * a.keyCap + q;
+	const size_t slot = static_cast<size_t>(f) * a.keyCap + static_cast<size_t>(place);
 	a.keys[slot] = k;
 	if (a.moments) { a.moments[2 * slot] = m01; a.moments[2 * slot + 1] = m10; }
 }
@@ -133,25 +142,24 @@ __global__ __launch_bounds__(256) void orb_orient_kernel(OrbKeyArgs a)
 constexpr int kPatchSide = 2 * kOrbBorder + 1;   // 37
 constexpr int kPatchDwords = 10;                  // a patch row in the LDS: 40 bytes from the dword boundary at or below xi - 18
 
+// The descriptor of one keypoint by one wave (4 waves a workgroup; every wave of the workgroup calls this: the LDS variant has a barrier).  plane: the
+// blurred plane of the keypoint's frame and level, W x H, stride S; nullptr = no such plane, a zero row.  have: this wave has a keypoint (*key, row).
 template <bool LDS>
-__global__ __launch_bounds__(256) void orb_brief_kernel(OrbDescArgs a)
+__device__ __forceinline__ void brief_wave(const uint8_t* __restrict__ plane, int W, int H, int S, float scale, bool have, const compvhip_keypoint* key, uint8_t* row,
+                                           uint32_t* sPatch)
 {
-	__shared__ uint32_t sPatch[LDS ? 4 * kPatchSide * kPatchDwords : 1];
-	const int f = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = blockIdx.x * 4 + wave;
-	const bool have = q < usedCount(a.keyCounts, f, a.keyCap);          // not a return: the LDS variant has a barrier
-	const size_t slot = static_cast<size_t>(f) * a.keyCap + (have ? q : 0);
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	int xi = 0, yi = 0;
 	float fcos = 1.f, fsin = 0.f;
 	if (have) {
-		const compvhip_keypoint k = a.keys[slot];
-		xi = static_cast<int>(static_cast<double>(__fmul_rn(k.x, a.scale)) + 0.5);          // :279-288
-		yi = static_cast<int>(static_cast<double>(__fmul_rn(k.y, a.scale)) + 0.5);
+		const compvhip_keypoint k = *key;
+		xi = static_cast<int>(static_cast<double>(__fmul_rn(k.x, scale)) + 0.5);          // :279-288
+		yi = static_cast<int>(static_cast<double>(__fmul_rn(k.y, scale)) + 0.5);
 		const float rad = __fmul_rn(k.orient, kOrbPiOver180);
 		fcos = static_cast<float>(cos(static_cast<double>(rad))); fsin = static_cast<float>(sin(static_cast<double>(rad)));
 	}
 	// (compared without adding to xi: a caller's record may hold anything)
-	const bool inside = have && xi >= kOrbBorder && xi < a.W - kOrbBorder && yi >= kOrbBorder && yi < a.H - kOrbBorder;
-	const uint8_t* __restrict__ plane = a.blurred + static_cast<size_t>(f) * a.frameStride;
+	const bool inside = have && plane && xi >= kOrbBorder && xi < W - kOrbBorder && yi >= kOrbBorder && yi < H - kOrbBorder;
 	const int x0 = (xi - kOrbBorder) & ~3, y0 = yi - kOrbBorder;
 	const uint8_t* patch = nullptr;
 	if (LDS) {
@@ -160,7 +168,7 @@ __global__ __launch_bounds__(256) void orb_brief_kernel(OrbDescArgs a)
 			for (int i = lane; i < kPatchSide * kPatchDwords; i += 64) {
 				const int r = i / kPatchDwords, d = i - r * kPatchDwords;
 				const int x = x0 + 4 * d;          // S % 4 == 0: a dword that starts inside the row ends inside it
-				sP[i] = x < a.S ? *reinterpret_cast<const uint32_t*>(plane + static_cast<size_t>(y0 + r) * a.S + x) : 0u;
+				sP[i] = x < S ? *reinterpret_cast<const uint32_t*>(plane + static_cast<size_t>(y0 + r) * S + x) : 0u;
 			}
 		}
 		__syncthreads();
@@ -183,8 +191,8 @@ __global__ __launch_bounds__(256) void orb_brief_kernel(OrbDescArgs a)
 				vb = patch[(yb + kOrbBorder) * (4 * kPatchDwords) + (xi + xb - x0)];
 			}
 			else {
-				va = plane[static_cast<size_t>(yi + ya) * a.S + (xi + xa)];
-				vb = plane[static_cast<size_t>(yi + yb) * a.S + (xi + xb)];
+				va = plane[static_cast<size_t>(yi + ya) * S + (xi + xa)];
+				vb = plane[static_cast<size_t>(yi + yb) * S + (xi + xb)];
 			}
 			word[k] = __ballot(va < vb);
 		}
@@ -193,8 +201,45 @@ __global__ __launch_bounds__(256) void orb_brief_kernel(OrbDescArgs a)
 		const unsigned long long lo = word[2 * lane], hi = word[2 * lane + 1];
 		u32x4a4 v;
 		v.x = static_cast<uint32_t>(lo); v.y = static_cast<uint32_t>(lo >> 32); v.z = static_cast<uint32_t>(hi); v.w = static_cast<uint32_t>(hi >> 32);
-		*reinterpret_cast<u32x4a4*>(a.desc + slot * a.descStride + 16 * lane) = v;
+		*reinterpret_cast<u32x4a4*>(row + 16 * lane) = v;
 	}
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(256) void orb_brief_kernel(OrbDescArgs a)
+{
+	__shared__ uint32_t sPatch[LDS ? 4 * kPatchSide * kPatchDwords : 1];
+	const int f = blockIdx.y, q = blockIdx.x * 4 + (threadIdx.x >> 6);
+	const bool have = q < usedCount(a.keyCounts, f, a.keyCap);          // not a return: the LDS variant has a barrier
+	const size_t slot = static_cast<size_t>(f) * a.keyCap + (have ? q : 0);
+	brief_wave<LDS>(a.blurred + static_cast<size_t>(f) * a.frameStride, a.W, a.H, a.S, a.scale, have, a.keys + slot, a.desc + slot * a.descStride, sPatch);
+}
+
+// The same over the concatenated list of a pyramid: the wave takes plane, size, stride and scale from the level table by its keypoint's `level`
+// (wave-uniform, so the table is read with scalar loads).  A level outside the table or without a plane: a zero row.
+template <bool LDS>
+__global__ __launch_bounds__(256) void orb_brief_pyramid_kernel(OrbPyrDescArgs a)
+{
+	__shared__ uint32_t sPatch[LDS ? 4 * kPatchSide * kPatchDwords : 1];
+	const int f = blockIdx.y, q = blockIdx.x * 4 + (threadIdx.x >> 6);
+	const bool have = q < usedCount(a.keyCounts, f, a.keyCap);
+	const size_t slot = static_cast<size_t>(f) * a.keyCap + (have ? q : 0);
+	const int level = __builtin_amdgcn_readfirstlane(have ? a.keys[slot].level : -1);
+	const bool known = level >= 0 && level < a.levels;
+	const OrbLevelPlane& L = a.lv[known ? level : 0];
+	const uint8_t* plane = known && L.blurred ? L.blurred + static_cast<size_t>(f) * L.frameStride : nullptr;
+	brief_wave<LDS>(plane, L.W, L.H, L.S, L.scale, have, a.keys + slot, a.desc + slot * a.descStride, sPatch);
+}
+
+// counts of the pyramid's own, [active][frames], into the caller's arrays: one lane per (frame, level)
+__global__ __launch_bounds__(256) void orb_pyramid_counts_kernel(OrbPyrCountArgs a)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= a.frames * a.levels) return;
+	const int f = i / a.levels, l = i - f * a.levels;
+	if (l == 0) a.keyCounts[f] = a.totals[f];
+	if (a.levelCounts) a.levelCounts[i] = l < a.active ? a.lvKeys[l * a.frames + f] : 0;
+	if (a.levelCorners) a.levelCorners[i] = l < a.active ? a.lvCorners[l * a.frames + f] : 0;
 }
 
 } // namespace
@@ -222,6 +267,27 @@ hipError_t launch_orb_brief(const OrbDescArgs& a, int frames, bool lds, hipStrea
 	const dim3 grid(static_cast<unsigned>((a.keyCap + 3) / 4), frames);
 	if (lds) hipLaunchKernelGGL(orb_brief_kernel<true>, grid, dim3(256), 0, stream, a);
 	else hipLaunchKernelGGL(orb_brief_kernel<false>, grid, dim3(256), 0, stream, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_orb_brief_pyramid(const OrbPyrDescArgs& a, int frames, bool lds, hipStream_t stream)
+{
+	if (frames < 1 || frames > 65535 || !a.keyCap || a.keyCap > static_cast<size_t>(INT32_MAX) || !a.keys || !a.keyCounts || !a.desc) return hipErrorInvalidValue;
+	if (a.levels < 1 || a.levels > kPyrMaxLevels || a.descStride < 32 || (a.descStride & 3)) return hipErrorInvalidValue;
+	for (int l = 0; l < a.levels; ++l) {
+		const OrbLevelPlane& L = a.lv[l];
+		if (L.blurred && (L.W < kPatchSide || L.H < kPatchSide || L.S < L.W || (L.S & 3) || (L.frameStride & 3) || (reinterpret_cast<uintptr_t>(L.blurred) & 3))) return hipErrorInvalidValue;
+	}
+	const dim3 grid(static_cast<unsigned>((a.keyCap + 3) / 4), frames);
+	if (lds) hipLaunchKernelGGL(orb_brief_pyramid_kernel<true>, grid, dim3(256), 0, stream, a);
+	else hipLaunchKernelGGL(orb_brief_pyramid_kernel<false>, grid, dim3(256), 0, stream, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_orb_pyramid_counts(const OrbPyrCountArgs& a, hipStream_t stream)
+{
+	if (a.frames < 1 || a.levels < 1 || a.levels > kPyrMaxLevels || a.active < 1 || a.active > a.levels || !a.totals || !a.lvKeys || !a.lvCorners || !a.keyCounts) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(orb_pyramid_counts_kernel, dim3((a.frames * a.levels + 255) / 256), dim3(256), 0, stream, a);
 	return hipGetLastError();
 }
 

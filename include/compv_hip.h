@@ -685,7 +685,7 @@ COMPVHIP_API int compvhip_matcher_get_timing(compvhip_matcher* matcher, const ch
 /* ---- ORB: keypoint orientation and rotated-BRIEF descriptors (docs/kernels/orb.md) ------------------------------------------------------
  * The intensity-centroid orientation of CompVCornerDeteORB::processLevelAt (core/features/orb/compv_core_feature_orb_dete.cxx:281-358) and the
  * BRIEF-256/31 of CompVCornerDescORB (compv_core_feature_orb_desc.cxx:206-319) for ONE pyramid level: a plan is the level's geometry, the calls
- * take the level's number and scale factor.  (No pyramid here: it only adds planes and plans.)  Every output is defined bit for bit.
+ * take the level's number and scale factor.  (The pyramid over them: compvhip_orbpyr below.)  Every output is defined bit for bit.
  * Keypoints, from a corner list {x, y, strength} of a gray frame I of W x H:
  *  1. Border erase (eraseTooCloseToBorder, compv_common.h:657): with b = 18 = (31 + 5) >> 1, a corner with x < b, x + b >= W, y < b or
  *     y + b >= H is dropped; the survivors keep their order.
@@ -742,6 +742,91 @@ COMPVHIP_API int compvhip_plan_orb_describe(compvhip_plan* plan, const uint8_t* 
  * *kept receives the number of keypoints (<= n).  Synchronous, on the context's cached single-frame plan. */
 COMPVHIP_API int compvhip_orb_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_corner* corners, size_t n,
                                  int level, float scale, compvhip_keypoint* keypoints, uint8_t* desc, size_t descStride, size_t* kept);
+
+/* ---- bilinear scale and the ORB scale pyramid (docs/kernels/scale.md, docs/kernels/orb.md) ------------------------------------------------
+ * CompVCornerDeteORB::process (core/features/orb/compv_core_feature_orb_dete.cxx:148-358) is defined over a pyramid: every level scaled from the
+ * original frame, a feature quota per level, the levels' lists concatenated in level order.  Every output is defined bit for bit.
+ * A. Bilinear scale (CompVImageScaleBilinear, base/image/compv_image_scale_bilinear.cxx:48-88,149-192, through CompVImage::scale,
+ *    compv_image.cxx:852-905).  Source Win x Hin, destination Wout x Hout, uint8, one plane:
+ *  1. sx = (int)(((float)Win / (float)Wout) * 256.f), every operation in float32, truncated; sy likewise.
+ *  2. Both ratios (float)Win / (float)Wout and (float)Hin / (float)Hout must lie in (0, 256): anything else, or a size of 0, is
+ *     COMPVHIP_E_INVALID_PARAMETER (the reference only warns and distorts).
+ *  3. Output pixel (i, j): x = i * sx, y = j * sy; nx = x >> 8, ny = y >> 8; x0 = x & 255, x1 = 255 - x0, y0 = y & 255, y1 = 255 - y0;
+ *     A = n0 * x1 + n1 * x0, B = n2 * x1 + n3 * x0 with n0 = I(nx, ny), n1 = I(nx + 1, ny), n2 = I(nx, ny + 1), n3 = I(nx + 1, ny + 1);
+ *     out = (uint8)(((y1 * A) >> 16) + ((y0 * B) >> 16)) -- two separate shifts, as the reference's live branch and its AVX2 leaf's two mulhi.
+ *     The weights sum to 255, not 256: the reference's arithmetic, kept.  Everything fits in uint32.
+ *  4. Wout == Win and Hout == Hin is a copy (the clone branch of CompVImage::scale), not the arithmetic of 3.
+ *  5. Neighbour indices are clamped to Win - 1 and Hin - 1.  A strict downscale never reaches past them; for an upscale the reference reads its
+ *     stride padding and one row past the plane, so the clamp is this library's rule there.
+ *  6. Columns >= Wout of the destination stride are never written (the AVX2 leaf scribbles there).
+ * B. Pyramid geometry (CompVImageScalePyramid, base/image/compv_image_scale_pyramid.cxx:16-46,163-168):
+ *  1. sf[0] = 1.f, sf[l] = sf[l - 1] * scaleFactor in float32 (sf[1] = scaleFactor); sfs = 1.f + sf[1] + ... accumulated in float32 in level
+ *     order (0.83, 8 levels: 4.5574746).
+ *  2. W_l = (size_t)((float)W * sf[l]), H_l likewise; every level is scaled FROM THE ORIGINAL frame by A.  Level 0 is the caller's frame
+ *     itself and is not copied.
+ *  3. levels in 1 .. 16, 0 < scaleFactor < 1, level 0 at least 37 x 37: anything else is COMPVHIP_E_INVALID_PARAMETER.
+ *  4. A level with W_l < 37 or H_l < 37 is EMPTY: it owns no plane and contributes no keypoint (the border erase would remove every corner
+ *     of it anyway; the reference runs FAST on it for nothing and fails at size 0).
+ * C. Detection per level (processLevelAt, :281-358):
+ *  1. FAST on the level plane by the FAST section above, with the pyramid's threshold, fastType and nonmax.
+ *  2. Quota: with maxFeatures > 0, nf = ((float)maxFeatures / sfs) * sf[l] in float32, quota = max(10, (int32)((double)nf + 0.5)); a level with
+ *     more corners is cut by rule 7 of the FAST section with maxFeatures = quota (ties at the cut stay, raster order).  maxFeatures <= 0: no cut.
+ *  3. Border erase, moments, orientation and record as compvhip_plan_orb_keypoints with level = l and scale = sf[l].
+ *  4. Frame f's keypoints are the levels' lists in level order, each level in its own (raster) order.  d_keyCounts[f] is the total BEFORE
+ *     clipping to keyCap; the first min(total, keyCap) records are written and nothing behind them (a clip may fall inside a level).
+ *  5. d_levelCounts (optional, [frames][levels] int32): the survivors of each level before clipping; 0 for an empty level.
+ *  6. d_levelCorners (optional, [frames][levels] int32): the FAST count of the level after the cut and BEFORE clipping to the object's
+ *     cornerCap -- a value above cornerCap says that the level's list was truncated to its raster prefix.
+ * D. Description (CompVCornerDescORB::describe, compv_core_feature_orb_desc.cxx:206-319):
+ *  1. Each non-empty level plane is blurred out of place (5 taps, sigma 2.0, Q16), as the single-level path does.
+ *  2. Each keypoint is described on the plane of ITS OWN `level` field with sf[level], by the descriptor rules of the ORB section.
+ *  3. A keypoint whose level is outside 0 .. levels - 1, whose level is empty, or that sits inside the 18-pixel margin gets a zero row in place.
+ *  4. The caller's keypoints may mix levels in any order (what CompVCornerDescORB::process accepts). */
+typedef struct compvhip_orbpyr compvhip_orbpyr;
+typedef struct compvhip_orbpyr_opts {
+	int levels; float scaleFactor;           /* 8, 0.83f */
+	int threshold, fastType, nonmax;         /* 20, 9, 1 */
+	int maxFeatures;                         /* 2000; <= 0: no cut */
+} compvhip_orbpyr_opts;
+
+/* A pyramid for `frames` frames of W x H with stride S (S % 8 == 0; frames [frames][H][S]).  It owns lighter state than per-level plans (no
+ * Canny / Hough scratch), all allocated here except the index list and the blurred planes, which come with the first call that needs them:
+ * level planes, levels 1 .. of the non-empty ones, [frames][H_l][S_l] with S_l = W_l rounded up to 8; the same again, level 0 included, blurred
+ * (first describe); ONE corner list [frames][cornerCap] and ONE FAST score map [frames][H][S] that the levels use in turn, with FAST's
+ * frames * (2 * H + 257) int32; frames * keyCap int32 source indices (first detect, again for a larger keyCap); (3 * levels + 1) * frames int32
+ * counts.  cornerCap >= 1.  Destroy a pyramid BEFORE its context; compvhip_live_allocations then returns to its earlier value.  Like a plan,
+ * a pyramid is not re-entrant: its calls share the scratch and must be ordered on one stream. */
+COMPVHIP_API int compvhip_orbpyr_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size_t frames, const compvhip_orbpyr_opts* opts, size_t cornerCap,
+                                        compvhip_orbpyr** pyramid);
+COMPVHIP_API void compvhip_orbpyr_destroy(compvhip_orbpyr* pyramid);
+/* Host arithmetic only: size, stride, sf[level] and quota (0 without a cut) of a level; an empty level has S == 0.  Any output may be NULL. */
+COMPVHIP_API int compvhip_orbpyr_geometry(const compvhip_orbpyr* pyramid, int level, size_t* W, size_t* H, size_t* S, float* scale, int* quota);
+/* The device plane [frames][H_l][S_l] of a level as the last call built it: blurred == 0 the scaled plane (level 0: the caller's d_gray of that
+ * call), else the blurred one.  COMPVHIP_E_INVALID_STATE before a call built it, COMPVHIP_E_INVALID_PARAMETER for an empty level. */
+COMPVHIP_API int compvhip_orbpyr_plane(compvhip_orbpyr* pyramid, int level, int blurred, const uint8_t** d_plane);
+/* C. for every frame.  d_gray 8-byte aligned; d_keypoints: [frames][keyCap] (NULL with keyCap == 0: counts only); counts 4-byte aligned.
+ * Asynchronous on `stream`, never synchronises the host, deterministic run to run. */
+COMPVHIP_API int compvhip_orbpyr_detect(compvhip_orbpyr* pyramid, const uint8_t* d_gray, compvhip_keypoint* d_keypoints, size_t keyCap, int32_t* d_keyCounts,
+                                        int32_t* d_levelCounts, int32_t* d_levelCorners, void* stream);
+/* D. for every frame; rows as compvhip_plan_orb_describe writes them (rows q >= min(count, keyCap) are never written).  reusePlanes != 0:
+ * describe on the planes the preceding compvhip_orbpyr_detect built from the same d_gray (COMPVHIP_E_INVALID_STATE when there was none);
+ * reusePlanes == 0 rebuilds them.  Asynchronous on `stream`, never synchronises the host. */
+COMPVHIP_API int compvhip_orbpyr_describe(compvhip_orbpyr* pyramid, const uint8_t* d_gray, int reusePlanes, const compvhip_keypoint* d_keypoints, size_t keyCap,
+                                          const int32_t* d_keyCounts, uint8_t* d_desc, size_t descStride, void* stream);
+/* A. for every frame of a plan: d_in [frames][H][S] of the plan's geometry -> d_out [frames][Hout][Sout] (Sout >= Wout; sizes up to 32767; the
+ * buffers must not overlap).  A destination that is dword-aligned in pointer and stride is written with dword stores.  Asynchronous on `stream`. */
+COMPVHIP_API int compvhip_plan_scale(compvhip_plan* src, const uint8_t* d_in, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
+/* A. for one HOST plane (sizes 1 .. 32767).  Synchronous. */
+COMPVHIP_API int compvhip_scale_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint8_t* out, size_t Wout, size_t Hout, size_t Sout);
+/* C. and D. for one HOST frame (37 <= W, H <= 32767; opts == NULL: the defaults).  *n receives the number of keypoints; when it exceeds cap only
+ * the first cap records and rows are written and COMPVHIP_E_OUT_OF_BOUND is returned, as compvhip_fast_u8 does.  Synchronous. */
+COMPVHIP_API int compvhip_orb_pyramid_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_orbpyr_opts* opts,
+                                         compvhip_keypoint* keypoints, uint8_t* desc, size_t descStride, size_t cap, size_t* n);
+/* Per-kernel timing of the pyramid's last call, as compvhip_matcher_set_timing / _get_timing: entries scale_bilinear_kernel, then per level
+ * fast_score_kernel, fast_list_kernels, orb_select_kernel, orb_orient_kernel, then orb_pyramid_counts_kernel (detect); scale_bilinear_kernel,
+ * convlt_fxp_kernels per level, orb_brief_pyramid_kernel (describe). */
+COMPVHIP_API int compvhip_orbpyr_set_timing(compvhip_orbpyr* pyramid, int enabled);
+COMPVHIP_API int compvhip_orbpyr_get_timing(compvhip_orbpyr* pyramid, const char** names, float* ms, int cap);
 
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
