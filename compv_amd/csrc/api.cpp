@@ -174,8 +174,8 @@ ShtArgs shtArgs(compvhip_plan* p, int threshold)
 int ensurePreproc(compvhip_plan* p)
 {
 	compvhip_ctx* ctx = p->ctx;
-	if (!p->hist) HIPCHK(ctx, dmalloc(ctx, &p->hist, static_cast<size_t>(256) * kOtsuMaxChunks * p->frames));
-	if (!p->otsu) HIPCHK(ctx, dmalloc(ctx, &p->otsu, p->frames));
+	HIPCHK(ctx, p->hist.reserve(ctx, static_cast<size_t>(256) * kOtsuMaxChunks * p->frames));
+	HIPCHK(ctx, p->otsu.reserve(ctx, p->frames));
 	return COMPVHIP_OK;
 }
 
@@ -266,9 +266,7 @@ int compvhip_api::ensureSht(compvhip_plan* p)
 {
 	if (p->shtReady) return COMPVHIP_OK;
 	compvhip_ctx* ctx = p->ctx;
-	// a previous attempt may have failed half way (out of memory): start from a clean slate instead of leaking its buffers
-	dfree(ctx, p->sinQ); dfree(ctx, p->cosQ); dfree(ctx, p->cosT); dfree(ctx, p->invSinT);
-	dfree(ctx, p->edges); dfree(ctx, p->acc);
+	// (a previous attempt may have failed half way, out of memory: shtReady is still false, and reserve reuses what that attempt allocated)
 	size_t R, T; float step;
 	int rc = shtDims(p->W, p->H, p->thetaDeg, &R, &T, &step);
 	if (rc) return fail(ctx, rc, "invalid SHT geometry");
@@ -279,8 +277,8 @@ int compvhip_api::ensureSht(compvhip_plan* p)
 	p->accFrameStride = static_cast<size_t>(p->accPitch) * T;
 	std::vector<int32_t> s, c;
 	shtTables(p->thetaDeg, T, s, c);
-	HIPCHK(ctx, dmalloc(ctx, &p->sinQ, T));
-	HIPCHK(ctx, dmalloc(ctx, &p->cosQ, T));
+	HIPCHK(ctx, p->sinQ.reserve(ctx, T));
+	HIPCHK(ctx, p->cosQ.reserve(ctx, T));
 	HIPCHK(ctx, hipMemcpy(p->sinQ, s.data(), T * sizeof(int32_t), hipMemcpyHostToDevice));
 	HIPCHK(ctx, hipMemcpy(p->cosQ, c.data(), T * sizeof(int32_t), hipMemcpyHostToDevice));
 	{
@@ -292,14 +290,13 @@ int compvhip_api::ensureSht(compvhip_plan* p)
 			ct[t] = libmCosf(theta);
 			ist[t] = 1.f / libmSinf(theta);
 		}
-		HIPCHK(ctx, dmalloc(ctx, &p->cosT, T));
-		HIPCHK(ctx, dmalloc(ctx, &p->invSinT, T));
+		HIPCHK(ctx, p->cosT.reserve(ctx, T));
+		HIPCHK(ctx, p->invSinT.reserve(ctx, T));
 		HIPCHK(ctx, hipMemcpy(p->cosT, ct.data(), T * sizeof(float), hipMemcpyHostToDevice));
 		HIPCHK(ctx, hipMemcpy(p->invSinT, ist.data(), T * sizeof(float), hipMemcpyHostToDevice));
 	}
 	{
 		if (p->vt.tiles <= 0 || p->vtKt.size() != static_cast<size_t>(p->vt.tiles) * T) return fail(ctx, COMPVHIP_E_INVALID_STATE, "vote tiles were not planned");
-		dfree(ctx, p->dKt); dfree(ctx, p->dRowBase); dfree(ctx, p->partLo); dfree(ctx, p->partHi); dfree(ctx, p->colFlag);
 		{
 			// accumulator rows the NMS has to look at, per group of 8 theta columns (+ the column either side): the union of the tiles' windows
 			const int tiles = p->vt.tiles, Rw = p->vt.Rw, groups = sht_nms_groups(static_cast<int>(T));
@@ -324,30 +321,28 @@ int compvhip_api::ensureSht(compvhip_plan* p)
 				}
 				reach[t] = make_int2(lo, hi);
 			}
-			dfree(ctx, p->reach);
-			HIPCHK(ctx, dmalloc(ctx, &p->reach, reach.size()));
+			HIPCHK(ctx, p->reach.reserve(ctx, reach.size()));
 			HIPCHK(ctx, hipMemcpy(p->reach, reach.data(), reach.size() * sizeof(int2), hipMemcpyHostToDevice));
-			dfree(ctx, p->nmsRange);
-			HIPCHK(ctx, dmalloc(ctx, &p->nmsRange, range.size()));
+			HIPCHK(ctx, p->nmsRange.reserve(ctx, range.size()));
 			HIPCHK(ctx, hipMemcpy(p->nmsRange, range.data(), range.size() * sizeof(int2), hipMemcpyHostToDevice));
 		}
-		HIPCHK(ctx, dmalloc(ctx, &p->dKt, p->vtKt.size()));
-		HIPCHK(ctx, dmalloc(ctx, &p->dRowBase, p->vtRowBase.size()));
+		HIPCHK(ctx, p->dKt.reserve(ctx, p->vtKt.size()));
+		HIPCHK(ctx, p->dRowBase.reserve(ctx, p->vtRowBase.size()));
 		HIPCHK(ctx, hipMemcpy(p->dKt, p->vtKt.data(), p->vtKt.size() * sizeof(int32_t), hipMemcpyHostToDevice));
 		HIPCHK(ctx, hipMemcpy(p->dRowBase, p->vtRowBase.data(), p->vtRowBase.size() * sizeof(int32_t), hipMemcpyHostToDevice));
 		{
 			// partial windows: one byte plane for the low bytes of the counts, one for the high bytes (only written / read for the few columns
 			// that hold a count >= 256: a tile's share of a strong line), one flag byte per column
 			const size_t cols = p->frames * p->vt.tiles * static_cast<size_t>(p->vt.Tpad);
-			HIPCHK(ctx, dmalloc(ctx, &p->partLo, cols * p->vt.rwPitch));
-			HIPCHK(ctx, dmalloc(ctx, &p->partHi, cols * p->vt.rwPitch));
-			HIPCHK(ctx, dmalloc(ctx, &p->colFlag, cols));
+			HIPCHK(ctx, p->partLo.reserve(ctx, cols * p->vt.rwPitch));
+			HIPCHK(ctx, p->partHi.reserve(ctx, cols * p->vt.rwPitch));
+			HIPCHK(ctx, p->colFlag.reserve(ctx, cols));
 		}
 		p->vt.kt = p->dKt; p->vt.rowBase = p->dRowBase; p->vt.partLo = p->partLo; p->vt.partHi = p->partHi; p->vt.colFlag = p->colFlag; p->vt.reach = p->reach; p->vt.tileCounts = p->tileCounts;
 		p->edgeCap = static_cast<size_t>(p->vt.tiles) * p->vt.tileCap; // per frame: one list of TW * TH entries per tile
 	}
-	HIPCHK(ctx, dmalloc(ctx, &p->edges, p->edgeCap * p->frames));
-	HIPCHK(ctx, dmalloc(ctx, &p->acc, p->accFrameStride * p->frames));
+	HIPCHK(ctx, p->edges.reserve(ctx, p->edgeCap * p->frames));
+	HIPCHK(ctx, p->acc.reserve(ctx, p->accFrameStride * p->frames));
 	HIPCHK(ctx, hipMemset(p->acc, 0, sizeof(uint16_t) * p->accFrameStride * p->frames)); // rows [Rp, accPitch) stay zero for ever
 	// line key = frameTag | strength (strengthBits); the accumulator cell rides as the sort value (sht_nms / rank / emit kernels).  A cell of
 	// column theta counts the pixels with (x*cosQ + y*sinQ) in one 65536-wide interval; max(|cosQ|,|sinQ|) >= 46340 so every x (or every y)
@@ -360,10 +355,9 @@ int compvhip_api::ensureSht(compvhip_plan* p)
 	p->keyBits = frameBits + p->strengthBits;
 	if (R * T >= (static_cast<size_t>(1) << 32)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "theta step too small: the accumulator has 2^32 cells or more"); // 32-bit cell values
 	if (p->keyBits > 32) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "too many frames for a 32-bit line key");
-	dfree(ctx, p->nmsFlags);
 	{
 		const size_t frows = sht_nms_rows(static_cast<int>(R)), fgroups = static_cast<size_t>(sht_nms_groups(static_cast<int>(T)));
-		HIPCHK(ctx, dmalloc(ctx, &p->nmsFlags, frows * fgroups * p->frames));
+		HIPCHK(ctx, p->nmsFlags.reserve(ctx, frows * fgroups * p->frames));
 		HIPCHK(ctx, hipMemset(p->nmsFlags, 0, frows * fgroups * p->frames)); // the NMS kernel skips the blocks no window reaches
 		if (sht_lines_blocks(static_cast<int>(R)) != p->lineBlocks) return fail(ctx, COMPVHIP_E_INVALID_STATE, "row-block counters were sized for another accumulator");
 	}
@@ -376,25 +370,25 @@ int compvhip_api::ensureLineCap(compvhip_plan* p, size_t cap)
 	compvhip_ctx* ctx = p->ctx;
 	cap = std::min(cap, p->R * p->T);
 	if (cap <= p->lineCap) return COMPVHIP_OK;
-	dfree(ctx, p->keysA); dfree(ctx, p->keysB); dfree(ctx, p->valsA); dfree(ctx, p->valsB); dfree(ctx, p->sortTemp); dfree(ctx, p->chunkHist); dfree(ctx, p->strengthStart);
-	p->lineCap = 0; p->deviceSort = false;
-	HIPCHK(ctx, dmalloc(ctx, &p->keysA, cap * p->frames));
-	HIPCHK(ctx, dmalloc(ctx, &p->keysB, cap * p->frames));
-	HIPCHK(ctx, dmalloc(ctx, &p->valsA, cap * p->frames));
-	HIPCHK(ctx, dmalloc(ctx, &p->valsB, cap * p->frames));
+	p->lineCap = 0; p->deviceSort = false;   // (until everything below is there: a failed attempt runs again)
+	// Each reserve replaces one buffer: while the keys grow, the smaller values, sort scratch and histograms of the old capacity are still there (the hand-written
+	// version freed all seven first).  Same allocations, same sizes; the peak during a regrow is higher by at most the old capacity's buffers.
+	HIPCHK(ctx, p->keysA.reserve(ctx, cap * p->frames));
+	HIPCHK(ctx, p->keysB.reserve(ctx, cap * p->frames));
+	HIPCHK(ctx, p->valsA.reserve(ctx, cap * p->frames));
+	HIPCHK(ctx, p->valsB.reserve(ctx, cap * p->frames));
 	size_t tb = 0;
 	hipError_t e = sht_sort_pairs(nullptr, tb, p->keysA, p->keysB, p->valsA, p->valsB, cap * p->frames, p->keyBits, nullptr);
 	if (e != hipSuccess) return fail(ctx, COMPVHIP_E_HIP, "radix sort size query", e);
 	p->sortTempBytes = tb;
-	uint8_t* tmp = nullptr;
-	HIPCHK(ctx, dmalloc(ctx, &tmp, std::max<size_t>(tb, 16)));
-	p->sortTemp = tmp;
+	HIPCHK(ctx, p->sortTemp.reserve(ctx, std::max<size_t>(tb, 16)));
 	p->sortChunks = static_cast<int>((cap + kShtSortChunk - 1) / kShtSortChunk);
 	if (p->strengthBits <= kShtSortMaxStrengthBits && p->sortChunks <= kShtSortMaxChunks) {
-		HIPCHK(ctx, dmalloc(ctx, &p->chunkHist, p->frames * static_cast<size_t>(p->sortChunks) << kShtSortMaxStrengthBits));
-		HIPCHK(ctx, dmalloc(ctx, &p->strengthStart, p->frames << kShtSortMaxStrengthBits));
+		HIPCHK(ctx, p->chunkHist.reserve(ctx, p->frames * static_cast<size_t>(p->sortChunks) << kShtSortMaxStrengthBits));
+		HIPCHK(ctx, p->strengthStart.reserve(ctx, p->frames << kShtSortMaxStrengthBits));
 		p->deviceSort = true;
 	}
+	else { p->chunkHist.release(); p->strengthStart.release(); }   // grown past the device sort: its tables are of no use any more
 	p->lineCap = cap;
 	p->recentN = 0;   // totals clamped to another capacity
 	return COMPVHIP_OK;
@@ -447,14 +441,10 @@ void compvhip_ctx_destroy(compvhip_ctx* ctx)
 {
 	if (!ctx) return;
 	(void)hipSetDevice(ctx->device);
-	if (ctx->hostPlan) compvhip_plan_destroy(ctx->hostPlan);
-	ctx->dPacked.release(ctx); ctx->dHist.release(ctx); ctx->dIn.release(ctx); ctx->dOut.release(ctx); ctx->dCounts.release(ctx); ctx->dAccOut.release(ctx);
-	ctx->dSegLines.release(ctx); ctx->dSegs.release(ctx); ctx->dSegCount.release(ctx); ctx->dFits.release(ctx); ctx->dFitCount.release(ctx); ctx->dFitRefined.release(ctx);
-	ctx->dCompLabels.release(ctx); ctx->dComps.release(ctx); ctx->dCompCount.release(ctx); ctx->dFastCorners.release(ctx); ctx->dFastCount.release(ctx);
-	ctx->dOrbKeys.release(ctx); ctx->dOrbCount.release(ctx); ctx->dOrbDesc.release(ctx);
-	khtScratchFree(ctx, ctx->kht);
+	if (ctx->hostPlan) compvhip_plan_destroy(ctx->hostPlan);   // first: it counts in ctx->live
+	// the stream goes before the buffers do (by hand it went after them): every host entry point has drained it, hipStreamDestroy defers, hipFree synchronises
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-	delete ctx;
+	delete ctx;   // the staging buffers and the KHT scratch free themselves
 }
 
 const char* compvhip_last_error(const compvhip_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -542,41 +532,39 @@ int compvhip_plan_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size_t
 	p->tilesY = static_cast<int>((H + 63) / 64);
 	p->wb = p->tilesX * 16;
 	p->bitsFrameStride = static_cast<size_t>(p->wb) * H;
-	int rc = COMPVHIP_OK;
-	do {
-		if (dmalloc(ctx, &p->ebits, p->bitsFrameStride * frames) != hipSuccess) { rc = COMPVHIP_E_OUT_OF_MEMORY; break; }
-		if (dmalloc(ctx, &p->ubits, p->bitsFrameStride * frames) != hipSuccess) { rc = COMPVHIP_E_OUT_OF_MEMORY; break; }
-		// mask words past the last 496-column tile of a row are never written by the Canny kernel: they stay zero for ever
-		if (hipMemset(p->ebits, 0, sizeof(uint32_t) * p->bitsFrameStride * frames) != hipSuccess) { rc = COMPVHIP_E_HIP; break; }
-		if (hipMemset(p->ubits, 0, sizeof(uint32_t) * p->bitsFrameStride * frames) != hipSuccess) { rc = COMPVHIP_E_HIP; break; }
-		// the fills run on the null stream; the plan's kernels may be enqueued on non-blocking streams that do not wait for it
-		if (hipDeviceSynchronize() != hipSuccess) { rc = COMPVHIP_E_HIP; break; }
-		{
-			p->voteTiles = true;
-			size_t R = 0, T = 0; float step = 0.f;
-			if (p->voteTiles && shtDims(W, H, thetaDeg, &R, &T, &step) == COMPVHIP_OK && T >= 5) {
-				std::vector<int32_t> sq, cq;
-				shtTables(thetaDeg, T, sq, cq);
-				if (!planVoteTiles(W, H, frames, sq, cq, p->vt, p->vtKt, p->vtRowBase)) p->voteTiles = false;
-			}
-			else p->voteTiles = false;
-			p->lineBlocks = p->voteTiles ? sht_lines_blocks(static_cast<int>(R)) : 0;
-			p->nCounts = (2 + static_cast<size_t>(p->voteTiles ? p->vt.tiles : 0) + static_cast<size_t>(p->lineBlocks)) * frames + (frames + 1) * kFrameSlot;
+	// one way out of a failure: the half-built plan is deleted, its buffers free themselves
+	auto failed = [&](int rc) { compvhip_plan_destroy(p); return fail(ctx, rc, "plan allocation"); };
+	if (p->ebits.reserve(ctx, p->bitsFrameStride * frames) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	if (p->ubits.reserve(ctx, p->bitsFrameStride * frames) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	// mask words past the last 496-column tile of a row are never written by the Canny kernel: they stay zero for ever
+	if (hipMemset(p->ebits, 0, sizeof(uint32_t) * p->bitsFrameStride * frames) != hipSuccess) return failed(COMPVHIP_E_HIP);
+	if (hipMemset(p->ubits, 0, sizeof(uint32_t) * p->bitsFrameStride * frames) != hipSuccess) return failed(COMPVHIP_E_HIP);
+	// the fills run on the null stream; the plan's kernels may be enqueued on non-blocking streams that do not wait for it
+	if (hipDeviceSynchronize() != hipSuccess) return failed(COMPVHIP_E_HIP);
+	{
+		p->voteTiles = true;
+		size_t R = 0, T = 0; float step = 0.f;
+		if (p->voteTiles && shtDims(W, H, thetaDeg, &R, &T, &step) == COMPVHIP_OK && T >= 5) {
+			std::vector<int32_t> sq, cq;
+			shtTables(thetaDeg, T, sq, cq);
+			if (!planVoteTiles(W, H, frames, sq, cq, p->vt, p->vtKt, p->vtRowBase)) p->voteTiles = false;
 		}
-		if (dmalloc(ctx, &p->counters, p->nCounts + kMaxRounds) != hipSuccess) { rc = COMPVHIP_E_OUT_OF_MEMORY; break; }
-		p->edgeCounts = p->counters; p->lineCounts = p->counters + frames; p->tileCounts = p->counters + 2 * frames; p->blockCounts = p->counters + (2 + static_cast<size_t>(p->voteTiles ? p->vt.tiles : 0)) * frames; p->flags = p->counters + p->nCounts;
-		p->frameTotals = p->blockCounts + static_cast<size_t>(p->lineBlocks) * frames; p->lineTotal = reinterpret_cast<unsigned int*>(p->frameTotals + frames * kFrameSlot);
-		if (const char* e = getenv("COMPVHIP_RESOLVE_WRAP")) { const int v = atoi(e); if (v >= 8 && v <= kMaxRounds && (v & 3) == 0) p->maxRounds = v; }
-		if (hipMemset(p->counters, 0, sizeof(int) * (p->nCounts + kMaxRounds)) != hipSuccess) { rc = COMPVHIP_E_HIP; break; }
-		if (dmalloc(ctx, &p->thrDev, frames) != hipSuccess) { rc = COMPVHIP_E_OUT_OF_MEMORY; break; }
-		if (dmalloc(ctx, &p->dirty, canny_resolve_dirty_bytes(static_cast<int>(H), p->wb, static_cast<int>(frames))) != hipSuccess) { rc = COMPVHIP_E_OUT_OF_MEMORY; break; }
-		if (dmalloc(ctx, &p->sums, frames * kFrameSlot) != hipSuccess) { rc = COMPVHIP_E_OUT_OF_MEMORY; break; }
-		if (hipHostMalloc(reinterpret_cast<void**>(&p->hFlags), sizeof(int) * 2 * (kAsyncDepth + 1)) != hipSuccess) { rc = COMPVHIP_E_OUT_OF_MEMORY; break; }
-		p->hTotals = reinterpret_cast<unsigned int*>(p->hFlags + kAsyncDepth + 1);
-		if (hipHostMalloc(reinterpret_cast<void**>(&p->hRounds), sizeof(int) * (kFrameSlot + 4) * kAsyncDepth, hipHostMallocMapped) != hipSuccess) { rc = COMPVHIP_E_OUT_OF_MEMORY; break; }
-		if (hipHostGetDevicePointer(reinterpret_cast<void**>(&p->hRoundsDev), p->hRounds, 0) != hipSuccess) { rc = COMPVHIP_E_HIP; break; }
-	} while (0);
-	if (rc) { compvhip_plan_destroy(p); return fail(ctx, rc, "plan allocation"); }
+		else p->voteTiles = false;
+		p->lineBlocks = p->voteTiles ? sht_lines_blocks(static_cast<int>(R)) : 0;
+		p->nCounts = (2 + static_cast<size_t>(p->voteTiles ? p->vt.tiles : 0) + static_cast<size_t>(p->lineBlocks)) * frames + (frames + 1) * kFrameSlot;
+	}
+	if (p->counters.reserve(ctx, p->nCounts + kMaxRounds) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	p->edgeCounts = p->counters; p->lineCounts = p->counters + frames; p->tileCounts = p->counters + 2 * frames; p->blockCounts = p->counters + (2 + static_cast<size_t>(p->voteTiles ? p->vt.tiles : 0)) * frames; p->flags = p->counters + p->nCounts;
+	p->frameTotals = p->blockCounts + static_cast<size_t>(p->lineBlocks) * frames; p->lineTotal = reinterpret_cast<unsigned int*>(p->frameTotals + frames * kFrameSlot);
+	if (const char* e = getenv("COMPVHIP_RESOLVE_WRAP")) { const int v = atoi(e); if (v >= 8 && v <= kMaxRounds && (v & 3) == 0) p->maxRounds = v; }
+	if (hipMemset(p->counters, 0, sizeof(int) * (p->nCounts + kMaxRounds)) != hipSuccess) return failed(COMPVHIP_E_HIP);
+	if (p->thrDev.reserve(ctx, frames) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	if (p->dirty.reserve(ctx, canny_resolve_dirty_bytes(static_cast<int>(H), p->wb, static_cast<int>(frames))) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	if (p->sums.reserve(ctx, frames * kFrameSlot) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	if (p->hFlags.reserve(2 * (kAsyncDepth + 1)) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	p->hTotals = reinterpret_cast<unsigned int*>(p->hFlags + kAsyncDepth + 1);
+	if (p->hRounds.reserve((kFrameSlot + 4) * kAsyncDepth, hipHostMallocMapped) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	if (hipHostGetDevicePointer(reinterpret_cast<void**>(&p->hRoundsDev), p->hRounds, 0) != hipSuccess) return failed(COMPVHIP_E_HIP);
 	*out = p;
 	return COMPVHIP_OK;
 }
@@ -586,26 +574,9 @@ void compvhip_plan_destroy(compvhip_plan* p)
 	if (!p) return;
 	compvhip_ctx* ctx = p->ctx;
 	(void)hipSetDevice(ctx->device);
-	timelineClear(p);
-	for (hipEvent_t e : p->eventPool) (void)hipEventDestroy(e);
+	timingTeardown(p);
 	for (auto& stp : p->steps) if (stp.done) (void)hipEventDestroy(stp.done);
-	dfree(ctx, p->dirty);
-	dfree(ctx, p->ebits); dfree(ctx, p->ubits); dfree(ctx, p->counters); dfree(ctx, p->thrDev); dfree(ctx, p->sums); dfree(ctx, p->tmpOut);
-	if (p->hFlags) (void)hipHostFree(p->hFlags);
-	if (p->hRounds) (void)hipHostFree(p->hRounds);
-	dfree(ctx, p->hist); dfree(ctx, p->otsu); dfree(ctx, p->blurTmp); dfree(ctx, p->grayTmp);
-	dfree(ctx, p->morphTmp);
-	dfree(ctx, p->fastWork); dfree(ctx, p->fastScores);
-	p->orbIndex.release(ctx); dfree(ctx, p->orbBlur);
-	for (KhtBatchState* b : p->khtBatch) khtBatchFree(ctx, b);
-	p->khtBatch.clear();
-	dfree(ctx, p->cosT); dfree(ctx, p->invSinT);
-	dfree(ctx, p->dKt); dfree(ctx, p->dRowBase); dfree(ctx, p->partLo); dfree(ctx, p->partHi); dfree(ctx, p->colFlag);
-	dfree(ctx, p->sinQ); dfree(ctx, p->cosQ); dfree(ctx, p->edges); dfree(ctx, p->acc);
-	dfree(ctx, p->keysA); dfree(ctx, p->keysB); dfree(ctx, p->valsA); dfree(ctx, p->valsB); dfree(ctx, p->nmsFlags); dfree(ctx, p->chunkHist); dfree(ctx, p->strengthStart);
-	dfree(ctx, p->nmsRange); dfree(ctx, p->reach); dfree(ctx, p->sortTemp); p->segPerLine.release(ctx);
-	dfree(ctx, p->compRows); dfree(ctx, p->compBits); dfree(ctx, p->compParent);
-	delete p;
+	delete p;   // every buffer frees itself; the batched KHT's states destroy their streams and events
 }
 
 int compvhip_plan_set_timing(compvhip_plan* p, int enabled)
@@ -618,14 +589,7 @@ int compvhip_plan_set_timing(compvhip_plan* p, int enabled)
 int compvhip_plan_get_timing(compvhip_plan* p, const char** names, float* ms, int cap)
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
-	(void)hipSetDevice(p->ctx->device);
-	if (!p->timeline.empty()) {
-		for (auto& t : p->timeline) (void)hipEventSynchronize(t.b);
-		timelineCollect(p);
-	}
-	const int n = std::min<int>(cap, static_cast<int>(p->timingMs.size()));
-	for (int i = 0; i < n; ++i) { if (names) names[i] = p->timingNames[i].c_str(); if (ms) ms[i] = p->timingMs[i]; }
-	return n;
+	return timingRead(p, p->ctx->device, names, ms, cap);
 }
 
 // The tile kernel writes E (edges so far), U (weak, unresolved) and the bytes of E; the resolve rounds finish the hysteresis on the
@@ -645,7 +609,7 @@ static int planCannyImpl(compvhip_plan* p, const uint8_t* d_in, float tLow, floa
 	const size_t bytes = p->S * p->H * p->frames;
 	const bool alias = (d_in < d_edges + bytes) && (d_edges < d_in + bytes);
 	if (alias) {
-		if (!p->tmpOut) HIPCHK(ctx, dmalloc(ctx, &p->tmpOut, bytes));
+		HIPCHK(ctx, p->tmpOut.reserve(ctx, bytes));
 		out = p->tmpOut;
 	}
 	p->patchOut = out;
@@ -734,7 +698,7 @@ int compvhip_plan_convlt1_fixedpoint(compvhip_plan* p, const uint8_t* d_in, cons
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const size_t span = p->S * p->H * p->frames;
 	const bool alias = (d_in < d_out + span) && (d_out < d_in + span);
-	if (alias && !p->blurTmp) HIPCHK(ctx, dmalloc(ctx, &p->blurTmp, span)); // only the in-place call needs the two-pass path
+	if (alias) HIPCHK(ctx, p->blurTmp.reserve(ctx, span)); // only the in-place call needs the two-pass path
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
 	Stamp s(p, st, "convlt_fxp_kernels");
@@ -863,7 +827,7 @@ static int enqueueStep(compvhip_plan* p, const StepParams& sp, hipStream_t st, b
 		// samples/hough_lines/main.cxx:102: CompVImage::convertGrayscale in front of everything else
 		uint8_t* gray = sp.d_gray;
 		if (!gray) {
-			if (!p->grayTmp) HIPCHK(ctx, dmalloc(ctx, &p->grayTmp, p->S * p->H * p->frames));
+			HIPCHK(ctx, p->grayTmp.reserve(ctx, p->S * p->H * p->frames));
 			gray = p->grayTmp;
 		}
 		if (p->timing && clearTimeline) timelineClear(p);

@@ -42,8 +42,7 @@ int compvhip_plan_houghsht_segments(compvhip_plan* p, const uint8_t* d_edges, co
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
-	for (const auto& stp : p->steps)
-		if (stp.used) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the lines)");
+	if (stepsInFlight(p)) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the lines)");
 	if (!segCap) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "segCap must be > 0");
 	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
 	return segmentsImpl(p, d_edges, p->S, d_lines, d_counts, lineCap, maxLines, minLength, maxGap, d_segs, segCap, d_segCounts, static_cast<hipStream_t>(stream));
@@ -82,8 +81,7 @@ int compvhip_plan_houghsht_fit(compvhip_plan* p, const uint8_t* d_edges, const c
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
-	for (const auto& stp : p->steps)
-		if (stp.used) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the lines)");
+	if (stepsInFlight(p)) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the lines)");
 	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
 	return fitImpl(p, d_edges, p->S, d_lines, d_counts, lineCap, maxLines, halfWidth, d_segs, d_segCounts, segCap, d_fits, fitCap, d_fitCounts, d_refined,
 	               static_cast<hipStream_t>(stream));
@@ -102,9 +100,9 @@ int compvhip_api::componentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_
 	if (p->W * p->H > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "W * H beyond 2^31");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const size_t frames = p->frames;
-	if (!p->compRows) HIPCHK(ctx, dmalloc(ctx, &p->compRows, p->H * frames));
-	if (d_edges && !p->compBits) HIPCHK(ctx, dmalloc(ctx, &p->compBits, p->bitsFrameStride * frames));
-	if (!d_labels && !p->compParent) HIPCHK(ctx, dmalloc(ctx, &p->compParent, p->W * p->H * frames));
+	HIPCHK(ctx, p->compRows.reserve(ctx, p->H * frames));
+	if (d_edges) HIPCHK(ctx, p->compBits.reserve(ctx, p->bitsFrameStride * frames));
+	if (!d_labels) HIPCHK(ctx, p->compParent.reserve(ctx, p->W * p->H * frames));
 	if (p->timing) timelineClear(p);
 	const int nf = static_cast<int>(frames);
 	if (d_edges) {
@@ -136,8 +134,7 @@ int compvhip_plan_components(compvhip_plan* p, const uint8_t* d_edges, int conne
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
-	for (const auto& stp : p->steps)
-		if (stp.used) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the masks)");
+	if (stepsInFlight(p)) return fail(ctx, COMPVHIP_E_INVALID_STATE, "asynchronous steps in flight: call compvhip_plan_wait first (a replayed step rewrites the masks)");
 	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "no edge masks of a Canny run on this plan: pass d_edges");
 	if (labelStride > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "labelStride beyond 2^31");
 	return componentsImpl(p, d_edges, p->S, connectivity, minPixels, d_labels, labelStride, d_comps, compCap, d_compCounts, static_cast<hipStream_t>(stream));
@@ -191,7 +188,7 @@ int compvhip_plan_threshold_adaptive(compvhip_plan* p, const uint8_t* d_in, size
 	const size_t span = p->S * p->H * p->frames;
 	const bool alias = planeOverlap(p, d_in, d_out);
 	if (alias && d_in != d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output overlap without being the same buffer");
-	if (alias && !p->morphTmp) HIPCHK(ctx, dmalloc(ctx, &p->morphTmp, span)); // a tile reads the halo its neighbours write: in place goes through the plan's plane
+	if (alias) HIPCHK(ctx, p->morphTmp.reserve(ctx, span)); // a tile reads the halo its neighbours write: in place goes through the plan's plane
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
 	AdaptArgs a;
@@ -281,7 +278,7 @@ int compvhip_plan_morph_ex(compvhip_plan* p, const uint8_t* d_in, const uint8_t*
 	if (planeOverlap(p, d_in, d_out)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap"); // compv_math_morph.cxx:140-145 reallocates
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const bool two = op == COMPVHIP_MORPH_OP_OPEN || op == COMPVHIP_MORPH_OP_CLOSE;
-	if (two && !p->morphTmp) HIPCHK(ctx, dmalloc(ctx, &p->morphTmp, p->S * p->H * p->frames));
+	if (two) HIPCHK(ctx, p->morphTmp.reserve(ctx, p->S * p->H * p->frames));
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
 	a.frameStride = p->S * p->H; a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S);
@@ -310,6 +307,21 @@ int compvhip_api::checkFast(compvhip_ctx* ctx, size_t W, size_t H, int fastType)
 	return COMPVHIP_OK;
 }
 
+// ints of FAST's scratch for `frames` planes of H rows: [frames][H] corners per row, [frames][256] score histogram, [frames] cut level, [frames][H] row scan
+static size_t fastWorkInts(size_t frames, size_t H) { return frames * (2 * H + 257); }
+
+// the arguments of launch_fast for `frames` planes [H][S] on `work` (fastWorkInts(frames, H) ints at least); enqueues the fill of the sums in it
+static hipError_t fastArgs(FastArgs& a, const uint8_t* plane, size_t W, size_t H, size_t S, size_t frames, int threshold, int fastType, int nonmax, int maxFeatures,
+                           int* work, uint8_t* scores, compvhip_corner* corners, size_t cornerCap, int32_t* counts, hipStream_t st)
+{
+	a.in = plane; a.scores = scores; a.frameStride = S * H;
+	a.W = static_cast<int>(W); a.H = static_cast<int>(H); a.S = static_cast<int>(S);
+	a.t = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold); a.N = fastType; a.nonmax = nonmax != 0; a.maxFeatures = maxFeatures;   // compv_core_feature_fast_dete.cxx:135
+	a.rowCounts = work; a.hist = a.rowCounts + frames * H; a.minScore = a.hist + frames * 256; a.rowOffsets = a.minScore + frames;
+	a.corners = corners; a.cornerCap = cornerCap; a.counts = counts;
+	return hipMemsetAsync(a.rowCounts, 0, frames * (H + 256) * sizeof(int), st);   // the row counts and the histogram are sums
+}
+
 int compvhip_plan_fast(compvhip_plan* p, const uint8_t* d_gray, int threshold, int fastType, int nonmax, int maxFeatures, uint8_t* d_scores,
                        compvhip_corner* d_corners, size_t cornerCap, int32_t* d_counts, void* stream)
 {
@@ -318,22 +330,17 @@ int compvhip_plan_fast(compvhip_plan* p, const uint8_t* d_gray, int threshold, i
 	if (!d_gray || !d_counts || (cornerCap && !d_corners)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame / count / corner pointer");
 	int rc = checkFast(ctx, p->W, p->H, fastType);
 	if (rc) return rc;
-	if ((reinterpret_cast<uintptr_t>(d_gray) & 7) || (reinterpret_cast<uintptr_t>(d_scores) & 7)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames must be 8-byte aligned");
-	if ((reinterpret_cast<uintptr_t>(d_corners) & 3) || (reinterpret_cast<uintptr_t>(d_counts) & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "records and counts must be 4-byte aligned");
+	if (misaligned(7, d_gray, d_scores)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames must be 8-byte aligned");
+	if (misaligned(3, d_corners, d_counts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "records and counts must be 4-byte aligned");
 	if (d_scores && planeOverlap(p, d_gray, d_scores)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frame and score map must not overlap");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t F = p->frames, H = p->H, work = F * (2 * H + 257);
-	if (!p->fastWork) HIPCHK(ctx, dmalloc(ctx, &p->fastWork, work));
-	if (!d_scores && !p->fastScores) HIPCHK(ctx, dmalloc(ctx, &p->fastScores, p->S * H * F));
+	const size_t F = p->frames, H = p->H;
+	HIPCHK(ctx, p->fastWork.reserve(ctx, fastWorkInts(F, H)));
+	if (!d_scores) HIPCHK(ctx, p->fastScores.reserve(ctx, p->S * H * F));
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
 	FastArgs a;
-	a.in = d_gray; a.scores = d_scores ? d_scores : p->fastScores; a.frameStride = p->S * H;
-	a.W = static_cast<int>(p->W); a.H = static_cast<int>(H); a.S = static_cast<int>(p->S);
-	a.t = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold); a.N = fastType; a.nonmax = nonmax != 0; a.maxFeatures = maxFeatures;   // :135
-	a.rowCounts = p->fastWork; a.hist = a.rowCounts + F * H; a.minScore = a.hist + F * 256; a.rowOffsets = a.minScore + F;
-	a.corners = d_corners; a.cornerCap = cornerCap; a.counts = d_counts;
-	HIPCHK(ctx, hipMemsetAsync(a.rowCounts, 0, F * (H + 256) * sizeof(int), st));   // the row counts and the histogram are sums
+	HIPCHK(ctx, fastArgs(a, d_gray, p->W, H, p->S, F, threshold, fastType, nonmax, maxFeatures, p->fastWork, d_scores ? d_scores : p->fastScores, d_corners, cornerCap, d_counts, st));
 	{ Stamp s(p, st, "fast_score_kernel"); HIPCHK(ctx, launch_fast(a, static_cast<int>(F), 0, st)); }
 	{ Stamp s(p, st, "fast_list_kernels"); HIPCHK(ctx, launch_fast(a, static_cast<int>(F), 1, st)); }   // cut level, row recount, scan, emit
 	return COMPVHIP_OK;
@@ -356,8 +363,7 @@ int compvhip_plan_orb_keypoints(compvhip_plan* p, const uint8_t* d_gray, const c
 	int rc = checkOrb(ctx, p->W, p->H, scale);
 	if (rc) return rc;
 	if (cornerCap > static_cast<size_t>(INT32_MAX) || keyCap > static_cast<size_t>(INT32_MAX) || p->frames > 65535) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity beyond 2^31 or more than 65535 frames");
-	if ((reinterpret_cast<uintptr_t>(d_corners) & 3) || (reinterpret_cast<uintptr_t>(d_cornerCounts) & 3) || (reinterpret_cast<uintptr_t>(d_keypoints) & 3) ||
-	    (reinterpret_cast<uintptr_t>(d_keyCounts) & 3) || (reinterpret_cast<uintptr_t>(d_moments) & 3) || (reinterpret_cast<uintptr_t>(d_gray) & 3))
+	if (misaligned(3, d_corners, d_cornerCounts, d_keypoints, d_keyCounts, d_moments, d_gray))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames, records, counts and moments must be 4-byte aligned");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const int frames = static_cast<int>(p->frames);
@@ -383,7 +389,7 @@ int compvhip_plan_orb_describe(compvhip_plan* p, const uint8_t* d_gray, const co
 	if (rc) return rc;
 	if (descStride < 32 || (descStride & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descStride below 32 or no multiple of 4");
 	if (keyCap > static_cast<size_t>(INT32_MAX) || p->frames > 65535) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity beyond 2^31 or more than 65535 frames");
-	if ((reinterpret_cast<uintptr_t>(d_gray) & 3) || (reinterpret_cast<uintptr_t>(d_keypoints) & 3) || (reinterpret_cast<uintptr_t>(d_keyCounts) & 3) || (reinterpret_cast<uintptr_t>(d_desc) & 3))
+	if (misaligned(3, d_gray, d_keypoints, d_keyCounts, d_desc))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames, records, counts and descriptors must be 4-byte aligned");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const int frames = static_cast<int>(p->frames);
@@ -393,7 +399,7 @@ int compvhip_plan_orb_describe(compvhip_plan* p, const uint8_t* d_gray, const co
 		p->orbBriefLds = e ? !strcmp(e, "lds") : kOrbBriefLdsDefault;
 		p->orbKernReady = true;
 	}
-	if (blur && !p->orbBlur) HIPCHK(ctx, dmalloc(ctx, &p->orbBlur, p->S * p->H * p->frames));
+	if (blur) HIPCHK(ctx, p->orbBlur.reserve(ctx, p->S * p->H * p->frames));
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
 	if (blur) {   // out of place: the fused kernel, no intermediate
@@ -472,13 +478,13 @@ int compvhip_orbpyr_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size
 		y->active = l + 1;
 		if (l) planeBytes += alignUp(L.S * L.H * frames, 256);
 	}
-	if (compvhip_gauss_kernel_fixedpoint(5, 2.0f, y->kern) != COMPVHIP_OK) { delete y; return fail(ctx, COMPVHIP_E_INVALID_STATE, "Gaussian kernel"); }   // compv_core_feature_orb_desc.cxx:119-120
+	if (compvhip_gauss_kernel_fixedpoint(5, 2.0f, y->kern) != COMPVHIP_OK) { compvhip_orbpyr_destroy(y); return fail(ctx, COMPVHIP_E_INVALID_STATE, "Gaussian kernel"); }   // compv_core_feature_orb_desc.cxx:119-120
 	const char* e = getenv("COMPVHIP_ORB_BRIEF");   // the lab knob of compvhip_plan_orb_describe
 	if (e) y->briefLds = !strcmp(e, "lds");
 	const size_t L = static_cast<size_t>(opts->levels);
-	if (dmalloc(ctx, &y->planes, planeBytes) != hipSuccess || dmalloc(ctx, &y->corners, frames * cornerCap) != hipSuccess ||
-	    dmalloc(ctx, &y->fastWork, frames * (2 * H + 257)) != hipSuccess || dmalloc(ctx, &y->fastScores, S * H * frames) != hipSuccess ||
-	    dmalloc(ctx, &y->counts, (3 * L + 1) * frames) != hipSuccess) {
+	if (y->planes.reserve(ctx, planeBytes) != hipSuccess || y->corners.reserve(ctx, frames * cornerCap) != hipSuccess ||
+	    y->fastWork.reserve(ctx, fastWorkInts(frames, H)) != hipSuccess || y->fastScores.reserve(ctx, S * H * frames) != hipSuccess ||
+	    y->counts.reserve(ctx, (3 * L + 1) * frames) != hipSuccess) {
 		compvhip_orbpyr_destroy(y);
 		return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "pyramid planes / scratch");
 	}
@@ -491,12 +497,8 @@ int compvhip_orbpyr_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size
 void compvhip_orbpyr_destroy(compvhip_orbpyr* y)
 {
 	if (!y) return;
-	compvhip_ctx* ctx = y->ctx;
-	(void)hipSetDevice(ctx->device);
-	timelineClear(y);
-	for (hipEvent_t e : y->eventPool) (void)hipEventDestroy(e);
-	dfree(ctx, y->planes); dfree(ctx, y->blurredAll); dfree(ctx, y->corners); dfree(ctx, y->fastWork); dfree(ctx, y->fastScores); dfree(ctx, y->counts);
-	y->index.release(ctx);
+	(void)hipSetDevice(y->ctx->device);
+	timingTeardown(y);
 	delete y;
 }
 
@@ -510,14 +512,7 @@ int compvhip_orbpyr_set_timing(compvhip_orbpyr* y, int enabled)
 int compvhip_orbpyr_get_timing(compvhip_orbpyr* y, const char** names, float* ms, int cap)
 {
 	if (!y) return COMPVHIP_E_INVALID_PARAMETER;
-	(void)hipSetDevice(y->ctx->device);
-	if (!y->timeline.empty()) {
-		for (auto& t : y->timeline) (void)hipEventSynchronize(t.b);
-		timelineCollect(y);
-	}
-	const int n = std::min<int>(cap, static_cast<int>(y->timingMs.size()));
-	for (int i = 0; i < n; ++i) { if (names) names[i] = y->timingNames[i].c_str(); if (ms) ms[i] = y->timingMs[i]; }
-	return n;
+	return timingRead(y, y->ctx->device, names, ms, cap);
 }
 
 int compvhip_orbpyr_geometry(const compvhip_orbpyr* y, int level, size_t* W, size_t* H, size_t* S, float* scale, int* quota)
@@ -547,7 +542,7 @@ namespace {
 int checkPyrFrame(compvhip_orbpyr* y, const uint8_t* d_gray)
 {
 	if (!d_gray) return fail(y->ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
-	if (reinterpret_cast<uintptr_t>(d_gray) & 7) return fail(y->ctx, COMPVHIP_E_INVALID_PARAMETER, "frames must be 8-byte aligned");
+	if (misaligned(7, d_gray)) return fail(y->ctx, COMPVHIP_E_INVALID_PARAMETER, "frames must be 8-byte aligned");
 	return COMPVHIP_OK;
 }
 
@@ -579,8 +574,7 @@ int compvhip_orbpyr_detect(compvhip_orbpyr* y, const uint8_t* d_gray, compvhip_k
 	int rc = checkPyrFrame(y, d_gray);
 	if (rc) return rc;
 	if (!d_keyCounts || (keyCap && !d_keypoints) || keyCap > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null count / keypoint pointer or keyCap beyond 2^31");
-	if ((reinterpret_cast<uintptr_t>(d_keypoints) & 3) || (reinterpret_cast<uintptr_t>(d_keyCounts) & 3) || (reinterpret_cast<uintptr_t>(d_levelCounts) & 3) ||
-	    (reinterpret_cast<uintptr_t>(d_levelCorners) & 3))
+	if (misaligned(3, d_keypoints, d_keyCounts, d_levelCounts, d_levelCorners))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "records and counts must be 4-byte aligned");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	HIPCHK(ctx, y->index.reserve(ctx, y->frames * keyCap));
@@ -592,17 +586,12 @@ int compvhip_orbpyr_detect(compvhip_orbpyr* y, const uint8_t* d_gray, compvhip_k
 	HIPCHK(ctx, hipMemsetAsync(totals, 0, F * sizeof(int32_t), st));          // nothing in front of level 0
 	rc = pyrScale(y, d_gray, st);
 	if (rc) return rc;
-	const int t = y->opts.threshold;
 	for (int l = 0; l < y->active; ++l) {
 		const compvhip_orbpyr::Level& L = y->lv[l];
 		const uint8_t* plane = l ? L.plane : d_gray;
 		FastArgs a;
-		a.in = plane; a.scores = y->fastScores; a.frameStride = L.S * L.H;
-		a.W = static_cast<int>(L.W); a.H = static_cast<int>(L.H); a.S = static_cast<int>(L.S);
-		a.t = t < 0 ? 0 : (t > 255 ? 255 : t); a.N = y->opts.fastType; a.nonmax = y->opts.nonmax != 0; a.maxFeatures = y->opts.maxFeatures > 0 ? L.quota : -1;
-		a.rowCounts = y->fastWork; a.hist = a.rowCounts + F * L.H; a.minScore = a.hist + F * 256; a.rowOffsets = a.minScore + F;
-		a.corners = y->corners; a.cornerCap = y->cornerCap; a.counts = lvCorners + l * F;
-		HIPCHK(ctx, hipMemsetAsync(a.rowCounts, 0, F * (L.H + 256) * sizeof(int), st));   // the row counts and the histogram are sums
+		HIPCHK(ctx, fastArgs(a, plane, L.W, L.H, L.S, F, y->opts.threshold, y->opts.fastType, y->opts.nonmax, y->opts.maxFeatures > 0 ? L.quota : -1, y->fastWork, y->fastScores,
+		                     y->corners, y->cornerCap, lvCorners + l * F, st));
 		{ Stamp s(y, st, "fast_score_kernel"); HIPCHK(ctx, launch_fast(a, frames, 0, st)); }
 		{ Stamp s(y, st, "fast_list_kernels"); HIPCHK(ctx, launch_fast(a, frames, 1, st)); }
 		OrbKeyArgs k;
@@ -629,7 +618,7 @@ int compvhip_orbpyr_describe(compvhip_orbpyr* y, const uint8_t* d_gray, int reus
 	if (rc) return rc;
 	if (!d_keypoints || !d_keyCounts || !d_desc || !keyCap || keyCap > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null keypoint / count / descriptor pointer, keyCap == 0 or beyond 2^31");
 	if (descStride < 32 || (descStride & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descStride below 32 or no multiple of 4");
-	if ((reinterpret_cast<uintptr_t>(d_keypoints) & 3) || (reinterpret_cast<uintptr_t>(d_keyCounts) & 3) || (reinterpret_cast<uintptr_t>(d_desc) & 3))
+	if (misaligned(3, d_keypoints, d_keyCounts, d_desc))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "records, counts and descriptors must be 4-byte aligned");
 	if (reusePlanes && y->planesOf != d_gray) return fail(ctx, COMPVHIP_E_INVALID_STATE, "reusePlanes: no planes of a compvhip_orbpyr_detect call on this d_gray");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -638,7 +627,7 @@ int compvhip_orbpyr_describe(compvhip_orbpyr* y, const uint8_t* d_gray, int reus
 	if (!y->blurredAll) {
 		size_t bytes = 0;
 		for (int l = 0; l < y->active; ++l) bytes += alignUp(y->lv[l].S * y->lv[l].H * F, 256);
-		HIPCHK(ctx, dmalloc(ctx, &y->blurredAll, bytes));
+		HIPCHK(ctx, y->blurredAll.reserve(ctx, bytes));
 		size_t off = 0;
 		for (int l = 0; l < y->active; ++l) { y->lv[l].blurred = y->blurredAll + off; off += alignUp(y->lv[l].S * y->lv[l].H * F, 256); }
 	}
@@ -673,7 +662,7 @@ int checkMatchBuffers(compvhip_matcher* m, const uint8_t* d_query, size_t queryS
 	if (!d_query || !d_train) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null descriptor pointer");
 	if (queryStride < bytes || trainStride < bytes || (queryStride & 3) || (trainStride & 3) || queryStride > 65536 || trainStride > 65536)
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descriptor stride below descBytes, above 65536 or no multiple of 4");
-	if ((reinterpret_cast<uintptr_t>(d_query) & 3) || (reinterpret_cast<uintptr_t>(d_train) & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descriptors must be 4-byte aligned");
+	if (misaligned(3, d_query, d_train)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descriptors must be 4-byte aligned");
 	return COMPVHIP_OK;
 }
 } // namespace
@@ -704,7 +693,7 @@ int compvhip_matcher_create(compvhip_ctx* ctx, size_t descBytes, size_t queryCap
 	m->pairs = static_cast<int>(pairs); m->knn = knn;
 	const size_t tSlices = (trainCap + kMatchTrainSlice - 1) / kMatchTrainSlice, qSlices = (queryCap + kMatchTrainSlice - 1) / kMatchTrainSlice;
 	const size_t words = pairs * std::max(tSlices * static_cast<size_t>(knn) * queryCap, qSlices * trainCap);
-	if (dmalloc(ctx, &m->partial, words) != hipSuccess || dmalloc(ctx, &m->reverse, pairs * trainCap) != hipSuccess) {
+	if (m->partial.reserve(ctx, words) != hipSuccess || m->reverse.reserve(ctx, pairs * trainCap) != hipSuccess) {
 		compvhip_matcher_destroy(m);
 		return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "matcher scratch");
 	}
@@ -715,11 +704,8 @@ int compvhip_matcher_create(compvhip_ctx* ctx, size_t descBytes, size_t queryCap
 void compvhip_matcher_destroy(compvhip_matcher* m)
 {
 	if (!m) return;
-	compvhip_ctx* ctx = m->ctx;
-	(void)hipSetDevice(ctx->device);
-	timelineClear(m);
-	for (hipEvent_t e : m->eventPool) (void)hipEventDestroy(e);
-	dfree(ctx, m->partial); dfree(ctx, m->reverse);
+	(void)hipSetDevice(m->ctx->device);
+	timingTeardown(m);
 	delete m;
 }
 
@@ -733,14 +719,7 @@ int compvhip_matcher_set_timing(compvhip_matcher* m, int enabled)
 int compvhip_matcher_get_timing(compvhip_matcher* m, const char** names, float* ms, int cap)
 {
 	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
-	(void)hipSetDevice(m->ctx->device);
-	if (!m->timeline.empty()) {
-		for (auto& t : m->timeline) (void)hipEventSynchronize(t.b);
-		timelineCollect(m);
-	}
-	const int n = std::min<int>(cap, static_cast<int>(m->timingMs.size()));
-	for (int i = 0; i < n; ++i) { if (names) names[i] = m->timingNames[i].c_str(); if (ms) ms[i] = m->timingMs[i]; }
-	return n;
+	return timingRead(m, m->ctx->device, names, ms, cap);
 }
 
 int compvhip_matcher_knn(compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
@@ -750,8 +729,8 @@ int compvhip_matcher_knn(compvhip_matcher* m, const uint8_t* d_query, size_t que
 	compvhip_ctx* ctx = m->ctx;
 	int rc = checkMatchBuffers(m, d_query, queryStride, d_train, trainStride);
 	if (rc) return rc;
-	if (!d_matches || (reinterpret_cast<uintptr_t>(d_matches) & 15)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records: null or not 16-byte aligned");
-	if ((reinterpret_cast<uintptr_t>(d_queryCounts) & 3) || (reinterpret_cast<uintptr_t>(d_trainCounts) & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "counts must be 4-byte aligned");
+	if (!d_matches || misaligned(15, d_matches)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records: null or not 16-byte aligned");
+	if (misaligned(3, d_queryCounts, d_trainCounts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "counts must be 4-byte aligned");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (m->timing) timelineClear(m);
@@ -769,8 +748,8 @@ int compvhip_matcher_good(compvhip_matcher* m, const compvhip_match* d_matches, 
 	compvhip_ctx* ctx = m->ctx;
 	if (!opts || !d_matches || !d_goodCounts || (goodCap && !d_good)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null options / match / count / good pointer");
 	if (opts->ratio > 0.0 && m->knn < 2) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "the ratio test needs knn >= 2");
-	if ((reinterpret_cast<uintptr_t>(d_matches) & 15) || (reinterpret_cast<uintptr_t>(d_good) & 15)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records must be 16-byte aligned");
-	if ((reinterpret_cast<uintptr_t>(d_queryCounts) & 3) || (reinterpret_cast<uintptr_t>(d_trainCounts) & 3) || (reinterpret_cast<uintptr_t>(d_goodCounts) & 3))
+	if (misaligned(15, d_matches, d_good)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records must be 16-byte aligned");
+	if (misaligned(3, d_queryCounts, d_trainCounts, d_goodCounts))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "counts must be 4-byte aligned");
 	if (opts->crossCheck) {
 		int rc = checkMatchBuffers(m, d_query, queryStride, d_train, trainStride);

@@ -167,19 +167,16 @@ static int convlt1I16(compvhip_ctx* ctx, const void* in, bool inIsU8, size_t W, 
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const size_t es = inIsU8 ? 1 : 2;
 	const size_t Sd = alignUp(W, 64);
-	uint8_t* dIn = nullptr; int16_t* dTmp = nullptr; int16_t* dOut = nullptr;
-	int rc = COMPVHIP_OK;
-	do {
-		if (dmalloc(ctx, &dIn, Sd * H * es) != hipSuccess || dmalloc(ctx, &dTmp, Sd * H) != hipSuccess || dmalloc(ctx, &dOut, Sd * H) != hipSuccess) { rc = fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "convolution buffers"); break; }
-		hipError_t e = hipMemcpy2DAsync(dIn, Sd * es, in, S * es, W * es, H, hipMemcpyHostToDevice, ctx->stream);
-		if (e == hipSuccess) e = launch_convlt_i16(dIn, inIsU8, dTmp, dOut, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), static_cast<int>(Sd), vtKern, hzKern,
-		                                           static_cast<int>(kernSize), ctx->stream);
-		if (e == hipSuccess) e = hipMemcpy2DAsync(out, So * 2, dOut, Sd * 2, W * 2, H, hipMemcpyDeviceToHost, ctx->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-		if (e != hipSuccess) rc = fail(ctx, COMPVHIP_E_HIP, "integer convolution", e);
-	} while (0);
-	dfree(ctx, dIn); dfree(ctx, dTmp); dfree(ctx, dOut);
-	return rc;
+	DevBuf<uint8_t> dIn; DevBuf<int16_t> dTmp, dOut;   // freed on the way out
+	if (dIn.reserve(ctx, Sd * H * es) != hipSuccess || dTmp.reserve(ctx, Sd * H) != hipSuccess || dOut.reserve(ctx, Sd * H) != hipSuccess)
+		return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "convolution buffers");
+	hipError_t e = hipMemcpy2DAsync(dIn, Sd * es, in, S * es, W * es, H, hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess) e = launch_convlt_i16(dIn, inIsU8, dTmp, dOut, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), static_cast<int>(Sd), vtKern, hzKern,
+	                                           static_cast<int>(kernSize), ctx->stream);
+	if (e == hipSuccess) e = hipMemcpy2DAsync(out, So * 2, dOut, Sd * 2, W * 2, H, hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e != hipSuccess) return fail(ctx, COMPVHIP_E_HIP, "integer convolution", e);
+	return COMPVHIP_OK;
 }
 
 int compvhip_convlt1_8u16s16s(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const int16_t* vtKern, const int16_t* hzKern, size_t kernSize,
@@ -548,10 +545,10 @@ int compvhip_match_hamming_u8(compvhip_ctx* ctx, const uint8_t* query, size_t Q,
 	compvhip_matcher* m = nullptr;
 	int rc = compvhip_matcher_create(ctx, S, Q, T, 1, knn, &m);
 	if (rc) return rc;
-	uint8_t* dDesc = nullptr; compvhip_match* dMatches = nullptr;
+	DevBuf<uint8_t> dDesc; DevBuf<compvhip_match> dMatches;   // freed on the way out, behind the drain of the stream below
 	const size_t nRows = std::min<size_t>(static_cast<size_t>(knn), T);
 	do {
-		if (dmalloc(ctx, &dDesc, (Q + T) * S) != hipSuccess || dmalloc(ctx, &dMatches, static_cast<size_t>(knn) * Q) != hipSuccess) { rc = fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "match staging"); break; }
+		if (dDesc.reserve(ctx, (Q + T) * S) != hipSuccess || dMatches.reserve(ctx, static_cast<size_t>(knn) * Q) != hipSuccess) { rc = fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "match staging"); break; }
 		hipError_t e = hipMemsetAsync(dDesc, 0, (Q + T) * S, ctx->stream);          // the zero bytes that pad a row to a dword multiple
 		if (e == hipSuccess) e = hipMemcpy2DAsync(dDesc, S, query, queryStride, cols, Q, hipMemcpyHostToDevice, ctx->stream);
 		if (e == hipSuccess) e = hipMemcpy2DAsync(dDesc + Q * S, S, train, trainStride, cols, T, hipMemcpyHostToDevice, ctx->stream);
@@ -566,7 +563,6 @@ int compvhip_match_hamming_u8(compvhip_ctx* ctx, const uint8_t* query, size_t Q,
 		*rows = nRows;
 	} while (0);
 	(void)hipStreamSynchronize(ctx->stream);
-	dfree(ctx, dDesc); dfree(ctx, dMatches);
 	compvhip_matcher_destroy(m);
 	return rc;
 }

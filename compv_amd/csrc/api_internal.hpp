@@ -4,6 +4,7 @@
 #include "../../include/compv_hip.h"
 #include "kernels.hpp"
 #include "kht.hpp"
+#include "device_memory.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -22,59 +23,6 @@
 
 using namespace compvhip;
 
-namespace compvhip_api {
-void countLive(compvhip_ctx* ctx, long delta);   // ctx->live += delta (defined below compvhip_ctx)
-
-template <typename T>
-hipError_t dmalloc(compvhip_ctx* ctx, T** p, size_t count)
-{
-	*p = nullptr;
-	if (!count) return hipSuccess;
-	hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-	if (e == hipSuccess && ctx) countLive(ctx, 1);
-	return e;
-}
-template <typename T>
-void dfree(compvhip_ctx* ctx, T*& p)
-{
-	if (p) { (void)hipFree(p); if (ctx) countLive(ctx, -1); p = nullptr; }
-}
-
-// Growable device memory: a pointer and its capacity in elements, one hipMalloc through dmalloc / dfree (ctx->live counts it once).  A request that fits
-// reuses the buffer; after a failed allocation it is {nullptr, 0}, so a later, smaller request allocates again instead of trusting a stale capacity.
-template <typename T>
-struct DevBuf {
-	T* ptr = nullptr; size_t cap = 0;
-	operator T*() const { return ptr; }
-	hipError_t reserve(compvhip_ctx* ctx, size_t n)   // room for n elements: exactly n when it has to allocate
-	{
-		if (cap >= n) return hipSuccess;
-		release(ctx);
-		const hipError_t e = dmalloc(ctx, &ptr, n);
-		if (e == hipSuccess) cap = n;
-		return e;
-	}
-	// n + 25 % + 1024 when it has to allocate (frames of a stream resemble each other: no reallocation for a slightly denser one)
-	hipError_t grow(compvhip_ctx* ctx, size_t n) { return cap >= n ? hipSuccess : reserve(ctx, n + n / 4 + 1024); }
-	void release(compvhip_ctx* ctx) { dfree(ctx, ptr); cap = 0; }
-};
-// the same for pinned host memory (not counted in ctx->live)
-template <typename T>
-struct PinBuf {
-	T* ptr = nullptr; size_t cap = 0;
-	operator T*() const { return ptr; }
-	hipError_t reserve(size_t n)
-	{
-		if (cap >= n) return hipSuccess;
-		release();
-		const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T));
-		if (e == hipSuccess) cap = n; else ptr = nullptr;
-		return e;
-	}
-	hipError_t grow(size_t n) { return cap >= n ? hipSuccess : reserve(n + n / 4 + 1024); }
-	void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; cap = 0; }
-};
-} // namespace compvhip_api
 using namespace compvhip_api;   // (this header serves the api*.cpp files only)
 
 constexpr int kMaxRounds = 4096;       // hysteresis round flag slots (a multiple of 4); a frame that needs more rounds reuses them (enqueueResolve)
@@ -85,14 +33,13 @@ constexpr size_t kMaxTimeline = 4096;     // timing entries kept while nobody re
 
 // device tables of the canonical KHT path's line fields (khtCanonTables), built once per geometry
 struct KhtCanonTabs {
-	float* rho = nullptr; float* theta = nullptr;
+	DevBuf<float> rho, theta;
 	size_t W = 0, H = 0; double dRho = 0.0, dTheta = 0.0;
 };
 
-// Device + host scratch of ONE KHT frame in flight: the context owns one for its host entry point, a plan one per worker thread of
-// compvhip_plan_houghkht (every worker has its own HIP stream; nothing in here is shared between threads).
+// Device + host scratch of ONE KHT frame in flight: the context owns one for its host entry point (compvhip_houghkht_u8).
 struct KhtScratch {
-	hipStream_t stream = nullptr; bool ownStream = false;
+	hipStream_t stream = nullptr;   // the context's
 	DevBuf<int32_t> counts; DevBuf<KhtVoteParams> params; DevBuf<KhtCell> cells; DevBuf<int> cellCount;
 	DevBuf<KhtPoint> pts;
 	DevBuf<KhtSpan> spans, scratch; DevBuf<KhtSubdivFrame> stack; DevBuf<KhtKernel> kernelsDev;   // one slot per possible cluster, all four
@@ -134,12 +81,22 @@ struct KhtBatchState {
 	std::vector<KhtBatchFrame> frames;
 	hipEvent_t syncEv = nullptr;   // blocking-sync event: a controller that waits for a GPU stage SLEEPS (hipStreamSynchronize spins on a CPU of the quota the workers need)
 	double stageMs[6] = {};   // of the groups this state handled in the current call
+	KhtBatchState() = default;
+	KhtBatchState(const KhtBatchState&) = delete;
+	// (the plan's device is current: compvhip_plan_destroy) events and stream here; the buffers free themselves AFTER this body, so the stream goes before them
+	// (khtBatchFree released them first).  compvhip_plan_houghkht is synchronous: the stream is idle, hipStreamDestroy defers anyway and hipFree synchronises.
+	~KhtBatchState()
+	{
+		for (hipEvent_t e : ready) (void)hipEventDestroy(e);
+		if (syncEv) (void)hipEventDestroy(syncEv);
+		if (stream) (void)hipStreamDestroy(stream);
+	}
 };
 
 struct compvhip_ctx {
 	int device = 0;
 	std::string err;
-	std::atomic<long> live{0};   // hipMalloc / hipFree balance; KHT workers of a plan allocate from their own threads
+	LiveCount live{0};           // hipMalloc / hipFree balance; KHT workers of a plan allocate from their own threads
 	hipStream_t stream = nullptr;      // stream of the host entry points
 	compvhip_plan* hostPlan = nullptr; // single-frame plan cached for the host entry points
 	DevBuf<uint8_t> dIn, dOut;         // device staging of the host entry points (bytes)
@@ -187,12 +144,12 @@ struct compvhip_plan : TimingState {
 	// canny
 	int tilesX = 0, tilesY = 0, wb = 0;
 	size_t bitsFrameStride = 0;
-	uint32_t* ebits = nullptr; uint32_t* ubits = nullptr;
-	int* counters = nullptr;  // ONE device allocation zeroed by ONE memset per step: [edgeCounts frames][lineCounts frames][tileCounts frames*tiles][blockCounts frames*lineBlocks][frameTotals frames*kFrameSlot][lineTotal kFrameSlot][flags kMaxRounds]
+	DevBuf<uint32_t> ebits, ubits;
+	DevBuf<int> counters;     // ONE device allocation zeroed by ONE memset per step: [edgeCounts frames][lineCounts frames][tileCounts frames*tiles][blockCounts frames*lineBlocks][frameTotals frames*kFrameSlot][lineTotal kFrameSlot][flags kMaxRounds]
 	size_t nCounts = 0;       // ints in front of the flags
-	int* flags = nullptr; int* hFlags = nullptr; // device (inside counters) / pinned host (kAsyncDepth + 1 slots)
-	int* frameTotals = nullptr; unsigned int* lineTotal = nullptr; // device (inside counters): NMS survivors per frame (one per 128-byte line) / key slots in use
-	unsigned int* hTotals = nullptr;             // pinned host (behind hFlags): lineTotal of the synchronous call (slot 0) and of the asynchronous steps (1 + ticket)
+	int* flags = nullptr; PinBuf<int> hFlags;    // device (a view into counters) / pinned host (2 * (kAsyncDepth + 1) slots: the flags, then hTotals)
+	int* frameTotals = nullptr; unsigned int* lineTotal = nullptr; // device (views into counters): NMS survivors per frame (one per 128-byte line) / key slots in use
+	unsigned int* hTotals = nullptr;             // pinned host (a view into hFlags, behind the flags): lineTotal of the synchronous call (slot 0) and of the asynchronous steps (1 + ticket)
 	// The line sort covers the key slots that exist.  A synchronous step reads their number before it enqueues the sort; an asynchronous step cannot, so it
 	// sorts a range predicted from the totals of the plan's last steps (0 = none seen yet: the whole capacity) -- compvhip_plan_wait compares with the step's
 	// real total and replays the step when the prediction was too small.
@@ -200,53 +157,53 @@ struct compvhip_plan : TimingState {
 	// speculative hysteresis rounds of a step: what the plan's last 8 asynchronous steps needed (the first round that changed nothing, inclusive), at least 2, at
 	// most kSpecRounds; a step that needs more is replayed by compvhip_plan_wait and teaches the plan
 	int specRounds = kSpecRounds; unsigned char recentRounds[8] = {}; int recentRoundsN = 0;
-	int* hRoundsDev = nullptr; int* stepHostSlot = nullptr;   // hRounds as the device sees it / the slot of the asynchronous step being enqueued (nullptr otherwise)
-	int* hRounds = nullptr;                      // pinned host, per ticket: [0] the step's line total (the last int of its counter slot ... see runStepAsync), [kFrameSlot .. +3] its first 4 round flags
+	int* hRoundsDev = nullptr; int* stepHostSlot = nullptr;   // hRounds as the device sees it (a view) / the slot of the asynchronous step being enqueued (nullptr otherwise)
+	PinBuf<int> hRounds;                         // pinned host (hipHostMallocMapped), per ticket: [0] the step's line total (the last int of its counter slot ... see runStepAsync), [kFrameSlot .. +3] its first 4 round flags
 	int roundsUsed = 0;
 	int maxRounds = kMaxRounds; // flag slots in use (COMPVHIP_RESOLVE_WRAP lowers it: tests of the slot reuse)
 	bool countersFresh = false; // the step's memset already zeroed the edge/line counts (no second fill in front of the SHT stage)
-	int2* thrDev = nullptr; unsigned int* sums = nullptr;
-	uint8_t* dirty = nullptr;  // per-workgroup change flags of the resolve rounds
-	uint8_t* patchOut = nullptr; uint8_t* copyBack = nullptr; // byte map the tile kernel writes and the resolve rounds patch / in-place target of the last Canny call
-	uint8_t* grayTmp = nullptr; // luma plane of a packed-input step when the caller does not want it (compvhip_plan_pipeline_ex)
-	uint8_t* tmpOut = nullptr; // aliasing (in == out) scratch: a tile may still read the row halo a neighbour has overwritten
+	DevBuf<int2> thrDev; DevBuf<unsigned int> sums;
+	DevBuf<uint8_t> dirty;     // per-workgroup change flags of the resolve rounds
+	uint8_t* patchOut = nullptr; uint8_t* copyBack = nullptr; // (views: the caller's buffers or tmpOut) byte map the tile kernel writes and the resolve rounds patch / in-place target of the last Canny call
+	DevBuf<uint8_t> grayTmp;    // luma plane of a packed-input step when the caller does not want it (compvhip_plan_pipeline_ex)
+	DevBuf<uint8_t> tmpOut;    // aliasing (in == out) scratch: a tile may still read the row halo a neighbour has overwritten
 	bool bitsValid = false;
 	// sht
 	bool shtReady = false;
 	size_t R = 0, T = 0; float thetaStep = 0.f; int accPitch = 0;
-	uint8_t* blurTmp = nullptr;                       // u8 intermediate of the fixed-point convolution
-	uint32_t* hist = nullptr; int32_t* otsu = nullptr; // pre-processing scratch: partial histograms, [frames] Otsu level
-	float* cosT = nullptr; float* invSinT = nullptr; // toCartesian tables: cosf(theta_col), 1/sinf(theta_col)
-	int32_t* sinQ = nullptr; int32_t* cosQ = nullptr;
-	uint32_t* edges = nullptr; size_t edgeCap = 0; int* edgeCounts = nullptr;
-	uint16_t* acc = nullptr; size_t accFrameStride = 0;
-	uint32_t* keysA = nullptr; uint32_t* keysB = nullptr; uint32_t* valsA = nullptr; uint32_t* valsB = nullptr; size_t lineCap = 0; int* lineCounts = nullptr;
-	int2* reach = nullptr;                       // [T] accumulator rows the windows of a theta cover
-	int2* nmsRange = nullptr;                    // [column groups of the NMS] accumulator rows the windows can reach
-	uint8_t* nmsFlags = nullptr;                 // NMS survivors (flag planes)
-	int* blockCounts = nullptr; int lineBlocks = 0;   // NMS survivors per 64 accumulator rows (part of `counters`)
-	void* sortTemp = nullptr; size_t sortTempBytes = 0;
+	DevBuf<uint8_t> blurTmp;                          // u8 intermediate of the fixed-point convolution
+	DevBuf<uint32_t> hist; DevBuf<int32_t> otsu;       // pre-processing scratch: partial histograms, [frames] Otsu level
+	DevBuf<float> cosT, invSinT;                     // toCartesian tables: cosf(theta_col), 1/sinf(theta_col)
+	DevBuf<int32_t> sinQ, cosQ;
+	DevBuf<uint32_t> edges; size_t edgeCap = 0; int* edgeCounts = nullptr;   // edgeCounts: a view into counters
+	DevBuf<uint16_t> acc; size_t accFrameStride = 0;
+	DevBuf<uint32_t> keysA, keysB, valsA, valsB; size_t lineCap = 0; int* lineCounts = nullptr;   // lineCounts: a view into counters
+	DevBuf<int2> reach;                          // [T] accumulator rows the windows of a theta cover
+	DevBuf<int2> nmsRange;                       // [column groups of the NMS] accumulator rows the windows can reach
+	DevBuf<uint8_t> nmsFlags;                    // NMS survivors (flag planes)
+	int* blockCounts = nullptr; int lineBlocks = 0;   // NMS survivors per 64 accumulator rows (a view into counters)
+	DevBuf<uint8_t> sortTemp; size_t sortTempBytes = 0;
 	DevBuf<int32_t> segPerLine;   // line segments (sht_segments_kernels.hip): segments per line, then their prefix sums
 	// connected components (components_kernels.hip), allocated on first use: survivors per row [frames][H]; the packed copy of a byte edge map
 	// [frames][H][wb]; parent words [frames][H][W] of the calls without a label map (with one, the parent words live in it)
-	int32_t* compRows = nullptr; uint32_t* compBits = nullptr; int32_t* compParent = nullptr;
-	uint8_t* morphTmp = nullptr;                 // thresholding / morphology (morph_kernels.hip), allocated on first use: the u8 plane [frames][H][S] between the two basic operations of an OPEN / CLOSE, and the out-of-place target of an in-place adaptive threshold
+	DevBuf<int32_t> compRows; DevBuf<uint32_t> compBits; DevBuf<int32_t> compParent;
+	DevBuf<uint8_t> morphTmp;                    // thresholding / morphology (morph_kernels.hip), allocated on first use: the u8 plane [frames][H][S] between the two basic operations of an OPEN / CLOSE, and the out-of-place target of an in-place adaptive threshold
 	// FAST corners (fast_kernels.hip), allocated on first use: [frames][H] corners per row, [frames][H] their scan, [frames][256] score histogram, [frames] cut
 	// level -- one allocation; and the score map [frames][H][S] of the calls that do not want one
-	int* fastWork = nullptr; uint8_t* fastScores = nullptr;
+	DevBuf<int> fastWork; DevBuf<uint8_t> fastScores;
 	// ORB (orb_kernels.hip), allocated on first use: [frames][keyCap] source indices of the surviving corners (grows with the largest keyCap seen); the blurred
 	// batch [frames][H][S] of the describe calls with blur != 0; the Q16 Gaussian (5, 2.0f), computed once; which byte-read variant of orb_brief_kernel runs
-	DevBuf<int32_t> orbIndex; uint8_t* orbBlur = nullptr; uint16_t orbKern[5] = {}; bool orbKernReady = false; bool orbBriefLds = false;
+	DevBuf<int32_t> orbIndex; DevBuf<uint8_t> orbBlur; uint16_t orbKern[5] = {}; bool orbKernReady = false; bool orbBriefLds = false;
 	int strengthBits = 16, keyBits = 0;
 	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
-	uint16_t* chunkHist = nullptr; uint32_t* strengthStart = nullptr; int sortChunks = 0; bool deviceSort = false;
+	DevBuf<uint16_t> chunkHist; DevBuf<uint32_t> strengthStart; int sortChunks = 0; bool deviceSort = false;
 	// voting over image tiles (planned at plan creation: the per-tile edge counters live in `counters`)
 	bool voteTiles = false;                      // the tile grid exists
-	ShtTileArgs vt = {};                         // geometry + device tables
+	ShtTileArgs vt = {};                         // geometry + device tables (views of the five buffers below, of reach and of tileCounts)
 	std::vector<int32_t> vtKt, vtRowBase;        // host copies of the [tiles][T] tables
-	int32_t* dKt = nullptr; int32_t* dRowBase = nullptr; uint8_t* partLo = nullptr; uint8_t* partHi = nullptr; uint8_t* colFlag = nullptr; int* tileCounts = nullptr;
+	DevBuf<int32_t> dKt, dRowBase; DevBuf<uint8_t> partLo, partHi, colFlag; int* tileCounts = nullptr;   // tileCounts: a view into counters
 	// batched KHT (compvhip_plan_houghkht): one scratch set + stream per worker thread, stage clocks of the last call
-	std::vector<KhtBatchState*> khtBatch;        // device / pinned buffers and per-frame host state of the batched call: one per group of frames in flight
+	std::vector<std::unique_ptr<KhtBatchState>> khtBatch;       // device / pinned buffers and per-frame host state of the batched call: one per group of frames in flight
 	std::vector<std::unique_ptr<KhtPeaksWork>> khtWork;   // sort + sweep workspace (axes, 1.6 MB visited map at 4K) of WORKER w: it stays in that core's cache from frame to frame
 	double khtStageMs[6] = {}; double khtWallMs = 0.0; int khtThreads = 0;
 	// asynchronous steps (compvhip_plan_pipeline_async / compvhip_plan_wait)
@@ -259,8 +216,8 @@ struct compvhip_plan : TimingState {
 struct compvhip_matcher : TimingState {
 	compvhip_ctx* ctx = nullptr;
 	int descDwords = 0, queryCap = 0, trainCap = 0, pairs = 0, knn = 0;
-	uint32_t* partial = nullptr;        // keys of the slice kernel: max of the forward ([pairs][train slices][knn][queryCap]) and the reverse ([pairs][query slices][trainCap]) run
-	compvhip_match* reverse = nullptr;  // [pairs][trainCap]: best query of every train row (cross check)
+	DevBuf<uint32_t> partial;           // keys of the slice kernel: max of the forward ([pairs][train slices][knn][queryCap]) and the reverse ([pairs][query slices][trainCap]) run
+	DevBuf<compvhip_match> reverse;     // [pairs][trainCap]: best query of every train row (cross check)
 };
 // ORB pyramid (scale_kernels.hip, fast_kernels.hip, orb_kernels.hip): the levels' geometry and the scratch they share.  `active` levels (a prefix: the sizes
 // only shrink) are at least 37 x 37; the others are empty.
@@ -269,20 +226,18 @@ struct compvhip_orbpyr : TimingState {
 	size_t W = 0, H = 0, S = 0, frames = 0, cornerCap = 0;
 	compvhip_orbpyr_opts opts = {};
 	int active = 0;
-	struct Level { size_t W = 0, H = 0, S = 0; float sf = 0.f; int quota = 0; uint8_t* plane = nullptr; uint8_t* blurred = nullptr; } lv[kPyrMaxLevels];
-	uint8_t* planes = nullptr;          // levels 1 .. active - 1, [frames][H_l][S_l] each, one allocation
-	uint8_t* blurredAll = nullptr;      // levels 0 .. active - 1 blurred, one allocation (first describe)
-	compvhip_corner* corners = nullptr; // [frames][cornerCap], one level at a time
-	int* fastWork = nullptr; uint8_t* fastScores = nullptr;   // as compvhip_plan's, sized for level 0
+	struct Level { size_t W = 0, H = 0, S = 0; float sf = 0.f; int quota = 0; uint8_t* plane = nullptr; uint8_t* blurred = nullptr; } lv[kPyrMaxLevels];   // plane / blurred: views into planes / blurredAll
+	DevBuf<uint8_t> planes;             // levels 1 .. active - 1, [frames][H_l][S_l] each, one allocation
+	DevBuf<uint8_t> blurredAll;         // levels 0 .. active - 1 blurred, one allocation (first describe)
+	DevBuf<compvhip_corner> corners;    // [frames][cornerCap], one level at a time
+	DevBuf<int> fastWork; DevBuf<uint8_t> fastScores;         // as compvhip_plan's, sized for level 0
 	DevBuf<int32_t> index;              // [frames][keyCap] source indices of a level's survivors
-	int32_t* counts = nullptr;          // [levels][frames] FAST counts, [levels][frames] survivors, [levels + 1][frames] running totals (row 0 stays 0)
-	const uint8_t* planesOf = nullptr;  // the d_gray the level planes were scaled from (nullptr: none yet)
+	DevBuf<int32_t> counts;             // [levels][frames] FAST counts, [levels][frames] survivors, [levels + 1][frames] running totals (row 0 stays 0)
+	const uint8_t* planesOf = nullptr;  // (the caller's) the d_gray the level planes were scaled from (nullptr: none yet)
 	const uint8_t* blurredOf = nullptr; // the same for the blurred planes
 	uint16_t kern[5] = {}; bool briefLds = kOrbBriefLdsDefault;
 };
 namespace compvhip_api {
-
-inline void countLive(compvhip_ctx* ctx, long delta) { ctx->live += delta; }
 
 inline int fail(compvhip_ctx* ctx, int code, const char* what, hipError_t e = hipSuccess)
 {
@@ -349,6 +304,38 @@ inline void timelineCollect(TimingState* p)
 	timelineClear(p);
 }
 
+// the body of the *_get_timing entry points: wait for the entries still pending, collect them, hand out up to cap of the last collection
+inline int timingRead(TimingState* p, int device, const char** names, float* ms, int cap)
+{
+	(void)hipSetDevice(device);
+	if (!p->timeline.empty()) {
+		for (auto& t : p->timeline) (void)hipEventSynchronize(t.b);
+		timelineCollect(p);
+	}
+	const int n = std::min<int>(cap, static_cast<int>(p->timingMs.size()));
+	for (int i = 0; i < n; ++i) { if (names) names[i] = p->timingNames[i].c_str(); if (ms) ms[i] = p->timingMs[i]; }
+	return n;
+}
+
+// the events of the timeline and of the pool (the destroy functions; the handle's device is current)
+inline void timingTeardown(TimingState* p)
+{
+	timelineClear(p);
+	for (hipEvent_t e : p->eventPool) (void)hipEventDestroy(e);
+	p->eventPool.clear();
+}
+
+// an asynchronous step of the plan has not been waited for (its replay would rewrite the plan's masks and the caller's lines)
+inline bool stepsInFlight(const compvhip_plan* p)
+{
+	for (const auto& stp : p->steps) if (stp.used) return true;
+	return false;
+}
+
+// one of the pointers has a bit of `mask` set (a null pointer counts as aligned)
+template <typename... P>
+bool misaligned(uintptr_t mask, const P*... ptrs) { return ((reinterpret_cast<uintptr_t>(ptrs) | ...) & mask) != 0; }
+
 // ---- functions called across files ----
 // api.cpp
 int shtDims(size_t W, size_t H, float thetaDeg, size_t* R, size_t* T, float* step);
@@ -383,6 +370,4 @@ MatchSliceArgs matchForward(const compvhip_matcher* m, const uint8_t* d_query, s
                             const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches);
 // api_kht.cpp
 size_t hostCpuBudget();
-void khtScratchFree(compvhip_ctx* ctx, KhtScratch& k);
-void khtBatchFree(compvhip_ctx* ctx, KhtBatchState* b);
 } // namespace compvhip_api

@@ -33,31 +33,6 @@ size_t compvhip_api::hostCpuBudget()
 	return std::max<size_t>(1, n);
 }
 
-void compvhip_api::khtScratchFree(compvhip_ctx* ctx, KhtScratch& k)
-{
-	k.counts.release(ctx); k.params.release(ctx); k.cells.release(ctx); k.cellCount.release(ctx);
-	k.pts.release(ctx); k.spans.release(ctx); k.kernelsDev.release(ctx);
-	k.strings.release(ctx); k.counts32.release(ctx); k.scratch.release(ctx); k.stack.release(ctx);
-	dfree(ctx, k.tabs.rho); dfree(ctx, k.tabs.theta); k.canonLines.release(ctx); k.canonCount.release(ctx);
-	k.linked.release();
-	if (k.ownStream && k.stream) { (void)hipStreamDestroy(k.stream); k.stream = nullptr; }
-}
-
-void compvhip_api::khtBatchFree(compvhip_ctx* ctx, KhtBatchState* b)
-{
-	if (!b) return;
-	b->dBits.release(ctx); b->pts.release(ctx); b->strings.release(ctx); b->counts32.release(ctx); b->totals.release(ctx);
-	b->spans.release(ctx); b->scratch.release(ctx); b->stack.release(ctx); b->kernelsDev.release(ctx);
-	b->counts.release(ctx); b->params.release(ctx); b->cells.release(ctx); b->cellCount.release(ctx);
-	dfree(ctx, b->tabs.rho); dfree(ctx, b->tabs.theta); b->canonLines.release(ctx); b->canonCounts.release(ctx);
-	b->canonLinesHost.release(); b->hostBits.release(); b->linked.release(); b->stringsHost.release();
-	b->kernelsHost.release(); b->paramsHost.release(); b->cellsHost.release();
-	for (hipEvent_t e : b->ready) (void)hipEventDestroy(e);
-	if (b->syncEv) (void)hipEventDestroy(b->syncEv);
-	if (b->stream) (void)hipStreamDestroy(b->stream);
-	delete b;
-}
-
 // ---- KHT -----------------------------------------------------------------------------------------------------------------------
 // All of it works on ONE KhtScratch (its stream, its device buffers) and reports failures through K.err: the batched entry point runs
 // several of these at the same time on worker threads, so nothing below touches ctx->err or any other shared state (ctx->live is atomic).
@@ -141,15 +116,15 @@ static int khtBuildKernels(compvhip_ctx* ctx, KhtScratch& K, size_t W, size_t H,
 static hipError_t khtCanonTabs(compvhip_ctx* ctx, KhtCanonTabs& t, const KhtAxes& ax, hipStream_t st)
 {
 	if (t.rho && t.W == ax.W && t.H == ax.H && t.dRho == ax.dRho && t.dTheta == ax.dThetaDeg) return hipSuccess;
-	dfree(ctx, t.rho); dfree(ctx, t.theta);
+	t.rho.release(); t.theta.release();   // tables of another geometry: exactly the new size, not the larger of the two
 	std::vector<float> rho, theta;
 	khtCanonTables(ax, rho, theta);
-	hipError_t e = dmalloc(ctx, &t.rho, rho.size());
-	if (e == hipSuccess) e = dmalloc(ctx, &t.theta, theta.size());
+	hipError_t e = t.rho.reserve(ctx, rho.size());
+	if (e == hipSuccess) e = t.theta.reserve(ctx, theta.size());
 	if (e == hipSuccess) e = hipMemcpyAsync(t.rho, rho.data(), rho.size() * sizeof(float), hipMemcpyHostToDevice, st);
 	if (e == hipSuccess) e = hipMemcpyAsync(t.theta, theta.data(), theta.size() * sizeof(float), hipMemcpyHostToDevice, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	if (e != hipSuccess) { dfree(ctx, t.rho); dfree(ctx, t.theta); return e; }
+	if (e != hipSuccess) { t.rho.release(); t.theta.release(); return e; }   // no half-filled tables: t.rho == nullptr, the next call builds them
 	t.W = ax.W; t.H = ax.H; t.dRho = ax.dRho; t.dTheta = ax.dThetaDeg;
 	return hipSuccess;
 }
@@ -693,9 +668,9 @@ static int khtPlanEntry(compvhip_plan* p, const uint8_t* d_edges, float rho, flo
 	HIPCHK(ctx, hipDeviceSynchronize());
 	const size_t G0 = std::min<size_t>(F, group), words = ((W + 31) / 32) * H;
 	while (p->khtBatch.size() < K) {
-		KhtBatchState* b = new (std::nothrow) KhtBatchState();
+		std::unique_ptr<KhtBatchState> b(new (std::nothrow) KhtBatchState());
 		if (!b) return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "KHT batch state");
-		p->khtBatch.push_back(b);
+		p->khtBatch.push_back(std::move(b));
 	}
 	for (size_t k = 0; k < K; ++k) {
 		KhtBatchState& B = *p->khtBatch[k];
