@@ -31,6 +31,7 @@ MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 STREL_RECT, STREL_DIAMOND, STREL_CROSS = 0, 1, 2
 BORDER_ZERO, BORDER_REPLICATE = 0, 2
 MORPH_KERNEL_AUTO, MORPH_KERNEL_GENERAL, MORPH_KERNEL_SEPARABLE = 0, 1, 2
+INTERP_NEAREST, INTERP_BILINEAR, INTERP_BILINEAR_FLOAT32 = 0, 1, 2
 CORNER_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("strength", "<i4")])   # compvhip_corner
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("strength", "<f4"), ("orient", "<f4"), ("level", "<i4"), ("size", "<f4")])   # compvhip_keypoint = CompVInterestPoint
 MATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imageIdx", "<i4"), ("distance", "<i4")])   # compvhip_match = CompVDMatch
@@ -59,6 +60,7 @@ EXPORTS = [
     "compvhip_matcher_set_timing", "compvhip_matcher_get_timing",
     "compvhip_orbpyr_create", "compvhip_orbpyr_destroy", "compvhip_orbpyr_geometry", "compvhip_orbpyr_plane", "compvhip_orbpyr_detect", "compvhip_orbpyr_describe",
     "compvhip_plan_scale", "compvhip_scale_u8", "compvhip_orb_pyramid_u8", "compvhip_orbpyr_set_timing", "compvhip_orbpyr_get_timing",
+    "compvhip_warp_tables", "compvhip_plan_remap", "compvhip_plan_warp_inverse", "compvhip_remap_u8", "compvhip_warp_inverse_u8",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -124,6 +126,18 @@ class Keypoint(C.Structure):
 class MatchOpts(C.Structure):
     """compvhip_match_opts (include/compv_hip.h): ratio <= 0 / maxDistance < 0 / crossCheck == 0 switch a test off"""
     _fields_ = [("ratio", C.c_double), ("maxDistance", C.c_int), ("crossCheck", C.c_int)]
+
+
+class Roi(C.Structure):
+    """compvhip_roi (include/compv_hip.h): the source rectangle of a remap, inclusive"""
+    _fields_ = [("left", C.c_float), ("right", C.c_float), ("top", C.c_float), ("bottom", C.c_float)]
+
+
+def _roi(roi):
+    """None, a Roi or (left, right, top, bottom) -> what ctypes passes for a const compvhip_roi*"""
+    if roi is None:
+        return None
+    return C.byref(roi if isinstance(roi, Roi) else Roi(*roi))
 
 
 class OrbPyramidOpts(C.Structure):
@@ -246,6 +260,11 @@ def load():
     L.compvhip_orbpyr_describe.argtypes = [vp, vp, i32, vp, sz, vp, vp, sz, vp]
     L.compvhip_plan_scale.argtypes = [vp, vp, vp, sz, sz, sz, vp]
     L.compvhip_scale_u8.argtypes = [vp, vp, sz, sz, sz, vp, sz, sz, sz]
+    L.compvhip_warp_tables.argtypes = [vp, i32, sz, sz, vp, vp, vp, vp, vp, vp]
+    L.compvhip_plan_remap.argtypes = [vp, vp, vp, vp, sz, i32, C.POINTER(Roi), C.c_uint8, vp, sz, sz, sz, vp]
+    L.compvhip_plan_warp_inverse.argtypes = [vp, vp, vp, i32, sz, i32, C.c_uint8, vp, sz, sz, sz, vp]
+    L.compvhip_remap_u8.argtypes = [vp, vp, sz, sz, sz, vp, vp, i32, C.POINTER(Roi), C.c_uint8, vp, sz, sz, sz]
+    L.compvhip_warp_inverse_u8.argtypes = [vp, vp, sz, sz, sz, vp, i32, i32, C.c_uint8, vp, sz, sz, sz]
     L.compvhip_orb_pyramid_u8.argtypes = [vp, vp, sz, sz, sz, C.POINTER(OrbPyramidOpts), vp, vp, sz, sz, C.POINTER(sz)]
     L.compvhip_orbpyr_set_timing.argtypes = [vp, i32]
     L.compvhip_orbpyr_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
@@ -260,6 +279,21 @@ def load():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def warp_tables(M, out_w, out_h):
+    """compvhip_warp_tables (host arithmetic, no GPU): the running-sum tables of a (2, 3) or (3, 3) float32 matrix -> (ac, df, gi, by, ey, hy); gi and hy are
+    None for two rows"""
+    L = load()
+    M = np.ascontiguousarray(M, np.float32)
+    assert M.ndim == 2 and M.shape[1] == 3
+    rows = M.shape[0]
+    ac, df, gi = (np.zeros(out_w, np.float32) for _ in range(3))
+    by, ey, hy = (np.zeros(out_h, np.float32) for _ in range(3))
+    rc = L.compvhip_warp_tables(_ptr(M), rows, out_w, out_h, _ptr(ac), _ptr(df), _ptr(gi) if rows == 3 else None, _ptr(by), _ptr(ey), _ptr(hy) if rows == 3 else None)
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_warp_tables")
+    return (ac, df, gi, by, ey, hy) if rows == 3 else (ac, df, None, by, ey, None)
 
 
 class Context:
@@ -471,6 +505,26 @@ class Context:
         self._chk(self.lib.compvhip_scale_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(out), out_w, out_h, out_w))
         return out
 
+    def remap(self, img, map_x, map_y, interp=INTERP_BILINEAR, roi=None, default=0):
+        """compvhip_remap_u8 (CompVImageRemap::process): map_x, map_y (out_h, out_w) float32 -> the (out_h, out_w) plane, uint8 or (INTERP_BILINEAR_FLOAT32)
+        float32.  roi: None, a Roi or (left, right, top, bottom)."""
+        H, W = img.shape
+        map_x, map_y = np.ascontiguousarray(map_x, np.float32), np.ascontiguousarray(map_y, np.float32)
+        assert map_x.ndim == 2 and map_x.shape == map_y.shape
+        out_h, out_w = map_x.shape
+        out = np.empty((out_h, out_w), np.float32 if interp == INTERP_BILINEAR_FLOAT32 else np.uint8)
+        self._chk(self.lib.compvhip_remap_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(map_x), _ptr(map_y), interp, _roi(roi), default, _ptr(out), out_w, out_h, out_w))
+        return out
+
+    def warp_inverse(self, img, M, out_w, out_h, interp=INTERP_BILINEAR, default=0):
+        """compvhip_warp_inverse_u8 (CompVImage::warpInverse): M (2, 3) or (3, 3) float32, destination to source -> the (out_h, out_w) plane"""
+        H, W = img.shape
+        M = np.ascontiguousarray(M, np.float32)
+        assert M.ndim == 2 and M.shape[1] == 3
+        out = np.empty((out_h, out_w), np.float32 if interp == INTERP_BILINEAR_FLOAT32 else np.uint8)
+        self._chk(self.lib.compvhip_warp_inverse_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(M), M.shape[0], interp, default, _ptr(out), out_w, out_h, out_w))
+        return out
+
     def orb_pyramid(self, img, opts=None, cap=4096):
         """compvhip_orb_pyramid_u8 (CompVCornerDeteORB::process + CompVCornerDescORB::process): -> (keypoints KEYPOINT_DTYPE in level order, descriptors
         (n, 32) uint8).  opts: OrbPyramidOpts or None for the defaults.  The call is repeated with a larger buffer when `cap` was too small."""
@@ -641,6 +695,19 @@ class Plan:
     def scale(self, d_in, d_out, out_w, out_h, out_stride, stream=0):
         """compvhip_plan_scale: the plan's frames [frames][H][S] -> d_out [frames][out_h][out_stride], bilinear"""
         self.ctx._chk(self.lib.compvhip_plan_scale(self.h, d_in or None, d_out or None, out_w, out_h, out_stride, stream))
+
+    def remap(self, d_in, d_map_x, d_map_y, map_count, interp, d_out, out_w, out_h, out_stride, roi=None, default=0, stream=0):
+        """compvhip_plan_remap: the plan's frames -> d_out [frames][out_h][out_stride] (uint8, or float32 with out_stride in elements) through the device maps
+        [map_count][out_h * out_w] float32, map_count 1 (shared) or frames.  roi: None, a Roi or (left, right, top, bottom)."""
+        self.ctx._chk(self.lib.compvhip_plan_remap(self.h, d_in or None, d_map_x or None, d_map_y or None, map_count, interp, _roi(roi), default, d_out or None,
+                                                   out_w, out_h, out_stride, stream))
+
+    def warp_inverse(self, d_in, M, interp, d_out, out_w, out_h, out_stride, default=0, stream=0):
+        """compvhip_plan_warp_inverse: M is a HOST array (rows, 3) for all frames or (frames, rows, 3), rows 2 or 3, float32"""
+        M = np.ascontiguousarray(M, np.float32)
+        assert M.ndim in (2, 3) and M.shape[-1] == 3
+        count = 1 if M.ndim == 2 else M.shape[0]
+        self.ctx._chk(self.lib.compvhip_plan_warp_inverse(self.h, d_in or None, _ptr(M), M.shape[-2], count, interp, default, d_out or None, out_w, out_h, out_stride, stream))
 
     def pipeline(self, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap, d_counts, stream=0):
         self.ctx._chk(self.lib.compvhip_plan_pipeline(self.h, d_in, tLow, tHigh, threshold, max_lines, d_edges, d_lines, line_cap,

@@ -1,5 +1,5 @@
 // api_features.cpp -- plan-level calls of the features built on the Canny / SHT plan: line segments, line fits, connected components,
-// thresholding and morphology, FAST corners, ORB keypoints and descriptors, bilinear scale and the ORB pyramid, brute-force matching.
+// thresholding and morphology, FAST corners, ORB keypoints and descriptors, bilinear scale and the ORB pyramid, remap and inverse warp, brute-force matching.
 #include "api_internal.hpp"
 
 // what the segment and the fit kernels read alike: the edge pixels, the vote's tables, the lines
@@ -441,6 +441,117 @@ int compvhip_plan_scale(compvhip_plan* p, const uint8_t* d_in, uint8_t* d_out, s
 	if (p->timing) timelineClear(p);
 	Stamp s(p, st, "scale_bilinear_kernel");
 	return scaleImpl(ctx, d_in, p->W, p->H, p->S, p->frames, d_out, Wout, Hout, Sout, st);
+}
+
+// ---- remap and inverse warp (remap_kernels.hip; definition in include/compv_hip.h) ------------------------------------------------------------------
+int compvhip_warp_tables(const float* M, int rows, size_t Wout, size_t Hout, float* ac, float* df, float* gi, float* by, float* ey, float* hy)
+{
+	if (!M || (rows != 2 && rows != 3) || !Wout || !Hout || !ac || !df || !by || !ey || (rows == 3 && (!gi || !hy))) return COMPVHIP_E_INVALID_PARAMETER;
+	// compv_image.cxx:1031-1048,1114-1137: running sums, one float32 addition per entry (this file is built with -ffp-contract=off)
+	const float a = M[0], b = M[1], c = M[2], d = M[3], e = M[4], f = M[5];
+	ac[0] = c; df[0] = f;
+	for (size_t x = 1; x < Wout; ++x) { ac[x] = ac[x - 1] + a; df[x] = df[x - 1] + d; }
+	by[0] = 0.f; ey[0] = 0.f;
+	for (size_t y = 1; y < Hout; ++y) { by[y] = by[y - 1] + b; ey[y] = ey[y - 1] + e; }
+	if (rows == 3) {
+		const float g = M[6], h = M[7];
+		gi[0] = M[8];
+		for (size_t x = 1; x < Wout; ++x) gi[x] = gi[x - 1] + g;
+		hy[0] = 0.f;
+		for (size_t y = 1; y < Hout; ++y) hy[y] = hy[y - 1] + h;
+	}
+	return COMPVHIP_OK;
+}
+
+int compvhip_api::remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, int interp, const compvhip_roi* roi, void* d_out,
+                               size_t Wout, size_t Hout, size_t Sout, uint8_t defaultValue, RemapArgs* a)
+{
+	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	if (interp != COMPVHIP_INTERP_NEAREST && interp != COMPVHIP_INTERP_BILINEAR && interp != COMPVHIP_INTERP_BILINEAR_FLOAT32)
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "unknown interpolation");
+	if (!W || !H || !Wout || !Hout || Wout > 32767 || Hout > 32767 || W > 32767 || H > 32767 || S < W || Sout < Wout || Sout > static_cast<size_t>(INT32_MAX) || !frames ||
+	    frames > static_cast<size_t>(INT32_MAX) || S * H > static_cast<size_t>(INT32_MAX))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "remap: a size of 0 or beyond 32767, Sout < Wout, or a frame beyond 2^31 bytes");
+	const size_t elem = interp == COMPVHIP_INTERP_BILINEAR_FLOAT32 ? sizeof(float) : 1;
+	if (elem > 1 && misaligned(3, d_out)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "float32 destination not 4-byte aligned");
+	const uint8_t* const o = static_cast<const uint8_t*>(d_out);
+	if (d_in < o + Sout * Hout * frames * elem && o < d_in + S * H * frames) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap");
+	*a = RemapArgs{};
+	a->in = d_in; a->inFrameStride = S * H; a->W = static_cast<int>(W); a->H = static_cast<int>(H); a->S = static_cast<int>(S);
+	a->out = d_out; a->outFrameStride = Sout * Hout; a->Wout = static_cast<int>(Wout); a->Hout = static_cast<int>(Hout); a->Sout = static_cast<int>(Sout);
+	a->defaultValue = defaultValue; a->frames = static_cast<int>(frames);
+	// compv_image_remap.cxx:346-360 (COMPV_MATH_CLIP3(lo, hi, v) = v < lo ? lo : (v > hi ? hi : v))
+	const float w1 = static_cast<float>(W - 1), h1 = static_cast<float>(H - 1);
+	auto clip3 = [](float lo, float hi, float v) { return v < lo ? lo : (v > hi ? hi : v); };
+	a->left = 0.f; a->right = w1; a->top = 0.f; a->bottom = h1;
+	if (roi) {
+		a->left = clip3(0.f, w1, roi->left); a->right = clip3(a->left, w1, roi->right);
+		a->top = clip3(0.f, h1, roi->top); a->bottom = clip3(a->top, h1, roi->bottom);
+		// a NaN passes the clip and fails every compare of the inside test: nothing is inside, which the empty ROI says as well
+		if (!(a->left <= a->right && a->top <= a->bottom)) { a->left = a->top = 1.f; a->right = a->bottom = 0.f; }
+	}
+	return COMPVHIP_OK;
+}
+
+int compvhip_api::warpUpload(compvhip_ctx* ctx, WarpTables* t, const float* M, int rows, size_t count, RemapArgs* a, hipStream_t st)
+{
+	const size_t Wout = static_cast<size_t>(a->Wout), Hout = static_cast<size_t>(a->Hout), per = static_cast<size_t>(rows) * (Wout + Hout), total = per * count;
+	WarpTables::Slot& s = t->slot[t->next];
+	t->next = (t->next + 1) % kAsyncDepth;
+	if (s.copied) HIPCHK(ctx, hipEventSynchronize(s.copied));          // the copy that last read this slot (kAsyncDepth calls ago)
+	else HIPCHK(ctx, hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+	HIPCHK(ctx, s.host.reserve(total));
+	HIPCHK(ctx, t->dev.reserve(ctx, total));          // grows only: a reallocation frees with hipFree, which waits for the kernels that still read the old one
+	for (size_t m = 0; m < count; ++m) {
+		float* cols = s.host + m * per;
+		float* rws = cols + static_cast<size_t>(rows) * Wout;
+		const int rc = compvhip_warp_tables(M + m * static_cast<size_t>(rows) * 3, rows, Wout, Hout, cols, cols + Wout, rows == 3 ? cols + 2 * Wout : nullptr, rws, rws + Hout,
+		                                    rows == 3 ? rws + 2 * Hout : nullptr);
+		if (rc) return fail(ctx, rc, "warp tables");
+	}
+	HIPCHK(ctx, hipMemcpyAsync(t->dev, s.host, total * sizeof(float), hipMemcpyHostToDevice, st));
+	HIPCHK(ctx, hipEventRecord(s.copied, st));
+	a->tables = t->dev; a->coordFrameStride = per;
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_remap(compvhip_plan* p, const uint8_t* d_in, const float* d_mapX, const float* d_mapY, size_t mapCount, int interp, const compvhip_roi* roi,
+                        uint8_t defaultValue, void* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (!d_mapX || !d_mapY || misaligned(3, d_mapX, d_mapY)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null or misaligned map");
+	if (mapCount != 1 && mapCount != p->frames) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "mapCount must be 1 or the plan's frames");
+	RemapArgs a;
+	int rc = remapPrepare(ctx, d_in, p->W, p->H, p->S, p->frames, interp, roi, d_out, Wout, Hout, Sout, defaultValue, &a);
+	if (rc) return rc;
+	a.mapX = d_mapX; a.mapY = d_mapY; a.coordFrameStride = Wout * Hout;
+	if (p->timing) timelineClear(p);
+	Stamp s(p, st, "remap_kernel");
+	HIPCHK(ctx, launch_remap(a, kRemapMap, interp, mapCount != 1, st));
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_warp_inverse(compvhip_plan* p, const uint8_t* d_in, const float* M, int rows, size_t matrixCount, int interp, uint8_t defaultValue, void* d_out,
+                               size_t Wout, size_t Hout, size_t Sout, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (!M || (rows != 2 && rows != 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "M must be a 2 x 3 or 3 x 3 float32 matrix");
+	if (matrixCount != 1 && matrixCount != p->frames) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "matrixCount must be 1 or the plan's frames");
+	RemapArgs a;
+	int rc = remapPrepare(ctx, d_in, p->W, p->H, p->S, p->frames, interp, nullptr, d_out, Wout, Hout, Sout, defaultValue, &a);
+	if (rc) return rc;
+	rc = warpUpload(ctx, &p->warp, M, rows, matrixCount, &a, st);
+	if (rc) return rc;
+	if (p->timing) timelineClear(p);
+	Stamp s(p, st, "warp_inverse_kernel");
+	HIPCHK(ctx, launch_remap(a, rows == 3 ? kRemapWarp3 : kRemapWarp2, interp, matrixCount != 1, st));
+	return COMPVHIP_OK;
 }
 
 int compvhip_orbpyr_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size_t frames, const compvhip_orbpyr_opts* opts, size_t cornerCap, compvhip_orbpyr** out)

@@ -460,6 +460,57 @@ int compvhip_scale_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, 
 	return rc;
 }
 
+// remap and inverse warp of one host plane: the staging of both (no plan: neither has a minimum size).  `coords` enqueues the coordinate source into `a`.
+template <typename Coords>   // int coords(RemapArgs*)
+static int hostRemap(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, int interp, const compvhip_roi* roi, uint8_t defaultValue, void* out, size_t Wout,
+                     size_t Hout, size_t Sout, int source, const Coords& coords)
+{
+	if (!in || !out || S < W || Sout < Wout) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image or stride < width");
+	if (!W || !H || !Wout || !Hout || W > 32767 || H > 32767 || Wout > 32767 || Hout > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (1..32767)");
+	if (interp != COMPVHIP_INTERP_NEAREST && interp != COMPVHIP_INTERP_BILINEAR && interp != COMPVHIP_INTERP_BILINEAR_FLOAT32)
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "unknown interpolation");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t elem = interp == COMPVHIP_INTERP_BILINEAR_FLOAT32 ? sizeof(float) : 1;
+	const size_t Sd = alignUp(W, 64), Sod = alignUp(Wout, 64);
+	HIPCHK(ctx, ctx->dIn.reserve(ctx, Sd * H));
+	HIPCHK(ctx, ctx->dOut.reserve(ctx, Sod * Hout * elem));
+	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
+	RemapArgs a;
+	int rc = remapPrepare(ctx, ctx->dIn, W, H, Sd, 1, interp, roi, ctx->dOut.ptr, Wout, Hout, Sod, defaultValue, &a);
+	if (!rc) rc = coords(&a);
+	if (!rc) {
+		const hipError_t e = launch_remap(a, source, interp, false, ctx->stream);
+		if (e != hipSuccess) rc = fail(ctx, COMPVHIP_E_HIP, "launch_remap", e);
+	}
+	if (!rc) HIPCHK(ctx, download(ctx, out, Sout * elem, ctx->dOut, Sod * elem, Wout * elem, Hout));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // also after a failure: no copy from the caller's memory stays in flight
+	return rc;
+}
+
+int compvhip_remap_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const float* mapX, const float* mapY, int interp, const compvhip_roi* roi,
+                      uint8_t defaultValue, void* out, size_t Wout, size_t Hout, size_t Sout)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!mapX || !mapY) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null map");
+	return hostRemap(ctx, in, W, H, S, interp, roi, defaultValue, out, Wout, Hout, Sout, kRemapMap, [&](RemapArgs* a) -> int {
+		const size_t n = Wout * Hout;
+		HIPCHK(ctx, ctx->dMap.reserve(ctx, 2 * n));
+		HIPCHK(ctx, hipMemcpyAsync(ctx->dMap, mapX, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+		HIPCHK(ctx, hipMemcpyAsync(ctx->dMap + n, mapY, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+		a->mapX = ctx->dMap; a->mapY = ctx->dMap + n; a->coordFrameStride = n;
+		return COMPVHIP_OK;
+	});
+}
+
+int compvhip_warp_inverse_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const float* M, int rows, int interp, uint8_t defaultValue, void* out,
+                             size_t Wout, size_t Hout, size_t Sout)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!M || (rows != 2 && rows != 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "M must be a 2 x 3 or 3 x 3 float32 matrix");
+	return hostRemap(ctx, in, W, H, S, interp, nullptr, defaultValue, out, Wout, Hout, Sout, rows == 3 ? kRemapWarp3 : kRemapWarp2,
+	                 [&](RemapArgs* a) -> int { return warpUpload(ctx, &ctx->warp, M, rows, 1, a, ctx->stream); });
+}
+
 int compvhip_orb_pyramid_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_orbpyr_opts* opts, compvhip_keypoint* keypoints,
                             uint8_t* desc, size_t descStride, size_t cap, size_t* n)
 {

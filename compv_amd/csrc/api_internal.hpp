@@ -93,6 +93,18 @@ struct KhtBatchState {
 	}
 };
 
+// The running-sum tables of an inverse warp (compvhip_warp_tables) on their way to the device: built on the host into a ring of pinned staging slots and
+// uploaded in stream order into `dev`.  A slot is written again only after the copy that last read it has completed (its event), so kAsyncDepth calls
+// can be enqueued without the host waiting for the device.
+struct WarpTables {
+	DevBuf<float> dev;                 // [1 or frames] x { ac, df[, gi] of Wout values, by, ey[, hy] of Hout values }
+	struct Slot { PinBuf<float> host; hipEvent_t copied = nullptr; } slot[kAsyncDepth];
+	int next = 0;
+	WarpTables() = default;
+	WarpTables(const WarpTables&) = delete;
+	~WarpTables() { for (auto& s : slot) if (s.copied) (void)hipEventDestroy(s.copied); }   // (the owner's device is current: compvhip_plan_destroy, compvhip_ctx_destroy)
+};
+
 struct compvhip_ctx {
 	int device = 0;
 	std::string err;
@@ -117,6 +129,8 @@ struct compvhip_ctx {
 	DevBuf<compvhip_keypoint> dOrbKeys;     // staging of compvhip_orb_u8 (the corners and their number travel through dFastCorners / dFastCount): the records ...
 	DevBuf<int32_t> dOrbCount;              // ... their number ...
 	DevBuf<uint8_t> dOrbDesc;               // ... and the descriptor rows
+	DevBuf<float> dMap;                     // staging of compvhip_remap_u8: mapX, then mapY
+	WarpTables warp;                        // tables of compvhip_warp_inverse_u8
 	KhtScratch kht;                    // KHT scratch of the host entry point (compvhip_houghkht_u8)
 };
 
@@ -194,6 +208,7 @@ struct compvhip_plan : TimingState {
 	// ORB (orb_kernels.hip), allocated on first use: [frames][keyCap] source indices of the surviving corners (grows with the largest keyCap seen); the blurred
 	// batch [frames][H][S] of the describe calls with blur != 0; the Q16 Gaussian (5, 2.0f), computed once; which byte-read variant of orb_brief_kernel runs
 	DevBuf<int32_t> orbIndex; DevBuf<uint8_t> orbBlur; uint16_t orbKern[5] = {}; bool orbKernReady = false; bool orbBriefLds = false;
+	WarpTables warp;             // inverse warp (remap_kernels.hip), allocated on first use: the matrices' running-sum tables and their pinned staging
 	int strengthBits = 16, keyBits = 0;
 	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
 	DevBuf<uint16_t> chunkHist; DevBuf<uint32_t> strengthStart; int sortChunks = 0; bool deviceSort = false;
@@ -366,6 +381,11 @@ int morphPrepare(compvhip_ctx* ctx, size_t W, size_t H, const uint8_t* strel, si
 int checkFast(compvhip_ctx* ctx, size_t W, size_t H, int fastType);
 int checkOrb(compvhip_ctx* ctx, size_t W, size_t H, float scale);
 int scaleImpl(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, hipStream_t st);
+// remap and inverse warp: validates everything but the coordinate source and fills `a` (roi == nullptr: the whole frame)
+int remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, int interp, const compvhip_roi* roi, void* d_out, size_t Wout,
+                 size_t Hout, size_t Sout, uint8_t defaultValue, RemapArgs* a);
+// builds the tables of `count` matrices in a staging slot of `t`, enqueues their upload and points `a` at the device copy
+int warpUpload(compvhip_ctx* ctx, WarpTables* t, const float* M, int rows, size_t count, RemapArgs* a, hipStream_t st);
 MatchSliceArgs matchForward(const compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
                             const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches);
 // api_kht.cpp

@@ -419,4 +419,29 @@ struct ScaleArgs {
 bool scale_level_init(ScaleLevel& lv, int Win, int Hin);
 hipError_t launch_scale_bilinear(ScaleArgs& a, int frames, hipStream_t stream);   // fills blockEnd
 
+// ---- remap and inverse warp (remap_kernels.hip) -----------------------------------------------------------------------------------------------
+// CompVImageRemap::process / CompVImage::warpInverse: a per-pixel gather at coordinates that come from a float32 map or from the running-sum tables
+// of a matrix (include/compv_hip.h, section "remap and inverse warp")
+enum { kRemapMap = 0, kRemapWarp2 = 1, kRemapWarp3 = 2 };                  // coordinate source
+enum { kRemapNearest = 0, kRemapBilinear = 1, kRemapBilinearF32 = 2 };     // = COMPVHIP_INTERP_*
+constexpr int kRemapFramesPerGroup = 8;   // frames a workgroup loops over with one set of coordinates when the map / matrix is shared
+struct RemapArgs {
+	const uint8_t* in;        // [frames][H][S]
+	size_t inFrameStride;
+	int W, H, S;
+	void* out;                // uint8 or float32 [frames][Hout][Sout]
+	size_t outFrameStride;    // in elements, like Sout
+	int Wout, Hout, Sout;
+	const float* mapX; const float* mapY;   // kRemapMap: [1 or frames][Hout * Wout] each
+	const float* tables;      // kRemapWarp2 / 3: [1 or frames] x { ac, df[, gi] of Wout values, by, ey[, hy] of Hout values }
+	size_t coordFrameStride;  // floats from one frame's map / tables to the next (ignored when they are shared)
+	float left, right, top, bottom;   // the clipped ROI: inside the frame, or empty (left > right)
+	int defaultValue;         // 0 .. 255
+	int frames;
+	int framesPerGroup, group0, tilesX, wide, mapVec;   // filled by launch_remap
+};
+// perFrame: every frame has a map / tables of its own (coordFrameStride apart); otherwise all frames share the first.  S >= 2 (the bilinear forms load
+// 2-byte pairs inside a row); hipErrorInvalidValue for that, for a ROI that is neither empty nor inside the frame, and for sizes whose frame exceeds 2^31 bytes.
+hipError_t launch_remap(const RemapArgs& a, int source, int interp, bool perFrame, hipStream_t stream);
+
 } // namespace compvhip

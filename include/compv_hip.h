@@ -828,6 +828,61 @@ COMPVHIP_API int compvhip_orb_pyramid_u8(compvhip_ctx* ctx, const uint8_t* gray,
 COMPVHIP_API int compvhip_orbpyr_set_timing(compvhip_orbpyr* pyramid, int enabled);
 COMPVHIP_API int compvhip_orbpyr_get_timing(compvhip_orbpyr* pyramid, const char** names, float* ms, int cap);
 
+/* ---- remap and inverse warp (docs/kernels/remap.md) -------------------------------------------------------------------------------------------
+ * CompVImageRemap::process (base/image/compv_image_remap.cxx) and CompVImage::warpInverse (base/image/compv_image.cxx:997-1195), float32 maps and
+ * matrices, one uint8 plane.  Every output is defined bit for bit.  Source Win x Hin, destination Wout x Hout; all floating point is float32, one
+ * rounding per operation, unless a step says otherwise.
+ * A. Coordinates (x, y) in the source of output pixel (i, j):
+ *  1. Remap: two float32 planes of Wout * Hout values, row-major without stride: x = mapX[j * Wout + i], y = mapY[j * Wout + i].
+ *  2. Inverse warp: a matrix M = {a b c; d e f[; g h M22]} of 2 x 3 or 3 x 3 float32, row-major, mapping destination to source.  Six tables of
+ *     sequential running sums (compvhip_warp_tables): ac[0] = c, ac[i] = ac[i - 1] + a; df[0] = f, df[i] = df[i - 1] + d; gi[0] = M22,
+ *     gi[i] = gi[i - 1] + g; by[0] = 0, by[j] = by[j - 1] + b; ey and hy likewise with e and h.  X = ac[i] + by[j], Y = df[i] + ey[j].
+ *     2 x 3: x = X, y = Y.  3 x 3: Z = gi[i] + hy[j], s = 1.f / Z (correctly rounded IEEE division), x = X * s, y = Y * s: two multiplications
+ *     by the reciprocal, not two divisions.  The running sums are the definition: a * i + c is a different number.
+ * B. ROI {left, right, top, bottom}.  Remap: the caller's, clipped as compv_image_remap.cxx:348-354 does -- left to [0, Win - 1], right to
+ *    [left, Win - 1], top to [0, Hin - 1], bottom to [top, Hin - 1] -- or, without one, the whole frame.  Inverse warp: always the whole frame.
+ *    A pixel is INSIDE iff x >= left && x <= right && y >= top && y <= bottom (ordered compares: a NaN is outside).  An outside pixel gets
+ *    defaultValue: the byte for uint8 output, (float)defaultValue for float32 output.
+ * C. COMPVHIP_INTERP_NEAREST, inside: out = I[(int)((double)y + 0.5)][(int)((double)x + 0.5)].
+ * D. COMPVHIP_INTERP_BILINEAR and _BILINEAR_FLOAT32, inside: x1 = (int)x, x2 = min((int)(x + 1.f), Win - 1), y1 = (int)y,
+ *    y2 = min((int)(y + 1.f), Hin - 1) -- the neighbours clamp to the frame, not to the ROI; xf = x - (float)x1, yf = y - (float)y1, xy = xf * yf;
+ *    A = ((1.f - xf) - yf) + xy, B = xf - xy, C = yf - xy, each operation rounded on its own;
+ *    p = fma(I[y2][x2], xy, fma(I[y2][x1], C, fma(I[y1][x2], B, I[y1][x1] * A))) -- one product and three FUSED multiply-adds, which is what the
+ *    reference's AVX2 leaf computes as its build contracts it.  uint8 output is (uint8)p by truncation (p lies in [0, 256)); float32 output is p.
+ * E. Where this library differs from the reference:
+ *  1. float32 output is the value of D for every pixel.  The reference's rows overwrite the last (j * Wout) % 8 values of the row before with
+ *     values of other map entries when Wout % 8 != 0; that is not reproduced.
+ *  2. Elements >= Wout of a destination row are never written.
+ *  3. The reference picks a leaf without fused operations when the caller's map is not 32-byte aligned; this library always computes D.
+ *  4. float64 maps and matrices, the bicubic interpolation and the forward CompVImage::warp are not provided: a caller inverts on the host.
+ * Refused with COMPVHIP_E_INVALID_PARAMETER, the destination untouched: a null pointer; a size of 0 or beyond 32767; Sout < Wout (for float32
+ * output Sout counts ELEMENTS); rows other than 2 or 3; a count other than 1 or the plan's frames; an unknown interpolation; a float32
+ * destination that is not 4-byte aligned; source and destination that overlap. */
+#define COMPVHIP_INTERP_NEAREST 0
+#define COMPVHIP_INTERP_BILINEAR 1
+#define COMPVHIP_INTERP_BILINEAR_FLOAT32 2          /* bilinear, float32 destination */
+typedef struct compvhip_roi { float left, right, top, bottom; } compvhip_roi;
+/* A.2 on the host, no context: the tables of one matrix (rows = 2: gi and hy may be NULL and are not written).  ac, df, gi: Wout values; by, ey,
+ * hy: Hout values. */
+COMPVHIP_API int compvhip_warp_tables(const float* M, int rows, size_t Wout, size_t Hout, float* ac, float* df, float* gi, float* by, float* ey, float* hy);
+/* Remap for every frame of a plan: d_in [frames][H][S] of the plan's geometry -> d_out [frames][Hout][Sout], uint8 or (COMPVHIP_INTERP_BILINEAR_FLOAT32)
+ * float32.  d_mapX, d_mapY: device, [mapCount][Hout * Wout] float32 each; mapCount == 1: all frames share the map (a workgroup then reads its part of
+ * the map once for 8 frames); mapCount == frames: one map per frame.  roi == NULL: the whole frame.  A destination that is aligned in pointer, stride
+ * and frame size (4 bytes for uint8, 16 for float32) is written with vector stores.  Asynchronous on `stream`, never synchronises the host. */
+COMPVHIP_API int compvhip_plan_remap(compvhip_plan* plan, const uint8_t* d_in, const float* d_mapX, const float* d_mapY, size_t mapCount, int interp,
+                                     const compvhip_roi* roi, uint8_t defaultValue, void* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
+/* Inverse warp for every frame of a plan.  M: HOST, [matrixCount][rows][3] float32, rows 2 or 3; matrixCount 1 or frames.  The tables of A.2 are
+ * built on the host into pinned staging owned by the plan and uploaded in stream order; M may be reused as soon as the call returns.  Asynchronous
+ * on `stream`: the host waits only when 4 earlier uploads of the plan are all still pending.  Timing entries (compvhip_plan_set_timing):
+ * remap_kernel, warp_inverse_kernel. */
+COMPVHIP_API int compvhip_plan_warp_inverse(compvhip_plan* plan, const uint8_t* d_in, const float* M, int rows, size_t matrixCount, int interp,
+                                            uint8_t defaultValue, void* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
+/* Both for one HOST plane (sizes 1 .. 32767) with host maps / a host matrix; S and Sout in elements.  Synchronous. */
+COMPVHIP_API int compvhip_remap_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const float* mapX, const float* mapY, int interp,
+                                   const compvhip_roi* roi, uint8_t defaultValue, void* out, size_t Wout, size_t Hout, size_t Sout);
+COMPVHIP_API int compvhip_warp_inverse_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const float* M, int rows, int interp,
+                                          uint8_t defaultValue, void* out, size_t Wout, size_t Hout, size_t Sout);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel
