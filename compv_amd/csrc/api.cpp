@@ -170,7 +170,15 @@ ShtArgs shtArgs(compvhip_plan* p, int threshold)
 	return a;
 }
 
-// Enqueue canny tiles + `rounds` speculative resolve rounds starting at p->roundsUsed.
+// What one step carries from the function that decides it to the ones that use it.  The entry point (or runStepSync / runStepAsync) owns it; nothing of it
+// outlives the call.
+struct StepRun {
+	uint8_t* patchOut = nullptr;   // (a view: the caller's edge buffer or tmpOut) the byte map the tile kernel writes and the resolve rounds patch
+	uint8_t* copyBack = nullptr;   // in-place Canny (patchOut is tmpOut): the caller's buffer the finished map is copied to; nullptr otherwise
+	int roundsUsed = 0;            // resolve rounds enqueued so far = the flag slot of the next one
+	int* hostSlot = nullptr;       // asynchronous step: the ticket's pinned slot as the device sees it (ShtOpts::hostSlot); nullptr otherwise
+};
+
 int ensurePreproc(compvhip_plan* p)
 {
 	compvhip_ctx* ctx = p->ctx;
@@ -180,12 +188,12 @@ int ensurePreproc(compvhip_plan* p)
 }
 
 // thrMode: COMPVHIP_CANNY_THRESHOLD_* (per-frame device thresholds for PERCENT_OF_MEAN and OTSU)
-int enqueueCanny(compvhip_plan* p, const uint8_t* d_in, uint8_t* d_out, int tLow, int tHigh, int ksize, int thrMode, float fLow, float fHigh, hipStream_t st)
+int enqueueCanny(compvhip_plan* p, StepRun& run, const uint8_t* d_in, int tLow, int tHigh, int ksize, int thrMode, float fLow, float fHigh, hipStream_t st)
 {
 	compvhip_ctx* ctx = p->ctx;
 	CannyArgs a;
 	a.zero = nullptr; a.nZero = 0;
-	a.in = d_in; a.out = d_out; a.ebits = p->ebits; a.ubits = p->ubits; a.thrDev = (thrMode != COMPVHIP_CANNY_THRESHOLD_COMPARE_TO_GRADIENT) ? p->thrDev : nullptr;
+	a.in = d_in; a.out = run.patchOut; a.ebits = p->ebits; a.ubits = p->ubits; a.thrDev = (thrMode != COMPVHIP_CANNY_THRESHOLD_COMPARE_TO_GRADIENT) ? p->thrDev : nullptr;
 	a.inFrameStride = p->S * p->H; a.outFrameStride = p->S * p->H; a.bitsFrameStride = p->bitsFrameStride;
 	a.W = static_cast<int>(p->W); a.H = static_cast<int>(p->H); a.S = static_cast<int>(p->S); a.So = static_cast<int>(p->S);
 	a.wb = p->wb; a.tilesX = p->tilesX; a.tilesY = p->tilesY; a.tLow = tLow; a.tHigh = tHigh; a.ksize = ksize;
@@ -206,7 +214,7 @@ int enqueueCanny(compvhip_plan* p, const uint8_t* d_in, uint8_t* d_out, int tLow
 	// (round 6: the hipMemsetAsync it replaces was a launch of its own on the lane's chain)
 	a.zero = p->counters; a.nZero = static_cast<int>(p->nCounts + kMaxRounds);
 	p->countersFresh = true;
-	p->roundsUsed = 0;
+	run.roundsUsed = 0;
 	{
 		Stamp s(p, st, "canny_tile_kernel");
 		HIPCHK(ctx, launch_canny_tiles(a, static_cast<int>(p->frames), gap, st));
@@ -214,24 +222,24 @@ int enqueueCanny(compvhip_plan* p, const uint8_t* d_in, uint8_t* d_out, int tLow
 	return COMPVHIP_OK;
 }
 
-// d_out: the byte map to patch with the promoted pixels
-int enqueueResolve(compvhip_plan* p, uint8_t* d_out, int rounds, hipStream_t st)
+// `rounds` more resolve rounds, starting at run.roundsUsed; they patch the promoted pixels into run.patchOut
+int enqueueResolve(compvhip_plan* p, StepRun& run, int rounds, hipStream_t st)
 {
 	compvhip_ctx* ctx = p->ctx;
 	ResolveArgs r;
-	r.ebits = p->ebits; r.ubits = p->ubits; r.out = d_out; r.flags = p->flags; r.dirty = p->dirty;
+	r.ebits = p->ebits; r.ubits = p->ubits; r.out = run.patchOut; r.flags = p->flags; r.dirty = p->dirty;
 	r.outFrameStride = p->S * p->H; r.bitsFrameStride = p->bitsFrameStride;
 	r.H = static_cast<int>(p->H); r.So = static_cast<int>(p->S); r.wb = p->wb;
 	for (int i = 0; i < rounds; ++i) {
-		if (p->roundsUsed >= p->maxRounds) {
+		if (run.roundsUsed >= p->maxRounds) {
 			// More border crossings than flag slots (a weak chain that zigzags across a band border needs one round per crossing): the
 			// slots are reused.  The flood only ever adds pixels, so it terminates however many rounds that takes.  The sequence
 			// continues as round 4 -- same dirty-flag generation as round maxRounds, a multiple of 4 -- behind a "changed" in slot 3.
 			HIPCHK(ctx, hipMemsetAsync(p->flags + 3, 0, sizeof(int) * (p->maxRounds - 3), st));
 			HIPCHK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->flags + 3), 1, 1, st));
-			p->roundsUsed = 4;
+			run.roundsUsed = 4;
 		}
-		r.round = p->roundsUsed++;
+		r.round = run.roundsUsed++;
 		Stamp s(p, st, "canny_resolve_kernel");
 		HIPCHK(ctx, launch_canny_resolve(r, static_cast<int>(p->frames), st));
 	}
@@ -239,10 +247,10 @@ int enqueueResolve(compvhip_plan* p, uint8_t* d_out, int rounds, hipStream_t st)
 }
 
 // true when the last enqueued round changed nothing (fixed point reached). Synchronises the stream.
-int resolveConverged(compvhip_plan* p, hipStream_t st, bool* done)
+int resolveConverged(compvhip_plan* p, const StepRun& run, hipStream_t st, bool* done)
 {
 	compvhip_ctx* ctx = p->ctx;
-	const int last = p->roundsUsed - 1;
+	const int last = run.roundsUsed - 1;
 	HIPCHK(ctx, hipMemcpyAsync(p->hFlags, p->flags + last, sizeof(int), hipMemcpyDeviceToHost, st));
 	HIPCHK(ctx, hipStreamSynchronize(st));
 	*done = (p->hFlags[0] == 0);
@@ -390,7 +398,7 @@ int compvhip_api::ensureLineCap(compvhip_plan* p, size_t cap)
 	}
 	else { p->chunkHist.release(); p->strengthStart.release(); }   // grown past the device sort: its tables are of no use any more
 	p->lineCap = cap;
-	p->recentN = 0;   // totals clamped to another capacity
+	p->recentTotals.reset();   // totals clamped to another capacity
 	return COMPVHIP_OK;
 }
 
@@ -557,13 +565,14 @@ int compvhip_plan_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size_t
 	p->edgeCounts = p->counters; p->lineCounts = p->counters + frames; p->tileCounts = p->counters + 2 * frames; p->blockCounts = p->counters + (2 + static_cast<size_t>(p->voteTiles ? p->vt.tiles : 0)) * frames; p->flags = p->counters + p->nCounts;
 	p->frameTotals = p->blockCounts + static_cast<size_t>(p->lineBlocks) * frames; p->lineTotal = reinterpret_cast<unsigned int*>(p->frameTotals + frames * kFrameSlot);
 	if (const char* e = getenv("COMPVHIP_RESOLVE_WRAP")) { const int v = atoi(e); if (v >= 8 && v <= kMaxRounds && (v & 3) == 0) p->maxRounds = v; }
+	p->traceRounds = getenv("COMPVHIP_TRACE_ROUNDS") != nullptr;
 	if (hipMemset(p->counters, 0, sizeof(int) * (p->nCounts + kMaxRounds)) != hipSuccess) return failed(COMPVHIP_E_HIP);
 	if (p->thrDev.reserve(ctx, frames) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
 	if (p->dirty.reserve(ctx, canny_resolve_dirty_bytes(static_cast<int>(H), p->wb, static_cast<int>(frames))) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
 	if (p->sums.reserve(ctx, frames * kFrameSlot) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
-	if (p->hFlags.reserve(2 * (kAsyncDepth + 1)) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
-	p->hTotals = reinterpret_cast<unsigned int*>(p->hFlags + kAsyncDepth + 1);
-	if (p->hRounds.reserve((kFrameSlot + 4) * kAsyncDepth, hipHostMallocMapped) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	if (p->hFlags.reserve(2) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
+	p->hTotals = reinterpret_cast<unsigned int*>(p->hFlags + 1);
+	if (p->hRounds.reserve(kSlotStride * kAsyncDepth, hipHostMallocMapped) != hipSuccess) return failed(COMPVHIP_E_OUT_OF_MEMORY);
 	if (hipHostGetDevicePointer(reinterpret_cast<void**>(&p->hRoundsDev), p->hRounds, 0) != hipSuccess) return failed(COMPVHIP_E_HIP);
 	*out = p;
 	return COMPVHIP_OK;
@@ -593,9 +602,9 @@ int compvhip_plan_get_timing(compvhip_plan* p, const char** names, float* ms, in
 }
 
 // The tile kernel writes E (edges so far), U (weak, unresolved) and the bytes of E; the resolve rounds finish the hysteresis on the
-// masks and patch the promoted pixels into the byte map (p->patchOut; when in and out alias it is a scratch copy: a tile may still
+// masks and patch the promoted pixels into the byte map (run.patchOut; when in and out alias it is a scratch copy: a tile may still
 // read the row halo a neighbour has overwritten).
-static int planCannyImpl(compvhip_plan* p, const uint8_t* d_in, float tLow, float tHigh, int ksize, int type, uint8_t* d_edges, hipStream_t st,
+static int planCannyImpl(compvhip_plan* p, StepRun& run, const uint8_t* d_in, float tLow, float tHigh, int ksize, int type, uint8_t* d_edges, hipStream_t st,
                          bool waitConverged, bool clearTimeline = true)
 {
 	compvhip_ctx* ctx = p->ctx;
@@ -605,31 +614,27 @@ static int planCannyImpl(compvhip_plan* p, const uint8_t* d_in, float tLow, floa
 	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	if (p->timing && clearTimeline) timelineClear(p);
-	uint8_t* out = d_edges;
 	const size_t bytes = p->S * p->H * p->frames;
-	const bool alias = (d_in < d_edges + bytes) && (d_edges < d_in + bytes);
-	if (alias) {
-		HIPCHK(ctx, p->tmpOut.reserve(ctx, bytes));
-		out = p->tmpOut;
-	}
-	p->patchOut = out;
-	p->copyBack = alias ? d_edges : nullptr;
+	const bool alias = overlaps(d_in, bytes, d_edges, bytes);
+	if (alias) HIPCHK(ctx, p->tmpOut.reserve(ctx, bytes));
+	run.patchOut = alias ? p->tmpOut : d_edges;
+	run.copyBack = alias ? d_edges : nullptr;
 	if (p->W < static_cast<size_t>(ksize) || p->H < static_cast<size_t>(ksize)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image smaller than the kernel"); // compv_math_convlt.h:100
-	rc = enqueueCanny(p, d_in, out, lo, hi, ksize, type, tLow, tHigh, st);
+	rc = enqueueCanny(p, run, d_in, lo, hi, ksize, type, tLow, tHigh, st);
 	if (rc) return rc;
-	rc = enqueueResolve(p, p->patchOut, waitConverged ? kSpecRounds : p->specRounds, st);
+	rc = enqueueResolve(p, run, waitConverged ? kSpecRounds : p->specRounds, st);
 	if (rc) return rc;
 	if (waitConverged) {
 		for (;;) {
 			bool done = false;
-			rc = resolveConverged(p, st, &done);
+			rc = resolveConverged(p, run, st, &done);
 			if (rc) return rc;
 			if (done) break;
-			rc = enqueueResolve(p, p->patchOut, kSpecRounds, st);
+			rc = enqueueResolve(p, run, kSpecRounds, st);
 			if (rc) return rc;
 		}
 	}
-	if (p->copyBack) HIPCHK(ctx, hipMemcpyAsync(p->copyBack, out, bytes, hipMemcpyDeviceToDevice, st));
+	if (run.copyBack) HIPCHK(ctx, hipMemcpyAsync(run.copyBack, run.patchOut, bytes, hipMemcpyDeviceToDevice, st));
 	p->bitsValid = true;
 	return COMPVHIP_OK;
 }
@@ -637,7 +642,8 @@ static int planCannyImpl(compvhip_plan* p, const uint8_t* d_in, float tLow, floa
 int compvhip_plan_canny(compvhip_plan* p, const uint8_t* d_in, float tLow, float tHigh, int ksize, int type, uint8_t* d_edges, void* stream)
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
-	return planCannyImpl(p, d_in, tLow, tHigh, ksize, type, d_edges, static_cast<hipStream_t>(stream), true);
+	StepRun run;
+	return planCannyImpl(p, run, d_in, tLow, tHigh, ksize, type, d_edges, static_cast<hipStream_t>(stream), true);
 }
 
 int compvhip_api::pixfmtBytes(int fmt)
@@ -646,14 +652,20 @@ int compvhip_api::pixfmtBytes(int fmt)
 	return fmt <= COMPVHIP_FMT_BGRA32 ? 4 : (fmt <= COMPVHIP_FMT_BGR24 ? 3 : (fmt == COMPVHIP_FMT_Y ? 1 : 2));
 }
 
+int compvhip_api::checkPixfmt(compvhip_ctx* ctx, int fmt, size_t W)
+{
+	if (!pixfmtBytes(fmt)) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "pixel format without a grayscale conversion"); // conv_to_grayscale.cxx:86-88
+	if ((fmt == COMPVHIP_FMT_YUYV422 || fmt == COMPVHIP_FMT_UYVY422) && (W & 1)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "packed 4:2:2 needs an even width");
+	return COMPVHIP_OK;
+}
+
 int compvhip_plan_grayscale(compvhip_plan* p, const uint8_t* d_in, int pixfmt, uint8_t* d_gray, void* stream)
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_in || !d_gray) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
-	if (!pixfmtBytes(pixfmt)) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "pixel format without a grayscale conversion"); // conv_to_grayscale.cxx:86-88
-	if ((pixfmt == COMPVHIP_FMT_YUYV422 || pixfmt == COMPVHIP_FMT_UYVY422) && (p->W & 1))
-		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "packed 4:2:2 needs an even width");
+	const int rc = checkPixfmt(ctx, pixfmt, p->W);
+	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
@@ -697,7 +709,7 @@ int compvhip_plan_convlt1_fixedpoint(compvhip_plan* p, const uint8_t* d_in, cons
 	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const size_t span = p->S * p->H * p->frames;
-	const bool alias = (d_in < d_out + span) && (d_out < d_in + span);
+	const bool alias = overlaps(d_in, span, d_out, span);
 	if (alias) HIPCHK(ctx, p->blurTmp.reserve(ctx, span)); // only the in-place call needs the two-pass path
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
@@ -715,7 +727,7 @@ int compvhip_plan_edge_dete(compvhip_plan* p, const uint8_t* d_in, int op, uint8
 	if (op != COMPVHIP_OP_SOBEL && op != COMPVHIP_OP_SCHARR && op != COMPVHIP_OP_PREWITT)
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "invalid detector id"); // edge_dete.cxx:246
 	const size_t bytes = p->S * p->H * p->frames;
-	if ((d_in < d_out + bytes) && (d_out < d_in + bytes)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "d_in and d_out must not alias");
+	if (overlaps(d_in, bytes, d_out, bytes)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "d_in and d_out must not alias");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
@@ -729,9 +741,9 @@ int compvhip_plan_edge_dete(compvhip_plan* p, const uint8_t* d_in, int op, uint8
 	return COMPVHIP_OK;
 }
 
-// sortN: kSortAll, kSortExact or a number of key slots (api_internal.hpp)
+// o.sortN: kSortAll, kSortExact or a number of key slots (api_internal.hpp)
 int compvhip_api::planShtImpl(compvhip_plan* p, const uint8_t* d_edges, int threshold, int maxLines, compvhip_line* d_lines, size_t lineCap, int32_t* d_counts,
-                              hipStream_t st, bool clearTimeline, bool pairsOnly, size_t sortN)
+                              hipStream_t st, const ShtOpts& o)
 {
 	compvhip_ctx* ctx = p->ctx;
 	if (threshold <= 0) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "threshold must be > 0"); // houghsht.cxx:82
@@ -741,8 +753,9 @@ int compvhip_api::planShtImpl(compvhip_plan* p, const uint8_t* d_edges, int thre
 	if (rc) return rc;
 	rc = ensureLineCap(p, std::max(lineCap, kMinLineCap));
 	if (rc) return rc;
-	if (p->timing && clearTimeline) timelineClear(p);
+	if (p->timing && o.clearTimeline) timelineClear(p);
 	const int frames = static_cast<int>(p->frames);
+	size_t sortN = o.sortN;
 	if (d_edges) {
 		Stamp s(p, st, "bytes_to_bits_kernel");
 		HIPCHK(ctx, launch_bytes_to_bits(d_edges, static_cast<int>(p->W), static_cast<int>(p->H), static_cast<int>(p->S), p->S * p->H, p->ebits, p->wb,
@@ -751,11 +764,11 @@ int compvhip_api::planShtImpl(compvhip_plan* p, const uint8_t* d_edges, int thre
 	}
 	ShtArgs a = shtArgs(p, threshold);
 	a.outCounts = d_counts;   // written by sht_lines_kernel together with the plan's own counts (was a device copy behind the sort)
-	a.hostStep = p->stepHostSlot; a.stepFlags = p->flags;   // asynchronous steps: line total + round flags straight into the ticket's pinned slot
+	a.hostStep = o.hostSlot; a.stepFlags = p->flags;   // asynchronous steps: line total + round flags straight into the ticket's pinned slot
 	const size_t capAll = p->lineCap * p->frames;
-	const bool deviceSort = p->deviceSort && !pairsOnly;   // every size read on the device: nothing to predict, nothing to pad
+	const bool deviceSort = p->deviceSort && !o.pairsOnly;   // every size read on the device: nothing to predict, nothing to pad
 	if (sortN != kSortExact) sortN = std::min(sortN, capAll);
-	a.sortN = (pairsOnly || deviceSort || sortN == kSortExact) ? 0 : sortN;
+	a.sortN = (o.pairsOnly || deviceSort || sortN == kSortExact) ? 0 : sortN;
 	if (!p->countersFresh) HIPCHK(ctx, hipMemsetAsync(p->counters, 0, sizeof(int) * p->nCounts, st)); // edge, line and tile counts
 	p->countersFresh = false;
 	{ Stamp s(p, st, "sht_compact_kernel"); HIPCHK(ctx, launch_sht_compact_tiles(a, p->vt, frames, st)); }
@@ -763,7 +776,7 @@ int compvhip_api::planShtImpl(compvhip_plan* p, const uint8_t* d_edges, int thre
 	{ Stamp s(p, st, "sht_reduce_kernel"); HIPCHK(ctx, launch_sht_reduce_tiles(a, p->vt, frames, st)); }
 	{ Stamp s(p, st, "sht_lines_kernel"); HIPCHK(ctx, launch_sht_lines(a, frames, st)); }
 	// pairsOnly (the host entry point): stop at the (key, cell) pairs in emission order -- the caller orders them itself (referenceLineOrder)
-	if (pairsOnly) {
+	if (o.pairsOnly) {
 		return COMPVHIP_OK;
 	}
 	if (deviceSort) {
@@ -800,7 +813,7 @@ int compvhip_plan_houghsht(compvhip_plan* p, const uint8_t* d_edges, int thresho
                            int32_t* d_counts, void* stream)
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
-	return planShtImpl(p, d_edges, threshold, maxLines, d_lines, lineCap, d_counts, static_cast<hipStream_t>(stream), true);
+	return planShtImpl(p, d_edges, threshold, maxLines, d_lines, lineCap, d_counts, static_cast<hipStream_t>(stream), ShtOpts());
 }
 
 // ---- the step: [grayscale ->] Canny (any kernel size / threshold mode) -> SHT [-> toCartesian], one enqueue ----------------------
@@ -808,17 +821,14 @@ static int checkStep(compvhip_plan* p, const StepParams& sp)
 {
 	compvhip_ctx* ctx = p->ctx;
 	if (!sp.d_in || !sp.d_edges) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
-	if (sp.pixfmt != COMPVHIP_FMT_Y) {
-		if (!pixfmtBytes(sp.pixfmt)) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "pixel format without a grayscale conversion"); // conv_to_grayscale.cxx:86-88
-		if ((sp.pixfmt == COMPVHIP_FMT_YUYV422 || sp.pixfmt == COMPVHIP_FMT_UYVY422) && (p->W & 1))
-			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "packed 4:2:2 needs an even width");
-	}
+	const int rc = checkPixfmt(ctx, sp.pixfmt, p->W);   // (COMPVHIP_FMT_Y passes: one byte, any width)
+	if (rc) return rc;
 	if (sp.d_cart && (!sp.d_lines || !sp.d_counts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "toCartesian needs the line and count buffers");
 	return COMPVHIP_OK;
 }
 
 // everything up to (not including) the convergence check, on `st`
-static int enqueueStep(compvhip_plan* p, const StepParams& sp, hipStream_t st, bool clearTimeline)
+static int enqueueStep(compvhip_plan* p, StepRun& run, const StepParams& sp, hipStream_t st, bool clearTimeline)
 {
 	compvhip_ctx* ctx = p->ctx;
 	HIPCHK(ctx, hipSetDevice(ctx->device));   // before the scratch allocation below: the caller's current device may be another GPU
@@ -838,7 +848,7 @@ static int enqueueStep(compvhip_plan* p, const StepParams& sp, hipStream_t st, b
 		HIPCHK(ctx, launch_gray(a, sp.pixfmt, static_cast<int>(p->frames), st));
 		luma = gray;
 	}
-	int rc = planCannyImpl(p, luma, sp.tLow, sp.tHigh, sp.ksize, sp.thresholdType, sp.d_edges, st, false, clearTimeline);
+	int rc = planCannyImpl(p, run, luma, sp.tLow, sp.tHigh, sp.ksize, sp.thresholdType, sp.d_edges, st, false, clearTimeline);
 	if (rc) return rc;
 	if (sp.d_otsu && sp.thresholdType == COMPVHIP_CANNY_THRESHOLD_OTSU)
 		HIPCHK(ctx, hipMemcpyAsync(sp.d_otsu, p->otsu, sizeof(int32_t) * p->frames, hipMemcpyDeviceToDevice, st));
@@ -847,9 +857,11 @@ static int enqueueStep(compvhip_plan* p, const StepParams& sp, hipStream_t st, b
 
 static int toCartesianImpl(compvhip_plan* p, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap, int maxLines, float* d_cart, void* stream);
 
-static int enqueueStepTail(compvhip_plan* p, const StepParams& sp, hipStream_t st, size_t sortN)
+static int enqueueStepTail(compvhip_plan* p, const StepRun& run, const StepParams& sp, hipStream_t st, size_t sortN)
 {
-	int rc = planShtImpl(p, nullptr, sp.threshold, sp.maxLines, sp.d_lines, sp.lineCap, sp.d_counts, st, false, false, sortN);
+	ShtOpts o;
+	o.clearTimeline = false; o.sortN = sortN; o.hostSlot = run.hostSlot;
+	int rc = planShtImpl(p, nullptr, sp.threshold, sp.maxLines, sp.d_lines, sp.lineCap, sp.d_counts, st, o);
 	if (rc) return rc;
 	if (sp.d_cart) {
 		rc = toCartesianImpl(p, sp.d_lines, sp.d_counts, sp.lineCap, sp.maxLines, sp.d_cart, st);   // d_counts = the UNCUT counts; only min(count, lineCap, maxLines) slots were decoded
@@ -862,30 +874,33 @@ static int runStepSync(compvhip_plan* p, const StepParams& sp, hipStream_t st)
 {
 	// Everything is enqueued back to back (speculative resolve rounds included); the convergence flag is checked once at the end and,
 	// in the rare case the hysteresis needed more rounds, the tail is replayed.
-	int rc = enqueueStep(p, sp, st, true);
+	StepRun run;
+	int rc = enqueueStep(p, run, sp, st, true);
 	if (rc) return rc;
 	const size_t bytes = p->S * p->H * p->frames;
 	for (;;) {
-		rc = enqueueStepTail(p, sp, st, kSortExact);
+		rc = enqueueStepTail(p, run, sp, st, kSortExact);
 		if (rc) return rc;
 		bool done = false;
-		rc = resolveConverged(p, st, &done);
+		rc = resolveConverged(p, run, st, &done);
 		if (rc) return rc;
 		if (done) break;
 		do {
-			rc = enqueueResolve(p, p->patchOut, kSpecRounds, st);
+			rc = enqueueResolve(p, run, kSpecRounds, st);
 			if (rc) return rc;
-			rc = resolveConverged(p, st, &done);
+			rc = resolveConverged(p, run, st, &done);
 			if (rc) return rc;
 		} while (!done);
-		if (p->copyBack) HIPCHK(p->ctx, hipMemcpyAsync(p->copyBack, p->patchOut, bytes, hipMemcpyDeviceToDevice, st));
+		if (run.copyBack) HIPCHK(p->ctx, hipMemcpyAsync(run.copyBack, run.patchOut, bytes, hipMemcpyDeviceToDevice, st));
 		// replay of the Hough stage on the now final masks
 	}
 	return COMPVHIP_OK;
 }
 
-// The step without its host round trip: the hysteresis flag of the last speculative round travels to a pinned host slot behind
-// the step's kernels and is looked at by compvhip_plan_wait(), normally while the NEXT step is already running.
+// The step without its host round trip.  What compvhip_plan_wait() needs -- the step's line total and its first four round flags -- is written by
+// sht_lines_kernel straight into the ticket's pinned, device-mapped slot and looked at there, normally while the NEXT step is already running: no copy behind
+// the step's kernels (rounds 2-5: three device-to-host copies, a device copy of the counts and a fill per step -- 30 us of stream operations between the last
+// kernel of a step and the first of the next on a lane, 5 now).
 static int runStepAsync(compvhip_plan* p, const StepParams& sp, hipStream_t st, int* ticket)
 {
 	compvhip_ctx* ctx = p->ctx;
@@ -895,40 +910,35 @@ static int runStepAsync(compvhip_plan* p, const StepParams& sp, hipStream_t st, 
 	if (slot < 0) return fail(ctx, COMPVHIP_E_INVALID_STATE, "too many steps in flight: call compvhip_plan_wait first");
 	const size_t bytes = p->S * p->H * p->frames;
 	const size_t inBytes = bytes * static_cast<size_t>(sp.pixfmt == COMPVHIP_FMT_Y ? 1 : pixfmtBytes(sp.pixfmt));
-	if ((sp.d_in < sp.d_edges + bytes) && (sp.d_edges < sp.d_in + inBytes))
+	if (overlaps(sp.d_in, inBytes, sp.d_edges, bytes))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "the asynchronous step needs distinct input and edge buffers"); // a replay re-reads d_in
 	compvhip_plan::AsyncStep& stp = p->steps[slot];
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	if (!stp.done) HIPCHK(ctx, hipEventCreateWithFlags(&stp.done, hipEventDisableTiming));
 	// timing events of asynchronous steps accumulate until compvhip_plan_get_timing reads them; beyond kMaxTimeline entries the oldest go
 	if (p->timeline.size() > kMaxTimeline) timelineClear(p);
-	int rc = enqueueStep(p, sp, st, false);
+	// The slot belongs to no step in flight.  Until this step's sht_lines_kernel writes it, it says "replay" (stepVerdict): a step whose lines kernel never ran
+	// is run again by compvhip_plan_wait, not accepted with the previous step's numbers.
+	int* slotHost = p->hRounds + kSlotStride * slot;
+	slotHost[kSlotTotal] = ~0;
+	for (int i = 0; i < 4; ++i) slotHost[kSlotFlags + i] = 1;
+	StepRun run;
+	run.hostSlot = p->hRoundsDev + kSlotStride * slot;
+	int rc = enqueueStep(p, run, sp, st, false);
 	if (rc) return rc;
-	// (capacities first: ensureLineCap may grow the key buffers and reset recentN -- totals clamped to the old capacity predict nothing)
+	// (capacities first: ensureLineCap may grow the key buffers and reset recentTotals -- totals clamped to the old capacity predict nothing)
 	rc = ensureSht(p);
 	if (rc) return rc;
 	rc = ensureLineCap(p, std::max(sp.lineCap, kMinLineCap));
 	if (rc) return rc;
-	// the sorted range: the largest total of the plan's recent steps + 1/16 + 4096 slots (nothing seen yet, or just reset: everything)
-	size_t sortN = kSortAll;
-	if (p->recentN > 0) {
-		unsigned int m = 0;
-		for (int i = 0; i < std::min(p->recentN, 8); ++i) m = std::max(m, p->recentTotals[i]);
-		sortN = static_cast<size_t>(m) + (m >> 4) + 4096;
-	}
-	if (p->deviceSort) sortN = kSortAll;   // sized on the device: no prediction to check
-	sortN = std::min(sortN, p->lineCap * p->frames);
-	// What compvhip_plan_wait needs -- the step's line total and its first four round flags -- is written by sht_lines_kernel straight into the ticket's pinned,
-	// device-mapped slot: no copy behind the step's kernels (rounds 2-5: three device-to-host copies, a device copy of the counts and a fill per step -- 30 us
-	// of stream operations between the last kernel of a step and the first of the next on a lane, 5 now)
+	const size_t capAll = p->lineCap * p->frames;
+	const size_t sortN = p->deviceSort ? capAll : asyncSortRange(p->recentTotals, capAll);   // (sized on the device: no prediction to check)
 	static_assert(kMaxRounds >= 4 && kSpecRounds <= 4, "the round flags compvhip_plan_wait looks at");
-	if (p->roundsUsed > 4) return fail(ctx, COMPVHIP_E_INVALID_STATE, "more speculative rounds than flags the step reports");
-	p->stepHostSlot = p->hRoundsDev + (kFrameSlot + 4) * slot;
-	rc = enqueueStepTail(p, sp, st, sortN);
-	p->stepHostSlot = nullptr;
+	if (run.roundsUsed > 4) return fail(ctx, COMPVHIP_E_INVALID_STATE, "more speculative rounds than flags the step reports");
+	rc = enqueueStepTail(p, run, sp, st, sortN);
 	if (rc) return rc;
 	HIPCHK(ctx, hipEventRecord(stp.done, st));
-	stp.used = true; stp.replay = false; stp.seq = ++p->stepSeq; stp.stream = st; stp.sp = sp; stp.sortN = sortN; stp.rounds = p->roundsUsed;
+	stp.used = true; stp.replay = false; stp.seq = ++p->stepSeq; stp.stream = st; stp.sp = sp; stp.sortN = sortN; stp.rounds = run.roundsUsed;
 	*ticket = slot;
 	return COMPVHIP_OK;
 }
@@ -985,25 +995,15 @@ int compvhip_plan_wait(compvhip_plan* p, int ticket)
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	HIPCHK(ctx, hipEventSynchronize(stp.done));
 	stp.used = false;
-	const int* stepOut = p->hRounds + (kFrameSlot + 4) * ticket;   // what the step's one device-to-host copy brought: line total, then (kFrameSlot ints on) the round flags
-	const unsigned int total = static_cast<unsigned int>(stepOut[0]);
-	p->recentTotals[p->recentN++ & 7] = total;
-	if (p->recentN >= 16) p->recentN -= 8;   // the ring index keeps counting, "entries seen" saturates at 8
-	const bool sorted = static_cast<size_t>(total) <= stp.sortN;   // the predicted range covered every line of the step
-	{
-		// rounds this step needed = the first round that changed nothing, inclusive (more than were enqueued: one more than that, at least)
-		const int* rf = stepOut + kFrameSlot;
-		int needed = std::min(stp.rounds, 4) + 1;
-		for (int i = 0; i < std::min(stp.rounds, 4); ++i) if (rf[i] == 0) { needed = i + 1; break; }
-		p->recentRounds[p->recentRoundsN++ & 7] = static_cast<unsigned char>(std::min(needed, 255));
-		if (p->recentRoundsN >= 16) p->recentRoundsN -= 8;
-		int m = 2;
-		for (int i = 0; i < std::min(p->recentRoundsN, 8); ++i) m = std::max<int>(m, p->recentRounds[i]);
-		p->specRounds = (p->recentRoundsN >= 4) ? std::min(m, kSpecRounds) : kSpecRounds;   // a few steps first, then as many as they needed
-		if (getenv("COMPVHIP_TRACE_ROUNDS")) fprintf(stderr, "plan %p ticket %d: rounds enqueued %d, flags %d %d %d %d, needed %d -> next %d\n", (void*)p, ticket, stp.rounds, rf[0], rf[1], rf[2], rf[3], needed, p->specRounds);
-	}
-	const int lastFlag = stepOut[kFrameSlot + std::max(0, std::min(stp.rounds, 4) - 1)];   // the flag of the step's last speculative round
-	if (lastFlag == 0 && sorted && !stp.replay) return COMPVHIP_OK; // the speculative rounds reached the fixed point and the sort covered the lines (the usual case)
+	const int* stepOut = p->hRounds + kSlotStride * ticket;   // what the step's sht_lines_kernel wrote into the ticket's pinned slot (or, if it never ran, runStepAsync's reset)
+	const unsigned int total = static_cast<unsigned int>(stepOut[kSlotTotal]);
+	const int* rf = stepOut + kSlotFlags;
+	const StepVerdict v = stepVerdict(stp.rounds, rf, total, stp.sortN, stp.replay);
+	p->recentTotals.push(total);
+	p->recentRounds.push(static_cast<unsigned int>(v.needed));
+	p->specRounds = nextSpecRounds(p->recentRounds);
+	if (p->traceRounds) fprintf(stderr, "plan %p ticket %d: rounds enqueued %d, flags %d %d %d %d, needed %d -> next %d\n", (void*)p, ticket, stp.rounds, rf[0], rf[1], rf[2], rf[3], v.needed, p->specRounds);
+	if (!v.replay) return COMPVHIP_OK; // the speculative rounds reached the fixed point and the sort covered the lines (the usual case)
 	// Rare: the hysteresis of this step needed more rounds than were enqueued (or it produced more lines than the sorted range held), and a later step may
 	// already have reused the plan's masks.  Let the stream drain and run the step again, synchronously, from its (unmodified) input.  The replay writes this
 	// step's output buffers AFTER the later steps of the plan ran: if they share those buffers (a caller that only consumes the newest

@@ -144,7 +144,7 @@ int compvhip_plan_components(compvhip_plan* p, const uint8_t* d_edges, int conne
 static bool planeOverlap(const compvhip_plan* p, const uint8_t* a, const uint8_t* b)
 {
 	const size_t span = p->S * p->H * p->frames;
-	return (a < b + span) && (b < a + span);
+	return overlaps(a, span, b, span);
 }
 
 // COMPV_MATH_ROUNDFU_2_NEAREST_INT(COMPV_MATH_CLIP3(0x00, 0xff, v), int) (compv_image_threshold.cxx:133-136,213-220)

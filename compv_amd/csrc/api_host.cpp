@@ -195,9 +195,9 @@ int compvhip_grayscale_u8(compvhip_ctx* ctx, const uint8_t* in, int pixfmt, size
 {
 	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
 	if (!in || !out || S < W || So < W || !W || !H || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image, stride < width or size out of range");
+	const int rc = checkPixfmt(ctx, pixfmt, W);
+	if (rc) return rc;
 	const int bpp = pixfmtBytes(pixfmt);
-	if (!bpp) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "pixel format without a grayscale conversion"); // conv_to_grayscale.cxx:86-88
-	if ((pixfmt == COMPVHIP_FMT_YUYV422 || pixfmt == COMPVHIP_FMT_UYVY422) && (W & 1)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "packed 4:2:2 needs an even width");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const size_t Sd = alignUp(W, 64);
 	HIPCHK(ctx, ctx->dPacked.reserve(ctx, Sd * H * bpp));
@@ -278,7 +278,9 @@ int compvhip_houghsht_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size
 	// the order the reference returns them in, and which equal-strength lines survive maxLines, is decided by its unstable std::sort
 	int32_t count = 0;
 	for (int attempt = 0; attempt < 2; ++attempt) {
-		rc = planShtImpl(p, ctx->dIn, threshold, 0, nullptr, 0, ctx->dCounts, ctx->stream, true, true);
+		ShtOpts o;
+		o.pairsOnly = true;
+		rc = planShtImpl(p, ctx->dIn, threshold, 0, nullptr, 0, ctx->dCounts, ctx->stream, o);
 		if (rc) return rc;
 		HIPCHK(ctx, hipMemcpyAsync(&count, ctx->dCounts, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
 		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

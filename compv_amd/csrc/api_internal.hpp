@@ -5,6 +5,7 @@
 #include "kernels.hpp"
 #include "kht.hpp"
 #include "device_memory.hpp"
+#include "step_policy.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -26,10 +27,12 @@ using namespace compvhip;
 using namespace compvhip_api;   // (this header serves the api*.cpp files only)
 
 constexpr int kMaxRounds = 4096;       // hysteresis round flag slots (a multiple of 4); a frame that needs more rounds reuses them (enqueueResolve)
-constexpr int kSpecRounds = 3;         // rounds enqueued speculatively between two convergence checks
 constexpr size_t kMinLineCap = 1u << 16;  // per-frame line-key slots: max(caller's lineCap, 65536), clamped to R*T (include/compv_hip.h, compvhip_plan_houghsht)
 constexpr int kAsyncDepth = 4;            // outstanding compvhip_plan_pipeline_async steps per plan
 constexpr size_t kMaxTimeline = 4096;     // timing entries kept while nobody reads them (asynchronous steps)
+// A ticket's pinned host slot, as sht_lines_kernel writes it through ShtArgs::hostStep (kernels.hpp: this mirrors the kernel side): the step's line total, then
+// (one 128-byte line on) its first four round flags
+constexpr int kSlotTotal = 0, kSlotFlags = kFrameSlot, kSlotStride = kFrameSlot + 4;
 
 // device tables of the canonical KHT path's line fields (khtCanonTables), built once per geometry
 struct KhtCanonTabs {
@@ -161,24 +164,26 @@ struct compvhip_plan : TimingState {
 	DevBuf<uint32_t> ebits, ubits;
 	DevBuf<int> counters;     // ONE device allocation zeroed by ONE memset per step: [edgeCounts frames][lineCounts frames][tileCounts frames*tiles][blockCounts frames*lineBlocks][frameTotals frames*kFrameSlot][lineTotal kFrameSlot][flags kMaxRounds]
 	size_t nCounts = 0;       // ints in front of the flags
-	int* flags = nullptr; PinBuf<int> hFlags;    // device (a view into counters) / pinned host (2 * (kAsyncDepth + 1) slots: the flags, then hTotals)
+	int* flags = nullptr; PinBuf<int> hFlags;    // device (a view into counters) / pinned host, 2 ints: [0] the round flag resolveConverged copies back, [1] hTotals
 	int* frameTotals = nullptr; unsigned int* lineTotal = nullptr; // device (views into counters): NMS survivors per frame (one per 128-byte line) / key slots in use
-	unsigned int* hTotals = nullptr;             // pinned host (a view into hFlags, behind the flags): lineTotal of the synchronous call (slot 0) and of the asynchronous steps (1 + ticket)
+	unsigned int* hTotals = nullptr;             // pinned host (a view into hFlags, behind the flag): lineTotal of a synchronous step, copied back in front of its sort (kSortExact)
 	// The line sort covers the key slots that exist.  A synchronous step reads their number before it enqueues the sort; an asynchronous step cannot, so it
-	// sorts a range predicted from the totals of the plan's last steps (0 = none seen yet: the whole capacity) -- compvhip_plan_wait compares with the step's
-	// real total and replays the step when the prediction was too small.
-	unsigned int recentTotals[8] = {}; int recentN = 0;
-	// speculative hysteresis rounds of a step: what the plan's last 8 asynchronous steps needed (the first round that changed nothing, inclusive), at least 2, at
-	// most kSpecRounds; a step that needs more is replayed by compvhip_plan_wait and teaches the plan
-	int specRounds = kSpecRounds; unsigned char recentRounds[8] = {}; int recentRoundsN = 0;
-	int* hRoundsDev = nullptr; int* stepHostSlot = nullptr;   // hRounds as the device sees it (a view) / the slot of the asynchronous step being enqueued (nullptr otherwise)
-	PinBuf<int> hRounds;                         // pinned host (hipHostMallocMapped), per ticket: [0] the step's line total (the last int of its counter slot ... see runStepAsync), [kFrameSlot .. +3] its first 4 round flags
-	int roundsUsed = 0;
+	// sorts a range predicted from the totals of the plan's last steps (asyncSortRange; none seen yet: the whole capacity) -- compvhip_plan_wait compares with
+	// the step's real total and replays the step when the prediction was too small.
+	Recent8 recentTotals;
+	// speculative hysteresis rounds of a step: what the plan's last 8 asynchronous steps needed (nextSpecRounds); a step that needs more is replayed by
+	// compvhip_plan_wait and teaches the plan
+	int specRounds = kSpecRounds; Recent8 recentRounds;
+	int* hRoundsDev = nullptr;                   // hRounds as the device sees it (a view)
+	PinBuf<int> hRounds;                         // pinned host (hipHostMallocMapped), kSlotStride ints per ticket: sht_lines_kernel writes the step's line total and round flags straight into it, compvhip_plan_wait reads them
 	int maxRounds = kMaxRounds; // flag slots in use (COMPVHIP_RESOLVE_WRAP lowers it: tests of the slot reuse)
-	bool countersFresh = false; // the step's memset already zeroed the edge/line counts (no second fill in front of the SHT stage)
+	bool traceRounds = false;   // COMPVHIP_TRACE_ROUNDS was set when the plan was made: compvhip_plan_wait prints what every ticket saw
+	// A fact about DEVICE memory that outlives a call: the edge, line and tile counts are zero because the last kernel enqueued that touches them is a Canny tile kernel,
+	// which clears them (enqueueCanny).  compvhip_plan_canny leaves it set, and a later compvhip_plan_houghsht relies on it and skips its own fill; every SHT stage
+	// uses the counts and clears the mark (planShtImpl).
+	bool countersFresh = false;
 	DevBuf<int2> thrDev; DevBuf<unsigned int> sums;
 	DevBuf<uint8_t> dirty;     // per-workgroup change flags of the resolve rounds
-	uint8_t* patchOut = nullptr; uint8_t* copyBack = nullptr; // (views: the caller's buffers or tmpOut) byte map the tile kernel writes and the resolve rounds patch / in-place target of the last Canny call
 	DevBuf<uint8_t> grayTmp;    // luma plane of a packed-input step when the caller does not want it (compvhip_plan_pipeline_ex)
 	DevBuf<uint8_t> tmpOut;    // aliasing (in == out) scratch: a tile may still read the row halo a neighbour has overwritten
 	bool bitsValid = false;
@@ -347,6 +352,9 @@ inline bool stepsInFlight(const compvhip_plan* p)
 	return false;
 }
 
+// the byte spans [a, a + bytesA) and [b, b + bytesB) share a byte
+inline bool overlaps(const uint8_t* a, size_t bytesA, const uint8_t* b, size_t bytesB) { return (a < b + bytesB) && (b < a + bytesA); }
+
 // one of the pointers has a bit of `mask` set (a null pointer counts as aligned)
 template <typename... P>
 bool misaligned(uintptr_t mask, const P*... ptrs) { return ((reinterpret_cast<uintptr_t>(ptrs) | ...) & mask) != 0; }
@@ -358,14 +366,21 @@ int ensureSht(compvhip_plan* p);
 int ensureLineCap(compvhip_plan* p, size_t cap);
 int validateCannyParams(compvhip_ctx* ctx, float tLow, float tHigh, int ksize, int type, int* lo, int* hi);
 int pixfmtBytes(int fmt);
+int checkPixfmt(compvhip_ctx* ctx, int fmt, size_t W);   // a format the grayscale kernel converts, at a width it can have
 int checkFxpKernel(compvhip_ctx* ctx, size_t W, size_t H, const uint16_t* vt, const uint16_t* hz, size_t k);
 // How many key slots the line sort covers (the reference sorts lines.size() elements, houghsht.cxx:241-249):
 //   kSortAll   the whole capacity, unused slots zeroed by sht_lines_kernel -- the stream-ordered entry point, which may not wait for the device;
 //   kSortExact the slots in use, read back behind sht_lines_kernel (one stream synchronisation) -- the synchronous step, which ends in one anyway;
 //   otherwise  that many slots (a prediction: the asynchronous step; the caller checks it against the real total later).
 constexpr size_t kSortAll = ~static_cast<size_t>(0), kSortExact = kSortAll - 1;
+struct ShtOpts {
+	bool clearTimeline = true;   // the call starts a new timeline (a step's Canny stage has started it already: false)
+	bool pairsOnly = false;      // stop at the (key, cell) pairs in emission order: no sort, no decode (the host entry point orders them itself)
+	size_t sortN = kSortAll;
+	int* hostSlot = nullptr;     // asynchronous steps: the ticket's pinned slot as the device sees it (ShtArgs::hostStep); nullptr: nothing is reported
+};
 int planShtImpl(compvhip_plan* p, const uint8_t* d_edges, int threshold, int maxLines, compvhip_line* d_lines, size_t lineCap, int32_t* d_counts,
-                hipStream_t st, bool clearTimeline, bool pairsOnly = false, size_t sortN = kSortAll);
+                hipStream_t st, const ShtOpts& o);
 // api_features.cpp
 constexpr size_t kFitMaxSide = 8192;   // the central moments stay below 2^63 up to here
 constexpr int kFitMaxHalfWidth = 8;

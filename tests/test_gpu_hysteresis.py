@@ -5,7 +5,8 @@ The cases come from tests/hysteresis_cases.py; tests/test_hysteresis_cases.py pr
 launches it needs at least.  Every device buffer sits between guard pages and every output starts filled with a sentinel (the arena of
 tests/test_gpu_plan_geometry.py).  A test that claims extra rounds or a replay shows that they happened: with plan.set_timing(1) the
 timeline of the last synchronous call (or of the replay inside compvhip_plan_wait, which runs as a synchronous step) holds one
-"canny_resolve_kernel" entry per launch; COMPVHIP_TRACE_ROUNDS=1 prints what an asynchronous ticket saw."""
+"canny_resolve_kernel" entry per launch; COMPVHIP_TRACE_ROUNDS=1 (read when a plan is made) prints what an asynchronous
+ticket saw."""
 import numpy as np
 import pytest
 

@@ -391,6 +391,43 @@ def test_plan_geometry_sweep(hip_ctx, oracle, W, H, S, F, theta):
         plan.close()
 
 
+def test_second_sht_on_the_plans_masks_clears_the_counters_itself(hip_ctx, oracle):
+    """compvhip_plan_canny zeroes the plan's edge, line and tile counts in its tile kernel, and the compvhip_plan_houghsht(d_edges = 0)
+    behind it relies on that and skips its own fill (countersFresh).  A second SHT on the same masks finds the first one's counts
+    there: it has to clear them itself and return the same lines, counts, edge counts and accumulators.  The smallest two-frame
+    geometry of the table whose frames have edges at all (at W = 17 the reference's column coverage [1, 1) + [16, 16) is empty)."""
+    from compv_amd import capi
+    W, H, S, F, theta = next(g for g in GEOMETRIES if g[3] == 2 and g[0] != 17)
+    assert (W, H) == (13, 70)
+    imgs = make_batch(W, H, F, W * 7 + H * 3 + F)
+    thr = sht_threshold(W, H)
+    e3 = [canny_expect(oracle, img, 3, capi.THRESHOLD_COMPARE_TO_GRADIENT, T_LOW, T_HIGH) for img in imgs]
+    exp = [sht_expect(oracle, m, theta, thr) for m in e3]
+    assert all(len(x[1]) > 0 for x in exp) and all((m != 0).any() for m in e3)   # counts that a missing fill would double
+    R, T, _ = oracle.sht_dims(W, H, theta)
+    A = Arena()
+    host_in = pad_frames(imgs, S, np.random.default_rng(W + H))
+    d_in = A.new(F * H * S, host_in)
+    A.keep(d_in, host_in)
+    d_out = A.new(F * H * S)
+    d_lines = A.new(F * LINE_CAP * 20)
+    d_counts = A.new(F * 4)
+    plan = capi.Plan(hip_ctx, W, H, S, F, theta)
+    try:
+        plan.canny(ptr(d_in), T_LOW, T_HIGH, ptr(d_out))
+        A.check("canny")
+        assert_maps(frames_view(d_out, F, H, S, W), e3, "canny")
+        for what in ("first houghsht(masks)", "second houghsht(masks)"):
+            A.refill(d_lines); A.refill(d_counts)
+            plan.houghsht(0, thr, 0, ptr(d_lines), LINE_CAP, ptr(d_counts))
+            A.check(what)
+            assert_lines(d_lines.cpu().numpy().reshape(F, LINE_CAP, 20), d_counts.cpu().numpy().view(np.int32), [x[1] for x in exp], what)
+            assert edge_counts(plan, F).tolist() == [int((m != 0).sum()) for m in e3], what
+            check_accs(plan, A, F, R, T, [x[0] for x in exp], what)
+    finally:
+        plan.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # the exchange-path batch
 # ---------------------------------------------------------------------------------------------------------------
