@@ -642,6 +642,7 @@ static int planCannyImpl(compvhip_plan* p, StepRun& run, const uint8_t* d_in, fl
 int compvhip_plan_canny(compvhip_plan* p, const uint8_t* d_in, float tLow, float tHigh, int ksize, int type, uint8_t* d_edges, void* stream)
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	if (int rc = refuseBeyondLaunchLimit(p->ctx, p->frames, "compvhip_plan_canny")) return rc;
 	StepRun run;
 	return planCannyImpl(p, run, d_in, tLow, tHigh, ksize, type, d_edges, static_cast<hipStream_t>(stream), true);
 }
@@ -705,7 +706,9 @@ int compvhip_plan_convlt1_fixedpoint(compvhip_plan* p, const uint8_t* d_in, cons
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
-	int rc = checkFxpKernel(ctx, p->W, p->H, vtKern, hzKern, kernSize);
+	int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_convlt1_fixedpoint");
+	if (rc) return rc;
+	rc = checkFxpKernel(ctx, p->W, p->H, vtKern, hzKern, kernSize);
 	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const size_t span = p->S * p->H * p->frames;
@@ -813,6 +816,7 @@ int compvhip_plan_houghsht(compvhip_plan* p, const uint8_t* d_edges, int thresho
                            int32_t* d_counts, void* stream)
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	if (int rc = refuseBeyondLaunchLimit(p->ctx, p->frames, "compvhip_plan_houghsht")) return rc;
 	return planShtImpl(p, d_edges, threshold, maxLines, d_lines, lineCap, d_counts, static_cast<hipStream_t>(stream), ShtOpts());
 }
 
@@ -820,8 +824,10 @@ int compvhip_plan_houghsht(compvhip_plan* p, const uint8_t* d_edges, int thresho
 static int checkStep(compvhip_plan* p, const StepParams& sp)
 {
 	compvhip_ctx* ctx = p->ctx;
+	int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_pipeline");   // the Canny resolve and the SHT stage are not sliced
+	if (rc) return rc;
 	if (!sp.d_in || !sp.d_edges) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
-	const int rc = checkPixfmt(ctx, sp.pixfmt, p->W);   // (COMPVHIP_FMT_Y passes: one byte, any width)
+	rc = checkPixfmt(ctx, sp.pixfmt, p->W);   // (COMPVHIP_FMT_Y passes: one byte, any width)
 	if (rc) return rc;
 	if (sp.d_cart && (!sp.d_lines || !sp.d_counts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "toCartesian needs the line and count buffers");
 	return COMPVHIP_OK;
@@ -1026,8 +1032,10 @@ static int toCartesianImpl(compvhip_plan* p, const compvhip_line* d_lines, const
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_lines || !d_counts || !d_cart) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null pointer");
+	int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_to_cartesian");
+	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	int rc = ensureSht(p);
+	rc = ensureSht(p);
 	if (rc) return rc;
 	const float widthF = static_cast<float>(p->W), heightF = static_cast<float>(p->H);
 	const float r = std::sqrt((widthF * widthF) + (heightF * heightF)); // houghsht.cxx:570
@@ -1048,8 +1056,11 @@ int compvhip_plan_acc(compvhip_plan* p, size_t frame, const uint16_t** d_acc, si
 
 int compvhip_plan_acc_export(compvhip_plan* p, size_t frame, int32_t* d_out, size_t outStride, void* stream)
 {
-	if (!p || !p->shtReady || frame >= p->frames || !d_out || outStride < p->T) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
+	// (a single frame, no frame index in the grid; but no call that fills the accumulators accepts such a plan: there is nothing to export)
+	if (int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_acc_export")) return rc;
+	if (!p->shtReady || frame >= p->frames || !d_out || outStride < p->T) return COMPVHIP_E_INVALID_PARAMETER;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	HIPCHK(ctx, launch_sht_acc_transpose(p->acc + frame * p->accFrameStride, static_cast<int>(p->R), static_cast<int>(p->T), p->accPitch, d_out, outStride,
 	                                     static_cast<hipStream_t>(stream)));

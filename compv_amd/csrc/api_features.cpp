@@ -328,7 +328,9 @@ int compvhip_plan_fast(compvhip_plan* p, const uint8_t* d_gray, int threshold, i
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_gray || !d_counts || (cornerCap && !d_corners)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame / count / corner pointer");
-	int rc = checkFast(ctx, p->W, p->H, fastType);
+	int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_fast");
+	if (rc) return rc;
+	rc = checkFast(ctx, p->W, p->H, fastType);
 	if (rc) return rc;
 	if (misaligned(7, d_gray, d_scores)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames must be 8-byte aligned");
 	if (misaligned(3, d_corners, d_counts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "records and counts must be 4-byte aligned");
@@ -360,9 +362,11 @@ int compvhip_plan_orb_keypoints(compvhip_plan* p, const uint8_t* d_gray, const c
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_gray || !d_corners || !d_cornerCounts || !d_keyCounts || (keyCap && !d_keypoints)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame / corner / count / keypoint pointer");
-	int rc = checkOrb(ctx, p->W, p->H, scale);
+	int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_orb_keypoints");
 	if (rc) return rc;
-	if (cornerCap > static_cast<size_t>(INT32_MAX) || keyCap > static_cast<size_t>(INT32_MAX) || p->frames > 65535) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity beyond 2^31 or more than 65535 frames");
+	rc = checkOrb(ctx, p->W, p->H, scale);
+	if (rc) return rc;
+	if (cornerCap > static_cast<size_t>(INT32_MAX) || keyCap > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity beyond 2^31");
 	if (misaligned(3, d_corners, d_cornerCounts, d_keypoints, d_keyCounts, d_moments, d_gray))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames, records, counts and moments must be 4-byte aligned");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -385,10 +389,12 @@ int compvhip_plan_orb_describe(compvhip_plan* p, const uint8_t* d_gray, const co
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_gray || !d_keypoints || !d_keyCounts || !d_desc || !keyCap) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame / keypoint / count / descriptor pointer or keyCap == 0");
-	int rc = checkOrb(ctx, p->W, p->H, scale);
+	int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_orb_describe");
+	if (rc) return rc;
+	rc = checkOrb(ctx, p->W, p->H, scale);
 	if (rc) return rc;
 	if (descStride < 32 || (descStride & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descStride below 32 or no multiple of 4");
-	if (keyCap > static_cast<size_t>(INT32_MAX) || p->frames > 65535) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity beyond 2^31 or more than 65535 frames");
+	if (keyCap > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity beyond 2^31");
 	if (misaligned(3, d_gray, d_keypoints, d_keyCounts, d_desc))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames, records, counts and descriptors must be 4-byte aligned");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -419,8 +425,8 @@ int compvhip_api::scaleImpl(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, si
                             hipStream_t st)
 {
 	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
-	if (!Wout || !Hout || Wout > 32767 || Hout > 32767 || W > 32767 || H > 32767 || Sout < Wout || Sout > static_cast<size_t>(INT32_MAX) || frames > 65535)
-		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "scale: a size of 0 or beyond 32767, Sout < Wout, or more than 65535 frames");
+	if (!Wout || !Hout || Wout > 32767 || Hout > 32767 || W > 32767 || H > 32767 || Sout < Wout || Sout > static_cast<size_t>(INT32_MAX))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "scale: a size of 0 or beyond 32767, or Sout < Wout");
 	const size_t inSpan = S * H * frames, outSpan = Sout * Hout * frames;
 	if (d_in < d_out + outSpan && d_out < d_in + inSpan) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap");
 	ScaleArgs a;
@@ -436,6 +442,7 @@ int compvhip_plan_scale(compvhip_plan* p, const uint8_t* d_in, uint8_t* d_out, s
 {
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
+	if (int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_scale")) return rc;   // (scaleImpl's other callers: one frame, or a pyramid's, limited at its creation)
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
@@ -564,8 +571,10 @@ int compvhip_orbpyr_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size
 	int rc = checkOrb(ctx, W, H, 1.f);
 	if (!rc) rc = checkFast(ctx, W, H, opts->fastType);
 	if (rc) return rc;
-	if (W > 32767 || H > 32767 || S < W || (S & 7) || !frames || frames > 65535 || !cornerCap || cornerCap > static_cast<size_t>(INT32_MAX))
-		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "pyramid: size beyond 32767, S < W or no multiple of 8, frames outside 1 .. 65535, or cornerCap outside 1 .. 2^31");
+	rc = refuseBeyondLaunchLimit(ctx, frames, "compvhip_orbpyr_create");   // every kernel of the pyramid has the frame index in blockIdx.y / .z
+	if (rc) return rc;
+	if (W > 32767 || H > 32767 || S < W || (S & 7) || !frames || !cornerCap || cornerCap > static_cast<size_t>(INT32_MAX))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "pyramid: size beyond 32767, S < W or no multiple of 8, no frames, or cornerCap outside 1 .. 2^31");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	compvhip_orbpyr* y = new (std::nothrow) compvhip_orbpyr();
 	if (!y) return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "pyramid");
@@ -796,7 +805,8 @@ int compvhip_matcher_create(compvhip_ctx* ctx, size_t descBytes, size_t queryCap
 	*out = nullptr;
 	if (descBytes < 4 || descBytes > 4 * static_cast<size_t>(kMatchMaxDwords) || (descBytes & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descBytes must be a multiple of 4 in 4..128");
 	if (knn < 1 || knn > kMatchMaxKnn) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "knn must be in 1..8");
-	if (!queryCap || !trainCap || !pairs || queryCap > kMatchMaxCap || trainCap > kMatchMaxCap || pairs > 65535) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity out of range");
+	if (int rc = refuseBeyondLaunchLimit(ctx, pairs, "compvhip_matcher_create (pairs)")) return rc;   // a pair is the matcher's frame: blockIdx.y / .z
+	if (!queryCap || !trainCap || !pairs || queryCap > kMatchMaxCap || trainCap > kMatchMaxCap) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity out of range");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	compvhip_matcher* m = new (std::nothrow) compvhip_matcher();
 	if (!m) return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "matcher");

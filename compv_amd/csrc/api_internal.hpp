@@ -5,6 +5,7 @@
 #include "kernels.hpp"
 #include "kht.hpp"
 #include "device_memory.hpp"
+#include "frame_slices.hpp"
 #include "step_policy.hpp"
 
 #include <hip/hip_runtime.h>
@@ -266,6 +267,15 @@ inline int fail(compvhip_ctx* ctx, int code, const char* what, hipError_t e = hi
 		if (e != hipSuccess) { ctx->err += ": "; ctx->err += hipGetErrorString(e); }
 	}
 	return code;
+}
+
+// Batches beyond kMaxFramesPerLaunch frames (frame_slices.hpp; include/compv_hip.h, "Batches beyond 65 535 frames").  A call whose launchers carry the frame
+// index in blockIdx.y / .z without slicing refuses such a batch here, BEFORE it allocates or enqueues anything: the answer never depends on what the runtime
+// makes of an oversized grid, and a sequence of launches never runs behind a rejected first one.  `what`: the call, for the message.
+inline int refuseBeyondLaunchLimit(compvhip_ctx* ctx, size_t frames, const char* what)
+{
+	if (frames <= static_cast<size_t>(kMaxFramesPerLaunch)) return COMPVHIP_OK;
+	return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, (std::string(what) + ": more than " + std::to_string(kMaxFramesPerLaunch) + " frames in one batch").c_str());
 }
 
 #define HIPCHK(ctx, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail((ctx), COMPVHIP_E_HIP, #call, e__); } while (0)

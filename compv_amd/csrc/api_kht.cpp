@@ -642,6 +642,7 @@ static int khtPlanEntry(compvhip_plan* p, const uint8_t* d_edges, float rho, flo
                         size_t clusterMinSize, double kernelMinHeight, int order, compvhip_line* lines, size_t cap, size_t* counts, double* gs, int hostThreads)
 {
 	compvhip_ctx* ctx = p->ctx;
+	if (int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_houghkht")) return rc;
 	if (!d_edges || !counts || (cap && !lines)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
 	const size_t W = p->W, H = p->H, S = p->S, F = p->frames;
 	KhtAxes ax;

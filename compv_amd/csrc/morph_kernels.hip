@@ -10,6 +10,7 @@
 // every row starts on a dword.  Columns >= W are read (they only ever feed border cells, whose value does not depend on them) and
 // never written.
 #include "device.hpp"
+#include "frame_slices.hpp"
 
 namespace compvhip {
 
@@ -46,12 +47,19 @@ __global__ __launch_bounds__(256) void threshold_kernel(ThreshArgs a)
 	else { storeRow4(row, x0, a.W, q.x); storeRow4(row, x0 + 4, a.W, q.y); }
 }
 
-hipError_t launch_threshold(const ThreshArgs& a, int frames, hipStream_t stream)
+hipError_t launch_threshold(const ThreshArgs& args, int frames, hipStream_t stream)
 {
-	const int groups = (a.W + 7) >> 3;
-	const long long total = static_cast<long long>(groups) * a.H;
-	hipLaunchKernelGGL(threshold_kernel, dim3(static_cast<unsigned>((total + 255) / 256), 1, frames), dim3(256), 0, stream, a);
-	return hipGetLastError();
+	const int groups = (args.W + 7) >> 3;
+	const long long total = static_cast<long long>(groups) * args.H;
+	if ((total + 255) / 256 > INT32_MAX) return hipErrorInvalidValue;
+	// the frame index rides in blockIdx.z: a slice starts at its own frame's planes and level
+	return for_frame_slices(frames, [&](int f0, int nf) {
+		ThreshArgs a = args;
+		a.in += static_cast<size_t>(f0) * a.frameStride; a.out += static_cast<size_t>(f0) * a.frameStride;
+		if (a.levels) a.levels += f0;
+		hipLaunchKernelGGL(threshold_kernel, dim3(static_cast<unsigned>((total + 255) / 256), 1, nf), dim3(256), 0, stream, a);
+		return hipGetLastError();
+	});
 }
 
 // ---- adaptive threshold ---------------------------------------------------------------------------------------------------------------
@@ -120,11 +128,15 @@ __global__ __launch_bounds__(256) void threshold_adaptive_kernel(AdaptArgs a)
 	}
 }
 
-hipError_t launch_threshold_adaptive(const AdaptArgs& a, int frames, hipStream_t stream)
+hipError_t launch_threshold_adaptive(const AdaptArgs& args, int frames, hipStream_t stream)
 {
-	if (a.r < 1 || a.r > 15) return hipErrorInvalidValue;
-	hipLaunchKernelGGL(threshold_adaptive_kernel, dim3((a.W + kAdTW - 1) / kAdTW, (a.H + kAdTH - 1) / kAdTH, frames), dim3(256), 0, stream, a);
-	return hipGetLastError();
+	if (args.r < 1 || args.r > 15) return hipErrorInvalidValue;
+	return for_frame_slices(frames, [&](int f0, int nf) {   // (blockIdx.z, as above)
+		AdaptArgs a = args;
+		a.in += static_cast<size_t>(f0) * a.frameStride; a.out += static_cast<size_t>(f0) * a.frameStride;
+		hipLaunchKernelGGL(threshold_adaptive_kernel, dim3((a.W + kAdTW - 1) / kAdTW, (a.H + kAdTH - 1) / kAdTH, nf), dim3(256), 0, stream, a);
+		return hipGetLastError();
+	});
 }
 
 // ---- morphology ----------------------------------------------------------------------------------------------------------------------
@@ -241,9 +253,9 @@ __global__ __launch_bounds__(256) void morph_separable_kernel(MorphArgs a)
 	}
 }
 
-hipError_t launch_morph(const MorphArgs& a, int frames, hipStream_t stream)
+// at most kMaxFramesPerLaunch frames: the frame index rides in blockIdx.z
+static hipError_t launch_morph_slice(const MorphArgs& a, int frames, hipStream_t stream)
 {
-	if (a.sw < 1 || a.sw > kMorphMaxStrel || a.sh < 1 || a.sh > kMorphMaxStrel || !(a.sw & 1) || !(a.sh & 1)) return hipErrorInvalidValue;
 	const dim3 grid((a.W + kMoTW - 1) / kMoTW, (a.H + kMoTH - 1) / kMoTH, frames), block(256);
 	if (a.kind == kMorphRect) {
 		if (a.dilate) hipLaunchKernelGGL((morph_separable_kernel<true, false>), grid, block, 0, stream, a);
@@ -258,6 +270,16 @@ hipError_t launch_morph(const MorphArgs& a, int frames, hipStream_t stream)
 		else hipLaunchKernelGGL((morph_general_kernel<false>), grid, block, 0, stream, a);
 	}
 	return hipGetLastError();
+}
+
+hipError_t launch_morph(const MorphArgs& args, int frames, hipStream_t stream)
+{
+	if (args.sw < 1 || args.sw > kMorphMaxStrel || args.sh < 1 || args.sh > kMorphMaxStrel || !(args.sw & 1) || !(args.sh & 1)) return hipErrorInvalidValue;
+	return for_frame_slices(frames, [&](int f0, int nf) {
+		MorphArgs a = args;
+		a.in += static_cast<size_t>(f0) * a.frameStride; a.out += static_cast<size_t>(f0) * a.frameStride;
+		return launch_morph_slice(a, nf, stream);
+	});
 }
 
 } // namespace compvhip

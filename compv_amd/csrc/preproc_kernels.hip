@@ -10,6 +10,7 @@
 //
 // Both are pure streaming kernels (HBM-bound): grayscale reads bpp B/px and writes 1 B/px; the histogram reads 1 B/px.
 #include "kernels.hpp"
+#include "frame_slices.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -93,7 +94,8 @@ __global__ __launch_bounds__(256) void gray_kernel(GrayArgs a)
 	*reinterpret_cast<uint2*>(a.out + ((size_t)frame * a.H + y) * (size_t)a.So + (size_t)g8 * 8) = o;
 }
 
-hipError_t launch_gray(const GrayArgs& a, int fmt, int frames, hipStream_t stream)
+// at most kMaxFramesPerLaunch frames: the frame index rides in blockIdx.z
+static hipError_t launch_gray_slice(const GrayArgs& a, int fmt, int frames, hipStream_t stream)
 {
 	const int groups = (a.W + 7) / 8;
 	dim3 grid((groups + 255) / 256, a.H, frames), block(256);
@@ -107,6 +109,17 @@ hipError_t launch_gray(const GrayArgs& a, int fmt, int frames, hipStream_t strea
 	default: return hipErrorInvalidValue;
 	}
 	return hipGetLastError();
+}
+
+hipError_t launch_gray(const GrayArgs& args, int fmt, int frames, hipStream_t stream)
+{
+	const int bpp = fmt < COMPVHIP_FMT_RGBA32 ? 0 : (fmt <= COMPVHIP_FMT_BGRA32 ? 4 : (fmt <= COMPVHIP_FMT_BGR24 ? 3 : (fmt == COMPVHIP_FMT_Y ? 1 : 2)));   // gray_kernel's
+	return for_frame_slices(frames, [&](int f0, int nf) {   // a slice starts at its own frame's samples (bpp bytes each) and luma bytes
+		GrayArgs a = args;
+		a.in += (size_t)f0 * a.H * (size_t)a.S * bpp;
+		a.out += (size_t)f0 * a.H * (size_t)a.So;
+		return launch_gray_slice(a, fmt, nf, stream);
+	});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -273,10 +286,18 @@ int otsu_hist_chunks(int H, int frames)
 hipError_t launch_otsu(const uint8_t* in, int W, int H, int S, size_t frameStride, int frames, float fLowFactor, float fHighFactor, uint32_t* hist,
                        int32_t* otsu, void* thr, hipStream_t stream)
 {
-	const int chunks = otsu_hist_chunks(H, frames);
-	hipLaunchKernelGGL(hist256_kernel, dim3(chunks, frames), dim3(kHistThreads), 0, stream, in, W, H, S, frameStride, hist);
-	hipLaunchKernelGGL(otsu_kernel, dim3(frames), dim3(256), 0, stream, hist, chunks, W * H, fLowFactor, fHighFactor, otsu, reinterpret_cast<int2*>(thr));
-	return hipGetLastError();
+	const int chunks = otsu_hist_chunks(H, frames);   // of the whole batch: every slice leaves the same partial histograms per frame
+	// The histogram kernel has the frame index in blockIdx.y; otsu_kernel has it in x, but runs slice by slice behind "its" histograms all the same, so that
+	// a slice whose first launch fails is never followed by levels computed from histograms that were not written
+	return for_frame_slices(frames, [&](int f0, int nf) {
+		uint32_t* const h = hist + (size_t)f0 * chunks * 256;
+		hipLaunchKernelGGL(hist256_kernel, dim3(chunks, nf), dim3(kHistThreads), 0, stream, in + (size_t)f0 * frameStride, W, H, S, frameStride, h);
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+		hipLaunchKernelGGL(otsu_kernel, dim3(nf), dim3(256), 0, stream, h, chunks, W * H, fLowFactor, fHighFactor, otsu ? otsu + f0 : nullptr,
+		                   thr ? reinterpret_cast<int2*>(thr) + f0 : nullptr);
+		return hipGetLastError();
+	});
 }
 
 } // namespace compvhip

@@ -20,6 +20,7 @@
 // This file: foreign edge maps -> bit masks, sht_nms_kernel / sht_lines_kernel, the library key sort + sht_decode_kernel (the
 // fallback of sht_sort_kernels.hip), sht_cartesian_kernel, the accumulator export.
 #include "kernels.hpp"
+#include "frame_slices.hpp"
 
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -449,9 +450,13 @@ __global__ __launch_bounds__(256) void sht_acc_transpose_kernel(const uint16_t* 
 hipError_t launch_bytes_to_bits(const uint8_t* edges, int W, int H, int S, size_t frameStride, uint32_t* ebits, int wb, size_t bitsFrameStride,
                                 int frames, hipStream_t stream)
 {
-	dim3 grid((wb + 255) / 256, H, frames);
-	hipLaunchKernelGGL(bytes_to_bits_kernel, grid, dim3(256), 0, stream, edges, W, H, S, frameStride, ebits, wb, bitsFrameStride);
-	return hipGetLastError();
+	// the frame index rides in blockIdx.z: a slice starts at its own frame's bytes and words
+	return for_frame_slices(frames, [&](int f0, int nf) {
+		dim3 grid((wb + 255) / 256, H, nf);
+		hipLaunchKernelGGL(bytes_to_bits_kernel, grid, dim3(256), 0, stream, edges + (size_t)f0 * frameStride, W, H, S, frameStride,
+		                   ebits + (size_t)f0 * bitsFrameStride, wb, bitsFrameStride);
+		return hipGetLastError();
+	});
 }
 
 int sht_nms_groups(int T) { return (T + kNmsCols - 1) / kNmsCols; }

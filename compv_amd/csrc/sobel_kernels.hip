@@ -206,6 +206,9 @@ static hipError_t launch_op(const EdgeDeteArgs& a0, int frames, hipStream_t stre
 	a.tilesX = (a.W + kEdCols - 1) / kEdCols;
 	a.tilesY = (a.H + kEdRows - 1) / kEdRows;
 	a.blockRows = a.tilesY;
+	// frames ride in the x extent only (xcd_tile_map): any batch whose workgroup index and counter offset (frame * kFrameSlot) stay ints
+	const long long workgroups = 8 * ((static_cast<long long>(a.blockRows) * frames + 7) / 8) * a.tilesX;
+	if (frames < 1 || frames > INT32_MAX / kFrameSlot || workgroups > INT32_MAX) return hipErrorInvalidValue;
 	a.groups = a.blockRows * frames;
 	hipError_t e = hipMemsetAsync(a.gmax, 0, sizeof(unsigned int) * frames * kFrameSlot, stream);
 	if (e != hipSuccess) return e;

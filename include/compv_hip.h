@@ -213,34 +213,48 @@ COMPVHIP_API int compvhip_host_cpu_budget(void);
  * Q16 sin/cos tables for thetaDeg.  Frames are independent units: one plan per GPU, shard frames across GPUs. */
 COMPVHIP_API int compvhip_plan_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size_t frames, float thetaDeg,
                                       compvhip_plan** plan);
+/* Batches beyond 65 535 frames.  A plan may hold any number of frames, but most kernels carry the frame index in a grid dimension that holds at most
+ * 65 535 (blockIdx.y / .z).  Every plan-form call therefore belongs to one of three classes, named beside it below, and the host decides which before
+ * the call allocates or enqueues anything (never by what the runtime makes of an oversized grid):
+ *   SLICED          the call launches its kernels in slices of at most 65 535 frames; any frame count gives what the same frames give in smaller batches.
+ *   FRAMES IN X     the frame index rides in the x extent (up to 2^31 - 1 workgroups): no limit of its own.
+ *   REFUSED         beyond 65 535 frames the call returns COMPVHIP_E_INVALID_PARAMETER, compvhip_last_error names the limit, nothing is allocated, enqueued
+ *                   or written.  Split the batch across plans of at most 65 535 frames.
+ * The text-detection chain (grayscale, otsu, threshold, threshold_adaptive, morph, components on the caller's bytes), the segment and fit calls on the
+ * caller's bytes, and remap / warp_inverse are SLICED; edge_dete has its FRAMES IN X; Canny and everything that needs its masks, the SHT, the batched KHT, the
+ * fixed-point blur, FAST, ORB and the bilinear scale are REFUSED, as are a compvhip_orbpyr of more than 65 535 frames and a compvhip_matcher of more than
+ * 65 535 pairs at their creation. */
 /* A plan must be destroyed BEFORE its context (it keeps a pointer to it); compvhip_ctx_destroy only releases the private
  * single-frame plan of the host entry points. */
 COMPVHIP_API void compvhip_plan_destroy(compvhip_plan* plan);
 
 /* Canny on `frames` device frames: d_in -> d_edges (both frames*S*H bytes, may alias).  Asynchronous on `stream`
- * (a hipStream_t; NULL = default stream) except for the hysteresis convergence check, which polls a device flag. */
+ * (a hipStream_t; NULL = default stream) except for the hysteresis convergence check, which polls a device flag.
+ * Beyond 65 535 frames: REFUSED (the resolve rounds index their change flags by the launch's frame extent). */
 COMPVHIP_API int compvhip_plan_canny(compvhip_plan* plan, const uint8_t* d_in, float tLow, float tHigh, int ksize,
                                      int thresholdType, uint8_t* d_edges, void* stream);
 
-/* compvhip_grayscale_u8 on `frames` device frames: d_in = [frames][H][S samples], d_gray = [frames][H][S].  Asynchronous. */
+/* compvhip_grayscale_u8 on `frames` device frames: d_in = [frames][H][S samples], d_gray = [frames][H][S].  Asynchronous.
+ * Beyond 65 535 frames: SLICED. */
 COMPVHIP_API int compvhip_plan_grayscale(compvhip_plan* plan, const uint8_t* d_in, int pixfmt, uint8_t* d_gray, void* stream);
 
-/* compvhip_otsu_u8 on `frames` device frames: d_thresholds[f] = Otsu level of frame f (device array).  Asynchronous. */
+/* compvhip_otsu_u8 on `frames` device frames: d_thresholds[f] = Otsu level of frame f (device array).  Asynchronous.
+ * Beyond 65 535 frames: SLICED (histograms and levels slice by slice). */
 COMPVHIP_API int compvhip_plan_otsu(compvhip_plan* plan, const uint8_t* d_gray, int32_t* d_thresholds, void* stream);
 
 /* compvhip_convlt1_fixedpoint_u8 on `frames` device frames (vtKern/hzKern are HOST arrays of kernSize weights); d_in and
- * d_out may alias.  Asynchronous. */
+ * d_out may alias.  Asynchronous.  Beyond 65 535 frames: REFUSED. */
 COMPVHIP_API int compvhip_plan_convlt1_fixedpoint(compvhip_plan* plan, const uint8_t* d_in, const uint16_t* vtKern, const uint16_t* hzKern,
                                                   size_t kernSize, uint8_t* d_out, void* stream);
 
 /* CompVHoughSht::toCartesian (core/features/hough/compv_core_feature_houghsht.cxx:264-304,566-589) on the device line arrays a
  * compvhip_plan_houghsht / _pipeline call produced: d_cart[f][i] = {a.x, a.y, b.x, b.y} of line i of frame f (a.z = b.z = 1), for
- * i < min(d_counts[f], lineCap).  Asynchronous. */
+ * i < min(d_counts[f], lineCap).  Asynchronous.  Beyond 65 535 frames: REFUSED (like the calls that produce such line arrays). */
 COMPVHIP_API int compvhip_plan_to_cartesian(compvhip_plan* plan, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap,
                                             float* d_cart, void* stream);
 
 /* Sobel / Scharr / Prewitt detector (compvhip_edge_dete_u8 semantics) on `frames` device frames; d_in and d_out must
- * not alias.  Fully asynchronous on `stream`. */
+ * not alias.  Fully asynchronous on `stream`.  Beyond 65 535 frames: FRAMES IN X. */
 COMPVHIP_API int compvhip_plan_edge_dete(compvhip_plan* plan, const uint8_t* d_in, int op, uint8_t* d_out, void* stream);
 
 /* SHT on the edge maps produced by the last compvhip_plan_canny() of this plan (uses its 1-bit edge masks, no byte
@@ -250,11 +264,13 @@ COMPVHIP_API int compvhip_plan_edge_dete(compvhip_plan* plan, const uint8_t* d_i
  * before clipping to lineCap).  The call is asynchronous and cannot grow its buffers after the fact: the device key buffer holds
  * min(R*T, max(lineCap, 65536)) candidates per frame, so whatever lineCap is, the lineCap STRONGEST lines are returned as long as
  * d_counts[f] <= max(lineCap, 65536); beyond that the key buffer overflowed and frame f's lines are an arbitrary subset -- call
- * again with lineCap >= d_counts[f] (the host entry point compvhip_houghsht_u8 does that by itself). */
+ * again with lineCap >= d_counts[f] (the host entry point compvhip_houghsht_u8 does that by itself).
+ * Beyond 65 535 frames: REFUSED (the whole SHT stage; its key buffers alone would run to gigabytes). */
 COMPVHIP_API int compvhip_plan_houghsht(compvhip_plan* plan, const uint8_t* d_edges, int threshold, int maxLines,
                                         compvhip_line* d_lines, size_t lineCap, int32_t* d_counts, void* stream);
 
-/* Sobel -> Canny -> HoughSHT in one call (the benchmark's "step"). */
+/* Sobel -> Canny -> HoughSHT in one call (the benchmark's "step").  Beyond 65 535 frames: REFUSED, like compvhip_plan_pipeline_async and
+ * compvhip_plan_pipeline_ex (Canny and the SHT are). */
 COMPVHIP_API int compvhip_plan_pipeline(compvhip_plan* plan, const uint8_t* d_in, float tLow, float tHigh,
                                         int threshold, int maxLines, uint8_t* d_edges,
                                         compvhip_line* d_lines, size_t lineCap, int32_t* d_counts, void* stream);
@@ -315,7 +331,8 @@ COMPVHIP_API int compvhip_plan_pipeline_ex(compvhip_plan* plan, const uint8_t* d
  * than cap lines (counts[f] tells); on any other failure the error text names the frame.  clusterMinSize must be >= 2 (for 1 the reference's
  * cluster subdivision does not terminate: a defined deviation, also of compvhip_houghkht_u8 / compvhip_houghkht_kernels_u8).
  * compvhip_plan_houghkht_stage_ms: the six stage clocks of the last call summed over its frames (compvhip_houghkht_stage_ms order), the wall
- * time of the call and the number of workers. */
+ * time of the call and the number of workers.
+ * Beyond 65 535 frames: REFUSED (compvhip_plan_houghkht_ex as well). */
 COMPVHIP_API int compvhip_plan_houghkht(compvhip_plan* plan, const uint8_t* d_edges, float rho, float thetaDeg, int threshold, int maxLines,
                                         double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight,
                                         compvhip_line* lines, size_t cap, size_t* counts, double* gs, int hostThreads);
@@ -360,7 +377,8 @@ COMPVHIP_API int compvhip_houghkht_ex_u8(compvhip_ctx* ctx, const uint8_t* edges
  * theta-major [T][accPitch] (pitch >= R).  compvhip_plan_acc_export gives the reference's int32 rho-major layout. */
 COMPVHIP_API int compvhip_plan_acc(compvhip_plan* plan, size_t frame, const uint16_t** d_acc, size_t* R, size_t* T, size_t* accPitch);
 /* Copies the accumulator of frame f into a caller DEVICE buffer in the reference layout: int32 [R][outStride]
- * (outStride >= T), i.e. acc[(barrier - rho) * outStride + t] (houghsht.cxx:430-431). */
+ * (outStride >= T), i.e. acc[(barrier - rho) * outStride + t] (houghsht.cxx:430-431).  Beyond 65 535 frames: REFUSED (one frame per call, but no
+ * call that fills the accumulators accepts such a plan). */
 COMPVHIP_API int compvhip_plan_acc_export(compvhip_plan* plan, size_t frame, int32_t* d_out, size_t outStride, void* stream);
 /* Number of edge pixels per frame voted by the last houghsht / pipeline step of this plan (device int32[frames]).  The SHT's voting
  * kernel counts them: a compvhip_plan_canny call alone resets them to zero, and before the plan's first SHT the call is refused. */
@@ -392,7 +410,7 @@ typedef struct compvhip_segment {
  * above are written, so a clipped result is a prefix of the full one.  Asynchronous on `stream` (the plan's SHT tables and a scratch array of
  * frames * min(lineCap, maxLines) counters are allocated on first use).  COMPVHIP_E_INVALID_STATE while the plan has asynchronous steps that
  * were not waited for (a replayed step rewrites d_lines later); COMPVHIP_E_INVALID_PARAMETER for minLength < 1, maxGap < 0, lineCap == 0 or
- * segCap == 0. */
+ * segCap == 0.  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there. */
 COMPVHIP_API int compvhip_plan_houghsht_segments(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts,
                                                  size_t lineCap, int maxLines, int minLength, int maxGap,
                                                  compvhip_segment* d_segs, size_t segCap, int32_t* d_segCounts, void* stream);
@@ -444,7 +462,7 @@ typedef struct compvhip_line_fit {
  * only).  d_refined: NULL, or frames * lineCap lines, of which the lines considered are written -- it feeds compvhip_plan_to_cartesian with the
  * same d_counts and lineCap; COMPVHIP_E_INVALID_PARAMETER in per-segment mode.  halfWidth outside 0 .. 8, lineCap == 0 or a null line / count
  * buffer: COMPVHIP_E_INVALID_PARAMETER; max(W, H) > 8192: COMPVHIP_E_NOT_IMPLEMENTED.  Asynchronous on `stream`; no scratch beyond the
- * plan's SHT tables. */
+ * plan's SHT tables.  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there. */
 COMPVHIP_API int compvhip_plan_houghsht_fit(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts,
                                             size_t lineCap, int maxLines, int halfWidth,
                                             const compvhip_segment* d_segs, const int32_t* d_segCounts, size_t segCap,
@@ -484,7 +502,7 @@ typedef struct compvhip_component {
  * with compCap == 0: counts only.  Bad connectivity, minPixels < 1, labelStride < W (with a label map): COMPVHIP_E_INVALID_PARAMETER.
  * Asynchronous on `stream`.  Scratch is owned by the plan and allocated on first use: frames * H int32, for byte maps a mask copy
  * (frames * H * wb words, 1/8 of the bytes), and -- only when d_labels == NULL -- one int32 parent word per pixel (frames * W * H * 4 bytes:
- * 33 MB per 4K frame); with a label map the parent words live in it (labelled in place). */
+ * 33 MB per 4K frame); with a label map the parent words live in it (labelled in place).  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there. */
 COMPVHIP_API int compvhip_plan_components(compvhip_plan* plan, const uint8_t* d_edges, int connectivity, int minPixels,
                                           int32_t* d_labels, size_t labelStride, compvhip_component* d_comps, size_t compCap,
                                           int32_t* d_compCounts, void* stream);
@@ -526,7 +544,7 @@ COMPVHIP_API int compvhip_threshold_u8(compvhip_ctx* ctx, const uint8_t* in, siz
                                        uint8_t* out, size_t So);
 /* The same on `frames` device frames.  d_levels != NULL: frame f is cut at d_levels[f] clipped to 0..255 and `threshold` is ignored --
  * the array compvhip_plan_otsu writes, so Otsu + binarise is CompVImage::thresholdOtsu(input, t, &output) (compv_image_threshold.cxx:110-113)
- * without a host round trip.  d_in and d_out may be the same buffer.  Columns >= W of d_out are never written. */
+ * without a host round trip.  d_in and d_out may be the same buffer.  Columns >= W of d_out are never written.  Beyond 65 535 frames: SLICED. */
 COMPVHIP_API int compvhip_plan_threshold(compvhip_plan* plan, const uint8_t* d_in, double threshold, const int32_t* d_levels,
                                          uint8_t* d_out, void* stream);
 
@@ -541,7 +559,8 @@ COMPVHIP_API int compvhip_plan_threshold(compvhip_plan* plan, const uint8_t* d_i
 COMPVHIP_API int compvhip_threshold_adaptive_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, size_t blockSize,
                                                 double delta, double maxVal, int invert, uint8_t* out, size_t So);
 /* The same on `frames` device frames, one fused kernel: the mean never reaches memory.  d_in == d_out is served through a plane the plan owns
- * (allocated on first use) and a device copy; any other overlap: COMPVHIP_E_INVALID_PARAMETER.  Columns >= W of d_out are never written. */
+ * (allocated on first use) and a device copy; any other overlap: COMPVHIP_E_INVALID_PARAMETER.  Columns >= W of d_out are never written.
+ * Beyond 65 535 frames: SLICED (in place, the device copy is one enqueue per frame). */
 COMPVHIP_API int compvhip_plan_threshold_adaptive(compvhip_plan* plan, const uint8_t* d_in, size_t blockSize, double delta, double maxVal,
                                                   int invert, uint8_t* d_out, void* stream);
 
@@ -564,7 +583,7 @@ COMPVHIP_API int compvhip_morph_strel(int type, size_t w, size_t h, uint8_t* str
 COMPVHIP_API int compvhip_morph_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint8_t* strel, size_t sw,
                                    size_t sh, int op, int border, uint8_t* out, size_t So);
 /* The same on `frames` device frames (strel is a HOST array).  An OPEN / CLOSE is two launches through a u8 plane [frames][H][S] the plan owns
- * (allocated on first use).  Columns >= W of d_out are never written. */
+ * (allocated on first use).  Columns >= W of d_out are never written.  Beyond 65 535 frames: SLICED (compvhip_plan_morph_ex as well). */
 COMPVHIP_API int compvhip_plan_morph(compvhip_plan* plan, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op,
                                      int border, uint8_t* d_out, void* stream);
 /* compvhip_plan_morph with the kernel named (COMPVHIP_MORPH_KERNEL_*): for measuring one kernel against the other and for testing both on
@@ -605,7 +624,7 @@ typedef struct compvhip_corner {
 /* Corners of all frames of the plan.  d_gray: [frames][H][S]; d_scores: NULL or a score map of the same geometry (8-byte aligned, must not
  * overlap d_gray); d_corners and d_counts: 4-byte aligned (anything else: COMPVHIP_E_INVALID_PARAMETER); d_corners == NULL with cornerCap == 0: counts only.  Asynchronous on `stream`; results are deterministic run to run.  Scratch
  * is owned by the plan, allocated on first use and released with it: frames * (2 * H + 257) int32, and -- only when d_scores == NULL -- a score
- * map of the plan's own. */
+ * map of the plan's own.  Beyond 65 535 frames: REFUSED. */
 COMPVHIP_API int compvhip_plan_fast(compvhip_plan* plan, const uint8_t* d_gray, int threshold, int fastType, int nonmax, int maxFeatures,
                                     uint8_t* d_scores, compvhip_corner* d_corners, size_t cornerCap, int32_t* d_counts, void* stream);
 
@@ -646,7 +665,8 @@ typedef struct compvhip_matcher compvhip_matcher;   /* scratch for `pairs` pairs
  * is allocated here -- pairs * max(ceil(trainCap / 128) * knn * queryCap, ceil(queryCap / 128) * trainCap) key words (the forward and the
  * reverse run share them) and pairs * trainCap records --
  * and released by compvhip_matcher_destroy: no later call allocates or synchronises.  Destroy a matcher BEFORE its context.  Like a plan, a
- * matcher is not re-entrant: its calls share the scratch and must be ordered on one stream. */
+ * matcher is not re-entrant: its calls share the scratch and must be ordered on one stream.  More than 65 535 pairs: REFUSED (a pair is the
+ * matcher's frame). */
 COMPVHIP_API int compvhip_matcher_create(compvhip_ctx* ctx, size_t descBytes, size_t queryCap, size_t trainCap, size_t pairs, int knn,
                                          compvhip_matcher** matcher);
 COMPVHIP_API void compvhip_matcher_destroy(compvhip_matcher* matcher);
@@ -726,7 +746,7 @@ typedef struct compvhip_keypoint {   /* CompVInterestPoint (compv_common.h:629),
  * device).  d_gray: [frames][H][S], 4-byte aligned; d_keypoints: [frames][keyCap] (NULL with keyCap == 0: counts only); d_moments: NULL or
  * [frames][keyCap][2] int32 = {m01, m10}; records, counts and moments 4-byte aligned; scale > 0 (anything else: COMPVHIP_E_INVALID_PARAMETER).
  * Asynchronous on `stream`, no atomic, deterministic.  Scratch is owned by the plan, allocated on first use (and again for a larger keyCap) and
- * released with it: frames * keyCap int32. */
+ * released with it: frames * keyCap int32.  Beyond 65 535 frames: REFUSED. */
 COMPVHIP_API int compvhip_plan_orb_keypoints(compvhip_plan* plan, const uint8_t* d_gray, const compvhip_corner* d_corners, size_t cornerCap,
                                              const int32_t* d_cornerCounts, int level, float scale, compvhip_keypoint* d_keypoints, size_t keyCap,
                                              int32_t* d_keyCounts, int32_t* d_moments, void* stream);
@@ -734,7 +754,7 @@ COMPVHIP_API int compvhip_plan_orb_keypoints(compvhip_plan* plan, const uint8_t*
 /* Descriptors of the keypoints (compvhip_plan_orb_keypoints' or the caller's own) with the level's `scale`.  descStride >= 32 and a multiple of 4,
  * d_desc 4-byte aligned, keyCap > 0 (anything else: COMPVHIP_E_INVALID_PARAMETER).  With descStride == 32, d_desc / d_keyCounts are what
  * compvhip_matcher_knn takes as d_query / d_queryCounts.  Asynchronous on `stream`.  Scratch, allocated on first use with blur != 0: one blurred
- * batch [frames][H][S]. */
+ * batch [frames][H][S].  Beyond 65 535 frames: REFUSED. */
 COMPVHIP_API int compvhip_plan_orb_describe(compvhip_plan* plan, const uint8_t* d_gray, const compvhip_keypoint* d_keypoints, size_t keyCap,
                                             const int32_t* d_keyCounts, float scale, int blur, uint8_t* d_desc, size_t descStride, void* stream);
 
@@ -795,7 +815,7 @@ typedef struct compvhip_orbpyr_opts {
  * (first describe); ONE corner list [frames][cornerCap] and ONE FAST score map [frames][H][S] that the levels use in turn, with FAST's
  * frames * (2 * H + 257) int32; frames * keyCap int32 source indices (first detect, again for a larger keyCap); (3 * levels + 1) * frames int32
  * counts.  cornerCap >= 1.  Destroy a pyramid BEFORE its context; compvhip_live_allocations then returns to its earlier value.  Like a plan,
- * a pyramid is not re-entrant: its calls share the scratch and must be ordered on one stream. */
+ * a pyramid is not re-entrant: its calls share the scratch and must be ordered on one stream.  More than 65 535 frames: REFUSED. */
 COMPVHIP_API int compvhip_orbpyr_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size_t frames, const compvhip_orbpyr_opts* opts, size_t cornerCap,
                                         compvhip_orbpyr** pyramid);
 COMPVHIP_API void compvhip_orbpyr_destroy(compvhip_orbpyr* pyramid);
@@ -814,7 +834,8 @@ COMPVHIP_API int compvhip_orbpyr_detect(compvhip_orbpyr* pyramid, const uint8_t*
 COMPVHIP_API int compvhip_orbpyr_describe(compvhip_orbpyr* pyramid, const uint8_t* d_gray, int reusePlanes, const compvhip_keypoint* d_keypoints, size_t keyCap,
                                           const int32_t* d_keyCounts, uint8_t* d_desc, size_t descStride, void* stream);
 /* A. for every frame of a plan: d_in [frames][H][S] of the plan's geometry -> d_out [frames][Hout][Sout] (Sout >= Wout; sizes up to 32767; the
- * buffers must not overlap).  A destination that is dword-aligned in pointer and stride is written with dword stores.  Asynchronous on `stream`. */
+ * buffers must not overlap).  A destination that is dword-aligned in pointer and stride is written with dword stores.  Asynchronous on `stream`.
+ * Beyond 65 535 frames: REFUSED. */
 COMPVHIP_API int compvhip_plan_scale(compvhip_plan* src, const uint8_t* d_in, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
 /* A. for one HOST plane (sizes 1 .. 32767).  Synchronous. */
 COMPVHIP_API int compvhip_scale_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint8_t* out, size_t Wout, size_t Hout, size_t Sout);
@@ -868,13 +889,14 @@ COMPVHIP_API int compvhip_warp_tables(const float* M, int rows, size_t Wout, siz
 /* Remap for every frame of a plan: d_in [frames][H][S] of the plan's geometry -> d_out [frames][Hout][Sout], uint8 or (COMPVHIP_INTERP_BILINEAR_FLOAT32)
  * float32.  d_mapX, d_mapY: device, [mapCount][Hout * Wout] float32 each; mapCount == 1: all frames share the map (a workgroup then reads its part of
  * the map once for 8 frames); mapCount == frames: one map per frame.  roi == NULL: the whole frame.  A destination that is aligned in pointer, stride
- * and frame size (4 bytes for uint8, 16 for float32) is written with vector stores.  Asynchronous on `stream`, never synchronises the host. */
+ * and frame size (4 bytes for uint8, 16 for float32) is written with vector stores.  Asynchronous on `stream`, never synchronises the host.
+ * Beyond 65 535 frames (shared map: beyond 65 535 groups of 8): SLICED. */
 COMPVHIP_API int compvhip_plan_remap(compvhip_plan* plan, const uint8_t* d_in, const float* d_mapX, const float* d_mapY, size_t mapCount, int interp,
                                      const compvhip_roi* roi, uint8_t defaultValue, void* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
 /* Inverse warp for every frame of a plan.  M: HOST, [matrixCount][rows][3] float32, rows 2 or 3; matrixCount 1 or frames.  The tables of A.2 are
  * built on the host into pinned staging owned by the plan and uploaded in stream order; M may be reused as soon as the call returns.  Asynchronous
  * on `stream`: the host waits only when 4 earlier uploads of the plan are all still pending.  Timing entries (compvhip_plan_set_timing):
- * remap_kernel, warp_inverse_kernel. */
+ * remap_kernel, warp_inverse_kernel.  Beyond 65 535 frames: SLICED, like compvhip_plan_remap. */
 COMPVHIP_API int compvhip_plan_warp_inverse(compvhip_plan* plan, const uint8_t* d_in, const float* M, int rows, size_t matrixCount, int interp,
                                             uint8_t defaultValue, void* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
 /* Both for one HOST plane (sizes 1 .. 32767) with host maps / a host matrix; S and Sout in elements.  Synchronous. */

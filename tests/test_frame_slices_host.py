@@ -1,6 +1,7 @@
 """for_frame_slices, the loop that launches a batch in slices of at most 65 535 frames (compv_amd/csrc/frame_slices.hpp): tests/host/frame_slices_check.cpp
-is a program of its own (standard library only, no GPU), built with the host C++ compiler and run as a child process.  No GPU test runs more than
-65 535 frames, so this is where the slicing arithmetic is executed."""
+is a program of its own (standard library only, no GPU), built with the host C++ compiler and run as a child process.  This is where the slicing
+arithmetic is executed on its own, at frame counts up to 2^31 - 1; what the kernels do with a later slice's frame offset is executed on the GPU by
+tests/test_gpu_large_batches.py (65 541, 131 073 and 524 285 frames)."""
 import os
 import shutil
 import subprocess
