@@ -35,6 +35,7 @@ INTERP_NEAREST, INTERP_BILINEAR, INTERP_BILINEAR_FLOAT32 = 0, 1, 2
 CORNER_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("strength", "<i4")])   # compvhip_corner
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("strength", "<f4"), ("orient", "<f4"), ("level", "<i4"), ("size", "<f4")])   # compvhip_keypoint = CompVInterestPoint
 MATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imageIdx", "<i4"), ("distance", "<i4")])   # compvhip_match = CompVDMatch
+HOMOGRAPHY_RESULT_DTYPE = np.dtype([("H", "<f8", (9,)), ("variance", "<f8"), ("inliers", "<i4"), ("bestTry", "<i4"), ("status", "<i4"), ("rotations", "<i4")])   # compvhip_homography_result
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -61,6 +62,8 @@ EXPORTS = [
     "compvhip_orbpyr_create", "compvhip_orbpyr_destroy", "compvhip_orbpyr_geometry", "compvhip_orbpyr_plane", "compvhip_orbpyr_detect", "compvhip_orbpyr_describe",
     "compvhip_plan_scale", "compvhip_scale_u8", "compvhip_orb_pyramid_u8", "compvhip_orbpyr_set_timing", "compvhip_orbpyr_get_timing",
     "compvhip_warp_tables", "compvhip_plan_remap", "compvhip_plan_warp_inverse", "compvhip_remap_u8", "compvhip_warp_inverse_u8",
+    "compvhip_homography_create", "compvhip_homography_destroy", "compvhip_homography_points", "compvhip_homography_find", "compvhip_homography_project",
+    "compvhip_homography_quads", "compvhip_homography_find_f64", "compvhip_homography_scores", "compvhip_homography_set_timing", "compvhip_homography_get_timing",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -126,6 +129,14 @@ class Keypoint(C.Structure):
 class MatchOpts(C.Structure):
     """compvhip_match_opts (include/compv_hip.h): ratio <= 0 / maxDistance < 0 / crossCheck == 0 switch a test off"""
     _fields_ = [("ratio", C.c_double), ("maxDistance", C.c_int), ("crossCheck", C.c_int)]
+
+
+class HomographyOpts(C.Structure):
+    """compvhip_homography_opts (include/compv_hip.h); the reference's outlier threshold is 30"""
+    _fields_ = [("tries", C.c_int32), ("seed", C.c_uint32), ("threshold", C.c_double)]
+
+    def __init__(self, tries=2000, seed=0, threshold=30.0):
+        super().__init__(int(tries), int(seed) & 0xffffffff, float(threshold))
 
 
 class Roi(C.Structure):
@@ -268,6 +279,17 @@ def load():
     L.compvhip_orb_pyramid_u8.argtypes = [vp, vp, sz, sz, sz, C.POINTER(OrbPyramidOpts), vp, vp, sz, sz, C.POINTER(sz)]
     L.compvhip_orbpyr_set_timing.argtypes = [vp, i32]
     L.compvhip_orbpyr_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
+    L.compvhip_homography_create.argtypes = [vp, sz, sz, sz, C.POINTER(vp)]
+    L.compvhip_homography_destroy.argtypes = [vp]
+    L.compvhip_homography_destroy.restype = None
+    L.compvhip_homography_points.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, i32, vp]
+    L.compvhip_homography_find.argtypes = [vp, vp, vp, vp, C.POINTER(HomographyOpts), vp, vp, vp, vp]
+    L.compvhip_homography_project.argtypes = [vp, vp, vp, sz, i32, vp, vp]
+    L.compvhip_homography_quads.argtypes = [C.c_uint32, sz, sz, sz, vp]
+    L.compvhip_homography_find_f64.argtypes = [vp, vp, vp, sz, C.POINTER(HomographyOpts), vp, vp, vp]
+    L.compvhip_homography_scores.argtypes = [vp, sz, vp, vp, vp, vp]
+    L.compvhip_homography_set_timing.argtypes = [vp, i32]
+    L.compvhip_homography_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -294,6 +316,16 @@ def warp_tables(M, out_w, out_h):
     if rc != OK:
         raise CompvHipError(rc, "compvhip_warp_tables")
     return (ac, df, gi, by, ey, hy) if rows == 3 else (ac, df, None, by, ey, None)
+
+
+def homography_quads(seed, pair, k, tries):
+    """compvhip_homography_quads (host arithmetic, no GPU): int32 (tries, 4), the point indices of every try of pair `pair` among k >= 4 points"""
+    L = load()
+    out = np.zeros((tries, 4), np.int32)
+    rc = L.compvhip_homography_quads(int(seed) & 0xffffffff, pair, k, tries, _ptr(out))
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_homography_quads")
+    return out
 
 
 class Context:
@@ -555,6 +587,20 @@ class Context:
         self._chk(self.lib.compvhip_match_hamming_u8(self.h, _ptr(query), Q, query.strides[0], _ptr(train), T, train.strides[0], cols, knn, _ptr(out), out.shape[1],
                                                      C.byref(rows)))
         return out[:rows.value, :Q]
+
+    def homography_find(self, src, dst, tries=2000, threshold=30.0, seed=0, quads=None, want_mask=True):
+        """compvhip_homography_find_f64 (CompVHomography<double>::find, every try run): src, dst (n, 2) float64 correspondences src -> dst ->
+        (HOMOGRAPHY_RESULT_DTYPE scalar, uint8 inlier mask of n or None).  quads: None or int32 (tries, 4), replacing the generator."""
+        src, dst = np.ascontiguousarray(src, np.float64).reshape(-1, 2), np.ascontiguousarray(dst, np.float64).reshape(-1, 2)
+        assert src.shape == dst.shape
+        n = len(src)
+        o = HomographyOpts(tries, seed, threshold)
+        q = None if quads is None else np.ascontiguousarray(quads, np.int32).reshape(tries, 4)
+        res = np.zeros(1, HOMOGRAPHY_RESULT_DTYPE)
+        mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
+        self._chk(self.lib.compvhip_homography_find_f64(self.h, _ptr(src) if n else None, _ptr(dst) if n else None, n, C.byref(o), _ptr(q) if q is not None else None,
+                                                        _ptr(res), _ptr(mask) if want_mask else None))
+        return res[0], (mask[:n] if want_mask else None)
 
     def houghkht(self, edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, order="reference"):
         """Returns (lines, GS); lines['row'] / ['col'] hold the rho / theta indices.  order: "reference" (compvhip_houghkht_u8: the reference's tie
@@ -824,6 +870,59 @@ class Matcher:
         names = (C.c_char_p * cap)()
         ms = (C.c_float * cap)()
         n = self.lib.compvhip_matcher_get_timing(self.h, names, ms, cap)
+        return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
+
+
+class Homography:
+    """Batched device-resident RANSAC homography (compvhip_homography).  Pointers are raw device addresses; 0 stands for NULL."""
+
+    def __init__(self, ctx, pairs, point_cap, max_tries=2000):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.compvhip_homography_create(ctx.h, pairs, point_cap, max_tries, C.byref(h)))
+        self.h = h
+        self.pairs, self.point_cap, self.max_tries = pairs, point_cap, max_tries
+
+    def close(self):
+        if self.h:
+            self.lib.compvhip_homography_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def points(self, d_good, good_cap, d_good_counts, d_query, query_cap, d_train, train_cap, train_shared=False, stream=0):
+        """compvhip_homography_points: gathers src = train positions, dst = query positions of the good records into the handle"""
+        self.ctx._chk(self.lib.compvhip_homography_points(self.h, d_good or None, good_cap, d_good_counts or None, d_query or None, query_cap, d_train or None,
+                                                          train_cap, int(bool(train_shared)), stream))
+
+    def find(self, d_src, d_dst, d_counts, d_results, d_mask=0, tries=None, threshold=30.0, seed=0, d_quads=0, stream=0):
+        """compvhip_homography_find: d_src = 0 takes the gathered points; d_results = [pairs] HOMOGRAPHY_RESULT_DTYPE records"""
+        o = HomographyOpts(self.max_tries if tries is None else tries, seed, threshold)
+        self.ctx._chk(self.lib.compvhip_homography_find(self.h, d_src or None, d_dst or None, d_counts or None, C.byref(o), d_quads or None, d_results or None,
+                                                        d_mask or None, stream))
+
+    def project(self, d_results, d_points, n, shared, d_out, stream=0):
+        """compvhip_homography_project: n points ([pairs][n] or one shared set [n] of {x, y} float64) through every pair's H"""
+        self.ctx._chk(self.lib.compvhip_homography_project(self.h, d_results or None, d_points or None, n, int(bool(shared)), d_out or None, stream))
+
+    def scores(self, tries, stream=0):
+        """compvhip_homography_scores (test hook): per pair and try the inlier count, variance and rotation count the last find() left -> three (pairs, tries) arrays"""
+        counts, var, rot = np.zeros((self.pairs, tries), np.int32), np.zeros((self.pairs, tries), np.float64), np.zeros((self.pairs, tries), np.int32)
+        self.ctx._chk(self.lib.compvhip_homography_scores(self.h, tries, _ptr(counts), _ptr(var), _ptr(rot), stream))
+        return counts, var, rot
+
+    def set_timing(self, mode=1):
+        self.ctx._chk(self.lib.compvhip_homography_set_timing(self.h, int(mode)))
+
+    def get_timing(self, cap=16):
+        names = (C.c_char_p * cap)()
+        ms = (C.c_float * cap)()
+        n = self.lib.compvhip_homography_get_timing(self.h, names, ms, cap)
         return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
 
 

@@ -240,6 +240,16 @@ struct compvhip_matcher : TimingState {
 	DevBuf<uint32_t> partial;           // keys of the slice kernel: max of the forward ([pairs][train slices][knn][queryCap]) and the reverse ([pairs][query slices][trainCap]) run
 	DevBuf<compvhip_match> reverse;     // [pairs][trainCap]: best query of every train row (cross check)
 };
+// RANSAC homography (homography_kernels.hip): every buffer is allocated by compvhip_homography_create
+struct compvhip_homography : TimingState {
+	compvhip_ctx* ctx = nullptr;
+	int pairs = 0, pointCap = 0, maxTries = 0;
+	DevBuf<double2> points;             // [4][pairs][pointCap]: gathered src, gathered dst, selected src, selected dst
+	DevBuf<int32_t> counts;             // [pairs] points gathered
+	DevBuf<double> tryF64;              // [pairs][maxTries][18] H and inverse, then [pairs][maxTries] variance
+	DevBuf<int32_t> tryI32;             // [3][pairs][maxTries]: state, rotations, inlier count
+	bool gathered = false;              // compvhip_homography_points has run
+};
 // ORB pyramid (scale_kernels.hip, fast_kernels.hip, orb_kernels.hip): the levels' geometry and the scratch they share.  `active` levels (a prefix: the sizes
 // only shrink) are at least 37 x 37; the others are empty.
 struct compvhip_orbpyr : TimingState {
@@ -304,6 +314,7 @@ struct Stamp {
 	Stamp(compvhip_plan* plan, hipStream_t stream, const char* name) : Stamp(plan, stream, name, stampWanted(plan, name)) {}
 	Stamp(compvhip_matcher* matcher, hipStream_t stream, const char* name) : Stamp(matcher, stream, name, matcher->timing != 0) {}
 	Stamp(compvhip_orbpyr* pyramid, hipStream_t stream, const char* name) : Stamp(pyramid, stream, name, pyramid->timing != 0) {}
+	Stamp(compvhip_homography* homography, hipStream_t stream, const char* name) : Stamp(homography, stream, name, homography->timing != 0) {}
 	Stamp(TimingState* state, hipStream_t stream, const char* name, bool wanted) : p(state), s(stream), idx(0), on(wanted)
 	{
 		if (!on) return;

@@ -336,6 +336,41 @@ struct MatchGoodArgs {
 };
 hipError_t launch_match_good(const MatchGoodArgs& a, int pairs, hipStream_t stream);
 
+// ---- RANSAC homography (homography_kernels.hip) ---------------------------------------------------------------------------------------------
+constexpr int kHomographySolveBlock = 64;    // tries of one workgroup of the solve kernel: one per lane, one wave (162 float64 of LDS per lane)
+constexpr int kHomographyScoreBlock = 256;   // tries of one workgroup of the score kernel, and the points it stages per round
+struct HomographyPointsArgs {
+	const compvhip_match* good; int goodCap;          // [pairs][goodCap]
+	const int32_t* goodCounts;                        // [pairs] (may exceed goodCap, may be negative); nullptr: goodCap
+	const compvhip_keypoint* query; int queryCap;     // [pairs][queryCap]
+	const compvhip_keypoint* train; int trainCap;     // [pairs][trainCap], or [trainCap] when trainShared
+	int trainShared;
+	double2* src; double2* dst; int pointCap;         // [pairs][pointCap]: train / query positions of the records kept
+	int32_t* counts;                                  // [pairs] records kept
+};
+hipError_t launch_homography_points(const HomographyPointsArgs& a, int pairs, hipStream_t stream);
+struct HomographyFindArgs {
+	const double2* src; const double2* dst;           // [pairs][pointCap]
+	const int32_t* counts; int pointCap;              // [pairs]; nullptr: pointCap
+	int tries, maxTries;
+	uint32_t seed; double threshold;
+	const int32_t* quads;                             // nullptr or [pairs][tries][4], 16-byte aligned
+	// scratch, [pairs][maxTries] each: 1 when the try has an H and an inverse; its Jacobi rotations; H then the inverse (18 float64); inlier count; variance
+	int32_t* state; int32_t* rotations; double* hyp; int32_t* scoreCount; double* scoreVar;
+	double2* selSrc; double2* selDst;                 // scratch [pairs][pointCap]: the inliers of the best try in index order
+	compvhip_homography_result* results;              // [pairs]
+	uint8_t* mask;                                    // nullptr or [pairs][pointCap]
+};
+hipError_t launch_homography_solve(const HomographyFindArgs& a, int pairs, hipStream_t stream);
+hipError_t launch_homography_score(const HomographyFindArgs& a, int pairs, hipStream_t stream);
+hipError_t launch_homography_refit(const HomographyFindArgs& a, int pairs, hipStream_t stream);
+struct HomographyProjectArgs {
+	const compvhip_homography_result* results;        // [pairs]
+	const double2* points; int n, shared;             // [pairs][n], or [n] when shared
+	double2* out;                                     // [pairs][n]
+};
+hipError_t launch_homography_project(const HomographyProjectArgs& a, int pairs, hipStream_t stream);
+
 // ---- ORB: keypoint orientation and rotated BRIEF (orb_kernels.hip) -------------------------------------------------------------------------
 // the byte-read variant of orb_brief_kernel that ships: at 32 x 4K with 2000 keypoints a frame the two measured alike (0.0678 ms with the LDS patch, 0.0680 ms
 // with bytes from global memory; docs/kernels/orb.md), so the first one built stays

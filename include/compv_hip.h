@@ -222,8 +222,8 @@ COMPVHIP_API int compvhip_plan_create(compvhip_ctx* ctx, size_t W, size_t H, siz
  *                   or written.  Split the batch across plans of at most 65 535 frames.
  * The text-detection chain (grayscale, otsu, threshold, threshold_adaptive, morph, components on the caller's bytes), the segment and fit calls on the
  * caller's bytes, and remap / warp_inverse are SLICED; edge_dete has its FRAMES IN X; Canny and everything that needs its masks, the SHT, the batched KHT, the
- * fixed-point blur, FAST, ORB and the bilinear scale are REFUSED, as are a compvhip_orbpyr of more than 65 535 frames and a compvhip_matcher of more than
- * 65 535 pairs at their creation. */
+ * fixed-point blur, FAST, ORB and the bilinear scale are REFUSED, as are a compvhip_orbpyr of more than 65 535 frames and a compvhip_matcher or a
+ * compvhip_homography of more than 65 535 pairs at their creation. */
 /* A plan must be destroyed BEFORE its context (it keeps a pointer to it); compvhip_ctx_destroy only releases the private
  * single-frame plan of the host entry points. */
 COMPVHIP_API void compvhip_plan_destroy(compvhip_plan* plan);
@@ -904,6 +904,102 @@ COMPVHIP_API int compvhip_remap_u8(compvhip_ctx* ctx, const uint8_t* in, size_t 
                                    const compvhip_roi* roi, uint8_t defaultValue, void* out, size_t Wout, size_t Hout, size_t Sout);
 COMPVHIP_API int compvhip_warp_inverse_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const float* M, int rows, int interp,
                                           uint8_t defaultValue, void* out, size_t Wout, size_t Hout, size_t Sout);
+
+/* ---- RANSAC homography (docs/kernels/homography.md) -----------------------------------------------------------------------------------------
+ * CompVHomography<double>::find (core/calib/compv_core_calib_homography.cxx:60-551) followed by CompVMathTransform::perspective2D, for `pairs`
+ * point sets at once, on the device: the step between compvhip_matcher_good and the 3 x 3 matrix compvhip_plan_warp_inverse consumes.  All
+ * arithmetic is IEEE binary64, one rounding per operation (no fused multiply-add), divisions and square roots correctly rounded, no transcendental
+ * function: tests/homography_model.py is the same definition in numpy and equals the device bit for bit.  Two departures from the reference, both
+ * deliberate: its random quads (std::random_device) are replaced by a counter hash, so a result is a function of the inputs; and its adaptive early
+ * exit (:318-331, a CPU time saver) is NOT reproduced -- all `tries` tries run.
+ * A pair has k correspondences src[i] -> dst[i] (src = the train side, dst = the query side, as samples/object_recognition passes them), either
+ *  - gathered by compvhip_homography_points from a good list: n = min(max(goodCount, 0), goodCap, pointCap) records are read; record r gives
+ *    src = (double)train[trainIdx].xy, dst = (double)query[queryIdx].xy; a record with queryIdx outside [0, queryCap) or trainIdx outside
+ *    [0, trainCap) is dropped, the others keep their order; k = the number kept; or
+ *  - given directly: two [pairs][pointCap] arrays of {x, y} float64 and d_counts, k = min(max(count, 0), pointCap) (d_counts == NULL: pointCap).
+ * A. Quads.  The four indices of pair p, try t, in uint32 wrap-around arithmetic: lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ *    x *= 0x846ca68b; x ^= x >> 16.  u(c) = lowbias32(lowbias32(lowbias32(seed ^ p) + t) + c), c = 0, 1, 2, ...; idx = ((uint64)u * k) >> 32.  Slots
+ *    0..3 fill in order; a draw equal to an earlier slot of the try is discarded; when c reaches 64 with slots open they take the smallest unused
+ *    indices in ascending order.  d_quads ([pairs][tries][4] int32) replaces the generator; a quad with an index outside [0, k) scores 0.
+ *    compvhip_homography_quads is the same function on the host.
+ * B. Collinearity of the quad's src points (:284-298): x0 == x1 ? (x0 == x2 && x0 == x3) : with slope = (y1 - y0) / (x1 - x0) and
+ *    intercept = y0 - slope * x0, y2 == slope * x2 + intercept && y3 == slope * x3 + intercept.  A collinear try scores 0.
+ * C. computeH(N points) (:346-495).  Per side the Hartley normalisation: t = (sum x, sum y) * (1 / N); mean = (sum sqrt(a * a + b * b)) * (1 / N) with
+ *    a = x - tx, b = y - ty; s = sqrt(2) / mean, or sqrt(2) when mean == 0; xn = s * x + (-(tx * s)).  Per point two rows of M
+ *    (compv_math_matrix.cxx:828-850): {-x, -y, -1, 0, 0, 0, X * x, X * y, X} and {0, 0, 0, -x, -y, -1, Y * x, Y * y, Y} with (x, y) = src, (X, Y) = dst
+ *    normalised.  S = MtM: entry (a, b) is the sum, over the points, of row0[a] * row0[b] and then row1[a] * row1[b], two additions per point.
+ *    Sums over N == 4 points run in index order from 0.0.  Sums over N > 4 points are sum64: point i adds to partial i mod 64 in ascending i, and
+ *    the partials fold with p[l] += p[l + stride] for stride 32, 16, ..., 1.
+ * D. Jacobi on D = S with Qt = I (compv_math_eigen.cxx).  Pivot: the largest |D[r][c]| over r > c, scanned in ascending r then c, the first
+ *    maximum wins.  Rotate while it is > 2^-52, at most 2430 times.  The angle theta = atan2(2 D[r][c], D[c][c] - D[r][r]) / 2 of :377-393, taken
+ *    algebraically: D[r][r] == D[c][c]: cos = sin = 0.70710678118654757; else y = 2 D[r][c], x = D[c][c] - D[r][r], rho = sqrt(x * x + y * y),
+ *    c2 = x / rho, s2 = y / rho; c2 >= 0: cos = sqrt((1 + c2) * 0.5), sin = s2 / (2 cos); else sin = copysign(sqrt((1 - c2) * 0.5), s2) (a zero s2
+ *    counts as positive), cos = s2 / (2 sin).  mulGA(A, r, c, cos, -sin) (compv_math_matrix.cxx:339-345: ai = ri * cos + (-sin) * rj,
+ *    aj = ri * sin + cos * rj) on the rows r, c of Qt, then of D, then -- the same formula on the elements -- on the columns r, c of D.  h = the row
+ *    of Qt at the smallest diagonal entry of D, scanning from index 8 downwards with strict <.  De-normalisation (:446-469): M = T1 * Hn^t,
+ *    H = T2 * M^t with T1 = {s, 0, 0; 0, s, 0; -tx s, -ty s, 1} of src, T2 = {1 / s, 0, tx; 0, 1 / s, ty; 0, 0, 1} of dst, every entry a three-term dot
+ *    product (a0 b0 + a1 b1) + a2 b2.  With promotion, |h| <= 2^-52 becomes 0 on the first eight entries.  H *= 1 / h22 when h22 != 0.
+ * E. Score of a try: H = computeH(the quad, no promotion); the inverse by the C formula of compv_math_matrix.cxx:520-544, a determinant of
+ *    exactly 0 scoring 0; d_i = mse(H src_i, dst_i) + mse(H^-1 dst_i, src_i) with mse of compv_math_stats.cxx:200-203 (X, Y, Z three-term dot
+ *    products with z = 1; scale = 1 / Z; ex = X * scale - bx; ey likewise; ex * ex + ey * ey); inlier iff d_i < threshold; count = the inliers;
+ *    mean = sum / count and variance = sum (d - mean)^2 / (count - 1), both sums over the inliers in index order; variance = DBL_MAX when
+ *    count < 2.  A try that scores 0 has count 0 and variance DBL_MAX.
+ * F. Selection over all tries: count >= 4, then the largest count, then the smallest variance, then the smallest t.
+ * G. Result: a best exists: status 0, H = computeH(the inliers of the best try in index order, promotion on), inliers = its count, variance and
+ *    bestTry its; none and k >= 4: status 1, H = computeH(all k points, promotion on) (:141-145), inliers 0; k < 4: status 2, H zeros, inliers 0.
+ *    status != 0: variance = DBL_MAX, bestTry = -1.  rotations = the Jacobi rotations of that last computeH.  The mask, [pairs][pointCap] bytes:
+ *    1 for an inlier of the best try, else 0, for i < k; bytes at and after k are never written.
+ * H. Projection (compv_math_transform.cxx:99-104): X, Y, Z three-term dot products, s = 1 / Z, (X * s, Y * s). */
+typedef struct compvhip_homography_opts {
+	int32_t tries;              /* 1 .. maxTries */
+	uint32_t seed;
+	double threshold;           /* > 0; the reference's is 30 */
+} compvhip_homography_opts;
+typedef struct compvhip_homography_result {
+	double H[9];
+	double variance;
+	int32_t inliers, bestTry, status, rotations;
+} compvhip_homography_result;
+typedef struct compvhip_homography compvhip_homography;   /* scratch for `pairs` pairs of at most pointCap points and maxTries tries; not tied to an image geometry */
+
+/* pairs, maxTries >= 1, pointCap >= 4 (anything else: COMPVHIP_E_INVALID_PARAMETER).  All scratch is allocated here -- per pair 4 * pointCap {x, y}
+ * float64 (gathered and selected points) and a count, per pair and try 19 float64 and 3 int32 -- and released by compvhip_homography_destroy: no
+ * later call allocates or synchronises (the two host forms excepted).  Destroy it BEFORE its context.  Not re-entrant: its calls share the scratch
+ * and must be ordered on one stream.  More than 65 535 pairs: REFUSED. */
+COMPVHIP_API int compvhip_homography_create(compvhip_ctx* ctx, size_t pairs, size_t pointCap, size_t maxTries, compvhip_homography** homography);
+COMPVHIP_API void compvhip_homography_destroy(compvhip_homography* homography);
+/* Gathers the pairs' points into the handle.  d_good: [pairs][goodCap] records, 16-byte aligned; d_goodCounts: [pairs] int32 or NULL (every pair
+ * full); d_query: [pairs][queryCap] keypoints; d_train: [pairs][trainCap], or ONE set [trainCap] with trainShared != 0; 4-byte aligned.
+ * Asynchronous on `stream`. */
+COMPVHIP_API int compvhip_homography_points(compvhip_homography* homography, const compvhip_match* d_good, size_t goodCap, const int32_t* d_goodCounts,
+                                            const compvhip_keypoint* d_query, size_t queryCap, const compvhip_keypoint* d_train, size_t trainCap,
+                                            int trainShared, void* stream);
+/* d_src, d_dst: [pairs][pointCap] {x, y} float64, 16-byte aligned, with d_counts; d_src == NULL: the points compvhip_homography_points gathered
+ * (d_dst and d_counts are then ignored).  d_quads: NULL or [pairs][opts->tries][4] int32, 16-byte aligned.  d_results: [pairs] records, 8-byte
+ * aligned.  d_mask: NULL or [pairs][pointCap] bytes.  A null handle, opts or d_results, tries < 1 or > maxTries, a threshold that is not > 0, a
+ * misaligned pointer: COMPVHIP_E_INVALID_PARAMETER, nothing written.  Asynchronous on `stream`; deterministic run to run. */
+COMPVHIP_API int compvhip_homography_find(compvhip_homography* homography, const double* d_src, const double* d_dst, const int32_t* d_counts,
+                                          const compvhip_homography_opts* opts, const int32_t* d_quads, compvhip_homography_result* d_results,
+                                          uint8_t* d_mask, void* stream);
+/* Sends n points through each pair's H.  d_points: [pairs][n] {x, y} float64, or ONE set [n] with shared != 0 (the train rectangle of the sample);
+ * d_out: [pairs][n]; both 16-byte aligned.  A pair of status 2 (H zeros) yields NaN.  Asynchronous on `stream`. */
+COMPVHIP_API int compvhip_homography_project(compvhip_homography* homography, const compvhip_homography_result* d_results, const double* d_points,
+                                             size_t n, int shared, double* d_out, void* stream);
+/* Item A on the host (standard library only, no GPU): quads[tries][4] of pair `pair` among k >= 4 points. */
+COMPVHIP_API int compvhip_homography_quads(uint32_t seed, size_t pair, size_t k, size_t tries, int32_t* quads);
+/* The whole call for one HOST pair of n points ({x, y} float64 each; n may be below 4: status 2).  quads: NULL or [opts->tries][4]; mask: NULL or n
+ * bytes.  Synchronous; allocates and frees its own scratch. */
+COMPVHIP_API int compvhip_homography_find_f64(compvhip_ctx* ctx, const double* src, const double* dst, size_t n, const compvhip_homography_opts* opts,
+                                              const int32_t* quads, compvhip_homography_result* result, uint8_t* mask);
+/* Test hook: what the last compvhip_homography_find left in the score scratch, copied to HOST arrays of [pairs][tries] (NULL: not wanted) --
+ * per try the inlier count, the variance and the Jacobi rotations of its computeH.  Entries of a pair with k < 4 are not defined.  Synchronises
+ * `stream`. */
+COMPVHIP_API int compvhip_homography_scores(compvhip_homography* homography, size_t tries, int32_t* counts, double* variances, int32_t* rotations,
+                                            void* stream);
+/* Per-kernel timing of the handle's last call, as compvhip_matcher_set_timing / _get_timing: entries homography_points_kernel;
+ * homography_solve_kernel, homography_score_kernel, homography_refit_kernel; homography_project_kernel. */
+COMPVHIP_API int compvhip_homography_set_timing(compvhip_homography* homography, int enabled);
+COMPVHIP_API int compvhip_homography_get_timing(compvhip_homography* homography, const char** names, float* ms, int cap);
 
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
