@@ -35,6 +35,9 @@ INTERP_NEAREST, INTERP_BILINEAR, INTERP_BILINEAR_FLOAT32 = 0, 1, 2
 CORNER_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("strength", "<i4")])   # compvhip_corner
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("strength", "<f4"), ("orient", "<f4"), ("level", "<i4"), ("size", "<f4")])   # compvhip_keypoint = CompVInterestPoint
 MATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imageIdx", "<i4"), ("distance", "<i4")])   # compvhip_match = CompVDMatch
+HOG_NORM_NONE, HOG_NORM_L1, HOG_NORM_L1SQRT, HOG_NORM_L2, HOG_NORM_L2HYS = 1, 2, 3, 4, 5          # COMPVHIP_HOG_NORM_* (0: the default, L2HYS)
+HOG_GRADIENT_SIGNED, HOG_GRADIENT_UNSIGNED = 1, 2                                              # COMPVHIP_HOG_GRADIENT_* (0: the default, signed)
+HOG_INTERP_NEAREST, HOG_INTERP_BILINEAR, HOG_INTERP_BILINEAR_LUT = 1, 2, 3                     # COMPVHIP_HOG_INTERP_* (0: the default, BILINEAR; _LUT is refused)
 HOMOGRAPHY_RESULT_DTYPE = np.dtype([("H", "<f8", (9,)), ("variance", "<f8"), ("inliers", "<i4"), ("bestTry", "<i4"), ("status", "<i4"), ("rotations", "<i4")])   # compvhip_homography_result
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
@@ -64,6 +67,7 @@ EXPORTS = [
     "compvhip_warp_tables", "compvhip_plan_remap", "compvhip_plan_warp_inverse", "compvhip_remap_u8", "compvhip_warp_inverse_u8",
     "compvhip_homography_create", "compvhip_homography_destroy", "compvhip_homography_points", "compvhip_homography_find", "compvhip_homography_project",
     "compvhip_homography_quads", "compvhip_homography_find_f64", "compvhip_homography_scores", "compvhip_homography_set_timing", "compvhip_homography_get_timing",
+    "compvhip_hog_geometry", "compvhip_plan_hog", "compvhip_hog_u8",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -137,6 +141,33 @@ class HomographyOpts(C.Structure):
 
     def __init__(self, tries=2000, seed=0, threshold=30.0):
         super().__init__(int(tries), int(seed) & 0xffffffff, float(threshold))
+
+
+class HogOpts(C.Structure):
+    """compvhip_hog_opts (include/compv_hip.h): a zero field takes the reference's default -- block 16 x 16, stride 8 x 8, cell 8 x 8, 9 bins, L2HYS, signed,
+    BILINEAR.  Keywords: block / stride / cell (a number, or (w, h)), nbins, norm (HOG_NORM_* or its name), signed, interp (HOG_INTERP_* or its name), or the
+    struct's own field names."""
+    _fields_ = [("size", C.c_uint32), ("blockW", C.c_int32), ("blockH", C.c_int32), ("strideW", C.c_int32), ("strideH", C.c_int32), ("cellW", C.c_int32),
+                ("cellH", C.c_int32), ("nbins", C.c_int32), ("blockNorm", C.c_int32), ("gradientSigned", C.c_int32), ("interp", C.c_int32)]
+    NORMS = {"none": HOG_NORM_NONE, "l1": HOG_NORM_L1, "l1sqrt": HOG_NORM_L1SQRT, "l2": HOG_NORM_L2, "l2hys": HOG_NORM_L2HYS}
+    INTERPS = {"nearest": HOG_INTERP_NEAREST, "bilinear": HOG_INTERP_BILINEAR, "bilinear_lut": HOG_INTERP_BILINEAR_LUT}
+
+    def __init__(self, block=0, stride=0, cell=0, nbins=0, norm=0, signed=None, interp=0, **fields):
+        pair = lambda v: (int(v), int(v)) if np.isscalar(v) else (int(v[0]), int(v[1]))          # noqa: E731
+        (bw, bh), (sw, sh), (cw, ch) = pair(block), pair(stride), pair(cell)
+        super().__init__(C.sizeof(HogOpts), bw, bh, sw, sh, cw, ch, int(nbins), self.NORMS.get(norm, norm), 0 if signed is None else (HOG_GRADIENT_SIGNED if signed else HOG_GRADIENT_UNSIGNED),
+                         self.INTERPS.get(interp, interp))
+        for k, v in fields.items():
+            if k not in dict(self._fields_) or k == "size":
+                raise TypeError("HogOpts has no field %r" % k)
+            setattr(self, k, int(v))
+
+
+def _hog_opts(opts, kw):
+    """a HogOpts, or the keywords of one"""
+    if opts is not None and kw:
+        raise TypeError("pass a HogOpts or keywords, not both")
+    return opts if opts is not None else HogOpts(**kw)
 
 
 class Roi(C.Structure):
@@ -290,6 +321,9 @@ def load():
     L.compvhip_homography_scores.argtypes = [vp, sz, vp, vp, vp, vp]
     L.compvhip_homography_set_timing.argtypes = [vp, i32]
     L.compvhip_homography_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
+    L.compvhip_hog_geometry.argtypes = [sz, sz, C.POINTER(HogOpts), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    L.compvhip_plan_hog.argtypes = [vp, vp, C.POINTER(HogOpts), vp, vp, sz, vp]
+    L.compvhip_hog_u8.argtypes = [vp, vp, sz, sz, sz, C.POINTER(HogOpts), vp, sz, C.POINTER(sz)]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -326,6 +360,18 @@ def homography_quads(seed, pair, k, tries):
     if rc != OK:
         raise CompvHipError(rc, "compvhip_homography_quads")
     return out
+
+
+def hog_geometry(W, H, opts=None, **kw):
+    """compvhip_hog_geometry (host arithmetic, no GPU): -> dict(cellsX, cellsY, blocksX, blocksY, descLen) of a W x H frame; CompvHipError where the device calls
+    would refuse the parameters"""
+    L = load()
+    o = _hog_opts(opts, kw)
+    v = [C.c_size_t(0) for _ in range(5)]
+    rc = L.compvhip_hog_geometry(W, H, C.byref(o), *[C.byref(x) for x in v])
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_hog_geometry")
+    return dict(zip(("cellsX", "cellsY", "blocksX", "blocksY", "descLen"), (x.value for x in v)))
 
 
 class Context:
@@ -529,6 +575,16 @@ class Context:
         self._chk(self.lib.compvhip_orb_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(corners) if n else None, n, level, scale, _ptr(keys) if n else None,
                                            _ptr(desc) if n else None, 32, C.byref(kept)))
         return keys[:kept.value], desc[:kept.value]
+
+    def hog(self, img, opts=None, **kw):
+        """compvhip_hog_u8 (CompVHOG, COMPV_HOGS_ID): the float32 descriptor of one gray frame; opts: a HogOpts, or its keywords (block=16, stride=8, cell=8,
+        nbins=9, norm="l2hys", signed=True, interp="bilinear")"""
+        H, W = img.shape
+        o = _hog_opts(opts, kw)
+        desc = np.zeros(hog_geometry(W, H, o)["descLen"], np.float32)
+        n = C.c_size_t(0)
+        self._chk(self.lib.compvhip_hog_u8(self.h, _ptr(img), W, H, img.strides[0], C.byref(o), _ptr(desc), desc.size, C.byref(n)))
+        return desc[:n.value]
 
     def scale(self, img, out_w, out_h):
         """compvhip_scale_u8 (CompVImage::scale, bilinear): -> the (out_h, out_w) plane"""
@@ -737,6 +793,12 @@ class Plan:
         """compvhip_plan_orb_describe: 32-byte rows at d_desc + (f * key_cap + q) * desc_stride; blur=False takes d_gray as already blurred."""
         self.ctx._chk(self.lib.compvhip_plan_orb_describe(self.h, d_gray, d_keypoints or None, key_cap, d_key_counts or None, scale, int(bool(blur)), d_desc or None,
                                                           desc_stride, stream))
+
+    def hog(self, d_gray, d_desc, desc_stride, d_cells=0, opts=None, stream=0, **kw):
+        """compvhip_plan_hog: the plan's frames -> float32 descriptors [frames][desc_stride] (desc_stride >= hog_geometry()'s descLen, in floats) and, with d_cells,
+        the cell map [frames][cellsY][cellsX][nbins]; opts: a HogOpts, or its keywords"""
+        o = _hog_opts(opts, kw)
+        self.ctx._chk(self.lib.compvhip_plan_hog(self.h, d_gray or None, C.byref(o), d_cells or None, d_desc or None, desc_stride, stream))
 
     def scale(self, d_in, d_out, out_w, out_h, out_stride, stream=0):
         """compvhip_plan_scale: the plan's frames [frames][H][S] -> d_out [frames][out_h][out_stride], bilinear"""

@@ -1035,3 +1035,90 @@ int compvhip_homography_scores(compvhip_homography* h, size_t tries, int32_t* co
 	HIPCHK(ctx, hipStreamSynchronize(st));
 	return COMPVHIP_OK;
 }
+
+// ---- HOG descriptors (hog_kernels.hip; definition in include/compv_hip.h) -----------------------------------------------------------------------------
+// Items 5, 6 and 8 of the definition: resolves the defaults, refuses what the definition refuses and fills the geometry fields of `a` (no pointer, no launch field)
+int compvhip_api::hogGeometry(compvhip_ctx* ctx, size_t W, size_t H, const compvhip_hog_opts* opts, HogArgs* a)
+{
+	if (!opts || opts->size != sizeof(compvhip_hog_opts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: null options, or their size field is not sizeof(compvhip_hog_opts)");
+	const int32_t given[10] = { opts->blockW, opts->blockH, opts->strideW, opts->strideH, opts->cellW, opts->cellH, opts->nbins, opts->blockNorm, opts->gradientSigned, opts->interp };
+	static const int32_t defaults[10] = { 16, 16, 8, 8, 8, 8, 9, COMPVHIP_HOG_NORM_L2HYS, COMPVHIP_HOG_GRADIENT_SIGNED, COMPVHIP_HOG_INTERP_BILINEAR };   // hog_std.cxx:459-467
+	int32_t o[10];
+	for (int i = 0; i < 10; ++i) {
+		if (given[i] < 0) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: a negative option");
+		o[i] = given[i] ? given[i] : defaults[i];
+	}
+	const int32_t nbins = o[6], norm = o[7], gradient = o[8], interp = o[9];
+	if (norm > COMPVHIP_HOG_NORM_L2HYS || gradient > COMPVHIP_HOG_GRADIENT_UNSIGNED) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: unknown block norm or gradient kind");
+	if (interp != COMPVHIP_HOG_INTERP_NEAREST && interp != COMPVHIP_HOG_INTERP_BILINEAR)
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: interpolation must be NEAREST or BILINEAR (BILINEAR_LUT is not supported)");
+	const int thetaMax = gradient == COMPVHIP_HOG_GRADIENT_SIGNED ? 360 : 180;
+	if (nbins < 2 || nbins > 360 || thetaMax % nbins) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: nbins must lie in 2..360 and divide 360 (signed) or 180 (unsigned)");
+	if (W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: frame beyond 32767");
+	int cells[2], valid[2], blocks[2], cpb[2], step[2];
+	for (int ax = 0; ax < 2; ++ax) {
+		const long long size = static_cast<long long>(ax ? H : W), block = o[ax], stride = o[2 + ax], cell = o[4 + ax];
+		if (block % cell) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: the block size must be a multiple of the cell size");
+		if (!(stride == cell || (2 * stride == cell && block == cell)))
+			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: per axis stride == cell, or 2 * stride == cell with block == cell");
+		if (size < block) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: the frame is smaller than a block");
+		const float ratio = static_cast<float>(stride) / static_cast<float>(cell);                                        // szStrideInCellsCount, hog_std.cxx:219
+		cells[ax] = static_cast<int>(static_cast<float>(size / cell) / ratio);                                            // :238-239
+		valid[ax] = cells[ax] - (static_cast<long long>(cells[ax] - 1) * stride + cell > size ? 1 : 0);                  // xGuard / yGuard, :249,255
+		blocks[ax] = static_cast<int>((size - block) / stride + 1);                                                       // :320-321
+		cpb[ax] = static_cast<int>(block / cell);
+		step[ax] = static_cast<int>(static_cast<double>(ratio) + 0.5);                                                    // COMPV_MATH_ROUNDFU_2_NEAREST_INT, :355,357
+		// what the reference asserts (:358): the last block's cells lie in the map
+		if (cells[ax] < 1 || static_cast<long long>(blocks[ax] - 1) * step[ax] + cpb[ax] > cells[ax]) return fail(ctx, COMPVHIP_E_INVALID_STATE, "HOG: a block leaves the cell map");
+	}
+	const long long count = static_cast<long long>(cpb[0]) * cpb[1] * nbins, mapFloats = static_cast<long long>(cells[0]) * cells[1] * nbins;
+	if (count > INT32_MAX || mapFloats > INT32_MAX || count * blocks[0] > INT32_MAX || count * blocks[0] * blocks[1] > INT32_MAX)
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: a block, the cell map or the descriptor of a frame has 2^31 floats or more");
+	a->W = static_cast<int>(W); a->H = static_cast<int>(H);
+	a->cellW = o[4]; a->cellH = o[5]; a->strideW = o[2]; a->strideH = o[3]; a->nbins = nbins;
+	a->interp = interp; a->gradientSigned = gradient == COMPVHIP_HOG_GRADIENT_SIGNED; a->norm = norm;
+	a->cellsX = cells[0]; a->cellsY = cells[1]; a->validX = valid[0]; a->validY = valid[1];
+	a->blocksX = blocks[0]; a->blocksY = blocks[1]; a->cpbX = cpb[0]; a->cpbY = cpb[1]; a->stepX = step[0]; a->stepY = step[1]; a->count = static_cast<int>(count);
+	a->cellsFrameStride = static_cast<size_t>(mapFloats);
+	a->gray = nullptr; a->frameStride = 0; a->S = 0; a->cells = nullptr; a->desc = nullptr; a->descStride = 0;
+	if (!hog_plan_launch(*a)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "HOG: three rows of one cell and the histogram exceed the LDS of a compute unit");
+	return COMPVHIP_OK;
+}
+
+int compvhip_hog_geometry(size_t W, size_t H, const compvhip_hog_opts* opts, size_t* cellsX, size_t* cellsY, size_t* blocksX, size_t* blocksY, size_t* descLen)
+{
+	HogArgs a;
+	const int rc = hogGeometry(nullptr, W, H, opts, &a);
+	if (rc) return rc;
+	if (cellsX) *cellsX = static_cast<size_t>(a.cellsX);
+	if (cellsY) *cellsY = static_cast<size_t>(a.cellsY);
+	if (blocksX) *blocksX = static_cast<size_t>(a.blocksX);
+	if (blocksY) *blocksY = static_cast<size_t>(a.blocksY);
+	if (descLen) *descLen = static_cast<size_t>(a.blocksX) * a.blocksY * a.count;
+	return COMPVHIP_OK;
+}
+
+int compvhip_plan_hog(compvhip_plan* p, const uint8_t* d_gray, const compvhip_hog_opts* opts, float* d_cells, float* d_desc, size_t descStride, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	compvhip_ctx* ctx = p->ctx;
+	if (!d_gray || !d_desc) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame / descriptor pointer");
+	HogArgs a;
+	const int rc = hogGeometry(ctx, p->W, p->H, opts, &a);
+	if (rc) return rc;
+	const size_t descLen = static_cast<size_t>(a.blocksX) * a.blocksY * a.count;
+	if (descStride < descLen) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descStride below the descriptor's length");
+	if (p->frames > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "frames beyond 2^31");
+	if (misaligned(3, d_cells, d_desc)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "cell map and descriptors must be 4-byte aligned");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	if (!d_cells) HIPCHK(ctx, p->hogCells.reserve(ctx, a.cellsFrameStride * p->frames));
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (p->timing) timelineClear(p);
+	a.gray = d_gray; a.frameStride = p->S * p->H; a.S = static_cast<int>(p->S);
+	a.cells = d_cells ? d_cells : p->hogCells.ptr; a.desc = d_desc; a.descStride = descStride;
+	hog_plan_launch(a);          // again with the frames' pointer and stride: whole dwords are loaded where they are 4-byte aligned
+	const int frames = static_cast<int>(p->frames);
+	{ Stamp s(p, st, "hog_cells_kernel"); HIPCHK(ctx, launch_hog_cells(a, frames, st)); }
+	{ Stamp s(p, st, "hog_blocks_kernel"); HIPCHK(ctx, launch_hog_blocks(a, frames, st)); }
+	return COMPVHIP_OK;
+}

@@ -447,6 +447,27 @@ int compvhip_orb_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, 
 	});
 }
 
+int compvhip_hog_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_hog_opts* opts, float* desc, size_t cap, size_t* n)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!gray || !n || (cap && !desc) || S < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null/invalid argument");
+	HogArgs a;
+	int rc = hogGeometry(ctx, W, H, opts, &a);
+	if (rc) return rc;
+	if (W < 3 || H < 3) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
+	const size_t descLen = static_cast<size_t>(a.blocksX) * a.blocksY * a.count;
+	*n = descLen;
+	if (cap < descLen) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "descriptor buffer too small");
+	return hostPlaneOp(ctx, gray, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p) -> int {
+		HIPCHK(ctx, ctx->dHogDesc.reserve(ctx, descLen));
+		int rc = compvhip_plan_hog(p, ctx->dIn, opts, nullptr, ctx->dHogDesc, descLen, ctx->stream);
+		if (rc) return rc;
+		HIPCHK(ctx, hipMemcpyAsync(desc, ctx->dHogDesc, descLen * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+		return COMPVHIP_OK;
+	});
+}
+
 int compvhip_scale_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint8_t* out, size_t Wout, size_t Hout, size_t Sout)
 {
 	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;

@@ -135,6 +135,7 @@ struct compvhip_ctx {
 	DevBuf<uint8_t> dOrbDesc;               // ... and the descriptor rows
 	DevBuf<float> dMap;                     // staging of compvhip_remap_u8: mapX, then mapY
 	WarpTables warp;                        // tables of compvhip_warp_inverse_u8
+	DevBuf<float> dHogDesc;                 // staging of compvhip_hog_u8: the descriptor
 	KhtScratch kht;                    // KHT scratch of the host entry point (compvhip_houghkht_u8)
 };
 
@@ -215,6 +216,7 @@ struct compvhip_plan : TimingState {
 	// batch [frames][H][S] of the describe calls with blur != 0; the Q16 Gaussian (5, 2.0f), computed once; which byte-read variant of orb_brief_kernel runs
 	DevBuf<int32_t> orbIndex; DevBuf<uint8_t> orbBlur; uint16_t orbKern[5] = {}; bool orbKernReady = false; bool orbBriefLds = false;
 	WarpTables warp;             // inverse warp (remap_kernels.hip), allocated on first use: the matrices' running-sum tables and their pinned staging
+	DevBuf<float> hogCells;      // HOG (hog_kernels.hip), allocated on first use without a caller's map: the cell map [frames][cellsY][cellsX][nbins]
 	int strengthBits = 16, keyBits = 0;
 	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
 	DevBuf<uint16_t> chunkHist; DevBuf<uint32_t> strengthStart; int sortChunks = 0; bool deviceSort = false;
@@ -416,6 +418,7 @@ int checkAdaptive(compvhip_ctx* ctx, size_t W, size_t H, size_t blockSize, doubl
 int morphPrepare(compvhip_ctx* ctx, size_t W, size_t H, const uint8_t* strel, size_t sw, size_t sh, int op, int border, int kernel, MorphArgs* a);
 int checkFast(compvhip_ctx* ctx, size_t W, size_t H, int fastType);
 int checkOrb(compvhip_ctx* ctx, size_t W, size_t H, float scale);
+int hogGeometry(compvhip_ctx* ctx, size_t W, size_t H, const compvhip_hog_opts* opts, HogArgs* a);   // the definition's items 5, 6, 8: refusals, defaults, geometry
 int scaleImpl(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, hipStream_t st);
 // remap and inverse warp: validates everything but the coordinate source and fills `a` (roi == nullptr: the whole frame)
 int remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, int interp, const compvhip_roi* roi, void* d_out, size_t Wout,

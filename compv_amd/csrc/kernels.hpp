@@ -479,4 +479,30 @@ struct RemapArgs {
 // 2-byte pairs inside a row); hipErrorInvalidValue for that, for a ROI that is neither empty nor inside the frame, and for sizes whose frame exceeds 2^31 bytes.
 hipError_t launch_remap(const RemapArgs& a, int source, int interp, bool perFrame, hipStream_t stream);
 
+// ---- HOG descriptors (hog_kernels.hip) ------------------------------------------------------------------------------------------------------------
+// CompVHOG (COMPV_HOGS_ID): per-cell orientation histograms, then the blocks' normalised vectors (include/compv_hip.h, section "HOG descriptors").
+// The geometry is worked out on the host (hogGeometry in api_features.cpp); every field below is resolved: no zero "default" is left.
+struct HogArgs {
+	const uint8_t* gray;      // [frames][H][S]
+	size_t frameStride;
+	int W, H, S;
+	int cellW, cellH, strideW, strideH, nbins;
+	int interp, gradientSigned, norm;   // hog::kInterp*, 0 / 1, hog::kNorm*
+	int cellsX, cellsY, validX, validY;   // the map's cells; the cells that are computed (the others hold 0)
+	float* cells;             // [frames][cellsY][cellsX][nbins]: the caller's, or the plan's scratch
+	size_t cellsFrameStride;  // cellsY * cellsX * nbins
+	int blocksX, blocksY, cpbX, cpbY, stepX, stepY, count;   // blocks; cells per block; map cells from one block to the next; cpbX * cpbY * nbins
+	float* desc;              // [frames][descStride]
+	size_t descStride;
+	// filled by hog_plan_launch: the cells a wave takes (nx across, ny down, nx * ny <= 64), cell rows staged at a time, the staged rows' pitch in bytes,
+	// whether whole dwords are loaded, the workgroups of a frame, the dynamic LDS of the cells kernel
+	int nx, ny, rowsPerChunk, pitch, dwords, tilesX, tilesY, ldsBytes;
+};
+constexpr size_t kHogLdsLimit = 160 * 1024;      // LDS of a CU: histogram [nbins][64] float32 and the staged rows of one wave share it
+constexpr size_t kHogTileBudget = 16 * 1024;     // staged rows of a wave: as many cell rows at a time as fit this (at least one)
+// fills the launch fields of `a`; false: a cell so wide that three rows of ONE cell and the histogram do not fit a CU's LDS
+bool hog_plan_launch(HogArgs& a);
+hipError_t launch_hog_cells(const HogArgs& a, int frames, hipStream_t stream);
+hipError_t launch_hog_blocks(const HogArgs& a, int frames, hipStream_t stream);
+
 } // namespace compvhip

@@ -221,7 +221,7 @@ COMPVHIP_API int compvhip_plan_create(compvhip_ctx* ctx, size_t W, size_t H, siz
  *   REFUSED         beyond 65 535 frames the call returns COMPVHIP_E_INVALID_PARAMETER, compvhip_last_error names the limit, nothing is allocated, enqueued
  *                   or written.  Split the batch across plans of at most 65 535 frames.
  * The text-detection chain (grayscale, otsu, threshold, threshold_adaptive, morph, components on the caller's bytes), the segment and fit calls on the
- * caller's bytes, and remap / warp_inverse are SLICED; edge_dete has its FRAMES IN X; Canny and everything that needs its masks, the SHT, the batched KHT, the
+ * caller's bytes, remap / warp_inverse and hog are SLICED; edge_dete has its FRAMES IN X; Canny and everything that needs its masks, the SHT, the batched KHT, the
  * fixed-point blur, FAST, ORB and the bilinear scale are REFUSED, as are a compvhip_orbpyr of more than 65 535 frames and a compvhip_matcher or a
  * compvhip_homography of more than 65 535 pairs at their creation. */
 /* A plan must be destroyed BEFORE its context (it keeps a pointer to it); compvhip_ctx_destroy only releases the private
@@ -1000,6 +1000,73 @@ COMPVHIP_API int compvhip_homography_scores(compvhip_homography* homography, siz
  * homography_solve_kernel, homography_score_kernel, homography_refit_kernel; homography_project_kernel. */
 COMPVHIP_API int compvhip_homography_set_timing(compvhip_homography* homography, int enabled);
 COMPVHIP_API int compvhip_homography_get_timing(compvhip_homography* homography, const char** names, float* ms, int cap);
+
+/* ---- HOG descriptors (docs/kernels/hog.md) --------------------------------------------------------------------------------------------------
+ * CompVHogStd::process (core/features/hog/compv_core_feature_hog_std.cxx; COMPV_HOGS_ID) on gray frames: per-cell orientation histograms, then the
+ * blocks' normalised vectors.  Every output is defined bit for bit.  All arithmetic is float32 with one rounding per operation; the divide and the
+ * square root are the correctly rounded ones; nothing is flushed to zero.  This is the reference with its AVX2 + FMA3 leaf switched off: compiled with
+ * -mfma, that leaf's two sub(mul()) expressions (..._hog_std_intrin_avx2.cxx:54-55) are contracted and the last bits differ (its unit test carries an
+ * md5 and an md5_fma column for this; the uncontracted one is canonical here).  For a frame I of W x H:
+ *  1. Gradient (base/compv_gradient_fast.cxx:111-162, 266-314): gx = I(x + 1, y) - I(x - 1, y), 0 in columns 0 and W - 1; gy = I(x, y + 1) - I(x, y - 1),
+ *     0 in rows 0 and H - 1.  Exact integers as float32.
+ *  2. Magnitude (base/math/compv_math_trig.cxx:497-509): m = sqrt(gx * gx + gy * gy).
+ *  3. Direction in degrees (:412-447, constants at compv_math.cxx:39-43): ax = |gx|, ay = |gy|; ax >= ay: c = ay / (ax + eps),
+ *     a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c with c2 = c * c; otherwise c = ax / (ay + eps) and a = 90 - that polynomial.  gx < 0: a = 180 - a;
+ *     then gy < 0: a = 360 - a.  eps = (float)2.2204460492503131e-16, p1 = 57.2836266f, p3 = -18.6674461f, p5 = 8.91400051f, p7 = -2.53972459f.
+ *  4. Binning (hog_std.cxx:564-632, 715-743): thetaMax = 360 (signed) or 180; theta = a - thetaMax when a > thetaMax, else a; w = thetaMax / nbins,
+ *     s = 1.f / w.  The pixels of a cell are walked row-major, each adding to the cell's histogram h:
+ *     NEAREST: b = (int)(theta * s); h[b] += m; a vote with b == nbins (theta == thetaMax: every pixel with gy == 0 and gx < 0 of an unsigned
+ *     gradient) is DROPPED (the reference writes it behind its histogram, into a float it clears afterwards).
+ *     BILINEAR: b = (int)(theta * s - 0.5f); d = (theta - (float)b * w) * s - 0.5f; v = |m * d|; the other bin is b + 1 when d >= 0, else b - 1, wrapped
+ *     into 0 .. nbins - 1; FIRST h[other] += v, THEN h[b] += m - v.  The order is part of the result.
+ *  5. Cell grid (:238-261): cell origins step by the block stride.  cellsX = (int)((float)(W / cellW) / ((float)strideW / (float)cellW)); the last column is
+ *     LEFT OUT when (cellsX - 1) * strideW + cellW > W; the same in y.  A left-out cell of the map holds 0 (the reference leaves it unwritten); no block
+ *     reads one.
+ *  6. Blocks (:318-376, 429-457): blocksX = (W - blockW) / strideW + 1, likewise in y.  Block (bx, by) takes, for each of its blockH / cellH cell rows,
+ *     the blockW / cellW adjacent map cells from index bx * round(strideW / cellW) of map row by * round(strideH / cellH) + row (round(x) = (int)(x + 0.5)).  Blocks
+ *     are stored row-major; inside a block: cell row, then cell, then bin.  descLen = blocksX * blocksY * count, count the floats of a block.
+ *  7. Norms (intrin/x86/compv_core_feature_hog_common_norm_intrin_sse2.cxx), one summation order for any count: two 4-lane accumulators are fed 8 terms
+ *     at a time (lane l of the first takes terms 8k + l, of the second 8k + 4 + l); one more group of 4 goes to the first if it fits; then
+ *     acc0 + acc1, then (l0 + l2) + (l1 + l3), then the remaining terms one by one, then + eps (1e-6f for L1 and L1SQRT, 1e-6f * 1e-6f for L2 and
+ *     L2HYS).  L1, L1SQRT: terms v, r = 1.f / sum; L2, L2HYS: terms v * v, r = 1.f / sqrt(sum).  Result v * r; sqrt(v * r) for L1SQRT; L2HYS is L2, then
+ *     min(., 0.2f), then L2 again.  NONE copies the cells.  (The reference's _9 variants are the same arithmetic.)
+ *  8. Accepted parameters.  block % cell == 0; per axis EITHER stride == cell OR 2 * stride == cell together with block == cell (the default shape and the
+ *     reference's unit-test shape; for any other mix the reference pairs map cells `stride` apart as if they were `cell` apart); 2 <= nbins <= 360 and
+ *     nbins divides thetaMax (otherwise the reference indexes outside its histogram); blockW <= W <= 32767, blockH <= H <= 32767; interpolation NEAREST
+ *     or BILINEAR (BILINEAR_LUT is refused: the reference itself calls it "not faster"); count and the floats of a frame's map and descriptor below 2^31.
+ *     One resource limit: a cell so wide that three of its rows and the histogram (nbins * 256 bytes) exceed the 160 KB of LDS (cellW beyond 22 000 at
+ *     360 bins).  Anything else: COMPVHIP_E_INVALID_PARAMETER, and nothing is written. */
+enum { COMPVHIP_HOG_NORM_DEFAULT = 0 /* L2HYS */, COMPVHIP_HOG_NORM_NONE = 1, COMPVHIP_HOG_NORM_L1 = 2, COMPVHIP_HOG_NORM_L1SQRT = 3, COMPVHIP_HOG_NORM_L2 = 4,
+       COMPVHIP_HOG_NORM_L2HYS = 5 };                      /* COMPV_HOG_BLOCK_NORM_* (compv_features.h:113-117) */
+enum { COMPVHIP_HOG_GRADIENT_DEFAULT = 0 /* signed */, COMPVHIP_HOG_GRADIENT_SIGNED = 1, COMPVHIP_HOG_GRADIENT_UNSIGNED = 2 };
+enum { COMPVHIP_HOG_INTERP_DEFAULT = 0 /* BILINEAR */, COMPVHIP_HOG_INTERP_NEAREST = 1, COMPVHIP_HOG_INTERP_BILINEAR = 2,
+       COMPVHIP_HOG_INTERP_BILINEAR_LUT = 3 /* refused */ };   /* COMPV_HOG_INTERPOLATION_* (compv_features.h:118-120) */
+/* Zero-initialise, set `size` = sizeof(compvhip_hog_opts) and what is needed: a zero field takes the reference's default (hog_std.cxx:459-467) -- block 16 x 16,
+ * stride 8 x 8, cell 8 x 8, 9 bins, L2HYS, signed, BILINEAR.  Another `size`, or a negative field: COMPVHIP_E_INVALID_PARAMETER. */
+typedef struct compvhip_hog_opts {
+	uint32_t size;
+	int32_t blockW, blockH, strideW, strideH, cellW, cellH, nbins;
+	int32_t blockNorm;          /* COMPVHIP_HOG_NORM_* */
+	int32_t gradientSigned;     /* COMPVHIP_HOG_GRADIENT_* */
+	int32_t interp;             /* COMPVHIP_HOG_INTERP_* */
+} compvhip_hog_opts;
+
+/* Items 5, 6 and 8 on the host (no GPU): the map's cells (left-out ones included), the blocks and the descriptor's length in floats of a W x H frame.  Any
+ * of the five outputs may be NULL.  Returns what the device calls return for the same W, H and opts. */
+COMPVHIP_API int compvhip_hog_geometry(size_t W, size_t H, const compvhip_hog_opts* opts, size_t* cellsX, size_t* cellsY, size_t* blocksX, size_t* blocksY,
+                                       size_t* descLen);
+
+/* Descriptors of all frames of the plan.  d_gray: [frames][H][S]; d_desc: [frames][descStride] float32, descStride >= descLen counted in floats, the floats
+ * behind descLen are never written; d_cells: NULL or the cell map [frames][cellsY][cellsX][nbins] float32; d_desc and d_cells 4-byte aligned.  A batch of
+ * crops is a plan of the crop's size with one frame per crop.  Asynchronous on `stream`, no atomic, deterministic.  Scratch is owned by the plan, allocated on
+ * first use with d_cells == NULL and released with it: one cell map.  Like every plan call it is not re-entrant.  Beyond 65 535 frames: SLICED. */
+COMPVHIP_API int compvhip_plan_hog(compvhip_plan* plan, const uint8_t* d_gray, const compvhip_hog_opts* opts, float* d_cells, float* d_desc, size_t descStride,
+                                   void* stream);
+
+/* The same for one HOST frame (3 <= W, H).  Synchronous, on the context's cached single-frame plan.  *n receives descLen; with cap < descLen nothing is
+ * computed or written and COMPVHIP_E_OUT_OF_BOUND is returned (cap == 0 with desc == NULL asks for the length). */
+COMPVHIP_API int compvhip_hog_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_hog_opts* opts, float* desc, size_t cap,
+                                 size_t* n);
 
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
