@@ -71,6 +71,12 @@ class Rig:
         self.d_counts = self.ar.new(4 * F)
         self.plan = capi.Plan(hip_ctx, W, H, S, F)
 
+    def set_content(self, valid, rng):
+        """other frames [F][H][W] for the next calls on the same plan; the padding columns get bytes of rng"""
+        self.valid = valid
+        self.host_in = pad_frames(valid, self.geom[2], rng)
+        self.ar.reload(self.d_in, self.host_in)
+
     def run(self, N, nonmax, t, max_features=-1, scores=True, cap=None, stream=0):
         cap = self.cap if cap is None else cap
         self.plan.fast(ptr(self.d_in), t, N, nonmax, max_features, ptr(self.d_scores) if scores else 0, ptr(self.d_rec) if cap else 0, cap, ptr(self.d_counts), stream)

@@ -68,6 +68,16 @@ class Rig:
     def close(self):
         self.plan.close()
 
+    def set_content(self, frames, opts, rng):
+        """other frames and options for the next calls on the same plan; the descriptor stride stays, so descLen may not exceed it.  Without misalign only."""
+        from compv_amd import capi
+        self.opts = hm.resolve(opts)
+        self.o = capi.HogOpts(**self.opts)
+        self.g = hm.geometry(self.W, self.H, self.opts)
+        self.desc_len = self.g["descLen"]
+        assert self.desc_len <= self.stride
+        self.ar.reload(self.d_raw, pad_frames(np.stack(frames), self.S, rng))
+
     def run(self, cells=True, stream=0, opts=None, stride=None):
         self.ar.refill(self.d_desc)
         self.ar.refill(self.d_cells)

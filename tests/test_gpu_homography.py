@@ -55,6 +55,13 @@ class Rig:
         self.d_mask = self.ar.new(self.pairs * point_cap)
         self.h = capi.Homography(hip_ctx, self.pairs, point_cap, max_tries)
 
+    def set_points(self, src, dst, counts):
+        """other points and device counts for the next calls on the same handle: src, dst [pairs][pointCap][2] (a rig made with a count array)"""
+        self.src, self.dst, self.counts = src, dst, list(counts)
+        self.ar.reload(self.d_src, u8(src))
+        self.ar.reload(self.d_dst, u8(dst))
+        self.ar.reload(self.d_counts, u8(np.asarray(counts, np.int32)))
+
     def k(self, p):
         return self.cap if self.counts is None else max(0, min(int(self.counts[p]), self.cap))
 

@@ -88,6 +88,12 @@ class Rig:
         self.d_gc = self.ar.new(4 * pairs)
         self.m = capi.Matcher(hip_ctx, desc_bytes, qcap, tcap, pairs, knn)
 
+    def set_counts(self, q_counts, t_counts):
+        """other device counts for the next calls on the same handle (a rig made with count arrays)"""
+        self.ar.reload(self.d_qc, np.asarray(q_counts, np.int32))
+        self.ar.reload(self.d_tc, np.asarray(t_counts, np.int32))
+        self.q_counts, self.t_counts = list(q_counts), list(t_counts)
+
     def sides(self, p):
         """the valid descriptor rows of pair p: (query rows, train rows)"""
         Q = self.qcap if self.q_counts is None else clip(self.q_counts[p], self.qcap)

@@ -116,6 +116,17 @@ class Rig:
         self.d_desc = self.ar.new(F * key_cap * desc_stride)
         self.plan = capi.Plan(hip_ctx, W, H, S, F)
 
+    def set_content(self, valid, rng, corner_counts=None):
+        """other frames [F][H][W] (and device corner counts: a prefix of every frame's list) for the next calls on the same plan"""
+        self.valid = valid
+        self.host_in = pad_frames(valid, self.geom[2], rng)
+        self.ar.reload(self.d_in, self.host_in)
+        if corner_counts is not None:
+            if not hasattr(self, "full_lists"):
+                self.full_lists = [c.copy() for c in self.lists]
+            self.lists = [c[:n] for c, n in zip(self.full_lists, corner_counts)]
+            self.ar.reload(self.d_ccounts, np.asarray([len(c) for c in self.lists], np.int32))
+
     def expected(self, level, scale):
         return [om.keypoints(self.valid[f], self.lists[f], level, scale) for f in range(self.geom[3])]
 

@@ -66,6 +66,12 @@ class Rig:
         self.d_desc = self.ar.new(F * key_cap * desc_stride)
         self.pyr = capi.OrbPyramid(hip_ctx, W, H, S, F, opts_of(levels, sf, mf, threshold), corner_cap)
 
+    def set_content(self, valid, rng):
+        """other frames [F][H][W] for the next calls on the same handle"""
+        self.valid = valid
+        self.host_in = pad_frames(valid, self.geom[2], rng)
+        self.ar.reload(self.d_in, self.host_in)
+
     def close(self):
         self.pyr.close()
 

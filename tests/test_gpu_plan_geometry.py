@@ -60,6 +60,14 @@ class Arena:
     def refill(self, body, fill=SENTINEL):
         body.fill_(fill)
 
+    def reload(self, body, host):
+        """new content for a buffer registered with keep(): the device bytes, and the copy check() holds them against"""
+        h = np.ascontiguousarray(host).view(np.uint8).reshape(-1).copy()
+        assert h.size == body.numel() and any(b is body for b, _ in self.kept)
+        body.copy_(self.torch.from_numpy(h))
+        self.torch.cuda.synchronize()
+        self.kept = [(b, h if b is body else old) for b, old in self.kept]
+
     def check(self, what):
         self.torch.cuda.synchronize()
         for raw in self.bufs:
