@@ -68,6 +68,8 @@ EXPORTS = [
     "compvhip_homography_create", "compvhip_homography_destroy", "compvhip_homography_points", "compvhip_homography_find", "compvhip_homography_project",
     "compvhip_homography_quads", "compvhip_homography_find_f64", "compvhip_homography_scores", "compvhip_homography_set_timing", "compvhip_homography_get_timing",
     "compvhip_hog_geometry", "compvhip_plan_hog", "compvhip_hog_u8",
+    "compvhip_integral_dims", "compvhip_plan_integral", "compvhip_integral_u8", "compvhip_plan_histogram", "compvhip_histogram_u8", "compvhip_plan_equalize",
+    "compvhip_equalize_u8", "compvhip_plan_projections", "compvhip_projections_u8",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -324,6 +326,15 @@ def load():
     L.compvhip_hog_geometry.argtypes = [sz, sz, C.POINTER(HogOpts), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_hog.argtypes = [vp, vp, C.POINTER(HogOpts), vp, vp, sz, vp]
     L.compvhip_hog_u8.argtypes = [vp, vp, sz, sz, sz, C.POINTER(HogOpts), vp, sz, C.POINTER(sz)]
+    L.compvhip_integral_dims.argtypes = [sz, sz, C.POINTER(sz), C.POINTER(sz)]
+    L.compvhip_plan_integral.argtypes = [vp, vp, vp, vp, sz, vp]
+    L.compvhip_integral_u8.argtypes = [vp, vp, sz, sz, sz, vp, vp, sz]
+    L.compvhip_plan_histogram.argtypes = [vp, vp, vp, vp]
+    L.compvhip_histogram_u8.argtypes = [vp, vp, sz, sz, sz, vp]
+    L.compvhip_plan_equalize.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp]
+    L.compvhip_equalize_u8.argtypes = [vp, vp, sz, sz, sz, vp, C.c_double, vp, sz, vp]
+    L.compvhip_plan_projections.argtypes = [vp, vp, vp, vp, vp]
+    L.compvhip_projections_u8.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -372,6 +383,17 @@ def hog_geometry(W, H, opts=None, **kw):
     if rc != OK:
         raise CompvHipError(rc, "compvhip_hog_geometry")
     return dict(zip(("cellsX", "cellsY", "blocksX", "blocksY", "descLen"), (x.value for x in v)))
+
+
+def integral_dims(W, H):
+    """compvhip_integral_dims (host arithmetic, no GPU): -> (rows, cols) = (H + 1, W + 1) of the integral images of a W x H frame; CompvHipError for W = 0,
+    H = 0, a side beyond 32 767 or 2^31 pixels and more -- what the device calls refuse"""
+    L = load()
+    rows, cols = C.c_size_t(0), C.c_size_t(0)
+    rc = L.compvhip_integral_dims(W, H, C.byref(rows), C.byref(cols))
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_integral_dims")
+    return rows.value, cols.value
 
 
 class Context:
@@ -586,6 +608,42 @@ class Context:
         self._chk(self.lib.compvhip_hog_u8(self.h, _ptr(img), W, H, img.strides[0], C.byref(o), _ptr(desc), desc.size, C.byref(n)))
         return desc[:n.value]
 
+    def integral(self, img, want_sum=True, want_sumsq=True, sum_stride=None):
+        """compvhip_integral_u8 (CompVImage::integral): -> (sum, sumsq), float64 (H + 1, W + 1) views of rows of sum_stride elements; None for one not wanted"""
+        H, W = img.shape
+        stride = W + 1 if sum_stride is None else sum_stride
+        s = np.zeros((H + 1, stride), np.float64) if want_sum else None
+        q = np.zeros((H + 1, stride), np.float64) if want_sumsq else None
+        self._chk(self.lib.compvhip_integral_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(s) if want_sum else None, _ptr(q) if want_sumsq else None, stride))
+        return (s[:, :W + 1] if want_sum else None), (q[:, :W + 1] if want_sumsq else None)
+
+    def histogram(self, img):
+        """compvhip_histogram_u8 (CompVImage::histogramBuild): -> uint32[256]"""
+        H, W = img.shape
+        hist = np.zeros(256, np.uint32)
+        self._chk(self.lib.compvhip_histogram_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(hist)))
+        return hist
+
+    def equalize(self, img, hist=None, scale=0.0, out_stride=None):
+        """compvhip_equalize_u8 (CompVImage::histogramEqualiz): -> (out, lut); hist: None (the frame's own) or uint32[256]; scale <= 0: 255 / (W * H)"""
+        H, W = img.shape
+        So = W if out_stride is None else out_stride
+        out = np.zeros((H, So), np.uint8)
+        lut = np.zeros(256, np.uint8)
+        if hist is not None:
+            hist = np.ascontiguousarray(hist, np.uint32)
+            assert hist.size == 256
+        self._chk(self.lib.compvhip_equalize_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(hist) if hist is not None else None, float(scale), _ptr(out), So, _ptr(lut)))
+        return out[:, :W], lut
+
+    def projections(self, img, want_x=True, want_y=True):
+        """compvhip_projections_u8 (CompVImage::histogramBuildProjectionX / Y): -> (projX int32[W], projY int32[H]); None for one not wanted"""
+        H, W = img.shape
+        px = np.zeros(W, np.int32) if want_x else None
+        py = np.zeros(H, np.int32) if want_y else None
+        self._chk(self.lib.compvhip_projections_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(px) if want_x else None, _ptr(py) if want_y else None))
+        return px, py
+
     def scale(self, img, out_w, out_h):
         """compvhip_scale_u8 (CompVImage::scale, bilinear): -> the (out_h, out_w) plane"""
         H, W = img.shape
@@ -799,6 +857,24 @@ class Plan:
         the cell map [frames][cellsY][cellsX][nbins]; opts: a HogOpts, or its keywords"""
         o = _hog_opts(opts, kw)
         self.ctx._chk(self.lib.compvhip_plan_hog(self.h, d_gray or None, C.byref(o), d_cells or None, d_desc or None, desc_stride, stream))
+
+    def integral(self, d_gray, d_sum, d_sumsq, sum_stride, stream=0):
+        """compvhip_plan_integral: the plan's frames -> float64 integral images [frames][H + 1][sum_stride] of the pixels (d_sum) and of their squares (d_sumsq);
+        either may be 0, sum_stride >= W + 1 in elements"""
+        self.ctx._chk(self.lib.compvhip_plan_integral(self.h, d_gray or None, d_sum or None, d_sumsq or None, sum_stride, stream))
+
+    def histogram(self, d_gray, d_hist, stream=0):
+        """compvhip_plan_histogram: the plan's frames -> uint32 [frames][256]"""
+        self.ctx._chk(self.lib.compvhip_plan_histogram(self.h, d_gray or None, d_hist or None, stream))
+
+    def equalize(self, d_gray, d_out, d_hist=0, scale=0.0, d_lut=0, stream=0):
+        """compvhip_plan_equalize: d_out [frames][H][S] (may be d_gray) = lut[d_gray]; d_hist: 0 (each frame's own histogram) or uint32 [frames][256]; scale <= 0:
+        255 / (W * H); d_lut: 0 or [frames][256] bytes"""
+        self.ctx._chk(self.lib.compvhip_plan_equalize(self.h, d_gray or None, d_hist or None, float(scale), d_out or None, d_lut or None, stream))
+
+    def projections(self, d_gray, d_proj_x, d_proj_y, stream=0):
+        """compvhip_plan_projections: the plan's frames -> int32 column sums [frames][W] and row sums [frames][H]; either may be 0"""
+        self.ctx._chk(self.lib.compvhip_plan_projections(self.h, d_gray or None, d_proj_x or None, d_proj_y or None, stream))
 
     def scale(self, d_in, d_out, out_w, out_h, out_stride, stream=0):
         """compvhip_plan_scale: the plan's frames [frames][H][S] -> d_out [frames][out_h][out_stride], bilinear"""

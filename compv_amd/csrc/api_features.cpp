@@ -1,5 +1,5 @@
 // api_features.cpp -- plan-level calls of the features built on the Canny / SHT plan: line segments, line fits, connected components,
-// thresholding and morphology, FAST corners, ORB keypoints and descriptors, bilinear scale and the ORB pyramid, remap and inverse warp, brute-force matching.
+// thresholding and morphology, FAST corners, ORB keypoints and descriptors, bilinear scale and the ORB pyramid, remap and inverse warp, brute-force matching, HOG, image statistics.
 #include "api_internal.hpp"
 
 // what the segment and the fit kernels read alike: the edge pixels, the vote's tables, the lines
@@ -1121,4 +1121,156 @@ int compvhip_plan_hog(compvhip_plan* p, const uint8_t* d_gray, const compvhip_ho
 	{ Stamp s(p, st, "hog_cells_kernel"); HIPCHK(ctx, launch_hog_cells(a, frames, st)); }
 	{ Stamp s(p, st, "hog_blocks_kernel"); HIPCHK(ctx, launch_hog_blocks(a, frames, st)); }
 	return COMPVHIP_OK;
+}
+
+// ---- image statistics (stats_kernels.hip; definition in include/compv_hip.h) ----------------------------------------------------------------------------
+int compvhip_api::integralDims(compvhip_ctx* ctx, size_t W, size_t H)
+{
+	if (!W || !H) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: an empty frame");
+	if (W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: frame beyond 32767");
+	if (W * H >= (static_cast<size_t>(1) << 31)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: 2^31 pixels or more");
+	return COMPVHIP_OK;
+}
+
+int compvhip_integral_dims(size_t W, size_t H, size_t* rows, size_t* cols)
+{
+	const int rc = integralDims(nullptr, W, H);
+	if (rc) return rc;
+	if (rows) *rows = H + 1;
+	if (cols) *cols = W + 1;
+	return COMPVHIP_OK;
+}
+
+namespace {
+// what every statistics call checks first: the frames and their geometry (a plan's holds by construction; the host calls come with any size)
+int statsCheck(const StatsFrames& g, const char* what)
+{
+	if (!g.d_gray) return fail(g.ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
+	if (!g.W || !g.H || g.W > 32767 || g.H > 32767 || g.S < g.W) return fail(g.ctx, COMPVHIP_E_INVALID_PARAMETER, what);
+	if (!g.frames || g.frames > static_cast<size_t>(INT32_MAX)) return fail(g.ctx, COMPVHIP_E_INVALID_PARAMETER, "frames beyond 2^31");
+	return COMPVHIP_OK;
+}
+// the entry of a kernel in the plan's timing (every kernel with mode 1; the host calls have no plan and no timing)
+struct StatsStamp : Stamp {
+	StatsStamp(const StatsFrames& g, const char* name) : Stamp(g.plan, g.st, name, g.plan && g.plan->timing == 1) {}
+};
+} // namespace
+
+int compvhip_api::integralImpl(const StatsFrames& g, double* d_sum, double* d_sumsq, size_t sumStride)
+{
+	compvhip_ctx* ctx = g.ctx;
+	int rc = statsCheck(g, "integral: frame size out of range (1..32767) or stride below the width");
+	if (rc) return rc;
+	if ((rc = integralDims(ctx, g.W, g.H))) return rc;
+	if (!d_sum && !d_sumsq) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: both outputs are NULL");
+	if (sumStride < g.W + 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: sumStride below W + 1");
+	if (misaligned(7, d_sum, d_sumsq)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: outputs must be 8-byte aligned");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int frames = static_cast<int>(g.frames), bands = stats_bands(static_cast<int>(g.H));
+	const size_t cols = g.frames * bands * g.W;
+	if (d_sum) HIPCHK(ctx, g.scratch->colSum.reserve(ctx, cols));
+	if (d_sumsq) HIPCHK(ctx, g.scratch->colSq.reserve(ctx, cols));
+	if (g.plan && g.plan->timing) timelineClear(g.plan);
+	StatsBandArgs b;
+	b.in = g.d_gray; b.frameStride = g.S * g.H; b.W = static_cast<int>(g.W); b.H = static_cast<int>(g.H); b.S = static_cast<int>(g.S); b.bands = bands;
+	b.colSum = d_sum ? g.scratch->colSum.ptr : nullptr; b.colSq = d_sumsq ? g.scratch->colSq.ptr : nullptr; b.rowSum = nullptr;
+	{ StatsStamp s(g, "stats_band_sums_kernel"); HIPCHK(ctx, launch_stats_band_sums(b, frames, g.st)); }
+	{ StatsStamp s(g, "stats_band_scan_kernel"); HIPCHK(ctx, launch_stats_band_scan(b.colSum, b.colSq, bands, b.W, nullptr, frames, g.st)); }
+	StatsIntegralArgs a;
+	a.in = b.in; a.frameStride = b.frameStride; a.W = b.W; a.H = b.H; a.S = b.S; a.bands = bands;
+	a.edgeSum = b.colSum; a.edgeSq = b.colSq; a.sum = d_sum; a.sumsq = d_sumsq; a.sumStride = sumStride;
+	{ StatsStamp s(g, "stats_integral_kernel"); HIPCHK(ctx, launch_stats_integral(a, frames, g.st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_api::histogramImpl(const StatsFrames& g, uint32_t* d_hist)
+{
+	compvhip_ctx* ctx = g.ctx;
+	const int rc = statsCheck(g, "histogram: frame size out of range (1..32767) or stride below the width");
+	if (rc) return rc;
+	if (!d_hist) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "histogram: null output");
+	if (misaligned(3, d_hist)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "histogram: the output must be 4-byte aligned");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int frames = static_cast<int>(g.frames), chunks = stats_row_chunks(static_cast<int>(g.H), frames);
+	HIPCHK(ctx, g.scratch->hist.reserve(ctx, g.frames * chunks * 256));
+	if (g.plan && g.plan->timing) timelineClear(g.plan);
+	{ StatsStamp s(g, "stats_hist_kernel");
+	  HIPCHK(ctx, launch_stats_hist(g.d_gray, static_cast<int>(g.W), static_cast<int>(g.H), static_cast<int>(g.S), g.S * g.H, frames, chunks, g.scratch->hist, g.st)); }
+	{ StatsStamp s(g, "stats_hist_finish_kernel"); HIPCHK(ctx, launch_stats_hist_finish(g.scratch->hist, chunks, d_hist, 0.f, nullptr, frames, g.st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_api::equalizeImpl(const StatsFrames& g, const uint32_t* d_hist, double scale, uint8_t* d_out, uint8_t* d_lut)
+{
+	compvhip_ctx* ctx = g.ctx;
+	const int rc = statsCheck(g, "equalize: frame size out of range (1..32767) or stride below the width");
+	if (rc) return rc;
+	if (!d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "equalize: null output frame");
+	if (misaligned(3, d_hist)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "equalize: the histogram must be 4-byte aligned");
+	const float scaleF = static_cast<float>(scale > 0.0 ? scale : 255.0 / static_cast<double>(g.W * g.H));
+	if (!(scale == scale) || !std::isfinite(scaleF)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "equalize: the scale is not a finite float32");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int frames = static_cast<int>(g.frames), chunks = stats_row_chunks(static_cast<int>(g.H), frames);
+	if (!d_hist) HIPCHK(ctx, g.scratch->hist.reserve(ctx, g.frames * chunks * 256));
+	if (!d_lut) HIPCHK(ctx, g.scratch->lut.reserve(ctx, g.frames * 256));
+	if (g.plan && g.plan->timing) timelineClear(g.plan);
+	uint8_t* const lut = d_lut ? d_lut : g.scratch->lut.ptr;
+	if (!d_hist) {
+		StatsStamp s(g, "stats_hist_kernel");
+		HIPCHK(ctx, launch_stats_hist(g.d_gray, static_cast<int>(g.W), static_cast<int>(g.H), static_cast<int>(g.S), g.S * g.H, frames, chunks, g.scratch->hist, g.st));
+	}
+	{ StatsStamp s(g, "stats_hist_finish_kernel");
+	  HIPCHK(ctx, launch_stats_hist_finish(d_hist ? d_hist : g.scratch->hist.ptr, d_hist ? 1 : chunks, nullptr, scaleF, lut, frames, g.st)); }
+	StatsEqualizeArgs a;
+	a.in = g.d_gray; a.out = d_out; a.lut = lut; a.frameStride = g.S * g.H; a.W = static_cast<int>(g.W); a.H = static_cast<int>(g.H); a.S = static_cast<int>(g.S);
+	{ StatsStamp s(g, "stats_equalize_kernel"); HIPCHK(ctx, launch_stats_equalize(a, frames, chunks, g.st)); }
+	return COMPVHIP_OK;
+}
+
+int compvhip_api::projectionsImpl(const StatsFrames& g, int32_t* d_projX, int32_t* d_projY)
+{
+	compvhip_ctx* ctx = g.ctx;
+	const int rc = statsCheck(g, "projections: frame size out of range (1..32767) or stride below the width");
+	if (rc) return rc;
+	if (!d_projX && !d_projY) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "projections: both outputs are NULL");
+	if (misaligned(3, d_projX, d_projY)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "projections: outputs must be 4-byte aligned");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int frames = static_cast<int>(g.frames), bands = stats_bands(static_cast<int>(g.H));
+	if (d_projX) HIPCHK(ctx, g.scratch->colSum.reserve(ctx, g.frames * bands * g.W));
+	if (g.plan && g.plan->timing) timelineClear(g.plan);
+	StatsBandArgs b;
+	b.in = g.d_gray; b.frameStride = g.S * g.H; b.W = static_cast<int>(g.W); b.H = static_cast<int>(g.H); b.S = static_cast<int>(g.S); b.bands = bands;
+	b.colSum = d_projX ? g.scratch->colSum.ptr : nullptr; b.colSq = nullptr; b.rowSum = d_projY;
+	{ StatsStamp s(g, "stats_band_sums_kernel"); HIPCHK(ctx, launch_stats_band_sums(b, frames, g.st)); }          // the frames are read once, here
+	if (d_projX) { StatsStamp s(g, "stats_band_scan_kernel"); HIPCHK(ctx, launch_stats_band_scan(b.colSum, nullptr, bands, b.W, d_projX, frames, g.st)); }
+	return COMPVHIP_OK;
+}
+
+static StatsFrames planFrames(compvhip_plan* p, const uint8_t* d_gray, void* stream)
+{
+	return StatsFrames{ p->ctx, p, &p->stats, d_gray, p->W, p->H, p->S, p->frames, static_cast<hipStream_t>(stream) };
+}
+
+int compvhip_plan_integral(compvhip_plan* p, const uint8_t* d_gray, double* d_sum, double* d_sumsq, size_t sumStride, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	return integralImpl(planFrames(p, d_gray, stream), d_sum, d_sumsq, sumStride);
+}
+
+int compvhip_plan_histogram(compvhip_plan* p, const uint8_t* d_gray, uint32_t* d_hist, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	return histogramImpl(planFrames(p, d_gray, stream), d_hist);
+}
+
+int compvhip_plan_equalize(compvhip_plan* p, const uint8_t* d_gray, const uint32_t* d_hist, double scale, uint8_t* d_out, uint8_t* d_lut, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	return equalizeImpl(planFrames(p, d_gray, stream), d_hist, scale, d_out, d_lut);
+}
+
+int compvhip_plan_projections(compvhip_plan* p, const uint8_t* d_gray, int32_t* d_projX, int32_t* d_projY, void* stream)
+{
+	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
+	return projectionsImpl(planFrames(p, d_gray, stream), d_projX, d_projY);
 }

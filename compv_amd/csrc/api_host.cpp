@@ -685,3 +685,88 @@ int compvhip_homography_find_f64(compvhip_ctx* ctx, const double* src, const dou
 	compvhip_homography_destroy(h);
 	return rc;
 }
+
+// ---- image statistics of one host frame (no plan: a plan has a minimum size, these calls have none) ------------------------------------------------------
+namespace {
+// the frame into dIn (rows of alignUp(W, 64) bytes), `run` on it, the stream waited for -- also after a failure: no copy from or to the caller's memory stays in flight
+template <typename Run>   // int run(const StatsFrames&)
+int hostStats(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const Run& run)
+{
+	if (!in || S < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image or stride < width");
+	if (!W || !H || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (1..32767)");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t Sd = alignUp(W, 64);
+	HIPCHK(ctx, ctx->dIn.reserve(ctx, Sd * H));
+	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
+	const int rc = run(StatsFrames{ ctx, nullptr, &ctx->stats, ctx->dIn, W, H, Sd, 1, ctx->stream });
+	const hipError_t e = hipStreamSynchronize(ctx->stream);
+	if (!rc && e != hipSuccess) return fail(ctx, COMPVHIP_E_HIP, "hipStreamSynchronize", e);
+	return rc;
+}
+} // namespace
+
+int compvhip_integral_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double* sum, double* sumsq, size_t sumStride)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	int rc = integralDims(ctx, W, H);
+	if (rc) return rc;
+	if (!sum && !sumsq) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: both outputs are NULL");
+	if (sumStride < W + 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: sumStride below W + 1");
+	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g) -> int {
+		const size_t cols = W + 1, plane = (H + 1) * cols;
+		HIPCHK(ctx, ctx->dStatsF64.reserve(ctx, 2 * plane));
+		double* const dSum = sum ? ctx->dStatsF64.ptr : nullptr;
+		double* const dSq = sumsq ? ctx->dStatsF64.ptr + plane : nullptr;
+		const int rc = integralImpl(g, dSum, dSq, cols);
+		if (rc) return rc;
+		if (sum) HIPCHK(ctx, hipMemcpy2DAsync(sum, sumStride * sizeof(double), dSum, cols * sizeof(double), cols * sizeof(double), H + 1, hipMemcpyDeviceToHost, ctx->stream));
+		if (sumsq) HIPCHK(ctx, hipMemcpy2DAsync(sumsq, sumStride * sizeof(double), dSq, cols * sizeof(double), cols * sizeof(double), H + 1, hipMemcpyDeviceToHost, ctx->stream));
+		return COMPVHIP_OK;
+	});
+}
+
+int compvhip_histogram_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint32_t* hist)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!hist) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "histogram: null output");
+	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g) -> int {
+		HIPCHK(ctx, ctx->dStatsU32.reserve(ctx, 256));
+		const int rc = histogramImpl(g, ctx->dStatsU32);
+		if (rc) return rc;
+		HIPCHK(ctx, hipMemcpyAsync(hist, ctx->dStatsU32, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		return COMPVHIP_OK;
+	});
+}
+
+int compvhip_equalize_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint32_t* hist, double scale, uint8_t* out, size_t So, uint8_t* lut)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!out || So < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "equalize: null output frame or stride < width");
+	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g) -> int {
+		HIPCHK(ctx, ctx->dStatsU32.reserve(ctx, 256 + 64));          // the caller's histogram, the table behind it
+		HIPCHK(ctx, ctx->dOut.reserve(ctx, g.S * H));
+		uint8_t* const dLut = reinterpret_cast<uint8_t*>(ctx->dStatsU32.ptr + 256);
+		if (hist) HIPCHK(ctx, hipMemcpyAsync(ctx->dStatsU32, hist, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+		const int rc = equalizeImpl(g, hist ? ctx->dStatsU32.ptr : nullptr, scale, ctx->dOut, dLut);
+		if (rc) return rc;
+		HIPCHK(ctx, download(ctx, out, So, ctx->dOut, g.S, W, H));
+		if (lut) HIPCHK(ctx, hipMemcpyAsync(lut, dLut, 256, hipMemcpyDeviceToHost, ctx->stream));
+		return COMPVHIP_OK;
+	});
+}
+
+int compvhip_projections_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, int32_t* projX, int32_t* projY)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!projX && !projY) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "projections: both outputs are NULL");
+	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g) -> int {
+		HIPCHK(ctx, ctx->dStatsU32.reserve(ctx, W + H));
+		int32_t* const dX = projX ? reinterpret_cast<int32_t*>(ctx->dStatsU32.ptr) : nullptr;
+		int32_t* const dY = projY ? reinterpret_cast<int32_t*>(ctx->dStatsU32.ptr) + W : nullptr;
+		const int rc = projectionsImpl(g, dX, dY);
+		if (rc) return rc;
+		if (projX) HIPCHK(ctx, hipMemcpyAsync(projX, dX, W * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+		if (projY) HIPCHK(ctx, hipMemcpyAsync(projY, dY, H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+		return COMPVHIP_OK;
+	});
+}

@@ -109,6 +109,12 @@ struct WarpTables {
 	~WarpTables() { for (auto& s : slot) if (s.copied) (void)hipEventDestroy(s.copied); }   // (the owner's device is current: compvhip_plan_destroy, compvhip_ctx_destroy)
 };
 
+// Scratch of the image statistics calls (stats_kernels.hip): the bands' column sums of p and of p * p, [frames][bands][W] each; the partial histograms
+// [frames][chunks][256]; the look-up tables [frames][256] of the equalisation calls that do not hand them out.  A plan owns one, the context one for its host calls.
+struct StatsScratch {
+	DevBuf<uint64_t> colSum, colSq; DevBuf<uint32_t> hist; DevBuf<uint8_t> lut;
+};
+
 struct compvhip_ctx {
 	int device = 0;
 	std::string err;
@@ -136,6 +142,9 @@ struct compvhip_ctx {
 	DevBuf<float> dMap;                     // staging of compvhip_remap_u8: mapX, then mapY
 	WarpTables warp;                        // tables of compvhip_warp_inverse_u8
 	DevBuf<float> dHogDesc;                 // staging of compvhip_hog_u8: the descriptor
+	StatsScratch stats;                     // scratch of the host statistics calls (they need no plan: a plan has a minimum size, these calls have none)
+	DevBuf<double> dStatsF64;               // staging of compvhip_integral_u8: sum, then sumsq, (H + 1) x (W + 1) each
+	DevBuf<uint32_t> dStatsU32;             // staging of the other statistics calls: a histogram (with the table behind it), or projX then projY
 	KhtScratch kht;                    // KHT scratch of the host entry point (compvhip_houghkht_u8)
 };
 
@@ -217,6 +226,7 @@ struct compvhip_plan : TimingState {
 	DevBuf<int32_t> orbIndex; DevBuf<uint8_t> orbBlur; uint16_t orbKern[5] = {}; bool orbKernReady = false; bool orbBriefLds = false;
 	WarpTables warp;             // inverse warp (remap_kernels.hip), allocated on first use: the matrices' running-sum tables and their pinned staging
 	DevBuf<float> hogCells;      // HOG (hog_kernels.hip), allocated on first use without a caller's map: the cell map [frames][cellsY][cellsX][nbins]
+	StatsScratch stats;          // image statistics (stats_kernels.hip), allocated on first use
 	int strengthBits = 16, keyBits = 0;
 	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
 	DevBuf<uint16_t> chunkHist; DevBuf<uint32_t> strengthStart; int sortChunks = 0; bool deviceSort = false;
@@ -419,6 +429,13 @@ int morphPrepare(compvhip_ctx* ctx, size_t W, size_t H, const uint8_t* strel, si
 int checkFast(compvhip_ctx* ctx, size_t W, size_t H, int fastType);
 int checkOrb(compvhip_ctx* ctx, size_t W, size_t H, float scale);
 int hogGeometry(compvhip_ctx* ctx, size_t W, size_t H, const compvhip_hog_opts* opts, HogArgs* a);   // the definition's items 5, 6, 8: refusals, defaults, geometry
+// image statistics on frames [frames][H][S] in device memory: the bodies of the plan calls (plan: whose timing they feed) and of the host calls (plan == nullptr)
+int integralDims(compvhip_ctx* ctx, size_t W, size_t H);   // the integral image's limits: 1 <= W, H <= 32 767, W * H < 2^31
+struct StatsFrames { compvhip_ctx* ctx; compvhip_plan* plan; StatsScratch* scratch; const uint8_t* d_gray; size_t W, H, S, frames; hipStream_t st; };
+int integralImpl(const StatsFrames& g, double* d_sum, double* d_sumsq, size_t sumStride);
+int histogramImpl(const StatsFrames& g, uint32_t* d_hist);
+int equalizeImpl(const StatsFrames& g, const uint32_t* d_hist, double scale, uint8_t* d_out, uint8_t* d_lut);
+int projectionsImpl(const StatsFrames& g, int32_t* d_projX, int32_t* d_projY);
 int scaleImpl(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, hipStream_t st);
 // remap and inverse warp: validates everything but the coordinate source and fills `a` (roi == nullptr: the whole frame)
 int remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, int interp, const compvhip_roi* roi, void* d_out, size_t Wout,

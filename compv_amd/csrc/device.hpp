@@ -41,6 +41,24 @@ __device__ __forceinline__ T wave_incl_scan(T x, int lane)
 	return x;
 }
 
+// The same for uint32 on the vector ALU alone: six v_add_u32 with a DPP operand (row_shr 1, 2, 4, 8 inside the rows of 16 lanes, then row_bcast:15 into
+// rows 1 and 3 and row_bcast:31 into rows 2 and 3), no trip through the LDS crossbar.  All 64 lanes must be active.  The total is readlane(result, 63).
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t v)          // the value of the lane CTRL names; 0 for a lane without a source or in a row outside ROWS
+{
+	return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, ROWS, 0xf, false));
+}
+__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t x)
+{
+	x += dpp_or_zero<0x111, 0xf>(x);          // row_shr:1
+	x += dpp_or_zero<0x112, 0xf>(x);          // row_shr:2
+	x += dpp_or_zero<0x114, 0xf>(x);          // row_shr:4
+	x += dpp_or_zero<0x118, 0xf>(x);          // row_shr:8
+	x += dpp_or_zero<0x142, 0xa>(x);          // row_bcast:15
+	x += dpp_or_zero<0x143, 0xc>(x);          // row_bcast:31
+	return x;
+}
+
 // Exclusive prefix sum of src[0 .. n) into dst[0 .. n) by one workgroup of THREADS threads (all of them call it); src may be dst.  n > THREADS goes in
 // rounds, the total of the earlier rounds carried in a register.  Every thread gets the total.
 template <int THREADS>

@@ -505,4 +505,48 @@ bool hog_plan_launch(HogArgs& a);
 hipError_t launch_hog_cells(const HogArgs& a, int frames, hipStream_t stream);
 hipError_t launch_hog_blocks(const HogArgs& a, int frames, hipStream_t stream);
 
+// ---- image statistics: integral images, histogram, equalisation, projections (stats_kernels.hip) -------------------------------------------------
+// CompVImage::integral / histogramBuild / histogramEqualiz / histogramBuildProjectionX / Y (include/compv_hip.h, section "image statistics")
+constexpr int kStatsBandRows = 16;      // rows of a band: one workgroup of the band-sums kernel, one wave of the integral kernel
+constexpr int kStatsTile = 64;          // columns of a tile of the integral kernel: one per lane
+constexpr int kStatsThreads = 256;      // threads of the band-sums kernel, four columns each: 1024 columns at a time (one wave, 256 columns, for frames of at most 256)
+constexpr int kStatsMaxChunks = 128;    // row chunks (= workgroups) per frame of the histogram and the equalisation kernel
+int stats_bands(int H);                 // ceil(H / kStatsBandRows)
+int stats_row_chunks(int H, int frames);   // row chunks of at least 16 rows: 1024 / frames of them, 1 .. kStatsMaxChunks
+struct StatsBandArgs {
+	const uint8_t* in;        // [frames][H][S]
+	size_t frameStride;
+	int W, H, S, bands;
+	uint64_t* colSum;         // [frames][bands][W] per band and column: the sum of the band's pixels (may be nullptr)
+	uint64_t* colSq;          // the same for their squares (may be nullptr)
+	int32_t* rowSum;          // [frames][H] the sum of every row = projY (may be nullptr)
+};
+hipError_t launch_stats_band_sums(const StatsBandArgs& a, int frames, hipStream_t stream);
+// projX == nullptr: colSum / colSq (either may be nullptr) become their exclusive prefix sums down the bands, in place; otherwise projX [frames][W] = the
+// total of colSum over the bands, and nothing else is written
+hipError_t launch_stats_band_scan(uint64_t* colSum, uint64_t* colSq, int bands, int W, int32_t* projX, int frames, hipStream_t stream);
+struct StatsIntegralArgs {
+	const uint8_t* in;        // [frames][H][S]
+	size_t frameStride;
+	int W, H, S, bands;
+	const uint64_t* edgeSum;  // [frames][bands][W]: what launch_stats_band_scan left (read with `sum`)
+	const uint64_t* edgeSq;   // (read with `sumsq`)
+	double* sum;              // [frames][H + 1][sumStride], or nullptr
+	double* sumsq;            // likewise; not both nullptr
+	size_t sumStride;         // >= W + 1, in elements
+};
+hipError_t launch_stats_integral(const StatsIntegralArgs& a, int frames, hipStream_t stream);
+// part: [frames][chunks][256] partial histograms, chunks = stats_row_chunks(H, frames)
+hipError_t launch_stats_hist(const uint8_t* in, int W, int H, int S, size_t frameStride, int frames, int chunks, uint32_t* part, hipStream_t stream);
+// hist (may be nullptr): [frames][256] the sum of the partial ones; lut (may be nullptr): [frames][256] min(trunc(float32(running sum) * scaleF), 255)
+hipError_t launch_stats_hist_finish(const uint32_t* part, int chunks, uint32_t* hist, float scaleF, uint8_t* lut, int frames, hipStream_t stream);
+struct StatsEqualizeArgs {
+	const uint8_t* in;        // [frames][H][S]
+	uint8_t* out;             // [frames][H][S]; may be `in`
+	const uint8_t* lut;       // [frames][256]
+	size_t frameStride;
+	int W, H, S;
+};
+hipError_t launch_stats_equalize(const StatsEqualizeArgs& a, int frames, int chunks, hipStream_t stream);
+
 } // namespace compvhip

@@ -221,7 +221,7 @@ COMPVHIP_API int compvhip_plan_create(compvhip_ctx* ctx, size_t W, size_t H, siz
  *   REFUSED         beyond 65 535 frames the call returns COMPVHIP_E_INVALID_PARAMETER, compvhip_last_error names the limit, nothing is allocated, enqueued
  *                   or written.  Split the batch across plans of at most 65 535 frames.
  * The text-detection chain (grayscale, otsu, threshold, threshold_adaptive, morph, components on the caller's bytes), the segment and fit calls on the
- * caller's bytes, remap / warp_inverse and hog are SLICED; edge_dete has its FRAMES IN X; Canny and everything that needs its masks, the SHT, the batched KHT, the
+ * caller's bytes, remap / warp_inverse, hog and the image statistics (integral, histogram, equalize, projections) are SLICED; edge_dete has its FRAMES IN X; Canny and everything that needs its masks, the SHT, the batched KHT, the
  * fixed-point blur, FAST, ORB and the bilinear scale are REFUSED, as are a compvhip_orbpyr of more than 65 535 frames and a compvhip_matcher or a
  * compvhip_homography of more than 65 535 pairs at their creation. */
 /* A plan must be destroyed BEFORE its context (it keeps a pointer to it); compvhip_ctx_destroy only releases the private
@@ -1067,6 +1067,52 @@ COMPVHIP_API int compvhip_plan_hog(compvhip_plan* plan, const uint8_t* d_gray, c
  * computed or written and COMPVHIP_E_OUT_OF_BOUND is returned (cap == 0 with desc == NULL asks for the length). */
 COMPVHIP_API int compvhip_hog_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_hog_opts* opts, float* desc, size_t cap,
                                  size_t* n);
+
+/* ---- image statistics: integral images, histogram, equalisation, projections (docs/kernels/stats.md) ------------------------------------------
+ * The static CompVImage functions integral (base/image/compv_image_integral.cxx), histogramBuild, histogramEqualiz, histogramBuildProjectionX / Y
+ * (base/image/compv_image.cxx:704-757,846, base/math/compv_math_histogram.cxx) on gray frames p of W x H.  Every output is defined bit for bit: all of it is
+ * integer arithmetic, the equalisation table two float32 operations on integers.  Common to the four plan calls: the frames are [frames][H][S] bytes in the
+ * plan's geometry and are never written (but for an in-place equalisation); bytes at columns >= W never count; no alignment is asked of the frames; the
+ * calls are asynchronous on `stream`, the frames independent, and beyond 65 535 frames the calls are SLICED.  Scratch is owned by the plan, allocated on
+ * first use and released with it.  A refusal returns COMPVHIP_E_INVALID_PARAMETER, names its reason in compvhip_last_error and happens before anything is
+ * allocated, enqueued or written.  The host forms take one frame of any size from 1 x 1 (they need no plan) and are synchronous.
+ *  1. Integral images: sum[y][x] = the sum of p[y'][x'] over y' < y, x' < x; sumsq[y][x] = the same sum of p[y'][x'] * p[y'][x'], for 0 <= y <= H,
+ *     0 <= x <= W, as float64.  Row 0 and column 0 are zeros and are written.  With W, H <= 32 767 and W * H < 2^31 every value is an integer below 2^47:
+ *     exact in float64 in any summation order (the kernels carry u32 along a row, u64 down a column, and convert once at the store).  The reference's
+ *     layout is CompVMat::newObjAligned<double>(H + 1, W + 1); here the stride is the caller's.
+ *  2. Histogram: hist[v] = the number of pixels that equal v, uint32, 256 bins.
+ *  3. Equalisation (CompVImage::histogramEqualiz, compv_image.cxx:720-757): scaleF = (float)(scale > 0 ? scale : 255.0 / (double)(W * H)), computed on the
+ *     host; run = the running sum of the histogram, uint32 modulo 2^32; v = (float)run * scaleF -- the conversion rounds to nearest even, the multiply
+ *     rounds once --; lut[i] = min(trunc(v), 255); out[y][x] = lut[p[y][x]].  The reference converts v to uint8_t without saturation, which is undefined
+ *     for v >= 256 (only a caller's own scale or histogram gets there): the clamp is this library's definition of that case.  A scale that is NaN, or
+ *     not finite as a float32, is refused.
+ *  4. Projections: projX[x] = the sum of p[y][x] over y (buildProjectionX), projY[y] = the sum of p[y][x] over x (buildProjectionY), int32; at most
+ *     255 * 32 767. */
+
+/* Host arithmetic only: rows = H + 1, cols = W + 1 of the integral images of a W x H frame (either may be NULL); COMPVHIP_E_INVALID_PARAMETER for W = 0,
+ * H = 0, W or H beyond 32 767, or W * H >= 2^31 -- what the device calls refuse. */
+COMPVHIP_API int compvhip_integral_dims(size_t W, size_t H, size_t* rows, size_t* cols);
+
+/* d_sum, d_sumsq: [frames][H + 1][sumStride] float64, sumStride >= W + 1 counted in elements, 8-byte aligned; elements at columns > W are not written.
+ * Either may be NULL, not both.  Three kernels: the bands' column sums, their scan down the frame, the integral (one pass over 16-row bands). */
+COMPVHIP_API int compvhip_plan_integral(compvhip_plan* plan, const uint8_t* d_gray, double* d_sum, double* d_sumsq, size_t sumStride, void* stream);
+COMPVHIP_API int compvhip_integral_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double* sum, double* sumsq, size_t sumStride);
+
+/* d_hist: [frames][256] uint32, 4-byte aligned. */
+COMPVHIP_API int compvhip_plan_histogram(compvhip_plan* plan, const uint8_t* d_gray, uint32_t* d_hist, void* stream);
+COMPVHIP_API int compvhip_histogram_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint32_t* hist);
+
+/* d_hist: [frames][256], or NULL: each frame's own histogram (the reference's first overload; a non-NULL d_hist is its second).  d_out: [frames][H][S],
+ * columns >= W are not written; d_out == d_gray is allowed, as in the reference: the histogram of a frame is complete before any of its pixels is
+ * rewritten.  Any other overlap of the two is not.  d_lut: NULL or [frames][256] bytes, the tables. */
+COMPVHIP_API int compvhip_plan_equalize(compvhip_plan* plan, const uint8_t* d_gray, const uint32_t* d_hist, double scale, uint8_t* d_out, uint8_t* d_lut,
+                                        void* stream);
+COMPVHIP_API int compvhip_equalize_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint32_t* hist, double scale, uint8_t* out,
+                                      size_t So, uint8_t* lut);
+
+/* d_projX: [frames][W], d_projY: [frames][H], int32, dense, 4-byte aligned.  Either may be NULL, not both; with both the frames are read once. */
+COMPVHIP_API int compvhip_plan_projections(compvhip_plan* plan, const uint8_t* d_gray, int32_t* d_projX, int32_t* d_projY, void* stream);
+COMPVHIP_API int compvhip_projections_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, int32_t* projX, int32_t* projY);
 
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
