@@ -682,6 +682,7 @@ int compvhip_plan_otsu(compvhip_plan* p, const uint8_t* d_gray, int32_t* d_thres
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_gray || !d_thresholds) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null pointer");
+	if (misaligned(3, d_thresholds)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "levels must be 4-byte aligned");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	int rc = ensurePreproc(p);
 	if (rc) return rc;
@@ -750,6 +751,7 @@ int compvhip_api::planShtImpl(compvhip_plan* p, const uint8_t* d_edges, int thre
 {
 	compvhip_ctx* ctx = p->ctx;
 	if (threshold <= 0) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "threshold must be > 0"); // houghsht.cxx:82
+	if (misaligned(3, d_lines, d_counts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "lines and counts must be 4-byte aligned");
 	if (!d_edges && !p->bitsValid) return fail(ctx, COMPVHIP_E_INVALID_STATE, "no edge masks: run compvhip_plan_canny first or pass d_edges");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	int rc = ensureSht(p);
@@ -830,6 +832,7 @@ static int checkStep(compvhip_plan* p, const StepParams& sp)
 	rc = checkPixfmt(ctx, sp.pixfmt, p->W);   // (COMPVHIP_FMT_Y passes: one byte, any width)
 	if (rc) return rc;
 	if (sp.d_cart && (!sp.d_lines || !sp.d_counts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "toCartesian needs the line and count buffers");
+	if (misaligned(3, sp.d_lines, sp.d_counts, sp.d_otsu, sp.d_cart)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "lines, counts, levels and endpoints must be 4-byte aligned");
 	return COMPVHIP_OK;
 }
 
@@ -1032,6 +1035,7 @@ static int toCartesianImpl(compvhip_plan* p, const compvhip_line* d_lines, const
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_lines || !d_counts || !d_cart) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null pointer");
+	if (misaligned(3, d_lines, d_counts, d_cart)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "lines, counts and endpoints must be 4-byte aligned");
 	int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_to_cartesian");
 	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1060,6 +1064,7 @@ int compvhip_plan_acc_export(compvhip_plan* p, size_t frame, int32_t* d_out, siz
 	compvhip_ctx* ctx = p->ctx;
 	// (a single frame, no frame index in the grid; but no call that fills the accumulators accepts such a plan: there is nothing to export)
 	if (int rc = refuseBeyondLaunchLimit(ctx, p->frames, "compvhip_plan_acc_export")) return rc;
+	if (misaligned(3, d_out)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "the accumulator copy must be 4-byte aligned");
 	if (!p->shtReady || frame >= p->frames || !d_out || outStride < p->T) return COMPVHIP_E_INVALID_PARAMETER;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	HIPCHK(ctx, launch_sht_acc_transpose(p->acc + frame * p->accFrameStride, static_cast<int>(p->R), static_cast<int>(p->T), p->accPitch, d_out, outStride,

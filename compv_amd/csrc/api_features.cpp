@@ -19,6 +19,7 @@ int compvhip_api::segmentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_t 
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_lines || !d_counts || !d_segCounts || !lineCap || (segCap && !d_segs)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null line / count / segment buffer");
 	if (minLength < 1 || maxGap < 0) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "segments need minLength >= 1 and maxGap >= 0");
+	if (misaligned(3, d_lines, d_counts, d_segs, d_segCounts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "lines, segments and counts must be 4-byte aligned");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	int rc = ensureSht(p);
 	if (rc) return rc;
@@ -58,6 +59,8 @@ int compvhip_api::fitImpl(compvhip_plan* p, const uint8_t* d_edges, size_t edgeS
 	if (!d_lines || !d_counts || !d_fitCounts || !lineCap || (fitCap && !d_fits)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null line / count / fit buffer");
 	if (d_segs && (!d_segCounts || d_refined)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "per-segment fits need d_segCounts and take no d_refined");
 	if (halfWidth < 0 || halfWidth > kFitMaxHalfWidth) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "halfWidth must be 0 .. 8");
+	if (misaligned(3, d_lines, d_counts, d_segs, d_segCounts, d_fitCounts, d_refined) || misaligned(alignof(compvhip_line_fit) - 1, d_fits))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "fit records must be 8-byte aligned; lines, segments and counts 4-byte aligned");
 	if (std::max(p->W, p->H) > kFitMaxSide) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "line fits need max(W, H) <= 8192 (int64 central moments)");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	int rc = ensureSht(p);
@@ -97,6 +100,7 @@ int compvhip_api::componentsImpl(compvhip_plan* p, const uint8_t* d_edges, size_
 	if (minPixels < 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "minPixels must be >= 1");
 	if (!d_compCounts || (compCap && !d_comps)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null count / record buffer");
 	if (d_labels && labelStride < p->W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "labelStride < W");
+	if (misaligned(3, d_labels, d_comps, d_compCounts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "labels, records and counts must be 4-byte aligned");
 	if (p->W * p->H > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "W * H beyond 2^31");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const size_t frames = p->frames;
@@ -156,6 +160,7 @@ int compvhip_plan_threshold(compvhip_plan* p, const uint8_t* d_in, double thresh
 	compvhip_ctx* ctx = p->ctx;
 	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
 	if (!d_levels && !(threshold >= 0.0)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "threshold < 0"); // compv_image_threshold.cxx:120
+	if (misaligned(3, d_levels)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "levels must be 4-byte aligned");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	if (p->timing) timelineClear(p);
@@ -872,6 +877,7 @@ int compvhip_matcher_good(compvhip_matcher* m, const compvhip_match* d_matches, 
 	if (misaligned(15, d_matches, d_good)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records must be 16-byte aligned");
 	if (misaligned(3, d_queryCounts, d_trainCounts, d_goodCounts))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "counts must be 4-byte aligned");
+	if (misaligned(3, d_query, d_train)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descriptors must be 4-byte aligned");   // with or without the cross check, which alone reads them
 	if (opts->crossCheck) {
 		int rc = checkMatchBuffers(m, d_query, queryStride, d_train, trainStride);
 		if (rc) return rc;

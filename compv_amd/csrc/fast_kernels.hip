@@ -11,7 +11,8 @@
 //
 // For a pixel I with b = min(255, I + t), d = max(0, I - t) and ring pixels p_0 .. p_15 (clockwise from the top):
 //   D_k = max(0, d - p_k), B_k = max(0, p_k - b);  score = max over the 16 arcs of N consecutive k of min(D_k over the arc), and of min(B_k).
-// Integer arithmetic only.  Frames are a grid dimension (blockIdx.z); frame bases are 8-byte aligned and S % 8 == 0 (plan contract), so every
+// Integer arithmetic only.  Frames are a grid dimension (blockIdx.z); frame bases are 8-byte aligned (compvhip_plan_fast and the pyramid refuse
+// anything else before they enqueue) and S % 8 == 0 (plan contract), so every
 // row starts on a dword.  Columns >= W are read (they only ever feed pixels within 3 of the right edge, whose score is 0 by definition) and
 // never written.
 //

@@ -6,9 +6,12 @@
 //   CompVImageThreshold::adaptive    base/image/compv_image_threshold.cxx:183-317 (mean kernel, hz + vt fixed-point passes, 768-entry LUT)
 //   CompVMathMorph::process          base/math/compv_math_morph.cxx:95-123 (ops), 125-247 (basicOper), 542-674 (borders), 676-692 (leaf)
 //
-// Integer arithmetic only.  Frames are a grid dimension (blockIdx.z); frame bases are 8-byte aligned and S % 8 == 0 (plan contract), so
-// every row starts on a dword.  Columns >= W are read (they only ever feed border cells, whose value does not depend on them) and
-// never written.
+// Integer arithmetic only.  Frames are a grid dimension (blockIdx.z); S % 8 == 0 (plan contract), so every row starts a whole number of
+// 8-byte groups behind the frame base.  The base itself may sit at any byte (include/compv_hip.h: ANY BYTE): every access to the caller's
+// planes is a per-lane global load or store of 4 or 8 bytes at base + a multiple of its size, which the hardware takes at any address and
+// which stays inside the frame span; nothing rounds an address down, and no atomic touches a plane
+// (tests/test_gpu_pointer_alignment.py runs every kernel of this file off alignment).  Columns >= W are read (they only ever feed
+// border cells, whose value does not depend on them) and never written.
 #include "device.hpp"
 #include "frame_slices.hpp"
 

@@ -29,6 +29,8 @@ namespace compvhip {
 
 // ---------------------------------------------------------------------------------------------------------------
 // foreign edge maps: bytes -> bit mask (any non-zero byte is an edge: houghsht.cxx:159-165)
+// The caller's d_edges may start at any byte (include/compv_hip.h: ANY BYTE).  S % 16 == 0 only says that every row sits a whole number of
+// 16-byte groups behind the base; the two 16-byte loads are per-lane global loads, which the hardware takes at any address.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bytes_to_bits_kernel(const uint8_t* __restrict__ edges, int W, int H, int S, size_t frameStride,
                                                             uint32_t* __restrict__ ebits, int wb, size_t bitsFrameStride)

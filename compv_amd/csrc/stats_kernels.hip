@@ -15,8 +15,8 @@
 //                            increments plus its carry gives the integral at the band's upper edge; the prefixes are accumulated down the column in u64
 //                            registers and converted once at the store.  A store instruction writes 64 consecutive float64 of one row.  The frame is
 //                            read a second time here (2 B / px in all), a byte per lane.
-//   stats_hist_kernel<DWORDS>   A new kernel, not the one behind launch_otsu: that one loads 8-byte groups and so needs 8-byte aligned rows, which these
-//                            calls do not ask for; launch_otsu and its kernels are untouched.  It keeps that kernel's LDS layout ([256 bins][32 columns],
+//   stats_hist_kernel<DWORDS>   A new kernel, not the one behind launch_otsu: that one loads 8-byte groups (per lane, so the hardware takes them at any
+//                            address too, but a dword-aligned frame would pay for the split accesses), where these calls pick their arm by the pointer; launch_otsu and its kernels are untouched.  It keeps that kernel's LDS layout ([256 bins][32 columns],
 //                            a lane always uses column lane % 32) with one wave per row and four pixels per lane; partial histograms per row chunk, no
 //                            global atomic, no memset.
 //   stats_hist_finish_kernel Sums the partial histograms of a frame (or takes the caller's), writes the histogram and / or the equalisation look-up table.

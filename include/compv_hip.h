@@ -224,37 +224,49 @@ COMPVHIP_API int compvhip_plan_create(compvhip_ctx* ctx, size_t W, size_t H, siz
  * caller's bytes, remap / warp_inverse, hog and the image statistics (integral, histogram, equalize, projections) are SLICED; edge_dete has its FRAMES IN X; Canny and everything that needs its masks, the SHT, the batched KHT, the
  * fixed-point blur, FAST, ORB and the bilinear scale are REFUSED, as are a compvhip_orbpyr of more than 65 535 frames and a compvhip_matcher or a
  * compvhip_homography of more than 65 535 pairs at their creation. */
+/* Alignment of device pointers.  Every d_* pointer of the plan, pyramid, matcher and homography calls belongs to one of two classes, stated beside its call
+ * (tests/alignment_cases.py is the same list, and tests/test_alignment_cases.py fails when a pointer has no entry):
+ *   ANY BYTE        uint8 frames, edge maps and planes only: the pointer may start at any byte (a sub-buffer, a region of interest, frames behind a header).
+ *                   The call gives the bits it gives at an aligned pointer and writes nothing it does not write there.  Frame f starts S * H bytes after
+ *                   frame f - 1, whatever that does to its alignment.
+ *   N-BYTE ALIGNED  N = 4, 8 or 16: anything else is refused with COMPVHIP_E_INVALID_PARAMETER before the call allocates, enqueues or writes anything,
+ *                   and compvhip_last_error says so.  Every typed array is in this class at the alignment of its element: int32 / uint32 / float32 arrays
+ *                   and the records made of them (compvhip_line, _segment, _component, _corner, _keypoint) 4 bytes, float64 arrays, compvhip_line_fit and
+ *                   compvhip_homography_result 8 bytes, compvhip_match records and {x, y} float64 points 16 bytes.
+ * A null pointer where a call allows one counts as aligned.  A d_* parameter with two stars (compvhip_plan_acc, _edge_counts, compvhip_orbpyr_plane) is a HOST
+ * pointer that receives a device address.  The host entry points copy into buffers of their own and take any host pointer. */
 /* A plan must be destroyed BEFORE its context (it keeps a pointer to it); compvhip_ctx_destroy only releases the private
  * single-frame plan of the host entry points. */
 COMPVHIP_API void compvhip_plan_destroy(compvhip_plan* plan);
 
 /* Canny on `frames` device frames: d_in -> d_edges (both frames*S*H bytes, may alias).  Asynchronous on `stream`
  * (a hipStream_t; NULL = default stream) except for the hysteresis convergence check, which polls a device flag.
- * Beyond 65 535 frames: REFUSED (the resolve rounds index their change flags by the launch's frame extent). */
+ * Beyond 65 535 frames: REFUSED (the resolve rounds index their change flags by the launch's frame extent).  d_in and d_edges: ANY BYTE. */
 COMPVHIP_API int compvhip_plan_canny(compvhip_plan* plan, const uint8_t* d_in, float tLow, float tHigh, int ksize,
                                      int thresholdType, uint8_t* d_edges, void* stream);
 
 /* compvhip_grayscale_u8 on `frames` device frames: d_in = [frames][H][S samples], d_gray = [frames][H][S].  Asynchronous.
- * Beyond 65 535 frames: SLICED. */
+ * Beyond 65 535 frames: SLICED.  d_in and d_gray: ANY BYTE (the packed samples as well). */
 COMPVHIP_API int compvhip_plan_grayscale(compvhip_plan* plan, const uint8_t* d_in, int pixfmt, uint8_t* d_gray, void* stream);
 
 /* compvhip_otsu_u8 on `frames` device frames: d_thresholds[f] = Otsu level of frame f (device array).  Asynchronous.
- * Beyond 65 535 frames: SLICED (histograms and levels slice by slice). */
+ * Beyond 65 535 frames: SLICED (histograms and levels slice by slice).  d_gray: ANY BYTE; d_thresholds: 4-byte aligned. */
 COMPVHIP_API int compvhip_plan_otsu(compvhip_plan* plan, const uint8_t* d_gray, int32_t* d_thresholds, void* stream);
 
 /* compvhip_convlt1_fixedpoint_u8 on `frames` device frames (vtKern/hzKern are HOST arrays of kernSize weights); d_in and
- * d_out may alias.  Asynchronous.  Beyond 65 535 frames: REFUSED. */
+ * d_out may alias.  Asynchronous.  Beyond 65 535 frames: REFUSED.  d_in and d_out: ANY BYTE. */
 COMPVHIP_API int compvhip_plan_convlt1_fixedpoint(compvhip_plan* plan, const uint8_t* d_in, const uint16_t* vtKern, const uint16_t* hzKern,
                                                   size_t kernSize, uint8_t* d_out, void* stream);
 
 /* CompVHoughSht::toCartesian (core/features/hough/compv_core_feature_houghsht.cxx:264-304,566-589) on the device line arrays a
  * compvhip_plan_houghsht / _pipeline call produced: d_cart[f][i] = {a.x, a.y, b.x, b.y} of line i of frame f (a.z = b.z = 1), for
- * i < min(d_counts[f], lineCap).  Asynchronous.  Beyond 65 535 frames: REFUSED (like the calls that produce such line arrays). */
+ * i < min(d_counts[f], lineCap).  Asynchronous.  Beyond 65 535 frames: REFUSED (like the calls that produce such line arrays).  d_lines, d_counts and
+ * d_cart: 4-byte aligned. */
 COMPVHIP_API int compvhip_plan_to_cartesian(compvhip_plan* plan, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap,
                                             float* d_cart, void* stream);
 
 /* Sobel / Scharr / Prewitt detector (compvhip_edge_dete_u8 semantics) on `frames` device frames; d_in and d_out must
- * not alias.  Fully asynchronous on `stream`.  Beyond 65 535 frames: FRAMES IN X. */
+ * not alias.  Fully asynchronous on `stream`.  Beyond 65 535 frames: FRAMES IN X.  d_in and d_out: ANY BYTE. */
 COMPVHIP_API int compvhip_plan_edge_dete(compvhip_plan* plan, const uint8_t* d_in, int op, uint8_t* d_out, void* stream);
 
 /* SHT on the edge maps produced by the last compvhip_plan_canny() of this plan (uses its 1-bit edge masks, no byte
@@ -265,12 +277,13 @@ COMPVHIP_API int compvhip_plan_edge_dete(compvhip_plan* plan, const uint8_t* d_i
  * min(R*T, max(lineCap, 65536)) candidates per frame, so whatever lineCap is, the lineCap STRONGEST lines are returned as long as
  * d_counts[f] <= max(lineCap, 65536); beyond that the key buffer overflowed and frame f's lines are an arbitrary subset -- call
  * again with lineCap >= d_counts[f] (the host entry point compvhip_houghsht_u8 does that by itself).
- * Beyond 65 535 frames: REFUSED (the whole SHT stage; its key buffers alone would run to gigabytes). */
+ * Beyond 65 535 frames: REFUSED (the whole SHT stage; its key buffers alone would run to gigabytes).  d_edges: ANY BYTE; d_lines and d_counts: 4-byte
+ * aligned. */
 COMPVHIP_API int compvhip_plan_houghsht(compvhip_plan* plan, const uint8_t* d_edges, int threshold, int maxLines,
                                         compvhip_line* d_lines, size_t lineCap, int32_t* d_counts, void* stream);
 
 /* Sobel -> Canny -> HoughSHT in one call (the benchmark's "step").  Beyond 65 535 frames: REFUSED, like compvhip_plan_pipeline_async and
- * compvhip_plan_pipeline_ex (Canny and the SHT are). */
+ * compvhip_plan_pipeline_ex (Canny and the SHT are).  In all three, d_in and d_edges: ANY BYTE; d_lines and d_counts: 4-byte aligned. */
 COMPVHIP_API int compvhip_plan_pipeline(compvhip_plan* plan, const uint8_t* d_in, float tLow, float tHigh,
                                         int threshold, int maxLines, uint8_t* d_edges,
                                         compvhip_line* d_lines, size_t lineCap, int32_t* d_counts, void* stream);
@@ -309,9 +322,9 @@ typedef struct compvhip_pipeline_opts {
 	int ksize;              /* Sobel kernel size of the gradient: 3 or 5 (0 = 3) */
 	int thresholdType;      /* COMPVHIP_CANNY_THRESHOLD_* */
 	int pixfmt;             /* compvhip_pixfmt of d_in; COMPVHIP_FMT_Y (luma plane, stride S) or a packed format ([frames][H][S samples]): converted first */
-	uint8_t* d_gray;        /* packed input: receives the luma planes [frames][H][S] (NULL: plan-owned scratch) */
-	int32_t* d_otsu;        /* OTSU mode: receives the per-frame Otsu levels (NULL: not wanted) */
-	float* d_cart;          /* receives toCartesian's endpoints [frames][lineCap][4] (NULL: not wanted) */
+	uint8_t* d_gray;        /* packed input: receives the luma planes [frames][H][S] (NULL: plan-owned scratch); ANY BYTE */
+	int32_t* d_otsu;        /* OTSU mode: receives the per-frame Otsu levels (NULL: not wanted); 4-byte aligned */
+	float* d_cart;          /* receives toCartesian's endpoints [frames][lineCap][4] (NULL: not wanted); 4-byte aligned */
 } compvhip_pipeline_opts;
 /* ticket == NULL: synchronous like compvhip_plan_pipeline; otherwise asynchronous like compvhip_plan_pipeline_async (same rules: wait with
  * compvhip_plan_wait, d_in unmodified and distinct from d_edges until then). */
@@ -332,7 +345,7 @@ COMPVHIP_API int compvhip_plan_pipeline_ex(compvhip_plan* plan, const uint8_t* d
  * cluster subdivision does not terminate: a defined deviation, also of compvhip_houghkht_u8 / compvhip_houghkht_kernels_u8).
  * compvhip_plan_houghkht_stage_ms: the six stage clocks of the last call summed over its frames (compvhip_houghkht_stage_ms order), the wall
  * time of the call and the number of workers.
- * Beyond 65 535 frames: REFUSED (compvhip_plan_houghkht_ex as well). */
+ * Beyond 65 535 frames: REFUSED (compvhip_plan_houghkht_ex as well).  d_edges: ANY BYTE (in both calls; every other array is the host's). */
 COMPVHIP_API int compvhip_plan_houghkht(compvhip_plan* plan, const uint8_t* d_edges, float rho, float thetaDeg, int threshold, int maxLines,
                                         double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight,
                                         compvhip_line* lines, size_t cap, size_t* counts, double* gs, int hostThreads);
@@ -374,14 +387,16 @@ COMPVHIP_API int compvhip_houghkht_ex_u8(compvhip_ctx* ctx, const uint8_t* edges
                                          compvhip_line* lines, size_t cap, size_t* n, double* gs);
 
 /* Device accumulator of frame f after compvhip_plan_houghsht: uint16 (a cell never exceeds the pixels of a 1-px band),
- * theta-major [T][accPitch] (pitch >= R).  compvhip_plan_acc_export gives the reference's int32 rho-major layout. */
+ * theta-major [T][accPitch] (pitch >= R).  compvhip_plan_acc_export gives the reference's int32 rho-major layout.  d_acc: a HOST pointer that receives the
+ * device address. */
 COMPVHIP_API int compvhip_plan_acc(compvhip_plan* plan, size_t frame, const uint16_t** d_acc, size_t* R, size_t* T, size_t* accPitch);
 /* Copies the accumulator of frame f into a caller DEVICE buffer in the reference layout: int32 [R][outStride]
  * (outStride >= T), i.e. acc[(barrier - rho) * outStride + t] (houghsht.cxx:430-431).  Beyond 65 535 frames: REFUSED (one frame per call, but no
- * call that fills the accumulators accepts such a plan). */
+ * call that fills the accumulators accepts such a plan).  d_out: 4-byte aligned. */
 COMPVHIP_API int compvhip_plan_acc_export(compvhip_plan* plan, size_t frame, int32_t* d_out, size_t outStride, void* stream);
 /* Number of edge pixels per frame voted by the last houghsht / pipeline step of this plan (device int32[frames]).  The SHT's voting
- * kernel counts them: a compvhip_plan_canny call alone resets them to zero, and before the plan's first SHT the call is refused. */
+ * kernel counts them: a compvhip_plan_canny call alone resets them to zero, and before the plan's first SHT the call is refused.  d_edge_counts: a HOST
+ * pointer that receives the device address. */
 COMPVHIP_API int compvhip_plan_edge_counts(compvhip_plan* plan, const int32_t** d_edge_counts);
 
 /* ---- Hough line SEGMENTS: where along an SHT line its edge pixels are ----------------------------------------
@@ -410,7 +425,8 @@ typedef struct compvhip_segment {
  * above are written, so a clipped result is a prefix of the full one.  Asynchronous on `stream` (the plan's SHT tables and a scratch array of
  * frames * min(lineCap, maxLines) counters are allocated on first use).  COMPVHIP_E_INVALID_STATE while the plan has asynchronous steps that
  * were not waited for (a replayed step rewrites d_lines later); COMPVHIP_E_INVALID_PARAMETER for minLength < 1, maxGap < 0, lineCap == 0 or
- * segCap == 0.  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there. */
+ * segCap == 0.  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there.
+ * d_edges: ANY BYTE; d_lines, d_counts, d_segs and d_segCounts: 4-byte aligned. */
 COMPVHIP_API int compvhip_plan_houghsht_segments(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts,
                                                  size_t lineCap, int maxLines, int minLength, int maxGap,
                                                  compvhip_segment* d_segs, size_t segCap, int32_t* d_segCounts, void* stream);
@@ -462,7 +478,8 @@ typedef struct compvhip_line_fit {
  * only).  d_refined: NULL, or frames * lineCap lines, of which the lines considered are written -- it feeds compvhip_plan_to_cartesian with the
  * same d_counts and lineCap; COMPVHIP_E_INVALID_PARAMETER in per-segment mode.  halfWidth outside 0 .. 8, lineCap == 0 or a null line / count
  * buffer: COMPVHIP_E_INVALID_PARAMETER; max(W, H) > 8192: COMPVHIP_E_NOT_IMPLEMENTED.  Asynchronous on `stream`; no scratch beyond the
- * plan's SHT tables.  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there. */
+ * plan's SHT tables.  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there.
+ * d_edges: ANY BYTE; d_fits: 8-byte aligned; d_lines, d_counts, d_segs, d_segCounts, d_fitCounts and d_refined: 4-byte aligned. */
 COMPVHIP_API int compvhip_plan_houghsht_fit(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts,
                                             size_t lineCap, int maxLines, int halfWidth,
                                             const compvhip_segment* d_segs, const int32_t* d_segCounts, size_t segCap,
@@ -502,7 +519,8 @@ typedef struct compvhip_component {
  * with compCap == 0: counts only.  Bad connectivity, minPixels < 1, labelStride < W (with a label map): COMPVHIP_E_INVALID_PARAMETER.
  * Asynchronous on `stream`.  Scratch is owned by the plan and allocated on first use: frames * H int32, for byte maps a mask copy
  * (frames * H * wb words, 1/8 of the bytes), and -- only when d_labels == NULL -- one int32 parent word per pixel (frames * W * H * 4 bytes:
- * 33 MB per 4K frame); with a label map the parent words live in it (labelled in place).  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there. */
+ * 33 MB per 4K frame); with a label map the parent words live in it (labelled in place).  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there.
+ * d_edges: ANY BYTE; d_labels, d_comps and d_compCounts: 4-byte aligned (the kernels run atomics on the label words and on the boxes). */
 COMPVHIP_API int compvhip_plan_components(compvhip_plan* plan, const uint8_t* d_edges, int connectivity, int minPixels,
                                           int32_t* d_labels, size_t labelStride, compvhip_component* d_comps, size_t compCap,
                                           int32_t* d_compCounts, void* stream);
@@ -544,7 +562,8 @@ COMPVHIP_API int compvhip_threshold_u8(compvhip_ctx* ctx, const uint8_t* in, siz
                                        uint8_t* out, size_t So);
 /* The same on `frames` device frames.  d_levels != NULL: frame f is cut at d_levels[f] clipped to 0..255 and `threshold` is ignored --
  * the array compvhip_plan_otsu writes, so Otsu + binarise is CompVImage::thresholdOtsu(input, t, &output) (compv_image_threshold.cxx:110-113)
- * without a host round trip.  d_in and d_out may be the same buffer.  Columns >= W of d_out are never written.  Beyond 65 535 frames: SLICED. */
+ * without a host round trip.  d_in and d_out may be the same buffer.  Columns >= W of d_out are never written.  Beyond 65 535 frames: SLICED.
+ * d_in and d_out: ANY BYTE; d_levels: 4-byte aligned. */
 COMPVHIP_API int compvhip_plan_threshold(compvhip_plan* plan, const uint8_t* d_in, double threshold, const int32_t* d_levels,
                                          uint8_t* d_out, void* stream);
 
@@ -560,7 +579,7 @@ COMPVHIP_API int compvhip_threshold_adaptive_u8(compvhip_ctx* ctx, const uint8_t
                                                 double delta, double maxVal, int invert, uint8_t* out, size_t So);
 /* The same on `frames` device frames, one fused kernel: the mean never reaches memory.  d_in == d_out is served through a plane the plan owns
  * (allocated on first use) and a device copy; any other overlap: COMPVHIP_E_INVALID_PARAMETER.  Columns >= W of d_out are never written.
- * Beyond 65 535 frames: SLICED (in place, the device copy is one enqueue per frame). */
+ * Beyond 65 535 frames: SLICED (in place, the device copy is one enqueue per frame).  d_in and d_out: ANY BYTE. */
 COMPVHIP_API int compvhip_plan_threshold_adaptive(compvhip_plan* plan, const uint8_t* d_in, size_t blockSize, double delta, double maxVal,
                                                   int invert, uint8_t* d_out, void* stream);
 
@@ -583,7 +602,8 @@ COMPVHIP_API int compvhip_morph_strel(int type, size_t w, size_t h, uint8_t* str
 COMPVHIP_API int compvhip_morph_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint8_t* strel, size_t sw,
                                    size_t sh, int op, int border, uint8_t* out, size_t So);
 /* The same on `frames` device frames (strel is a HOST array).  An OPEN / CLOSE is two launches through a u8 plane [frames][H][S] the plan owns
- * (allocated on first use).  Columns >= W of d_out are never written.  Beyond 65 535 frames: SLICED (compvhip_plan_morph_ex as well). */
+ * (allocated on first use).  Columns >= W of d_out are never written.  Beyond 65 535 frames: SLICED (compvhip_plan_morph_ex as well).  d_in and d_out: ANY
+ * BYTE (compvhip_plan_morph_ex as well). */
 COMPVHIP_API int compvhip_plan_morph(compvhip_plan* plan, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op,
                                      int border, uint8_t* d_out, void* stream);
 /* compvhip_plan_morph with the kernel named (COMPVHIP_MORPH_KERNEL_*): for measuring one kernel against the other and for testing both on
@@ -621,7 +641,7 @@ typedef struct compvhip_corner {
 	int32_t strength;           /* score + t - 1 */
 } compvhip_corner;
 
-/* Corners of all frames of the plan.  d_gray: [frames][H][S]; d_scores: NULL or a score map of the same geometry (8-byte aligned, must not
+/* Corners of all frames of the plan.  d_gray: [frames][H][S], 8-byte aligned; d_scores: NULL or a score map of the same geometry (8-byte aligned, must not
  * overlap d_gray); d_corners and d_counts: 4-byte aligned (anything else: COMPVHIP_E_INVALID_PARAMETER); d_corners == NULL with cornerCap == 0: counts only.  Asynchronous on `stream`; results are deterministic run to run.  Scratch
  * is owned by the plan, allocated on first use and released with it: frames * (2 * H + 257) int32, and -- only when d_scores == NULL -- a score
  * map of the plan's own.  Beyond 65 535 frames: REFUSED. */
@@ -673,14 +693,16 @@ COMPVHIP_API void compvhip_matcher_destroy(compvhip_matcher* matcher);
 
 /* d_query: [pairs][queryCap] rows of queryStride bytes (descBytes <= queryStride <= 65536, queryStride % 4 == 0, 4-byte aligned); d_train: the same with
  * trainCap / trainStride, or, with trainShared != 0, ONE train set [trainCap] and ONE train count that serve every pair (one trained object
- * against many frames).  d_matches: [pairs][knn][queryCap] records, 16-byte aligned.  Asynchronous on `stream`; deterministic run to run. */
+ * against many frames).  d_matches: [pairs][knn][queryCap] records, 16-byte aligned; d_queryCounts and d_trainCounts 4-byte aligned.  Asynchronous on `stream`;
+ * deterministic run to run. */
 COMPVHIP_API int compvhip_matcher_knn(compvhip_matcher* matcher, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts,
                                       const uint8_t* d_train, size_t trainStride, const int32_t* d_trainCounts, int trainShared,
                                       compvhip_match* d_matches, void* stream);
 
 /* The good list of the d_matches a compvhip_matcher_knn call of this matcher wrote for the same descriptors and counts.  The descriptors are
  * read by the cross check only (it runs the distance kernel with the roles swapped and knn = 1 into the matcher's scratch).  d_good:
- * [pairs][goodCap] records, 16-byte aligned (NULL with goodCap == 0: counts only); d_goodCounts: [pairs] int32.  opts == NULL, or
+ * [pairs][goodCap] records, 16-byte aligned (NULL with goodCap == 0: counts only); d_goodCounts: [pairs] int32; d_matches 16-byte aligned, the descriptors and
+ * the three count arrays 4-byte aligned.  opts == NULL, or
  * ratio > 0 on a matcher with knn < 2: COMPVHIP_E_INVALID_PARAMETER.  Asynchronous on `stream`. */
 COMPVHIP_API int compvhip_matcher_good(compvhip_matcher* matcher, const compvhip_match* d_matches,
                                        const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts,
@@ -752,7 +774,7 @@ COMPVHIP_API int compvhip_plan_orb_keypoints(compvhip_plan* plan, const uint8_t*
                                              int32_t* d_keyCounts, int32_t* d_moments, void* stream);
 
 /* Descriptors of the keypoints (compvhip_plan_orb_keypoints' or the caller's own) with the level's `scale`.  descStride >= 32 and a multiple of 4,
- * d_desc 4-byte aligned, keyCap > 0 (anything else: COMPVHIP_E_INVALID_PARAMETER).  With descStride == 32, d_desc / d_keyCounts are what
+ * d_gray, d_keypoints, d_keyCounts and d_desc 4-byte aligned, keyCap > 0 (anything else: COMPVHIP_E_INVALID_PARAMETER).  With descStride == 32, d_desc / d_keyCounts are what
  * compvhip_matcher_knn takes as d_query / d_queryCounts.  Asynchronous on `stream`.  Scratch, allocated on first use with blur != 0: one blurred
  * batch [frames][H][S].  Beyond 65 535 frames: REFUSED. */
 COMPVHIP_API int compvhip_plan_orb_describe(compvhip_plan* plan, const uint8_t* d_gray, const compvhip_keypoint* d_keypoints, size_t keyCap,
@@ -822,20 +844,23 @@ COMPVHIP_API void compvhip_orbpyr_destroy(compvhip_orbpyr* pyramid);
 /* Host arithmetic only: size, stride, sf[level] and quota (0 without a cut) of a level; an empty level has S == 0.  Any output may be NULL. */
 COMPVHIP_API int compvhip_orbpyr_geometry(const compvhip_orbpyr* pyramid, int level, size_t* W, size_t* H, size_t* S, float* scale, int* quota);
 /* The device plane [frames][H_l][S_l] of a level as the last call built it: blurred == 0 the scaled plane (level 0: the caller's d_gray of that
- * call), else the blurred one.  COMPVHIP_E_INVALID_STATE before a call built it, COMPVHIP_E_INVALID_PARAMETER for an empty level. */
+ * call), else the blurred one.  COMPVHIP_E_INVALID_STATE before a call built it, COMPVHIP_E_INVALID_PARAMETER for an empty level.  d_plane: a HOST
+ * pointer that receives the device address. */
 COMPVHIP_API int compvhip_orbpyr_plane(compvhip_orbpyr* pyramid, int level, int blurred, const uint8_t** d_plane);
-/* C. for every frame.  d_gray 8-byte aligned; d_keypoints: [frames][keyCap] (NULL with keyCap == 0: counts only); counts 4-byte aligned.
+/* C. for every frame.  d_gray 8-byte aligned; d_keypoints: [frames][keyCap] (NULL with keyCap == 0: counts only); keypoints and counts (d_keyCounts,
+ * d_levelCounts, d_levelCorners) 4-byte aligned.
  * Asynchronous on `stream`, never synchronises the host, deterministic run to run. */
 COMPVHIP_API int compvhip_orbpyr_detect(compvhip_orbpyr* pyramid, const uint8_t* d_gray, compvhip_keypoint* d_keypoints, size_t keyCap, int32_t* d_keyCounts,
                                         int32_t* d_levelCounts, int32_t* d_levelCorners, void* stream);
 /* D. for every frame; rows as compvhip_plan_orb_describe writes them (rows q >= min(count, keyCap) are never written).  reusePlanes != 0:
  * describe on the planes the preceding compvhip_orbpyr_detect built from the same d_gray (COMPVHIP_E_INVALID_STATE when there was none);
- * reusePlanes == 0 rebuilds them.  Asynchronous on `stream`, never synchronises the host. */
+ * reusePlanes == 0 rebuilds them.  d_gray 8-byte aligned; d_keypoints, d_keyCounts and d_desc 4-byte aligned.  Asynchronous on `stream`, never synchronises
+ * the host. */
 COMPVHIP_API int compvhip_orbpyr_describe(compvhip_orbpyr* pyramid, const uint8_t* d_gray, int reusePlanes, const compvhip_keypoint* d_keypoints, size_t keyCap,
                                           const int32_t* d_keyCounts, uint8_t* d_desc, size_t descStride, void* stream);
 /* A. for every frame of a plan: d_in [frames][H][S] of the plan's geometry -> d_out [frames][Hout][Sout] (Sout >= Wout; sizes up to 32767; the
  * buffers must not overlap).  A destination that is dword-aligned in pointer and stride is written with dword stores.  Asynchronous on `stream`.
- * Beyond 65 535 frames: REFUSED. */
+ * Beyond 65 535 frames: REFUSED.  d_in and d_out: ANY BYTE (a destination that is not dword-aligned is written byte by byte). */
 COMPVHIP_API int compvhip_plan_scale(compvhip_plan* src, const uint8_t* d_in, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
 /* A. for one HOST plane (sizes 1 .. 32767).  Synchronous. */
 COMPVHIP_API int compvhip_scale_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint8_t* out, size_t Wout, size_t Hout, size_t Sout);
@@ -890,13 +915,15 @@ COMPVHIP_API int compvhip_warp_tables(const float* M, int rows, size_t Wout, siz
  * float32.  d_mapX, d_mapY: device, [mapCount][Hout * Wout] float32 each; mapCount == 1: all frames share the map (a workgroup then reads its part of
  * the map once for 8 frames); mapCount == frames: one map per frame.  roi == NULL: the whole frame.  A destination that is aligned in pointer, stride
  * and frame size (4 bytes for uint8, 16 for float32) is written with vector stores.  Asynchronous on `stream`, never synchronises the host.
- * Beyond 65 535 frames (shared map: beyond 65 535 groups of 8): SLICED. */
+ * Beyond 65 535 frames (shared map: beyond 65 535 groups of 8): SLICED.  d_in: ANY BYTE; d_mapX and d_mapY: 4-byte aligned; d_out: ANY BYTE for uint8, 4-byte
+ * aligned for float32. */
 COMPVHIP_API int compvhip_plan_remap(compvhip_plan* plan, const uint8_t* d_in, const float* d_mapX, const float* d_mapY, size_t mapCount, int interp,
                                      const compvhip_roi* roi, uint8_t defaultValue, void* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
 /* Inverse warp for every frame of a plan.  M: HOST, [matrixCount][rows][3] float32, rows 2 or 3; matrixCount 1 or frames.  The tables of A.2 are
  * built on the host into pinned staging owned by the plan and uploaded in stream order; M may be reused as soon as the call returns.  Asynchronous
  * on `stream`: the host waits only when 4 earlier uploads of the plan are all still pending.  Timing entries (compvhip_plan_set_timing):
- * remap_kernel, warp_inverse_kernel.  Beyond 65 535 frames: SLICED, like compvhip_plan_remap. */
+ * remap_kernel, warp_inverse_kernel.  Beyond 65 535 frames: SLICED, like compvhip_plan_remap.  d_in: ANY BYTE; d_out: ANY BYTE for uint8, 4-byte aligned for
+ * float32. */
 COMPVHIP_API int compvhip_plan_warp_inverse(compvhip_plan* plan, const uint8_t* d_in, const float* M, int rows, size_t matrixCount, int interp,
                                             uint8_t defaultValue, void* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
 /* Both for one HOST plane (sizes 1 .. 32767) with host maps / a host matrix; S and Sout in elements.  Synchronous. */
@@ -976,7 +1003,7 @@ COMPVHIP_API int compvhip_homography_points(compvhip_homography* homography, con
                                             int trainShared, void* stream);
 /* d_src, d_dst: [pairs][pointCap] {x, y} float64, 16-byte aligned, with d_counts; d_src == NULL: the points compvhip_homography_points gathered
  * (d_dst and d_counts are then ignored).  d_quads: NULL or [pairs][opts->tries][4] int32, 16-byte aligned.  d_results: [pairs] records, 8-byte
- * aligned.  d_mask: NULL or [pairs][pointCap] bytes.  A null handle, opts or d_results, tries < 1 or > maxTries, a threshold that is not > 0, a
+ * aligned; d_counts 4-byte aligned.  d_mask: NULL or [pairs][pointCap] bytes, ANY BYTE.  A null handle, opts or d_results, tries < 1 or > maxTries, a threshold that is not > 0, a
  * misaligned pointer: COMPVHIP_E_INVALID_PARAMETER, nothing written.  Asynchronous on `stream`; deterministic run to run. */
 COMPVHIP_API int compvhip_homography_find(compvhip_homography* homography, const double* d_src, const double* d_dst, const int32_t* d_counts,
                                           const compvhip_homography_opts* opts, const int32_t* d_quads, compvhip_homography_result* d_results,
@@ -1056,7 +1083,7 @@ typedef struct compvhip_hog_opts {
 COMPVHIP_API int compvhip_hog_geometry(size_t W, size_t H, const compvhip_hog_opts* opts, size_t* cellsX, size_t* cellsY, size_t* blocksX, size_t* blocksY,
                                        size_t* descLen);
 
-/* Descriptors of all frames of the plan.  d_gray: [frames][H][S]; d_desc: [frames][descStride] float32, descStride >= descLen counted in floats, the floats
+/* Descriptors of all frames of the plan.  d_gray: [frames][H][S], ANY BYTE; d_desc: [frames][descStride] float32, descStride >= descLen counted in floats, the floats
  * behind descLen are never written; d_cells: NULL or the cell map [frames][cellsY][cellsX][nbins] float32; d_desc and d_cells 4-byte aligned.  A batch of
  * crops is a plan of the crop's size with one frame per crop.  Asynchronous on `stream`, no atomic, deterministic.  Scratch is owned by the plan, allocated on
  * first use with d_cells == NULL and released with it: one cell map.  Like every plan call it is not re-entrant.  Beyond 65 535 frames: SLICED. */
@@ -1072,7 +1099,8 @@ COMPVHIP_API int compvhip_hog_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t 
  * The static CompVImage functions integral (base/image/compv_image_integral.cxx), histogramBuild, histogramEqualiz, histogramBuildProjectionX / Y
  * (base/image/compv_image.cxx:704-757,846, base/math/compv_math_histogram.cxx) on gray frames p of W x H.  Every output is defined bit for bit: all of it is
  * integer arithmetic, the equalisation table two float32 operations on integers.  Common to the four plan calls: the frames are [frames][H][S] bytes in the
- * plan's geometry and are never written (but for an in-place equalisation); bytes at columns >= W never count; no alignment is asked of the frames; the
+ * plan's geometry and are never written (but for an in-place equalisation); bytes at columns >= W never count; no alignment is asked of the frames (d_gray: ANY
+ * BYTE); the
  * calls are asynchronous on `stream`, the frames independent, and beyond 65 535 frames the calls are SLICED.  Scratch is owned by the plan, allocated on
  * first use and released with it.  A refusal returns COMPVHIP_E_INVALID_PARAMETER, names its reason in compvhip_last_error and happens before anything is
  * allocated, enqueued or written.  The host forms take one frame of any size from 1 x 1 (they need no plan) and are synchronous.
@@ -1104,7 +1132,8 @@ COMPVHIP_API int compvhip_histogram_u8(compvhip_ctx* ctx, const uint8_t* in, siz
 
 /* d_hist: [frames][256], or NULL: each frame's own histogram (the reference's first overload; a non-NULL d_hist is its second).  d_out: [frames][H][S],
  * columns >= W are not written; d_out == d_gray is allowed, as in the reference: the histogram of a frame is complete before any of its pixels is
- * rewritten.  Any other overlap of the two is not.  d_lut: NULL or [frames][256] bytes, the tables. */
+ * rewritten.  Any other overlap of the two is not.  d_lut: NULL or [frames][256] bytes, the tables.  d_hist 4-byte aligned; d_out and d_lut ANY BYTE, like
+ * d_gray. */
 COMPVHIP_API int compvhip_plan_equalize(compvhip_plan* plan, const uint8_t* d_gray, const uint32_t* d_hist, double scale, uint8_t* d_out, uint8_t* d_lut,
                                         void* stream);
 COMPVHIP_API int compvhip_equalize_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint32_t* hist, double scale, uint8_t* out,
