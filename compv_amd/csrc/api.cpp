@@ -452,7 +452,7 @@ void compvhip_ctx_destroy(compvhip_ctx* ctx)
 	if (ctx->hostPlan) compvhip_plan_destroy(ctx->hostPlan);   // first: it counts in ctx->live
 	// the stream goes before the buffers do (by hand it went after them): every host entry point has drained it, hipStreamDestroy defers, hipFree synchronises
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-	delete ctx;   // the staging buffers and the KHT scratch free themselves
+	delete ctx;   // the staging buffers and the KHT group state free themselves (the state borrowed the stream: it destroys none)
 }
 
 const char* compvhip_last_error(const compvhip_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }

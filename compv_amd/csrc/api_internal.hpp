@@ -4,6 +4,7 @@
 #include "../../include/compv_hip.h"
 #include "kernels.hpp"
 #include "kht.hpp"
+#include "kht_group.hpp"
 #include "device_memory.hpp"
 #include "frame_slices.hpp"
 #include "step_policy.hpp"
@@ -41,59 +42,51 @@ struct KhtCanonTabs {
 	size_t W = 0, H = 0; double dRho = 0.0, dTheta = 0.0;
 };
 
-// Device + host scratch of ONE KHT frame in flight: the context owns one for its host entry point (compvhip_houghkht_u8).
-struct KhtScratch {
-	hipStream_t stream = nullptr;   // the context's
-	DevBuf<int32_t> counts; DevBuf<KhtVoteParams> params; DevBuf<KhtCell> cells; DevBuf<int> cellCount;
-	DevBuf<KhtPoint> pts;
-	DevBuf<KhtSpan> spans, scratch; DevBuf<KhtSubdivFrame> stack; DevBuf<KhtKernel> kernelsDev;   // one slot per possible cluster, all four
-	DevBuf<KhtStringDesc> strings; DevBuf<uint32_t> counts32;                                      // one per string (counts32: + 2)
-	KhtBitPlane plane;                                         // the linker's working copy (zero border, destroyed by the walk)
-	PinBuf<KhtPoint> linked;                                   // points of the strings, string after string: PINNED host memory, written by the linker, uploaded without staging
-	KhtPeaksWork peaks;                                        // sort records, visited map, axes of the peak stage
-	std::vector<KhtCell> cellsHost;                            // the vote cells of the frame, downloaded
-	KhtCanonTabs tabs; DevBuf<KhtLine> canonLines; DevBuf<int32_t> canonCount;   // canonical order: the frame's sorted lines, their count
-	double stageMs[6] = {};   // link, subdivide (GPU), statistics (GPU), prune + Gmin, vote + peaks (GPU), sort + sweep of the last call
-	std::string err;
-};
-
-struct KhtBatchFrame {      // host state of one frame of the batch; persists from call to call (vectors keep their capacity)
-	KhtBitPlane plane; size_t most = 0, ptsOff = 0, nPts = 0;
-	std::vector<KhtRange> strings; size_t slotBase = 0, slots = 0;
-	uint32_t nClusters = 0;
-	std::vector<KhtKernel> kernels; double hmax = 0.0, GS = 1.0; bool haveGS = false;
-	std::vector<KhtVoteParams> params; size_t paramsBase = 0;
+// Host state of one frame of a KHT group; persists from call to call (vectors keep their capacity)
+struct KhtFrameState : KhtFrameLayout {
+	KhtBitPlane plane; size_t most = 0, nPts = 0;              // the linker's working copy (zero border, destroyed by the walk), its set pixels, the points linked
+	std::vector<KhtKernel> kernels; double hmax = 0.0; bool haveGS = false;
 	std::vector<KhtCell> cells; size_t cellOff = 0; int cellCount = 0;
 	KhtPeaksWork peaks; std::vector<KhtLine> out;
 	double ms[6] = {};
 	int code = COMPVHIP_OK; std::string err;
 };
-struct KhtBatchState {
-	hipStream_t stream = nullptr;
-	DevBuf<uint32_t> dBits; PinBuf<uint32_t> hostBits;                                 // [frames of a group][wpr * H]: device / pinned
+// Device, pinned and host state of a GROUP of 1 <= G <= kKhtBatch KHT frames going through the stages together (api_kht.cpp).  A plan owns one per group in
+// flight, each with a stream and events of its own; the context owns one for its host entry points (G = 1), which borrows the context's stream.
+struct KhtGroupState {
+	hipStream_t stream = nullptr; bool ownsStream = false;                             // (borrowed: the owner of the stream destroys it)
+	DevBuf<uint32_t> dBits; PinBuf<uint32_t> hostBits;                                 // [frames of a group][wpr * H]: device / pinned (plan only: the host entry packs the caller's bytes)
 	std::vector<hipEvent_t> ready;                                                     // frame f's bit plane has arrived
 	PinBuf<KhtPoint> linked; DevBuf<KhtPoint> pts;                                     // points of every frame's strings: pinned arena (the linkers write it) / device
 	DevBuf<KhtStringDesc> strings; DevBuf<uint32_t> counts32; PinBuf<KhtStringDesc> stringsHost;
 	DevBuf<uint32_t> totals;                                                           // device [kKhtBatch + 1]: clusters per frame, truncation flag
-	DevBuf<KhtSpan> spans, scratch; DevBuf<KhtSubdivFrame> stack; DevBuf<KhtKernel> kernelsDev;
+	DevBuf<KhtSpan> spans, scratch; DevBuf<KhtSubdivFrame> stack; DevBuf<KhtKernel> kernelsDev;   // one slot per possible cluster, all four
 	PinBuf<KhtKernel> kernelsHost;
 	DevBuf<int32_t> counts;
 	DevBuf<KhtVoteParams> params; PinBuf<KhtVoteParams> paramsHost;
 	DevBuf<KhtCell> cells; DevBuf<int> cellCount; PinBuf<KhtCell> cellsHost;
 	KhtCanonTabs tabs; DevBuf<KhtLine> canonLines; DevBuf<int32_t> canonCounts;        // canonical order: [frames][cap] sorted lines, [kKhtBatch] counts (device)
 	PinBuf<KhtLine> canonLinesHost;
-	std::vector<KhtBatchFrame> frames;
-	hipEvent_t syncEv = nullptr;   // blocking-sync event: a controller that waits for a GPU stage SLEEPS (hipStreamSynchronize spins on a CPU of the quota the workers need)
-	double stageMs[6] = {};   // of the groups this state handled in the current call
-	KhtBatchState() = default;
-	KhtBatchState(const KhtBatchState&) = delete;
-	// (the plan's device is current: compvhip_plan_destroy) events and stream here; the buffers free themselves AFTER this body, so the stream goes before them
-	// (khtBatchFree released them first).  compvhip_plan_houghkht is synchronous: the stream is idle, hipStreamDestroy defers anyway and hipFree synchronises.
-	~KhtBatchState()
+	std::vector<KhtFrameState> frames;
+	// How a stage waits for the stream.  With this blocking-sync event the waiting thread SLEEPS: a plan's controllers (hipStreamSynchronize spins on a CPU of
+	// the quota the workers need).  Without it: hipStreamSynchronize, the host entry points' wait (one frame, nobody else wants the CPU).
+	hipEvent_t syncEv = nullptr;
+	double stageMs[6] = {};   // link, subdivide (GPU), statistics (GPU), prune + Gmin, vote + peaks (GPU), sort + sweep: of the groups this state handled in the current call
+	KhtGroupState() = default;
+	KhtGroupState(const KhtGroupState&) = delete;
+	hipError_t wait()
+	{
+		if (!syncEv) return hipStreamSynchronize(stream);
+		const hipError_t e = hipEventRecord(syncEv, stream);
+		return e != hipSuccess ? e : hipEventSynchronize(syncEv);
+	}
+	// (the owner's device is current: compvhip_plan_destroy, compvhip_ctx_destroy) the events and the stream it created; the buffers free themselves AFTER this
+	// body, so the stream goes before them.  The KHT calls are synchronous: the stream is idle, hipStreamDestroy defers anyway and hipFree synchronises.
+	~KhtGroupState()
 	{
 		for (hipEvent_t e : ready) (void)hipEventDestroy(e);
 		if (syncEv) (void)hipEventDestroy(syncEv);
-		if (stream) (void)hipStreamDestroy(stream);
+		if (ownsStream && stream) (void)hipStreamDestroy(stream);
 	}
 };
 
@@ -145,7 +138,7 @@ struct compvhip_ctx {
 	StatsScratch stats;                     // scratch of the host statistics calls (they need no plan: a plan has a minimum size, these calls have none)
 	DevBuf<double> dStatsF64;               // staging of compvhip_integral_u8: sum, then sumsq, (H + 1) x (W + 1) each
 	DevBuf<uint32_t> dStatsU32;             // staging of the other statistics calls: a histogram (with the table behind it), or projX then projY
-	KhtScratch kht;                    // KHT scratch of the host entry point (compvhip_houghkht_u8)
+	KhtGroupState kht;                 // the host KHT entry points' group of one frame (compvhip_houghkht_u8, _ex_u8, _kernels_u8); borrows `stream`
 };
 
 struct TimingEntry { const char* name; hipEvent_t a, b; };
@@ -235,8 +228,8 @@ struct compvhip_plan : TimingState {
 	ShtTileArgs vt = {};                         // geometry + device tables (views of the five buffers below, of reach and of tileCounts)
 	std::vector<int32_t> vtKt, vtRowBase;        // host copies of the [tiles][T] tables
 	DevBuf<int32_t> dKt, dRowBase; DevBuf<uint8_t> partLo, partHi, colFlag; int* tileCounts = nullptr;   // tileCounts: a view into counters
-	// batched KHT (compvhip_plan_houghkht): one scratch set + stream per worker thread, stage clocks of the last call
-	std::vector<std::unique_ptr<KhtBatchState>> khtBatch;       // device / pinned buffers and per-frame host state of the batched call: one per group of frames in flight
+	// batched KHT (compvhip_plan_houghkht): the states of the groups in flight, the workers' workspaces, stage clocks of the last call
+	std::vector<std::unique_ptr<KhtGroupState>> khtBatch;       // device / pinned buffers, stream and per-frame host state: one per group of frames in flight
 	std::vector<std::unique_ptr<KhtPeaksWork>> khtWork;   // sort + sweep workspace (axes, 1.6 MB visited map at 4K) of WORKER w: it stays in that core's cache from frame to frame
 	double khtStageMs[6] = {}; double khtWallMs = 0.0; int khtThreads = 0;
 	// asynchronous steps (compvhip_plan_pipeline_async / compvhip_plan_wait)

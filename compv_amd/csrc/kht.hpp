@@ -1,4 +1,4 @@
-// kht.hpp -- types shared by the host stages (kht_host.cpp), the GPU stages (kht_kernels.hip) and the C ABI (api.cpp) of
+// kht.hpp -- types shared by the host stages (kht_host.cpp), the GPU stages (kht_kernels.hip) and the C ABI (api_kht.cpp) of
 // the kernel-based Hough transform.  Reference: core/features/hough/compv_core_feature_houghkht.{h,cxx}.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -40,7 +40,7 @@ size_t khtLink(KhtBitPlane& plane, size_t minSize, KhtPoint* pts, std::vector<Kh
 void khtFinishKernels(std::vector<KhtKernel>& kernels, double& hmax);
 double khtPruneAndScale(std::vector<KhtKernel>& kernels, double hmax, double minHeight);
 void khtVoteParams(const KhtAxes& ax, const std::vector<KhtKernel>& kernels, std::vector<KhtVoteParams>& params);
-// buffers of the peak stage that survive from frame to frame (one per KhtScratch)
+// buffers of the peak stage that survive from frame to frame (one per frame of a group for the sweeps of the calling thread, one per pool worker for a plan call's)
 struct KhtPeaksWork {
 	struct Rec { int32_t count; uint32_t pos; };
 	struct Idx { uint32_t rho, theta; };
@@ -50,7 +50,7 @@ struct KhtPeaksWork {
 void khtPeaks(const KhtAxes& ax, std::vector<KhtCell>& cells, int maxLines, std::vector<KhtLine>& lines, KhtPeaksWork& work);
 
 // GPU stages.  Every launch covers the frames of a BATCH (compvhip_plan_houghkht: one launch per stage for up to kKhtBatch frames instead of one per frame;
-// the host entry point is a batch of one): strings, clusters and kernels of the frames sit one behind the other in shared arrays, the per-frame tables
+// the host entry points run a batch of one, through the same driver: api_kht.cpp): strings, clusters and kernels of the frames sit one behind the other in shared arrays, the per-frame tables
 // travel by value in the kernel arguments (blockIdx.y / .z = frame).
 constexpr int kKhtBatch = 32;      // frames a launch can cover (size of the by-value tables)
 constexpr int kKhtGroup = 8;       // frames compvhip_plan_houghkht puts through the stages together
