@@ -27,6 +27,7 @@ THRESHOLD_COMPARE_TO_GRADIENT, THRESHOLD_PERCENT_OF_MEAN, THRESHOLD_OTSU = 0, 1,
 (FMT_RGBA32, FMT_ARGB32, FMT_BGRA32, FMT_RGB24, FMT_BGR24, FMT_RGB565LE, FMT_RGB565BE, FMT_BGR565LE, FMT_BGR565BE,
  FMT_YUYV422, FMT_UYVY422, FMT_Y) = range(12)
 FMT_BYTES = [4, 4, 4, 3, 3, 2, 2, 2, 2, 2, 2, 1]
+FMT_NV12, FMT_NV21, FMT_YUV420P, FMT_YUV422P, FMT_YUV444P, FMT_HSV = range(12, 18)   # formats of the colour conversion calls only
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 STREL_RECT, STREL_DIAMOND, STREL_CROSS = 0, 1, 2
 BORDER_ZERO, BORDER_REPLICATE = 0, 2
@@ -70,6 +71,7 @@ EXPORTS = [
     "compvhip_hog_geometry", "compvhip_plan_hog", "compvhip_hog_u8",
     "compvhip_integral_dims", "compvhip_plan_integral", "compvhip_integral_u8", "compvhip_plan_histogram", "compvhip_histogram_u8", "compvhip_plan_equalize",
     "compvhip_equalize_u8", "compvhip_plan_projections", "compvhip_projections_u8",
+    "compvhip_convert_layout", "compvhip_convert_frames", "compvhip_convert_u8",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -190,6 +192,22 @@ class OrbPyramidOpts(C.Structure):
 
     def __init__(self, levels=8, scale_factor=0.83, threshold=20, fast_type=9, nonmax=True, max_features=2000):
         super().__init__(levels, scale_factor, threshold, fast_type, int(bool(nonmax)), max_features)
+
+
+class Image(C.Structure):
+    """compvhip_image (include/compv_hip.h): `frames` images of one format -- plane pointers, bytes from row to row and from frame to frame"""
+    _fields_ = [("pixfmt", C.c_int), ("plane", C.c_void_p * 3), ("rowBytes", C.c_size_t * 3), ("frameBytes", C.c_size_t * 3)]
+
+    def __init__(self, pixfmt, planes, row_bytes, frame_bytes=()):
+        """planes: addresses (int or None); row_bytes / frame_bytes: one value per plane"""
+        super().__init__()
+        self.pixfmt = pixfmt
+        for i, p in enumerate(planes):
+            self.plane[i] = p
+        for i, v in enumerate(row_bytes):
+            self.rowBytes[i] = v
+        for i, v in enumerate(frame_bytes):
+            self.frameBytes[i] = v
 
 
 class CompvHipError(RuntimeError):
@@ -335,6 +353,9 @@ def load():
     L.compvhip_equalize_u8.argtypes = [vp, vp, sz, sz, sz, vp, C.c_double, vp, sz, vp]
     L.compvhip_plan_projections.argtypes = [vp, vp, vp, vp, vp]
     L.compvhip_projections_u8.argtypes = [vp, vp, sz, sz, sz, vp, vp]
+    L.compvhip_convert_layout.argtypes = [i32, sz, sz, C.POINTER(i32), C.POINTER(sz), C.POINTER(sz)]
+    L.compvhip_convert_frames.argtypes = [vp, sz, sz, sz, C.POINTER(Image), C.POINTER(Image), vp]
+    L.compvhip_convert_u8.argtypes = [vp, sz, sz, C.POINTER(Image), C.POINTER(Image)]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -396,6 +417,17 @@ def integral_dims(W, H):
     return rows.value, cols.value
 
 
+def convert_layout(pixfmt, W, H):
+    """compvhip_convert_layout (host arithmetic, no GPU): -> (planes, minRowBytes[3], rows[3]) of a W x H image of the format; CompvHipError for an unknown
+    format or a zero size"""
+    L = load()
+    n, rb, rows = C.c_int(0), (C.c_size_t * 3)(), (C.c_size_t * 3)()
+    rc = L.compvhip_convert_layout(pixfmt, W, H, C.byref(n), rb, rows)
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_convert_layout")
+    return n.value, list(rb), list(rows)
+
+
 class Context:
     """One GPU context (compvhip_ctx)."""
 
@@ -443,6 +475,22 @@ class Context:
         out = np.empty((H, W), np.uint8)
         self._chk(self.lib.compvhip_grayscale_u8(self.h, _ptr(packed), pixfmt, W, H, S, _ptr(out), W))
         return out
+
+    def convert(self, planes, pixfmt_in, pixfmt_out, W, H):
+        """compvhip_convert_u8: planes -- the source's planes as 2-D uint8 arrays (rows contiguous, any row stride at or above the layout's minimum); returns
+        the destination's dense planes, rows x minRowBytes each (convert_layout)."""
+        n_in, _, _ = convert_layout(pixfmt_in, W, H)
+        n_out, rb, rows = convert_layout(pixfmt_out, W, H)
+        assert len(planes) == n_in and all(p.dtype == np.uint8 and p.ndim == 2 and p.strides[1] == 1 for p in planes)
+        out = [np.empty((rows[p], rb[p]), np.uint8) for p in range(n_out)]
+        src = Image(pixfmt_in, [p.ctypes.data for p in planes], [p.strides[0] for p in planes])
+        dst = Image(pixfmt_out, [p.ctypes.data for p in out], [p.strides[0] for p in out])
+        self._chk(self.lib.compvhip_convert_u8(self.h, W, H, C.byref(src), C.byref(dst)))
+        return out
+
+    def convert_frames(self, W, H, frames, src, dst, stream=0):
+        """compvhip_convert_frames on device memory: src, dst -- Image descriptions of `frames` images; asynchronous on `stream`"""
+        self._chk(self.lib.compvhip_convert_frames(self.h, W, H, frames, C.byref(src), C.byref(dst), stream))
 
     def convlt_fixedpoint(self, img, vt, hz):
         """CompVMathConvlt::convlt1FixedPoint (vt/hz: uint16 Q16 weights)."""

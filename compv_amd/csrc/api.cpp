@@ -655,6 +655,7 @@ int compvhip_api::pixfmtBytes(int fmt)
 
 int compvhip_api::checkPixfmt(compvhip_ctx* ctx, int fmt, size_t W)
 {
+	if (fmt > COMPVHIP_FMT_Y && fmt <= COMPVHIP_FMT_HSV) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "a format of the colour conversion calls only (compvhip_convert_frames)");
 	if (!pixfmtBytes(fmt)) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "pixel format without a grayscale conversion"); // conv_to_grayscale.cxx:86-88
 	if ((fmt == COMPVHIP_FMT_YUYV422 || fmt == COMPVHIP_FMT_UYVY422) && (W & 1)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "packed 4:2:2 needs an even width");
 	return COMPVHIP_OK;

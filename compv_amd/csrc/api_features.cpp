@@ -1280,3 +1280,62 @@ int compvhip_plan_projections(compvhip_plan* p, const uint8_t* d_gray, int32_t* 
 	if (!p) return COMPVHIP_E_INVALID_PARAMETER;
 	return projectionsImpl(planFrames(p, d_gray, stream), d_projX, d_projY);
 }
+
+// ---- colour conversion (include/compv_hip.h, "colour conversion") ---------------------------------------------------------------------------------
+static_assert(conv::kNV12 == COMPVHIP_FMT_NV12 && conv::kHSV == COMPVHIP_FMT_HSV && conv::kY == COMPVHIP_FMT_Y && conv::kRGBA32 == COMPVHIP_FMT_RGBA32, "convert_math.hpp restates compvhip_pixfmt");
+
+int compvhip_convert_layout(int pixfmt, size_t W, size_t H, int* planes, size_t minRowBytes[3], size_t rows[3])
+{
+	return conv::layout(pixfmt, W, H, planes, minRowBytes, rows) ? COMPVHIP_OK : COMPVHIP_E_INVALID_PARAMETER;
+}
+
+int compvhip_api::convertCheck(compvhip_ctx* ctx, size_t W, size_t H, size_t frames, const compvhip_image* in, const compvhip_image* out, ConvertArgs* a, ConvertGeometry* g)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!in || !out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "convert: null image description");
+	if (!W || !H || !frames) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "convert: W, H or frames is 0");
+	if (W > 32767 || H > 32767 || frames > 0x7fffffffu) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "convert: W or H beyond 32767, or frames beyond 2^31 - 1");
+	if (!conv::layout(in->pixfmt, W, H, &g->planesIn, g->minIn, g->rowsIn) || !conv::layout(out->pixfmt, W, H, &g->planesOut, g->minOut, g->rowsOut))
+		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "convert: unknown pixel format");
+	if (!conv::served(in->pixfmt, out->pixfmt)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "convert: this pair of formats is not served");
+	// a plane's byte range: from its first byte to the last byte of its last row in the last frame
+	struct Span { const uint8_t* p; size_t bytes, row, frame; };
+	Span si[3] = {}, so[3] = {};
+	auto spans = [&](const compvhip_image* im, int planes, const size_t* minRow, const size_t* rows, Span* s) -> const char* {
+		for (int p = 0; p < planes; ++p) {
+			if (!im->plane[p]) return "convert: a plane of the format is NULL";
+			if (im->rowBytes[p] < minRow[p]) return "convert: rowBytes below the plane's row";
+			const size_t one = (rows[p] - 1) * im->rowBytes[p] + minRow[p];
+			if (frames > 1 && im->frameBytes[p] < one) return "convert: frameBytes makes frames overlap";
+			s[p] = Span{ static_cast<const uint8_t*>(im->plane[p]), (frames - 1) * (frames > 1 ? im->frameBytes[p] : 0) + one, im->rowBytes[p], frames > 1 ? im->frameBytes[p] : 0 };
+		}
+		return nullptr;
+	};
+	if (const char* why = spans(in, g->planesIn, g->minIn, g->rowsIn, si)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, why);
+	if (const char* why = spans(out, g->planesOut, g->minOut, g->rowsOut, so)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, why);
+	for (int p = 0; p < g->planesOut; ++p)
+		for (int q = p + 1; q < g->planesOut; ++q)
+			if (overlaps(so[p].p, so[p].bytes, so[q].p, so[q].bytes)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "convert: two output planes overlap");
+	const bool threeToThree = (in->pixfmt == COMPVHIP_FMT_RGB24 || in->pixfmt == COMPVHIP_FMT_BGR24) && g->minOut[0] == g->minIn[0] && g->planesOut == 1;
+	for (int p = 0; p < g->planesIn; ++p)
+		for (int q = 0; q < g->planesOut; ++q) {
+			if (!overlaps(si[p].p, si[p].bytes, so[q].p, so[q].bytes)) continue;
+			if (threeToThree && si[p].p == so[q].p && si[p].row == so[q].row && si[p].frame == so[q].frame) continue;   // in place
+			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, threeToThree ? "convert: in place needs the same pointer, rowBytes and frameBytes" : "convert: an output plane overlaps an input plane");
+		}
+	*a = ConvertArgs{};
+	for (int p = 0; p < g->planesIn; ++p) { a->in[p] = si[p].p; a->inRow[p] = si[p].row; a->inFrame[p] = si[p].frame; }
+	for (int p = 0; p < g->planesOut; ++p) { a->out[p] = const_cast<uint8_t*>(so[p].p); a->outRow[p] = so[p].row; a->outFrame[p] = so[p].frame; }
+	a->W = static_cast<int>(W); a->H = static_cast<int>(H);
+	return COMPVHIP_OK;
+}
+
+int compvhip_convert_frames(compvhip_ctx* ctx, size_t W, size_t H, size_t frames, const compvhip_image* in, const compvhip_image* out, void* stream)
+{
+	ConvertArgs a; ConvertGeometry g;
+	const int rc = convertCheck(ctx, W, H, frames, in, out, &a, &g);
+	if (rc) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, launch_convert(a, in->pixfmt, out->pixfmt, static_cast<int>(frames), static_cast<hipStream_t>(stream)));
+	return COMPVHIP_OK;
+}

@@ -770,3 +770,30 @@ int compvhip_projections_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size
 		return COMPVHIP_OK;
 	});
 }
+
+// One frame of any served pair through the context's staging buffers: the planes lie one behind the other, rows 64-byte and planes 256-byte aligned
+// (the kernel's word path), in dPacked (source) and dOut (destination).
+int compvhip_convert_u8(compvhip_ctx* ctx, size_t W, size_t H, const compvhip_image* in, const compvhip_image* out)
+{
+	ConvertArgs h; ConvertGeometry g;
+	const int rc = convertCheck(ctx, W, H, 1, in, out, &h, &g);
+	if (rc) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	ConvertArgs d = h;
+	size_t offIn[3] = {}, offOut[3] = {}, bytesIn = 0, bytesOut = 0;
+	for (int p = 0; p < g.planesIn; ++p) { d.inRow[p] = alignUp(g.minIn[p], 64); offIn[p] = bytesIn; bytesIn += alignUp(d.inRow[p] * g.rowsIn[p], 256); }
+	for (int p = 0; p < g.planesOut; ++p) { d.outRow[p] = alignUp(g.minOut[p], 64); offOut[p] = bytesOut; bytesOut += alignUp(d.outRow[p] * g.rowsOut[p], 256); }
+	HIPCHK(ctx, ctx->dPacked.reserve(ctx, bytesIn));
+	HIPCHK(ctx, ctx->dOut.reserve(ctx, bytesOut));
+	for (int p = 0; p < g.planesIn; ++p) {
+		d.in[p] = ctx->dPacked + offIn[p];
+		HIPCHK(ctx, upload(ctx, ctx->dPacked + offIn[p], d.inRow[p], h.in[p], h.inRow[p], g.minIn[p], g.rowsIn[p]));
+	}
+	for (int p = 0; p < g.planesOut; ++p) d.out[p] = ctx->dOut + offOut[p];
+	hipError_t e = launch_convert(d, in->pixfmt, out->pixfmt, 1, ctx->stream);
+	for (int p = 0; p < g.planesOut && e == hipSuccess; ++p) e = download(ctx, h.out[p], h.outRow[p], d.out[p], d.outRow[p], g.minOut[p], g.rowsOut[p]);
+	const hipError_t es = hipStreamSynchronize(ctx->stream);   // also on failure: no copy from the caller's planes stays in flight
+	HIPCHK(ctx, e);
+	HIPCHK(ctx, es);
+	return COMPVHIP_OK;
+}

@@ -7,6 +7,7 @@
 #include "kht_group.hpp"
 #include "device_memory.hpp"
 #include "frame_slices.hpp"
+#include "convert_math.hpp"
 #include "step_policy.hpp"
 
 #include <hip/hip_runtime.h>
@@ -429,6 +430,9 @@ int integralImpl(const StatsFrames& g, double* d_sum, double* d_sumsq, size_t su
 int histogramImpl(const StatsFrames& g, uint32_t* d_hist);
 int equalizeImpl(const StatsFrames& g, const uint32_t* d_hist, double scale, uint8_t* d_out, uint8_t* d_lut);
 int projectionsImpl(const StatsFrames& g, int32_t* d_projX, int32_t* d_projY);
+// colour conversion: every refusal of compvhip_convert_frames (host or device pointers alike); fills `a`, the planes' row counts and least row bytes
+struct ConvertGeometry { int planesIn, planesOut; size_t minIn[3], rowsIn[3], minOut[3], rowsOut[3]; };
+int convertCheck(compvhip_ctx* ctx, size_t W, size_t H, size_t frames, const compvhip_image* in, const compvhip_image* out, ConvertArgs* a, ConvertGeometry* g);
 int scaleImpl(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, hipStream_t st);
 // remap and inverse warp: validates everything but the coordinate source and fills `a` (roi == nullptr: the whole frame)
 int remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, int interp, const compvhip_roi* roi, void* d_out, size_t Wout,

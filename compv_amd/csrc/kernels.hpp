@@ -71,6 +71,16 @@ struct EdgeDeteArgs {
 };
 hipError_t launch_edge_dete(const EdgeDeteArgs& a, int op, int frames, hipStream_t stream);
 
+// ---- colour conversion (convert_kernels.hip) -----------------------------------------------------------------
+struct ConvertArgs {
+	const uint8_t* in[3];     // planes of the source (unused: nullptr), any byte address
+	uint8_t* out[3];          // planes of the destination
+	size_t inRow[3], inFrame[3], outRow[3], outFrame[3];   // bytes from row to row and from frame to frame, per plane
+	int W, H;
+};
+// The (inFmt, outFmt) pair must be one that conv::served() lists (hipErrorInvalidValue otherwise).  Any frame count: sliced.
+hipError_t launch_convert(const ConvertArgs& a, int inFmt, int outFmt, int frames, hipStream_t stream);
+
 // ---- pre-processing (grayscale, Otsu) -----------------------------------------------------------------------
 struct GrayArgs {
 	const uint8_t* in;        // [frames][H][S samples of bpp bytes]

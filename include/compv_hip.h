@@ -65,7 +65,10 @@ typedef enum compvhip_pixfmt { /* packed input formats of CompVImage::convertGra
 	COMPVHIP_FMT_RGBA32 = 0, COMPVHIP_FMT_ARGB32 = 1, COMPVHIP_FMT_BGRA32 = 2, COMPVHIP_FMT_RGB24 = 3, COMPVHIP_FMT_BGR24 = 4,
 	COMPVHIP_FMT_RGB565LE = 5, COMPVHIP_FMT_RGB565BE = 6, COMPVHIP_FMT_BGR565LE = 7, COMPVHIP_FMT_BGR565BE = 8,
 	COMPVHIP_FMT_YUYV422 = 9, COMPVHIP_FMT_UYVY422 = 10,
-	COMPVHIP_FMT_Y = 11 /* the Y plane of Y / NV12 / NV21 / YUV420P / YVU420P / YUV422P / YUV444P: a copy */
+	COMPVHIP_FMT_Y = 11, /* the Y plane of Y / NV12 / NV21 / YUV420P / YVU420P / YUV422P / YUV444P: a copy */
+	/* formats of the colour conversion calls only (compvhip_convert_frames): every other call that takes a pixfmt refuses them with
+	 * COMPVHIP_E_INVALID_PARAMETER */
+	COMPVHIP_FMT_NV12 = 12, COMPVHIP_FMT_NV21 = 13, COMPVHIP_FMT_YUV420P = 14, COMPVHIP_FMT_YUV422P = 15, COMPVHIP_FMT_YUV444P = 16, COMPVHIP_FMT_HSV = 17
 } compvhip_pixfmt;
 
 /* One Hough line.  rho/theta/strength are CompVHoughLine's fields (compv_common.h:686-693); row/col are the
@@ -221,7 +224,7 @@ COMPVHIP_API int compvhip_plan_create(compvhip_ctx* ctx, size_t W, size_t H, siz
  *   REFUSED         beyond 65 535 frames the call returns COMPVHIP_E_INVALID_PARAMETER, compvhip_last_error names the limit, nothing is allocated, enqueued
  *                   or written.  Split the batch across plans of at most 65 535 frames.
  * The text-detection chain (grayscale, otsu, threshold, threshold_adaptive, morph, components on the caller's bytes), the segment and fit calls on the
- * caller's bytes, remap / warp_inverse, hog and the image statistics (integral, histogram, equalize, projections) are SLICED; edge_dete has its FRAMES IN X; Canny and everything that needs its masks, the SHT, the batched KHT, the
+ * caller's bytes, remap / warp_inverse, hog, the image statistics (integral, histogram, equalize, projections) and the colour conversion (compvhip_convert_frames) are SLICED; edge_dete has its FRAMES IN X; Canny and everything that needs its masks, the SHT, the batched KHT, the
  * fixed-point blur, FAST, ORB and the bilinear scale are REFUSED, as are a compvhip_orbpyr of more than 65 535 frames and a compvhip_matcher or a
  * compvhip_homography of more than 65 535 pairs at their creation. */
 /* Alignment of device pointers.  Every d_* pointer of the plan, pyramid, matcher and homography calls belongs to one of two classes, stated beside its call
@@ -1142,6 +1145,56 @@ COMPVHIP_API int compvhip_equalize_u8(compvhip_ctx* ctx, const uint8_t* in, size
 /* d_projX: [frames][W], d_projY: [frames][H], int32, dense, 4-byte aligned.  Either may be NULL, not both; with both the frames are read once. */
 COMPVHIP_API int compvhip_plan_projections(compvhip_plan* plan, const uint8_t* d_gray, int32_t* d_projX, int32_t* d_projY, void* stream);
 COMPVHIP_API int compvhip_projections_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, int32_t* projX, int32_t* projY);
+
+/* ---- colour conversion (docs/kernels/convert.md) -----------------------------------------------------------------------------------------------
+ * The RGBx, HSV and YUV444P arms of CompVImage::convert (base/image/compv_image.cxx:662-685); the grayscale arm is compvhip_grayscale_u8.  Stateless calls
+ * on the context: no scratch memory, no handle, one kernel (convert_kernel).  Every output byte is defined bit for bit.
+ * Planes and layout (compvhip_convert_layout): with cw = (W + 1) / 2, ch = (H + 1) / 2
+ *   RGBA32 ARGB32 BGRA32     1 plane, 4 W bytes per row          RGB24 BGR24 HSV    1 plane, 3 W bytes per row (HSV: packed H, S, V)
+ *   RGB565LE/BE BGR565LE/BE  1 plane, 2 W bytes per row          Y                  1 plane, W bytes per row
+ *   YUYV422 UYVY422          1 plane, 4 cw bytes per row (pairs of pixels share U and V)
+ *   NV12 NV21                Y: W x H; interleaved UV (NV21: VU): 2 cw bytes per row, ch rows
+ *   YUV420P                  Y: W x H; U, V: cw x ch             YUV422P   Y: W x H; U, V: cw x H          YUV444P   Y, U, V: W x H
+ * Pixel (x, y) reads chroma sample (x >> 1, y >> 1) of a 4:2:0 format and (x >> 1, y) of a 4:2:2 format.
+ * Served pairs and their definition:
+ *   to RGBA32 / RGB24 from NV12, NV21, YUV420P, YUV422P, YUV444P, YUYV422, UYVY422 (compv_image_conv_to_rgbx.cxx:625-776): with Y' = Y - 16, U' = U - 127,
+ *       V' = V - 127 (127 is the reference's constant), >> arithmetic, clamp8 to 0..255:
+ *         R = clamp8((37 Y' + 51 V') >> 5)    G = clamp8((37 Y' - 13 U' - 26 V') >> 5)    B = clamp8((37 Y' + 65 U') >> 5)    A = 255
+ *       and from COMPVHIP_FMT_Y: R = G = B = Y, A = 255 (:511-542)
+ *   RGBA32 -> RGB24; BGRA32 / BGR24 -> RGB24; RGBA32 / RGB24 -> BGR24 (:544-623): the channels, reordered, alpha dropped.  YUV sources are not served to
+ *       BGR / BGRA outputs.
+ *   to HSV from RGB24 and RGBA32 (compv_image_conv_hsv.cxx:285-310): max, min over r, g, b; minus = max - min; diff = g - b when max == r, else b - r
+ *       when max == g, else r - g; t43[i] = 43 * (1 / i) and t255[i] = 255 * (1 / i), a float32 division then a float32 product, entry 0 = 0;
+ *         H = (uint8)(int)round(float(diff) * t43[minus]) + (0 | 85 | 171, chosen like diff), modulo 256 (a negative hue wraps)
+ *         S = (uint8)(int)round(float(minus) * t255[max])        V = max
+ *       one float32 rounding per operation; round(f) = trunc(f + 0.5) for f >= 0, trunc(f - 0.5) below, computed in float64 (compv_math.h:59).
+ *       HSV is served from every YUV source above as well, defined as source -> RGB24 -> HSV (computed in registers, one kernel).
+ *   to YUV444P from RGBA32, ARGB32, BGRA32, RGB24, BGR24 and the four 5:6:5 formats (compv_image_conv_to_yuv444p.cxx; 5:6:5 channels are widened by bit
+ *       replication as in the grayscale call):
+ *         Y = ((33 R + 65 G + 13 B) >> 7) + 16    U = clamp8(((-38 R - 74 G + 112 B) >> 8) + 128)    V = clamp8(((112 R - 94 G - 18 B) >> 8) + 128)
+ * Pointers: every plane pointer is ANY BYTE; any rowBytes at or above the layout's minimum and any frameBytes that keeps frames apart are served.  When
+ * every plane pointer, rowBytes and (for more than one frame) frameBytes is a multiple of 16 the kernel moves whole words; anything else takes its
+ * byte loop and gives the same bytes.  Bytes between a row's end and rowBytes, and between frames, are never written.
+ * Aliasing: a plane's byte range runs from its first byte to the last byte of its last row in the last frame.  An output plane may share memory with
+ * an input plane only in the 3-byte-to-3-byte pairs (RGB24 -> HSV, RGB24 <-> BGR24), and only with the same pointer, rowBytes and frameBytes: in
+ * place.  Any other overlap of an input range with an output range, or of two output ranges, is refused.
+ * Refused with COMPVHIP_E_INVALID_PARAMETER before anything is allocated, enqueued or written, the reason in compvhip_last_error: a pair outside the
+ * list, W, H or frames of 0, W or H beyond 32 767, a missing plane, a rowBytes below the minimum, a frameBytes (frames > 1) below the plane's size, and
+ * the overlaps above.  Beyond 65 535 frames: SLICED. */
+typedef struct compvhip_image {     /* `frames` images of one format */
+	int pixfmt;
+	void* plane[3];                  /* unused planes NULL */
+	size_t rowBytes[3];              /* bytes from one row of the plane to the next */
+	size_t frameBytes[3];            /* bytes from frame f's plane to frame f+1's */
+} compvhip_image;
+
+/* Host arithmetic only: plane count, least row bytes and row count of each plane (entries of absent planes: 0); any output may be NULL.
+ * COMPVHIP_E_INVALID_PARAMETER for an unknown format or a zero size, nothing written. */
+COMPVHIP_API int compvhip_convert_layout(int pixfmt, size_t W, size_t H, int* planes, size_t minRowBytes[3], size_t rows[3]);
+/* device memory, asynchronous on `stream` */
+COMPVHIP_API int compvhip_convert_frames(compvhip_ctx* ctx, size_t W, size_t H, size_t frames, const compvhip_image* in, const compvhip_image* out, void* stream);
+/* host memory, one frame (frameBytes ignored), synchronous; staged through the context's device buffers */
+COMPVHIP_API int compvhip_convert_u8(compvhip_ctx* ctx, size_t W, size_t H, const compvhip_image* in, const compvhip_image* out);
 
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
