@@ -238,38 +238,53 @@ COMPVHIP_API int compvhip_plan_create(compvhip_ctx* ctx, size_t W, size_t H, siz
  *                   compvhip_homography_result 8 bytes, compvhip_match records and {x, y} float64 points 16 bytes.
  * A null pointer where a call allows one counts as aligned.  A d_* parameter with two stars (compvhip_plan_acc, _edge_counts, compvhip_orbpyr_plane) is a HOST
  * pointer that receives a device address.  The host entry points copy into buffers of their own and take any host pointer. */
+/* Stream order.  Every export that takes a `void* stream` (a hipStream_t; NULL = the default stream) belongs to one of two classes, and the two batched KHT
+ * calls, which take none, to a third.  The class stands beside each call as "Stream order: CLASS" (tests/stream_cases.py is the same list,
+ * tests/test_stream_cases.py fails when a call has no entry, tests/test_gpu_stream_order.py runs every call behind pending work on a non-blocking stream):
+ *   ASYNC           Everything the call does on the device -- kernels, clears, copies, the upload of what it derives from host arrays -- is ordered on `stream`:
+ *                   after what was enqueued there before the call, before what is enqueued there after it; nothing runs on another stream.  On a warm handle
+ *                   (the same call was made before and no scratch has to grow) it returns without waiting for the stream.  Host arrays and option structs
+ *                   passed to it (vtKern / hzKern, strel, M, roi, opts, compvhip_image) may be changed as soon as it has returned.
+ *   WAITS           The same ordering and the same rule for host arrays, but the call may wait for the stream before it returns.
+ *   DRAINS          compvhip_plan_houghkht and compvhip_plan_houghkht_ex take no stream: they drain the whole device first (hipDeviceSynchronize), so edge maps
+ *                   still being produced on ANY stream are complete when the workers read them, and they return with their results in host memory.
+ * Growing scratch: a later call with a larger capacity (lineCap beyond the plan's key slots, keyCap, a HOG layout with more cells on the plan's own map, a
+ * larger warp destination, ...) may have to reallocate plan-owned scratch.  Such a call may wait for the device, whatever its class, and it never disturbs a
+ * call that is still pending: the old buffer is released with hipFree, which returns only when the work that reads it has finished.
+ * Timing mode (compvhip_plan_set_timing and its siblings) records HIP events around the kernels and changes no class: compvhip_*_get_timing is what waits.
+ * The host entry points (*_u8, *_f64) are synchronous on the context's own stream. */
 /* A plan must be destroyed BEFORE its context (it keeps a pointer to it); compvhip_ctx_destroy only releases the private
  * single-frame plan of the host entry points. */
 COMPVHIP_API void compvhip_plan_destroy(compvhip_plan* plan);
 
 /* Canny on `frames` device frames: d_in -> d_edges (both frames*S*H bytes, may alias).  Asynchronous on `stream`
  * (a hipStream_t; NULL = default stream) except for the hysteresis convergence check, which polls a device flag.
- * Beyond 65 535 frames: REFUSED (the resolve rounds index their change flags by the launch's frame extent).  d_in and d_edges: ANY BYTE. */
+ * Beyond 65 535 frames: REFUSED (the resolve rounds index their change flags by the launch's frame extent).  d_in and d_edges: ANY BYTE.  Stream order: WAITS: the hysteresis convergence poll synchronises the stream at least once per call. */
 COMPVHIP_API int compvhip_plan_canny(compvhip_plan* plan, const uint8_t* d_in, float tLow, float tHigh, int ksize,
                                      int thresholdType, uint8_t* d_edges, void* stream);
 
 /* compvhip_grayscale_u8 on `frames` device frames: d_in = [frames][H][S samples], d_gray = [frames][H][S].  Asynchronous.
- * Beyond 65 535 frames: SLICED.  d_in and d_gray: ANY BYTE (the packed samples as well). */
+ * Beyond 65 535 frames: SLICED.  d_in and d_gray: ANY BYTE (the packed samples as well).  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_grayscale(compvhip_plan* plan, const uint8_t* d_in, int pixfmt, uint8_t* d_gray, void* stream);
 
 /* compvhip_otsu_u8 on `frames` device frames: d_thresholds[f] = Otsu level of frame f (device array).  Asynchronous.
- * Beyond 65 535 frames: SLICED (histograms and levels slice by slice).  d_gray: ANY BYTE; d_thresholds: 4-byte aligned. */
+ * Beyond 65 535 frames: SLICED (histograms and levels slice by slice).  d_gray: ANY BYTE; d_thresholds: 4-byte aligned.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_otsu(compvhip_plan* plan, const uint8_t* d_gray, int32_t* d_thresholds, void* stream);
 
 /* compvhip_convlt1_fixedpoint_u8 on `frames` device frames (vtKern/hzKern are HOST arrays of kernSize weights); d_in and
- * d_out may alias.  Asynchronous.  Beyond 65 535 frames: REFUSED.  d_in and d_out: ANY BYTE. */
+ * d_out may alias.  Asynchronous.  Beyond 65 535 frames: REFUSED.  d_in and d_out: ANY BYTE.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_convlt1_fixedpoint(compvhip_plan* plan, const uint8_t* d_in, const uint16_t* vtKern, const uint16_t* hzKern,
                                                   size_t kernSize, uint8_t* d_out, void* stream);
 
 /* CompVHoughSht::toCartesian (core/features/hough/compv_core_feature_houghsht.cxx:264-304,566-589) on the device line arrays a
  * compvhip_plan_houghsht / _pipeline call produced: d_cart[f][i] = {a.x, a.y, b.x, b.y} of line i of frame f (a.z = b.z = 1), for
  * i < min(d_counts[f], lineCap).  Asynchronous.  Beyond 65 535 frames: REFUSED (like the calls that produce such line arrays).  d_lines, d_counts and
- * d_cart: 4-byte aligned. */
+ * d_cart: 4-byte aligned.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_to_cartesian(compvhip_plan* plan, const compvhip_line* d_lines, const int32_t* d_counts, size_t lineCap,
                                             float* d_cart, void* stream);
 
 /* Sobel / Scharr / Prewitt detector (compvhip_edge_dete_u8 semantics) on `frames` device frames; d_in and d_out must
- * not alias.  Fully asynchronous on `stream`.  Beyond 65 535 frames: FRAMES IN X.  d_in and d_out: ANY BYTE. */
+ * not alias.  Fully asynchronous on `stream`.  Beyond 65 535 frames: FRAMES IN X.  d_in and d_out: ANY BYTE.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_edge_dete(compvhip_plan* plan, const uint8_t* d_in, int op, uint8_t* d_out, void* stream);
 
 /* SHT on the edge maps produced by the last compvhip_plan_canny() of this plan (uses its 1-bit edge masks, no byte
@@ -281,12 +296,12 @@ COMPVHIP_API int compvhip_plan_edge_dete(compvhip_plan* plan, const uint8_t* d_i
  * d_counts[f] <= max(lineCap, 65536); beyond that the key buffer overflowed and frame f's lines are an arbitrary subset -- call
  * again with lineCap >= d_counts[f] (the host entry point compvhip_houghsht_u8 does that by itself).
  * Beyond 65 535 frames: REFUSED (the whole SHT stage; its key buffers alone would run to gigabytes).  d_edges: ANY BYTE; d_lines and d_counts: 4-byte
- * aligned. */
+ * aligned.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_houghsht(compvhip_plan* plan, const uint8_t* d_edges, int threshold, int maxLines,
                                         compvhip_line* d_lines, size_t lineCap, int32_t* d_counts, void* stream);
 
 /* Sobel -> Canny -> HoughSHT in one call (the benchmark's "step").  Beyond 65 535 frames: REFUSED, like compvhip_plan_pipeline_async and
- * compvhip_plan_pipeline_ex (Canny and the SHT are).  In all three, d_in and d_edges: ANY BYTE; d_lines and d_counts: 4-byte aligned. */
+ * compvhip_plan_pipeline_ex (Canny and the SHT are).  In all three, d_in and d_edges: ANY BYTE; d_lines and d_counts: 4-byte aligned.  Stream order: WAITS (the convergence poll of its Canny). */
 COMPVHIP_API int compvhip_plan_pipeline(compvhip_plan* plan, const uint8_t* d_in, float tLow, float tHigh,
                                         int threshold, int maxLines, uint8_t* d_edges,
                                         compvhip_line* d_lines, size_t lineCap, int32_t* d_counts, void* stream);
@@ -310,7 +325,7 @@ COMPVHIP_API int compvhip_plan_pipeline(compvhip_plan* plan, const uint8_t* d_in
  * sorts a PREDICTED range of the line keys -- the largest line total of the plan's last 8 steps + 1/16 + 4096 -- and compvhip_plan_wait replays the
  * step when its real total exceeded the prediction.  Content whose line count jumps from step to step therefore replays often on such plans, and each
  * replay drains the stream and cascades to the later tickets that share output buffers; plans on the device-sized sort (every size up to 4095 x 4095
- * with at most 131 072 lines per frame, i.e. all BASELINE configurations) never replay for this reason. */
+ * with at most 131 072 lines per frame, i.e. all BASELINE configurations) never replay for this reason.  Stream order: ASYNC: compvhip_plan_wait is where the host waits. */
 COMPVHIP_API int compvhip_plan_pipeline_async(compvhip_plan* plan, const uint8_t* d_in, float tLow, float tHigh,
                                               int threshold, int maxLines, uint8_t* d_edges,
                                               compvhip_line* d_lines, size_t lineCap, int32_t* d_counts, void* stream, int* ticket);
@@ -330,7 +345,7 @@ typedef struct compvhip_pipeline_opts {
 	float* d_cart;          /* receives toCartesian's endpoints [frames][lineCap][4] (NULL: not wanted); 4-byte aligned */
 } compvhip_pipeline_opts;
 /* ticket == NULL: synchronous like compvhip_plan_pipeline; otherwise asynchronous like compvhip_plan_pipeline_async (same rules: wait with
- * compvhip_plan_wait, d_in unmodified and distinct from d_edges until then). */
+ * compvhip_plan_wait, d_in unmodified and distinct from d_edges until then).  Stream order: WAITS without a ticket; with a ticket it is ASYNC like compvhip_plan_pipeline_async.  opts may be changed as soon as the call has returned. */
 COMPVHIP_API int compvhip_plan_pipeline_ex(compvhip_plan* plan, const uint8_t* d_in, const compvhip_pipeline_opts* opts, uint8_t* d_edges,
                                            compvhip_line* d_lines, size_t lineCap, int32_t* d_counts, void* stream, int* ticket);
 
@@ -348,7 +363,7 @@ COMPVHIP_API int compvhip_plan_pipeline_ex(compvhip_plan* plan, const uint8_t* d
  * cluster subdivision does not terminate: a defined deviation, also of compvhip_houghkht_u8 / compvhip_houghkht_kernels_u8).
  * compvhip_plan_houghkht_stage_ms: the six stage clocks of the last call summed over its frames (compvhip_houghkht_stage_ms order), the wall
  * time of the call and the number of workers.
- * Beyond 65 535 frames: REFUSED (compvhip_plan_houghkht_ex as well).  d_edges: ANY BYTE (in both calls; every other array is the host's). */
+ * Beyond 65 535 frames: REFUSED (compvhip_plan_houghkht_ex as well).  d_edges: ANY BYTE (in both calls; every other array is the host's).  Stream order: DRAINS. */
 COMPVHIP_API int compvhip_plan_houghkht(compvhip_plan* plan, const uint8_t* d_edges, float rho, float thetaDeg, int threshold, int maxLines,
                                         double clusterMinDeviation, size_t clusterMinSize, double kernelMinHeight,
                                         compvhip_line* lines, size_t cap, size_t* counts, double* gs, int hostThreads);
@@ -383,7 +398,7 @@ typedef struct compvhip_kht_opts {
 /* compvhip_plan_houghkht / compvhip_houghkht_u8 with the knobs in opts (same buffers, capacity and error contract: COMPVHIP_E_OUT_OF_BOUND when a frame has
  * more than cap lines, counts[f] / *n tell how many).  opts == NULL or an unknown order: COMPVHIP_E_INVALID_PARAMETER.  In CANONICAL order the vote map
  * never leaves the device: the peaks of every frame are found and sorted on the GPU and only the lines and their counts are downloaded; the sixth stage
- * clock (sort + sweep on the host) reads 0 and the GPU peak and sort time is part of the fifth (vote + peaks). */
+ * clock (sort + sweep on the host) reads 0 and the GPU peak and sort time is part of the fifth (vote + peaks).  Stream order: DRAINS. */
 COMPVHIP_API int compvhip_plan_houghkht_ex(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_kht_opts* opts,
                                            compvhip_line* lines, size_t cap, size_t* counts, double* gs);
 COMPVHIP_API int compvhip_houghkht_ex_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size_t H, size_t S, const compvhip_kht_opts* opts,
@@ -395,7 +410,7 @@ COMPVHIP_API int compvhip_houghkht_ex_u8(compvhip_ctx* ctx, const uint8_t* edges
 COMPVHIP_API int compvhip_plan_acc(compvhip_plan* plan, size_t frame, const uint16_t** d_acc, size_t* R, size_t* T, size_t* accPitch);
 /* Copies the accumulator of frame f into a caller DEVICE buffer in the reference layout: int32 [R][outStride]
  * (outStride >= T), i.e. acc[(barrier - rho) * outStride + t] (houghsht.cxx:430-431).  Beyond 65 535 frames: REFUSED (one frame per call, but no
- * call that fills the accumulators accepts such a plan).  d_out: 4-byte aligned. */
+ * call that fills the accumulators accepts such a plan).  d_out: 4-byte aligned.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_acc_export(compvhip_plan* plan, size_t frame, int32_t* d_out, size_t outStride, void* stream);
 /* Number of edge pixels per frame voted by the last houghsht / pipeline step of this plan (device int32[frames]).  The SHT's voting
  * kernel counts them: a compvhip_plan_canny call alone resets them to zero, and before the plan's first SHT the call is refused.  d_edge_counts: a HOST
@@ -429,7 +444,7 @@ typedef struct compvhip_segment {
  * frames * min(lineCap, maxLines) counters are allocated on first use).  COMPVHIP_E_INVALID_STATE while the plan has asynchronous steps that
  * were not waited for (a replayed step rewrites d_lines later); COMPVHIP_E_INVALID_PARAMETER for minLength < 1, maxGap < 0, lineCap == 0 or
  * segCap == 0.  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there.
- * d_edges: ANY BYTE; d_lines, d_counts, d_segs and d_segCounts: 4-byte aligned. */
+ * d_edges: ANY BYTE; d_lines, d_counts, d_segs and d_segCounts: 4-byte aligned.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_houghsht_segments(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts,
                                                  size_t lineCap, int maxLines, int minLength, int maxGap,
                                                  compvhip_segment* d_segs, size_t segCap, int32_t* d_segCounts, void* stream);
@@ -482,7 +497,7 @@ typedef struct compvhip_line_fit {
  * same d_counts and lineCap; COMPVHIP_E_INVALID_PARAMETER in per-segment mode.  halfWidth outside 0 .. 8, lineCap == 0 or a null line / count
  * buffer: COMPVHIP_E_INVALID_PARAMETER; max(W, H) > 8192: COMPVHIP_E_NOT_IMPLEMENTED.  Asynchronous on `stream`; no scratch beyond the
  * plan's SHT tables.  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there.
- * d_edges: ANY BYTE; d_fits: 8-byte aligned; d_lines, d_counts, d_segs, d_segCounts, d_fitCounts and d_refined: 4-byte aligned. */
+ * d_edges: ANY BYTE; d_fits: 8-byte aligned; d_lines, d_counts, d_segs, d_segCounts, d_fitCounts and d_refined: 4-byte aligned.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_houghsht_fit(compvhip_plan* plan, const uint8_t* d_edges, const compvhip_line* d_lines, const int32_t* d_counts,
                                             size_t lineCap, int maxLines, int halfWidth,
                                             const compvhip_segment* d_segs, const int32_t* d_segCounts, size_t segCap,
@@ -523,7 +538,7 @@ typedef struct compvhip_component {
  * Asynchronous on `stream`.  Scratch is owned by the plan and allocated on first use: frames * H int32, for byte maps a mask copy
  * (frames * H * wb words, 1/8 of the bytes), and -- only when d_labels == NULL -- one int32 parent word per pixel (frames * W * H * 4 bytes:
  * 33 MB per 4K frame); with a label map the parent words live in it (labelled in place).  Beyond 65 535 frames: SLICED with the caller's d_edges; the plan's own masks exist only behind a Canny run, which is REFUSED there.
- * d_edges: ANY BYTE; d_labels, d_comps and d_compCounts: 4-byte aligned (the kernels run atomics on the label words and on the boxes). */
+ * d_edges: ANY BYTE; d_labels, d_comps and d_compCounts: 4-byte aligned (the kernels run atomics on the label words and on the boxes).  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_components(compvhip_plan* plan, const uint8_t* d_edges, int connectivity, int minPixels,
                                           int32_t* d_labels, size_t labelStride, compvhip_component* d_comps, size_t compCap,
                                           int32_t* d_compCounts, void* stream);
@@ -566,7 +581,7 @@ COMPVHIP_API int compvhip_threshold_u8(compvhip_ctx* ctx, const uint8_t* in, siz
 /* The same on `frames` device frames.  d_levels != NULL: frame f is cut at d_levels[f] clipped to 0..255 and `threshold` is ignored --
  * the array compvhip_plan_otsu writes, so Otsu + binarise is CompVImage::thresholdOtsu(input, t, &output) (compv_image_threshold.cxx:110-113)
  * without a host round trip.  d_in and d_out may be the same buffer.  Columns >= W of d_out are never written.  Beyond 65 535 frames: SLICED.
- * d_in and d_out: ANY BYTE; d_levels: 4-byte aligned. */
+ * d_in and d_out: ANY BYTE; d_levels: 4-byte aligned.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_threshold(compvhip_plan* plan, const uint8_t* d_in, double threshold, const int32_t* d_levels,
                                          uint8_t* d_out, void* stream);
 
@@ -582,7 +597,7 @@ COMPVHIP_API int compvhip_threshold_adaptive_u8(compvhip_ctx* ctx, const uint8_t
                                                 double delta, double maxVal, int invert, uint8_t* out, size_t So);
 /* The same on `frames` device frames, one fused kernel: the mean never reaches memory.  d_in == d_out is served through a plane the plan owns
  * (allocated on first use) and a device copy; any other overlap: COMPVHIP_E_INVALID_PARAMETER.  Columns >= W of d_out are never written.
- * Beyond 65 535 frames: SLICED (in place, the device copy is one enqueue per frame).  d_in and d_out: ANY BYTE. */
+ * Beyond 65 535 frames: SLICED (in place, the device copy is one enqueue per frame).  d_in and d_out: ANY BYTE.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_threshold_adaptive(compvhip_plan* plan, const uint8_t* d_in, size_t blockSize, double delta, double maxVal,
                                                   int invert, uint8_t* d_out, void* stream);
 
@@ -606,11 +621,11 @@ COMPVHIP_API int compvhip_morph_u8(compvhip_ctx* ctx, const uint8_t* in, size_t 
                                    size_t sh, int op, int border, uint8_t* out, size_t So);
 /* The same on `frames` device frames (strel is a HOST array).  An OPEN / CLOSE is two launches through a u8 plane [frames][H][S] the plan owns
  * (allocated on first use).  Columns >= W of d_out are never written.  Beyond 65 535 frames: SLICED (compvhip_plan_morph_ex as well).  d_in and d_out: ANY
- * BYTE (compvhip_plan_morph_ex as well). */
+ * BYTE (compvhip_plan_morph_ex as well).  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_morph(compvhip_plan* plan, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op,
                                      int border, uint8_t* d_out, void* stream);
 /* compvhip_plan_morph with the kernel named (COMPVHIP_MORPH_KERNEL_*): for measuring one kernel against the other and for testing both on
- * the same structuring element.  The result does not depend on it. */
+ * the same structuring element.  The result does not depend on it.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_morph_ex(compvhip_plan* plan, const uint8_t* d_in, const uint8_t* strel, size_t sw, size_t sh, int op,
                                         int border, int kernel, uint8_t* d_out, void* stream);
 
@@ -647,7 +662,7 @@ typedef struct compvhip_corner {
 /* Corners of all frames of the plan.  d_gray: [frames][H][S], 8-byte aligned; d_scores: NULL or a score map of the same geometry (8-byte aligned, must not
  * overlap d_gray); d_corners and d_counts: 4-byte aligned (anything else: COMPVHIP_E_INVALID_PARAMETER); d_corners == NULL with cornerCap == 0: counts only.  Asynchronous on `stream`; results are deterministic run to run.  Scratch
  * is owned by the plan, allocated on first use and released with it: frames * (2 * H + 257) int32, and -- only when d_scores == NULL -- a score
- * map of the plan's own.  Beyond 65 535 frames: REFUSED. */
+ * map of the plan's own.  Beyond 65 535 frames: REFUSED.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_fast(compvhip_plan* plan, const uint8_t* d_gray, int threshold, int fastType, int nonmax, int maxFeatures,
                                     uint8_t* d_scores, compvhip_corner* d_corners, size_t cornerCap, int32_t* d_counts, void* stream);
 
@@ -697,7 +712,7 @@ COMPVHIP_API void compvhip_matcher_destroy(compvhip_matcher* matcher);
 /* d_query: [pairs][queryCap] rows of queryStride bytes (descBytes <= queryStride <= 65536, queryStride % 4 == 0, 4-byte aligned); d_train: the same with
  * trainCap / trainStride, or, with trainShared != 0, ONE train set [trainCap] and ONE train count that serve every pair (one trained object
  * against many frames).  d_matches: [pairs][knn][queryCap] records, 16-byte aligned; d_queryCounts and d_trainCounts 4-byte aligned.  Asynchronous on `stream`;
- * deterministic run to run. */
+ * deterministic run to run.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_matcher_knn(compvhip_matcher* matcher, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts,
                                       const uint8_t* d_train, size_t trainStride, const int32_t* d_trainCounts, int trainShared,
                                       compvhip_match* d_matches, void* stream);
@@ -706,7 +721,7 @@ COMPVHIP_API int compvhip_matcher_knn(compvhip_matcher* matcher, const uint8_t* 
  * read by the cross check only (it runs the distance kernel with the roles swapped and knn = 1 into the matcher's scratch).  d_good:
  * [pairs][goodCap] records, 16-byte aligned (NULL with goodCap == 0: counts only); d_goodCounts: [pairs] int32; d_matches 16-byte aligned, the descriptors and
  * the three count arrays 4-byte aligned.  opts == NULL, or
- * ratio > 0 on a matcher with knn < 2: COMPVHIP_E_INVALID_PARAMETER.  Asynchronous on `stream`. */
+ * ratio > 0 on a matcher with knn < 2: COMPVHIP_E_INVALID_PARAMETER.  Asynchronous on `stream`.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_matcher_good(compvhip_matcher* matcher, const compvhip_match* d_matches,
                                        const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts,
                                        const uint8_t* d_train, size_t trainStride, const int32_t* d_trainCounts, int trainShared,
@@ -771,7 +786,7 @@ typedef struct compvhip_keypoint {   /* CompVInterestPoint (compv_common.h:629),
  * device).  d_gray: [frames][H][S], 4-byte aligned; d_keypoints: [frames][keyCap] (NULL with keyCap == 0: counts only); d_moments: NULL or
  * [frames][keyCap][2] int32 = {m01, m10}; records, counts and moments 4-byte aligned; scale > 0 (anything else: COMPVHIP_E_INVALID_PARAMETER).
  * Asynchronous on `stream`, no atomic, deterministic.  Scratch is owned by the plan, allocated on first use (and again for a larger keyCap) and
- * released with it: frames * keyCap int32.  Beyond 65 535 frames: REFUSED. */
+ * released with it: frames * keyCap int32.  Beyond 65 535 frames: REFUSED.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_orb_keypoints(compvhip_plan* plan, const uint8_t* d_gray, const compvhip_corner* d_corners, size_t cornerCap,
                                              const int32_t* d_cornerCounts, int level, float scale, compvhip_keypoint* d_keypoints, size_t keyCap,
                                              int32_t* d_keyCounts, int32_t* d_moments, void* stream);
@@ -779,7 +794,7 @@ COMPVHIP_API int compvhip_plan_orb_keypoints(compvhip_plan* plan, const uint8_t*
 /* Descriptors of the keypoints (compvhip_plan_orb_keypoints' or the caller's own) with the level's `scale`.  descStride >= 32 and a multiple of 4,
  * d_gray, d_keypoints, d_keyCounts and d_desc 4-byte aligned, keyCap > 0 (anything else: COMPVHIP_E_INVALID_PARAMETER).  With descStride == 32, d_desc / d_keyCounts are what
  * compvhip_matcher_knn takes as d_query / d_queryCounts.  Asynchronous on `stream`.  Scratch, allocated on first use with blur != 0: one blurred
- * batch [frames][H][S].  Beyond 65 535 frames: REFUSED. */
+ * batch [frames][H][S].  Beyond 65 535 frames: REFUSED.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_orb_describe(compvhip_plan* plan, const uint8_t* d_gray, const compvhip_keypoint* d_keypoints, size_t keyCap,
                                             const int32_t* d_keyCounts, float scale, int blur, uint8_t* d_desc, size_t descStride, void* stream);
 
@@ -852,18 +867,18 @@ COMPVHIP_API int compvhip_orbpyr_geometry(const compvhip_orbpyr* pyramid, int le
 COMPVHIP_API int compvhip_orbpyr_plane(compvhip_orbpyr* pyramid, int level, int blurred, const uint8_t** d_plane);
 /* C. for every frame.  d_gray 8-byte aligned; d_keypoints: [frames][keyCap] (NULL with keyCap == 0: counts only); keypoints and counts (d_keyCounts,
  * d_levelCounts, d_levelCorners) 4-byte aligned.
- * Asynchronous on `stream`, never synchronises the host, deterministic run to run. */
+ * Asynchronous on `stream`, never synchronises the host, deterministic run to run.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_orbpyr_detect(compvhip_orbpyr* pyramid, const uint8_t* d_gray, compvhip_keypoint* d_keypoints, size_t keyCap, int32_t* d_keyCounts,
                                         int32_t* d_levelCounts, int32_t* d_levelCorners, void* stream);
 /* D. for every frame; rows as compvhip_plan_orb_describe writes them (rows q >= min(count, keyCap) are never written).  reusePlanes != 0:
  * describe on the planes the preceding compvhip_orbpyr_detect built from the same d_gray (COMPVHIP_E_INVALID_STATE when there was none);
  * reusePlanes == 0 rebuilds them.  d_gray 8-byte aligned; d_keypoints, d_keyCounts and d_desc 4-byte aligned.  Asynchronous on `stream`, never synchronises
- * the host. */
+ * the host.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_orbpyr_describe(compvhip_orbpyr* pyramid, const uint8_t* d_gray, int reusePlanes, const compvhip_keypoint* d_keypoints, size_t keyCap,
                                           const int32_t* d_keyCounts, uint8_t* d_desc, size_t descStride, void* stream);
 /* A. for every frame of a plan: d_in [frames][H][S] of the plan's geometry -> d_out [frames][Hout][Sout] (Sout >= Wout; sizes up to 32767; the
  * buffers must not overlap).  A destination that is dword-aligned in pointer and stride is written with dword stores.  Asynchronous on `stream`.
- * Beyond 65 535 frames: REFUSED.  d_in and d_out: ANY BYTE (a destination that is not dword-aligned is written byte by byte). */
+ * Beyond 65 535 frames: REFUSED.  d_in and d_out: ANY BYTE (a destination that is not dword-aligned is written byte by byte).  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_scale(compvhip_plan* src, const uint8_t* d_in, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
 /* A. for one HOST plane (sizes 1 .. 32767).  Synchronous. */
 COMPVHIP_API int compvhip_scale_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint8_t* out, size_t Wout, size_t Hout, size_t Sout);
@@ -919,14 +934,14 @@ COMPVHIP_API int compvhip_warp_tables(const float* M, int rows, size_t Wout, siz
  * the map once for 8 frames); mapCount == frames: one map per frame.  roi == NULL: the whole frame.  A destination that is aligned in pointer, stride
  * and frame size (4 bytes for uint8, 16 for float32) is written with vector stores.  Asynchronous on `stream`, never synchronises the host.
  * Beyond 65 535 frames (shared map: beyond 65 535 groups of 8): SLICED.  d_in: ANY BYTE; d_mapX and d_mapY: 4-byte aligned; d_out: ANY BYTE for uint8, 4-byte
- * aligned for float32. */
+ * aligned for float32.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_remap(compvhip_plan* plan, const uint8_t* d_in, const float* d_mapX, const float* d_mapY, size_t mapCount, int interp,
                                      const compvhip_roi* roi, uint8_t defaultValue, void* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
 /* Inverse warp for every frame of a plan.  M: HOST, [matrixCount][rows][3] float32, rows 2 or 3; matrixCount 1 or frames.  The tables of A.2 are
  * built on the host into pinned staging owned by the plan and uploaded in stream order; M may be reused as soon as the call returns.  Asynchronous
  * on `stream`: the host waits only when 4 earlier uploads of the plan are all still pending.  Timing entries (compvhip_plan_set_timing):
  * remap_kernel, warp_inverse_kernel.  Beyond 65 535 frames: SLICED, like compvhip_plan_remap.  d_in: ANY BYTE; d_out: ANY BYTE for uint8, 4-byte aligned for
- * float32. */
+ * float32.  Stream order: ASYNC, with one exception: M is staged in a ring of 4 pinned slots, so a call may wait for the copy of the call four before it (never for more).  M may be changed as soon as the call has returned. */
 COMPVHIP_API int compvhip_plan_warp_inverse(compvhip_plan* plan, const uint8_t* d_in, const float* M, int rows, size_t matrixCount, int interp,
                                             uint8_t defaultValue, void* d_out, size_t Wout, size_t Hout, size_t Sout, void* stream);
 /* Both for one HOST plane (sizes 1 .. 32767) with host maps / a host matrix; S and Sout in elements.  Synchronous. */
@@ -1000,19 +1015,19 @@ COMPVHIP_API int compvhip_homography_create(compvhip_ctx* ctx, size_t pairs, siz
 COMPVHIP_API void compvhip_homography_destroy(compvhip_homography* homography);
 /* Gathers the pairs' points into the handle.  d_good: [pairs][goodCap] records, 16-byte aligned; d_goodCounts: [pairs] int32 or NULL (every pair
  * full); d_query: [pairs][queryCap] keypoints; d_train: [pairs][trainCap], or ONE set [trainCap] with trainShared != 0; 4-byte aligned.
- * Asynchronous on `stream`. */
+ * Asynchronous on `stream`.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_homography_points(compvhip_homography* homography, const compvhip_match* d_good, size_t goodCap, const int32_t* d_goodCounts,
                                             const compvhip_keypoint* d_query, size_t queryCap, const compvhip_keypoint* d_train, size_t trainCap,
                                             int trainShared, void* stream);
 /* d_src, d_dst: [pairs][pointCap] {x, y} float64, 16-byte aligned, with d_counts; d_src == NULL: the points compvhip_homography_points gathered
  * (d_dst and d_counts are then ignored).  d_quads: NULL or [pairs][opts->tries][4] int32, 16-byte aligned.  d_results: [pairs] records, 8-byte
  * aligned; d_counts 4-byte aligned.  d_mask: NULL or [pairs][pointCap] bytes, ANY BYTE.  A null handle, opts or d_results, tries < 1 or > maxTries, a threshold that is not > 0, a
- * misaligned pointer: COMPVHIP_E_INVALID_PARAMETER, nothing written.  Asynchronous on `stream`; deterministic run to run. */
+ * misaligned pointer: COMPVHIP_E_INVALID_PARAMETER, nothing written.  Asynchronous on `stream`; deterministic run to run.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_homography_find(compvhip_homography* homography, const double* d_src, const double* d_dst, const int32_t* d_counts,
                                           const compvhip_homography_opts* opts, const int32_t* d_quads, compvhip_homography_result* d_results,
                                           uint8_t* d_mask, void* stream);
 /* Sends n points through each pair's H.  d_points: [pairs][n] {x, y} float64, or ONE set [n] with shared != 0 (the train rectangle of the sample);
- * d_out: [pairs][n]; both 16-byte aligned.  A pair of status 2 (H zeros) yields NaN.  Asynchronous on `stream`. */
+ * d_out: [pairs][n]; both 16-byte aligned.  A pair of status 2 (H zeros) yields NaN.  Asynchronous on `stream`.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_homography_project(compvhip_homography* homography, const compvhip_homography_result* d_results, const double* d_points,
                                              size_t n, int shared, double* d_out, void* stream);
 /* Item A on the host (standard library only, no GPU): quads[tries][4] of pair `pair` among k >= 4 points. */
@@ -1023,7 +1038,7 @@ COMPVHIP_API int compvhip_homography_find_f64(compvhip_ctx* ctx, const double* s
                                               const int32_t* quads, compvhip_homography_result* result, uint8_t* mask);
 /* Test hook: what the last compvhip_homography_find left in the score scratch, copied to HOST arrays of [pairs][tries] (NULL: not wanted) --
  * per try the inlier count, the variance and the Jacobi rotations of its computeH.  Entries of a pair with k < 4 are not defined.  Synchronises
- * `stream`. */
+ * `stream`.  Stream order: WAITS: the arrays are the host's, the call returns when they are filled. */
 COMPVHIP_API int compvhip_homography_scores(compvhip_homography* homography, size_t tries, int32_t* counts, double* variances, int32_t* rotations,
                                             void* stream);
 /* Per-kernel timing of the handle's last call, as compvhip_matcher_set_timing / _get_timing: entries homography_points_kernel;
@@ -1089,7 +1104,7 @@ COMPVHIP_API int compvhip_hog_geometry(size_t W, size_t H, const compvhip_hog_op
 /* Descriptors of all frames of the plan.  d_gray: [frames][H][S], ANY BYTE; d_desc: [frames][descStride] float32, descStride >= descLen counted in floats, the floats
  * behind descLen are never written; d_cells: NULL or the cell map [frames][cellsY][cellsX][nbins] float32; d_desc and d_cells 4-byte aligned.  A batch of
  * crops is a plan of the crop's size with one frame per crop.  Asynchronous on `stream`, no atomic, deterministic.  Scratch is owned by the plan, allocated on
- * first use with d_cells == NULL and released with it: one cell map.  Like every plan call it is not re-entrant.  Beyond 65 535 frames: SLICED. */
+ * first use with d_cells == NULL and released with it: one cell map.  Like every plan call it is not re-entrant.  Beyond 65 535 frames: SLICED.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_hog(compvhip_plan* plan, const uint8_t* d_gray, const compvhip_hog_opts* opts, float* d_cells, float* d_desc, size_t descStride,
                                    void* stream);
 
@@ -1125,24 +1140,24 @@ COMPVHIP_API int compvhip_hog_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t 
 COMPVHIP_API int compvhip_integral_dims(size_t W, size_t H, size_t* rows, size_t* cols);
 
 /* d_sum, d_sumsq: [frames][H + 1][sumStride] float64, sumStride >= W + 1 counted in elements, 8-byte aligned; elements at columns > W are not written.
- * Either may be NULL, not both.  Three kernels: the bands' column sums, their scan down the frame, the integral (one pass over 16-row bands). */
+ * Either may be NULL, not both.  Three kernels: the bands' column sums, their scan down the frame, the integral (one pass over 16-row bands).  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_integral(compvhip_plan* plan, const uint8_t* d_gray, double* d_sum, double* d_sumsq, size_t sumStride, void* stream);
 COMPVHIP_API int compvhip_integral_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double* sum, double* sumsq, size_t sumStride);
 
-/* d_hist: [frames][256] uint32, 4-byte aligned. */
+/* d_hist: [frames][256] uint32, 4-byte aligned.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_histogram(compvhip_plan* plan, const uint8_t* d_gray, uint32_t* d_hist, void* stream);
 COMPVHIP_API int compvhip_histogram_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, uint32_t* hist);
 
 /* d_hist: [frames][256], or NULL: each frame's own histogram (the reference's first overload; a non-NULL d_hist is its second).  d_out: [frames][H][S],
  * columns >= W are not written; d_out == d_gray is allowed, as in the reference: the histogram of a frame is complete before any of its pixels is
  * rewritten.  Any other overlap of the two is not.  d_lut: NULL or [frames][256] bytes, the tables.  d_hist 4-byte aligned; d_out and d_lut ANY BYTE, like
- * d_gray. */
+ * d_gray.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_equalize(compvhip_plan* plan, const uint8_t* d_gray, const uint32_t* d_hist, double scale, uint8_t* d_out, uint8_t* d_lut,
                                         void* stream);
 COMPVHIP_API int compvhip_equalize_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint32_t* hist, double scale, uint8_t* out,
                                       size_t So, uint8_t* lut);
 
-/* d_projX: [frames][W], d_projY: [frames][H], int32, dense, 4-byte aligned.  Either may be NULL, not both; with both the frames are read once. */
+/* d_projX: [frames][W], d_projY: [frames][H], int32, dense, 4-byte aligned.  Either may be NULL, not both; with both the frames are read once.  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_plan_projections(compvhip_plan* plan, const uint8_t* d_gray, int32_t* d_projX, int32_t* d_projY, void* stream);
 COMPVHIP_API int compvhip_projections_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, int32_t* projX, int32_t* projY);
 
@@ -1191,7 +1206,7 @@ typedef struct compvhip_image {     /* `frames` images of one format */
 /* Host arithmetic only: plane count, least row bytes and row count of each plane (entries of absent planes: 0); any output may be NULL.
  * COMPVHIP_E_INVALID_PARAMETER for an unknown format or a zero size, nothing written. */
 COMPVHIP_API int compvhip_convert_layout(int pixfmt, size_t W, size_t H, int* planes, size_t minRowBytes[3], size_t rows[3]);
-/* device memory, asynchronous on `stream` */
+/* device memory, asynchronous on `stream`  Stream order: ASYNC. */
 COMPVHIP_API int compvhip_convert_frames(compvhip_ctx* ctx, size_t W, size_t H, size_t frames, const compvhip_image* in, const compvhip_image* out, void* stream);
 /* host memory, one frame (frameBytes ignored), synchronous; staged through the context's device buffers */
 COMPVHIP_API int compvhip_convert_u8(compvhip_ctx* ctx, size_t W, size_t H, const compvhip_image* in, const compvhip_image* out);
