@@ -33,6 +33,7 @@ STREL_RECT, STREL_DIAMOND, STREL_CROSS = 0, 1, 2
 BORDER_ZERO, BORDER_REPLICATE = 0, 2
 MORPH_KERNEL_AUTO, MORPH_KERNEL_GENERAL, MORPH_KERNEL_SEPARABLE = 0, 1, 2
 INTERP_NEAREST, INTERP_BILINEAR, INTERP_BILINEAR_FLOAT32 = 0, 1, 2
+INTERP_BICUBIC, INTERP_BICUBIC_FLOAT32 = 4, 5                    # 3 is unassigned
 CORNER_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("strength", "<i4")])   # compvhip_corner
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("strength", "<f4"), ("orient", "<f4"), ("level", "<i4"), ("size", "<f4")])   # compvhip_keypoint = CompVInterestPoint
 MATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imageIdx", "<i4"), ("distance", "<i4")])   # compvhip_match = CompVDMatch
@@ -700,22 +701,23 @@ class Context:
         return out
 
     def remap(self, img, map_x, map_y, interp=INTERP_BILINEAR, roi=None, default=0):
-        """compvhip_remap_u8 (CompVImageRemap::process): map_x, map_y (out_h, out_w) float32 -> the (out_h, out_w) plane, uint8 or (INTERP_BILINEAR_FLOAT32)
-        float32.  roi: None, a Roi or (left, right, top, bottom)."""
+        """compvhip_remap_u8 (CompVImageRemap::process): map_x, map_y (out_h, out_w) float32 -> the (out_h, out_w) plane, uint8 or (INTERP_BILINEAR_FLOAT32,
+        INTERP_BICUBIC_FLOAT32) float32.  interp: INTERP_NEAREST, _BILINEAR, _BICUBIC or one of the two _FLOAT32 forms.  roi: None, a Roi or (left, right, top, bottom)."""
         H, W = img.shape
         map_x, map_y = np.ascontiguousarray(map_x, np.float32), np.ascontiguousarray(map_y, np.float32)
         assert map_x.ndim == 2 and map_x.shape == map_y.shape
         out_h, out_w = map_x.shape
-        out = np.empty((out_h, out_w), np.float32 if interp == INTERP_BILINEAR_FLOAT32 else np.uint8)
+        out = np.empty((out_h, out_w), np.float32 if interp in (INTERP_BILINEAR_FLOAT32, INTERP_BICUBIC_FLOAT32) else np.uint8)
         self._chk(self.lib.compvhip_remap_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(map_x), _ptr(map_y), interp, _roi(roi), default, _ptr(out), out_w, out_h, out_w))
         return out
 
     def warp_inverse(self, img, M, out_w, out_h, interp=INTERP_BILINEAR, default=0):
-        """compvhip_warp_inverse_u8 (CompVImage::warpInverse): M (2, 3) or (3, 3) float32, destination to source -> the (out_h, out_w) plane"""
+        """compvhip_warp_inverse_u8 (CompVImage::warpInverse): M (2, 3) or (3, 3) float32, destination to source -> the (out_h, out_w) plane, uint8 or
+        (INTERP_BILINEAR_FLOAT32, INTERP_BICUBIC_FLOAT32) float32"""
         H, W = img.shape
         M = np.ascontiguousarray(M, np.float32)
         assert M.ndim == 2 and M.shape[1] == 3
-        out = np.empty((out_h, out_w), np.float32 if interp == INTERP_BILINEAR_FLOAT32 else np.uint8)
+        out = np.empty((out_h, out_w), np.float32 if interp in (INTERP_BILINEAR_FLOAT32, INTERP_BICUBIC_FLOAT32) else np.uint8)
         self._chk(self.lib.compvhip_warp_inverse_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(M), M.shape[0], interp, default, _ptr(out), out_w, out_h, out_w))
         return out
 

@@ -479,12 +479,13 @@ int compvhip_api::remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W,
                                size_t Wout, size_t Hout, size_t Sout, uint8_t defaultValue, RemapArgs* a)
 {
 	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
-	if (interp != COMPVHIP_INTERP_NEAREST && interp != COMPVHIP_INTERP_BILINEAR && interp != COMPVHIP_INTERP_BILINEAR_FLOAT32)
+	if (interp != COMPVHIP_INTERP_NEAREST && interp != COMPVHIP_INTERP_BILINEAR && interp != COMPVHIP_INTERP_BILINEAR_FLOAT32 && interp != COMPVHIP_INTERP_BICUBIC &&
+	    interp != COMPVHIP_INTERP_BICUBIC_FLOAT32)
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "unknown interpolation");
 	if (!W || !H || !Wout || !Hout || Wout > 32767 || Hout > 32767 || W > 32767 || H > 32767 || S < W || Sout < Wout || Sout > static_cast<size_t>(INT32_MAX) || !frames ||
 	    frames > static_cast<size_t>(INT32_MAX) || S * H > static_cast<size_t>(INT32_MAX))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "remap: a size of 0 or beyond 32767, Sout < Wout, or a frame beyond 2^31 bytes");
-	const size_t elem = interp == COMPVHIP_INTERP_BILINEAR_FLOAT32 ? sizeof(float) : 1;
+	const size_t elem = interp == COMPVHIP_INTERP_BILINEAR_FLOAT32 || interp == COMPVHIP_INTERP_BICUBIC_FLOAT32 ? sizeof(float) : 1;
 	if (elem > 1 && misaligned(3, d_out)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "float32 destination not 4-byte aligned");
 	const uint8_t* const o = static_cast<const uint8_t*>(d_out);
 	if (d_in < o + Sout * Hout * frames * elem && o < d_in + S * H * frames) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap");

@@ -491,10 +491,11 @@ static int hostRemap(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, s
 {
 	if (!in || !out || S < W || Sout < Wout) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image or stride < width");
 	if (!W || !H || !Wout || !Hout || W > 32767 || H > 32767 || Wout > 32767 || Hout > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (1..32767)");
-	if (interp != COMPVHIP_INTERP_NEAREST && interp != COMPVHIP_INTERP_BILINEAR && interp != COMPVHIP_INTERP_BILINEAR_FLOAT32)
+	if (interp != COMPVHIP_INTERP_NEAREST && interp != COMPVHIP_INTERP_BILINEAR && interp != COMPVHIP_INTERP_BILINEAR_FLOAT32 && interp != COMPVHIP_INTERP_BICUBIC &&
+	    interp != COMPVHIP_INTERP_BICUBIC_FLOAT32)
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "unknown interpolation");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t elem = interp == COMPVHIP_INTERP_BILINEAR_FLOAT32 ? sizeof(float) : 1;
+	const size_t elem = interp == COMPVHIP_INTERP_BILINEAR_FLOAT32 || interp == COMPVHIP_INTERP_BICUBIC_FLOAT32 ? sizeof(float) : 1;
 	const size_t Sd = alignUp(W, 64), Sod = alignUp(Wout, 64);
 	HIPCHK(ctx, ctx->dIn.reserve(ctx, Sd * H));
 	HIPCHK(ctx, ctx->dOut.reserve(ctx, Sod * Hout * elem));

@@ -468,7 +468,7 @@ hipError_t launch_scale_bilinear(ScaleArgs& a, int frames, hipStream_t stream); 
 // CompVImageRemap::process / CompVImage::warpInverse: a per-pixel gather at coordinates that come from a float32 map or from the running-sum tables
 // of a matrix (include/compv_hip.h, section "remap and inverse warp")
 enum { kRemapMap = 0, kRemapWarp2 = 1, kRemapWarp3 = 2 };                  // coordinate source
-enum { kRemapNearest = 0, kRemapBilinear = 1, kRemapBilinearF32 = 2 };     // = COMPVHIP_INTERP_*
+enum { kRemapNearest = 0, kRemapBilinear = 1, kRemapBilinearF32 = 2, kRemapBicubic = 4, kRemapBicubicF32 = 5 };     // = COMPVHIP_INTERP_* (3 is unassigned)
 constexpr int kRemapFramesPerGroup = 8;   // frames a workgroup loops over with one set of coordinates when the map / matrix is shared
 struct RemapArgs {
 	const uint8_t* in;        // [frames][H][S]
@@ -486,7 +486,7 @@ struct RemapArgs {
 	int framesPerGroup, group0, tilesX, wide, mapVec;   // filled by launch_remap
 };
 // perFrame: every frame has a map / tables of its own (coordFrameStride apart); otherwise all frames share the first.  S >= 2 (the bilinear forms load
-// 2-byte pairs inside a row); hipErrorInvalidValue for that, for a ROI that is neither empty nor inside the frame, and for sizes whose frame exceeds 2^31 bytes.
+// 2-byte pairs inside a row; the bicubic forms load 4-byte tap rows and need S >= 4); hipErrorInvalidValue for that, for a ROI that is neither empty nor inside the frame, and for sizes whose frame exceeds 2^31 bytes.
 hipError_t launch_remap(const RemapArgs& a, int source, int interp, bool perFrame, hipStream_t stream);
 
 // ---- HOG descriptors (hog_kernels.hip) ------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,10 @@
 //                           has its own), so a shared map is read once per 8 frames.  A pixel outside the ROI gathers from offset 0 and is replaced by
 //                           the default value afterwards: no divergent branch.  The bilinear forms load the two neighbours of a row as one 2-byte pair: 8 loads per lane
 //                           and frame in flight.  No LDS, no atomic.
+//   remap_bicubic_kernel<SRC, OutT>   The same tile, coordinates (remap_coords, shared), stores and frame loop for the bicubic forms (paragraph F of the
+//                           definition; the arithmetic is bicubic_math.hpp, unfused).  16 taps per pixel: a tap row is one unaligned 4-byte load whose bytes
+//                           the four packed selectors pick: 4 loads per pixel and frame.
+#include "bicubic_math.hpp"
 #include "device.hpp"
 #include "frame_slices.hpp"
 
@@ -29,18 +33,10 @@ __device__ __forceinline__ uint32_t load_pair(const uint8_t* p)
 	return v;
 }
 
-template <int SRC, int INTERP, typename OutT>
-__global__ __launch_bounds__(256) void remap_kernel(RemapArgs a)
+// ---- source coordinates of the lane's pixels (pixels >= n keep a NaN: outside, and never stored): shared by every kernel of this file ----
+template <int SRC>
+__device__ __forceinline__ void remap_coords(const RemapArgs& a, int f0, int j, int i0, int n, float (&x)[4], float (&y)[4])
 {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const int ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
-	const int j = ty * kRemapTileH + wave, i0 = tx * kRemapTileW + 4 * lane;
-	if (j >= a.Hout || i0 >= a.Wout) return;
-	const int f0 = (a.group0 + static_cast<int>(blockIdx.y)) * a.framesPerGroup, nf = min(a.framesPerGroup, a.frames - f0);
-	const int n = min(4, a.Wout - i0);          // pixels of this lane inside the row
-
-	// ---- source coordinates of the lane's pixels (pixels >= n keep a NaN: outside, and never stored) ----
-	float x[4], y[4];
 #pragma unroll
 	for (int b = 0; b < 4; ++b) x[b] = y[b] = __builtin_nanf("");
 	if (SRC == kRemapMap) {
@@ -71,6 +67,20 @@ __global__ __launch_bounds__(256) void remap_kernel(RemapArgs a)
 			else { x[b] = X; y[b] = Y; }
 		}
 	}
+}
+
+template <int SRC, int INTERP, typename OutT>
+__global__ __launch_bounds__(256) void remap_kernel(RemapArgs a)
+{
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
+	const int j = ty * kRemapTileH + wave, i0 = tx * kRemapTileW + 4 * lane;
+	if (j >= a.Hout || i0 >= a.Wout) return;
+	const int f0 = (a.group0 + static_cast<int>(blockIdx.y)) * a.framesPerGroup, nf = min(a.framesPerGroup, a.frames - f0);
+	const int n = min(4, a.Wout - i0);          // pixels of this lane inside the row
+
+	float x[4], y[4];
+	remap_coords<SRC>(a, f0, j, i0, n, x, y);
 
 	// ---- per pixel, once for all frames: inside, gather offsets, weights ----
 	bool inside[4];
@@ -139,12 +149,101 @@ __global__ __launch_bounds__(256) void remap_kernel(RemapArgs a)
 	}
 }
 
+// 4 adjacent bytes at any address, as one load
+__device__ __forceinline__ uint32_t load_quad(const uint8_t* p)
+{
+	uint32_t v;
+	__builtin_memcpy(&v, p, sizeof(v));
+	return v;
+}
+
+// Paragraph F of the definition; the arithmetic is bicubic_math.hpp, which the host checker compiles too.  A tap row is ONE 4-byte load at
+// base = quad_base(x_0, W) = min(x_0, max(W - 4, 0)) and tap k is byte x_k - base of it (0 .. 3 at both clamps); base + 3 stays inside the row because
+// S >= 4 (launch_remap).
+template <int SRC, typename OutT>
+__global__ __launch_bounds__(256) void remap_bicubic_kernel(RemapArgs a)
+{
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
+	const int j = ty * kRemapTileH + wave, i0 = tx * kRemapTileW + 4 * lane;
+	if (j >= a.Hout || i0 >= a.Wout) return;
+	const int f0 = (a.group0 + static_cast<int>(blockIdx.y)) * a.framesPerGroup, nf = min(a.framesPerGroup, a.frames - f0);
+	const int n = min(4, a.Wout - i0);          // pixels of this lane inside the row
+
+	float x[4], y[4];
+	remap_coords<SRC>(a, f0, j, i0, n, x, y);
+
+	// ---- per pixel, once for all frames: inside, the offset of tap row 0, the four tap selectors in one word, three row deltas, the fractions ----
+	bool inside[4];
+	int o0[4], d1[4], d2[4], d3[4];          // y_0 * S + base; (y_r - y_0) * S
+	uint32_t sel[4];          // byte k: the bit shift 8 * (x_k - base) into the loaded word
+	float xf[4], xf2[4], xf3[4], yf[4], yf2[4], yf3[4];
+#pragma unroll
+	for (int b = 0; b < 4; ++b) {
+		inside[b] = x[b] >= a.left && x[b] <= a.right && y[b] >= a.top && y[b] <= a.bottom;          // ordered compares: a NaN is outside
+		o0[b] = d1[b] = d2[b] = d3[b] = 0; sel[b] = 0; xf[b] = xf2[b] = xf3[b] = yf[b] = yf2[b] = yf3[b] = 0.f;
+		if (!inside[b]) continue;          // 0 <= x <= W - 1 and 0 <= y <= H - 1 from here on (the launch function checks the ROI)
+		int xi, yi;
+		bicubic::split(x[b], xi, xf[b], xf2[b], xf3[b]);
+		bicubic::split(y[b], yi, yf[b], yf2[b], yf3[b]);
+		int xk[4], yk[4];
+#pragma unroll
+		for (int k = 0; k < 4; ++k) { xk[k] = bicubic::clamp_tap(xi - 1 + k, a.W - 1); yk[k] = bicubic::clamp_tap(yi - 1 + k, a.H - 1); }   // to the frame, not to the ROI
+		const int base = bicubic::quad_base(xk[0], a.W);
+		sel[b] = static_cast<uint32_t>(xk[0] - base) << 3 | static_cast<uint32_t>(xk[1] - base) << 11 | static_cast<uint32_t>(xk[2] - base) << 19 |
+		         static_cast<uint32_t>(xk[3] - base) << 27;
+		o0[b] = yk[0] * a.S + base;
+		d1[b] = (yk[1] - yk[0]) * a.S; d2[b] = (yk[2] - yk[0]) * a.S; d3[b] = (yk[3] - yk[0]) * a.S;
+	}
+
+	const float defF = static_cast<float>(a.defaultValue);
+	for (int k = 0; k < nf; ++k) {
+		const uint8_t* __restrict__ src = a.in + static_cast<size_t>(f0 + k) * a.inFrameStride;
+		float p[4]; uint32_t q[4];
+#pragma unroll
+		for (int b = 0; b < 4; ++b) {
+			const uint8_t* const r0 = src + o0[b];          // an outside pixel gathers at offset 0 (bytes 0 .. 3 of the frame)
+			const int dr[4] = { 0, d1[b], d2[b], d3[b] };
+			const uint32_t s0 = sel[b] & 0xffu, s1 = sel[b] >> 8 & 0xffu, s2 = sel[b] >> 16 & 0xffu, s3 = sel[b] >> 24;
+			float c[4];
+#pragma unroll
+			for (int r = 0; r < 4; ++r) {
+				const uint32_t w = load_quad(r0 + dr[r]);
+				const uint32_t t0 = w >> s0 & 0xffu, t1 = w >> s1 & 0xffu, t2 = w >> s2 & 0xffu, t3 = w >> s3 & 0xffu;
+				c[r] = bicubic::hermite_row(static_cast<float>(t0), static_cast<float>(t1), static_cast<float>(t2), static_cast<float>(t3), xf[b], xf2[b], xf3[b]);
+			}
+			const float v = bicubic::clip255(bicubic::hermite_col(c[0], c[1], c[2], c[3], yf[b], yf2[b], yf3[b]));
+			p[b] = inside[b] ? v : defF;
+			q[b] = inside[b] ? static_cast<uint32_t>(bicubic::to_u8(v)) : static_cast<uint32_t>(a.defaultValue);
+		}
+		const size_t at = static_cast<size_t>(f0 + k) * a.outFrameStride + static_cast<size_t>(j) * a.Sout + i0;          // in elements
+		if (sizeof(OutT) == 1) {
+			uint8_t* __restrict__ dst = static_cast<uint8_t*>(a.out) + at;
+			if (a.wide && n == 4) *reinterpret_cast<uint32_t*>(dst) = q[0] | q[1] << 8 | q[2] << 16 | q[3] << 24;
+			else {
+#pragma unroll
+				for (int b = 0; b < 4; ++b) if (b < n) dst[b] = static_cast<uint8_t>(q[b]);
+			}
+		}
+		else {
+			float* __restrict__ dst = static_cast<float*>(a.out) + at;
+			if (a.wide && n == 4) *reinterpret_cast<float4*>(dst) = make_float4(p[0], p[1], p[2], p[3]);
+			else {
+#pragma unroll
+				for (int b = 0; b < 4; ++b) if (b < n) dst[b] = p[b];
+			}
+		}
+	}
+}
+
 template <int SRC>
 void launch_src(const RemapArgs& a, int interp, dim3 grid, hipStream_t stream)
 {
 	if (interp == kRemapNearest) hipLaunchKernelGGL((remap_kernel<SRC, kRemapNearest, uint8_t>), grid, dim3(256), 0, stream, a);
 	else if (interp == kRemapBilinear) hipLaunchKernelGGL((remap_kernel<SRC, kRemapBilinear, uint8_t>), grid, dim3(256), 0, stream, a);
-	else hipLaunchKernelGGL((remap_kernel<SRC, kRemapBilinear, float>), grid, dim3(256), 0, stream, a);
+	else if (interp == kRemapBilinearF32) hipLaunchKernelGGL((remap_kernel<SRC, kRemapBilinear, float>), grid, dim3(256), 0, stream, a);
+	else if (interp == kRemapBicubic) hipLaunchKernelGGL((remap_bicubic_kernel<SRC, uint8_t>), grid, dim3(256), 0, stream, a);
+	else hipLaunchKernelGGL((remap_bicubic_kernel<SRC, float>), grid, dim3(256), 0, stream, a);
 }
 
 } // namespace
@@ -153,14 +252,16 @@ hipError_t launch_remap(const RemapArgs& args, int source, int interp, bool perF
 {
 	RemapArgs a = args;
 	if (!a.in || !a.out || a.W < 1 || a.H < 1 || a.S < a.W || a.S < 2 || a.Wout < 1 || a.Hout < 1 || a.Sout < a.Wout || a.frames < 1) return hipErrorInvalidValue;
-	if (source < kRemapMap || source > kRemapWarp3 || interp < kRemapNearest || interp > kRemapBilinearF32) return hipErrorInvalidValue;
+	const bool bicubic = interp == kRemapBicubic || interp == kRemapBicubicF32;
+	if (source < kRemapMap || source > kRemapWarp3 || (interp != kRemapNearest && interp != kRemapBilinear && interp != kRemapBilinearF32 && !bicubic)) return hipErrorInvalidValue;
+	if (bicubic && a.S < 4) return hipErrorInvalidValue;          // the 4-byte tap rows; no caller comes here: a plan's stride is a multiple of 8, the host calls stage at 64
 	if (source == kRemapMap ? !a.mapX || !a.mapY : !a.tables) return hipErrorInvalidValue;
 	// every offset of a frame fits an int; the ROI is empty or lies in the frame, so an inside pixel never gathers outside it
 	if (static_cast<long long>(a.S) * a.H > INT32_MAX || a.W > (1 << 24) || a.H > (1 << 24)) return hipErrorInvalidValue;
 	const bool empty = !(a.left <= a.right && a.top <= a.bottom);
 	if (!empty && !(a.left >= 0.f && a.right <= static_cast<float>(a.W - 1) && a.top >= 0.f && a.bottom <= static_cast<float>(a.H - 1))) return hipErrorInvalidValue;
 	if (a.defaultValue < 0 || a.defaultValue > 255) return hipErrorInvalidValue;
-	const bool f32 = interp == kRemapBilinearF32;
+	const bool f32 = interp == kRemapBilinearF32 || interp == kRemapBicubicF32;
 	const uintptr_t mask = f32 ? 15u : 3u, unit = f32 ? 4u : 1u;          // float32: 16-byte vectors, Sout and the frame stride count elements
 	a.wide = !((reinterpret_cast<uintptr_t>(a.out) | static_cast<uintptr_t>(a.Sout) * unit | static_cast<uintptr_t>(a.outFrameStride) * unit) & mask);
 	a.framesPerGroup = perFrame ? 1 : kRemapFramesPerGroup;

@@ -918,19 +918,37 @@ COMPVHIP_API int compvhip_orbpyr_get_timing(compvhip_orbpyr* pyramid, const char
  *     values of other map entries when Wout % 8 != 0; that is not reproduced.
  *  2. Elements >= Wout of a destination row are never written.
  *  3. The reference picks a leaf without fused operations when the caller's map is not 32-byte aligned; this library always computes D.
- *  4. float64 maps and matrices, the bicubic interpolation and the forward CompVImage::warp are not provided: a caller inverts on the host.
+ *  4. float64 maps and matrices and the forward CompVImage::warp are not provided: a caller inverts on the host.
+ *  5. The reference's bicubic leaf tests `x < left || x > right || ...` and so takes a NaN coordinate for inside; this library keeps B for every
+ *     interpolation: a NaN is outside.
+ * F. Bicubic interpolation: COMPVHIP_INTERP_BICUBIC and _BICUBIC_FLOAT32, inside (compv_image_remap.cxx:293-310, compv_image_scale_bicubic.cxx:34-101).
+ *    Every operation below is rounded on its own and nothing is fused.
+ *  1. xi = (int)x, xf = x - floorf(x), xf2 = xf * xf, xf3 = xf2 * xf; yi, yf, yf2, yf3 likewise from y.  Taps x_k = clamp(xi - 1 + k, 0, Win - 1)
+ *     and y_k = clamp(yi - 1 + k, 0, Hin - 1) for k = 0..3: they clamp to the frame, not to the ROI.
+ *  2. Row r = 0..3, with A, B, C, D = (float)I[y_r][x_0], .. [x_3] (HERMITE4_32F_C): a = ((D - A) * 0.5f) + ((B - C) * 1.5f);
+ *     b = ((A + (B * -2.5f)) + (C * 2.0f)) + (D * -0.5f); c = (C - A) * 0.5f; c_r = ((a * xf3) + (c * xf)) + ((b * xf2) + B).
+ *  3. Column, with A, B, C, D = c_0 .. c_3 (HERMITE1_32F_C, a different association of the same polynomial):
+ *     a = ((A * -0.5f) + (B * 1.5f)) + ((C * -1.5f) + (D * 0.5f)); b = (A + (B * -2.5f)) + ((C * 2.0f) + (D * -0.5f));
+ *     c = (A * -0.5f) + (C * 0.5f); v = ((a * yf3) + (c * yf)) + ((b * yf2) + B).
+ *  4. w = v < 0 ? 0 : (v > 255 ? 255 : v), by compares (COMPV_MATH_CLIP3): a zero keeps its sign.  uint8 output is (uint8)w by truncation
+ *     (compv_math_cast.cxx:215); float32 output is w (CompVMathClip::clip3).
+ *  5. The parity target is the reference with every SIMD CPU flag switched off, its plain leaves, which tests/golden/make_golden_bicubic.py holds
+ *     tests/bicubic_model.py against on every element; how far the reference's SIMD build departs from them is recorded in the fixture
+ *     (docs/kernels/remap.md) and asserted nowhere.
  * Refused with COMPVHIP_E_INVALID_PARAMETER, the destination untouched: a null pointer; a size of 0 or beyond 32767; Sout < Wout (for float32
  * output Sout counts ELEMENTS); rows other than 2 or 3; a count other than 1 or the plan's frames; an unknown interpolation; a float32
  * destination that is not 4-byte aligned; source and destination that overlap. */
 #define COMPVHIP_INTERP_NEAREST 0
 #define COMPVHIP_INTERP_BILINEAR 1
 #define COMPVHIP_INTERP_BILINEAR_FLOAT32 2          /* bilinear, float32 destination */
+#define COMPVHIP_INTERP_BICUBIC 4                   /* bicubic, uint8 destination (3 is unassigned and refused) */
+#define COMPVHIP_INTERP_BICUBIC_FLOAT32 5           /* bicubic, float32 destination */
 typedef struct compvhip_roi { float left, right, top, bottom; } compvhip_roi;
 /* A.2 on the host, no context: the tables of one matrix (rows = 2: gi and hy may be NULL and are not written).  ac, df, gi: Wout values; by, ey,
  * hy: Hout values. */
 COMPVHIP_API int compvhip_warp_tables(const float* M, int rows, size_t Wout, size_t Hout, float* ac, float* df, float* gi, float* by, float* ey, float* hy);
-/* Remap for every frame of a plan: d_in [frames][H][S] of the plan's geometry -> d_out [frames][Hout][Sout], uint8 or (COMPVHIP_INTERP_BILINEAR_FLOAT32)
- * float32.  d_mapX, d_mapY: device, [mapCount][Hout * Wout] float32 each; mapCount == 1: all frames share the map (a workgroup then reads its part of
+/* Remap for every frame of a plan: d_in [frames][H][S] of the plan's geometry -> d_out [frames][Hout][Sout], uint8 or (the two _FLOAT32
+ * interpolations) float32.  d_mapX, d_mapY: device, [mapCount][Hout * Wout] float32 each; mapCount == 1: all frames share the map (a workgroup then reads its part of
  * the map once for 8 frames); mapCount == frames: one map per frame.  roi == NULL: the whole frame.  A destination that is aligned in pointer, stride
  * and frame size (4 bytes for uint8, 16 for float32) is written with vector stores.  Asynchronous on `stream`, never synchronises the host.
  * Beyond 65 535 frames (shared map: beyond 65 535 groups of 8): SLICED.  d_in: ANY BYTE; d_mapX and d_mapY: 4-byte aligned; d_out: ANY BYTE for uint8, 4-byte
