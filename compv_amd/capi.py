@@ -41,6 +41,8 @@ HOG_NORM_NONE, HOG_NORM_L1, HOG_NORM_L1SQRT, HOG_NORM_L2, HOG_NORM_L2HYS = 1, 2,
 HOG_GRADIENT_SIGNED, HOG_GRADIENT_UNSIGNED = 1, 2                                              # COMPVHIP_HOG_GRADIENT_* (0: the default, signed)
 HOG_INTERP_NEAREST, HOG_INTERP_BILINEAR, HOG_INTERP_BILINEAR_LUT = 1, 2, 3                     # COMPVHIP_HOG_INTERP_* (0: the default, BILINEAR; _LUT is refused)
 HOMOGRAPHY_RESULT_DTYPE = np.dtype([("H", "<f8", (9,)), ("variance", "<f8"), ("inliers", "<i4"), ("bestTry", "<i4"), ("status", "<i4"), ("rotations", "<i4")])   # compvhip_homography_result
+CURVEFIT_LINE, CURVEFIT_PARABOLA, CURVEFIT_PARABOLA_SIDEWAYS = 0, 1, 2                         # COMPVHIP_CURVEFIT_*
+CURVEFIT_RESULT_DTYPE = np.dtype([("A", "<f8"), ("B", "<f8"), ("C", "<f8"), ("inliers", "<i4"), ("bestTry", "<i4"), ("status", "<i4"), ("k", "<i4")])   # compvhip_curvefit_result
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -69,6 +71,9 @@ EXPORTS = [
     "compvhip_warp_tables", "compvhip_plan_remap", "compvhip_plan_warp_inverse", "compvhip_remap_u8", "compvhip_warp_inverse_u8",
     "compvhip_homography_create", "compvhip_homography_destroy", "compvhip_homography_points", "compvhip_homography_find", "compvhip_homography_project",
     "compvhip_homography_quads", "compvhip_homography_find_f64", "compvhip_homography_scores", "compvhip_homography_set_timing", "compvhip_homography_get_timing",
+    "compvhip_curvefit_create", "compvhip_curvefit_destroy", "compvhip_curvefit_points_from_labels", "compvhip_curvefit_find", "compvhip_curvefit_distances",
+    "compvhip_curvefit_scores", "compvhip_curvefit_gathered", "compvhip_curvefit_set_timing", "compvhip_curvefit_get_timing", "compvhip_curvefit_samples",
+    "compvhip_curvefit_find_f64",
     "compvhip_hog_geometry", "compvhip_plan_hog", "compvhip_hog_u8",
     "compvhip_integral_dims", "compvhip_plan_integral", "compvhip_integral_u8", "compvhip_plan_histogram", "compvhip_histogram_u8", "compvhip_plan_equalize",
     "compvhip_equalize_u8", "compvhip_plan_projections", "compvhip_projections_u8",
@@ -146,6 +151,27 @@ class HomographyOpts(C.Structure):
 
     def __init__(self, tries=2000, seed=0, threshold=30.0):
         super().__init__(int(tries), int(seed) & 0xffffffff, float(threshold))
+
+
+class CurvefitDesc(C.Structure):
+    """compvhip_curvefit_desc (include/compv_hip.h): the handle's capacities and the stream all its calls run on"""
+    _fields_ = [("size", C.c_uint32), ("sets", C.c_uint32), ("pointCap", C.c_uint32), ("maxTries", C.c_uint32), ("stream", C.c_void_p)]
+
+    def __init__(self, sets=1, point_cap=3, max_tries=2000, stream=0):
+        super().__init__(C.sizeof(CurvefitDesc), int(sets), int(point_cap), int(max_tries), stream or None)
+
+
+class CurvefitOpts(C.Structure):
+    """compvhip_curvefit_opts (include/compv_hip.h)"""
+    _fields_ = [("size", C.c_uint32), ("model", C.c_int32), ("tries", C.c_int32), ("seed", C.c_uint32), ("threshold", C.c_double)]
+
+    def __init__(self, model=CURVEFIT_LINE, tries=2000, seed=0, threshold=1.0):
+        super().__init__(C.sizeof(CurvefitOpts), int(model), int(tries), int(seed) & 0xffffffff, float(threshold))
+
+
+def curvefit_model_points(model):
+    """m of a COMPVHIP_CURVEFIT_* model: 2 for a line, 3 for a parabola"""
+    return 2 if model == CURVEFIT_LINE else 3
 
 
 class HogOpts(C.Structure):
@@ -342,6 +368,18 @@ def load():
     L.compvhip_homography_scores.argtypes = [vp, sz, vp, vp, vp, vp]
     L.compvhip_homography_set_timing.argtypes = [vp, i32]
     L.compvhip_homography_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
+    L.compvhip_curvefit_create.argtypes = [vp, C.POINTER(CurvefitDesc), C.POINTER(vp)]
+    L.compvhip_curvefit_destroy.argtypes = [vp]
+    L.compvhip_curvefit_destroy.restype = None
+    L.compvhip_curvefit_points_from_labels.argtypes = [vp, vp, sz, sz, sz, vp, sz, vp, sz]
+    L.compvhip_curvefit_find.argtypes = [vp, vp, vp, C.POINTER(CurvefitOpts), vp, vp, vp]
+    L.compvhip_curvefit_distances.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.compvhip_curvefit_scores.argtypes = [vp, sz, vp, vp]
+    L.compvhip_curvefit_gathered.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.compvhip_curvefit_set_timing.argtypes = [vp, i32]
+    L.compvhip_curvefit_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
+    L.compvhip_curvefit_samples.argtypes = [i32, C.c_uint32, sz, sz, sz, vp]
+    L.compvhip_curvefit_find_f64.argtypes = [vp, vp, sz, C.POINTER(CurvefitOpts), vp, vp, vp]
     L.compvhip_hog_geometry.argtypes = [sz, sz, C.POINTER(HogOpts), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_hog.argtypes = [vp, vp, C.POINTER(HogOpts), vp, vp, sz, vp]
     L.compvhip_hog_u8.argtypes = [vp, vp, sz, sz, sz, C.POINTER(HogOpts), vp, sz, C.POINTER(sz)]
@@ -392,6 +430,16 @@ def homography_quads(seed, pair, k, tries):
     rc = L.compvhip_homography_quads(int(seed) & 0xffffffff, pair, k, tries, _ptr(out))
     if rc != OK:
         raise CompvHipError(rc, "compvhip_homography_quads")
+    return out
+
+
+def curvefit_samples(model, seed, set_index, k, tries):
+    """compvhip_curvefit_samples (host arithmetic, no GPU): int32 (tries, m), the point indices of every try of set `set_index` among k > m points"""
+    L = load()
+    out = np.zeros((tries, curvefit_model_points(model)), np.int32)
+    rc = L.compvhip_curvefit_samples(int(model), int(seed) & 0xffffffff, set_index, k, tries, _ptr(out))
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_curvefit_samples")
     return out
 
 
@@ -766,6 +814,27 @@ class Context:
                                                         _ptr(res), _ptr(mask) if want_mask else None))
         return res[0], (mask[:n] if want_mask else None)
 
+    def _curvefit(self, model, points, threshold, tries, seed, samples, want_mask):
+        points = np.ascontiguousarray(points, np.float64).reshape(-1, 2)
+        n = len(points)
+        o = CurvefitOpts(model, tries, seed, threshold)
+        q = None if samples is None else np.ascontiguousarray(samples, np.int32).reshape(tries, curvefit_model_points(model))
+        res = np.zeros(1, CURVEFIT_RESULT_DTYPE)
+        mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
+        self._chk(self.lib.compvhip_curvefit_find_f64(self.h, _ptr(points) if n else None, n, C.byref(o), _ptr(q) if q is not None else None, _ptr(res),
+                                                      _ptr(mask) if want_mask else None))
+        return res[0], (mask[:n] if want_mask else None)
+
+    def fit_line(self, points, threshold=1.0, tries=2000, seed=0, samples=None, want_mask=True):
+        """compvhip_curvefit_find_f64 with the LINE model (CompVMathStatsFit::line, every try run): points (n, 2) float64 ->
+        (CURVEFIT_RESULT_DTYPE scalar with Ax + By + C = 0, uint8 inlier mask of n or None).  samples: None or int32 (tries, 2), replacing the generator."""
+        return self._curvefit(CURVEFIT_LINE, points, threshold, tries, seed, samples, want_mask)
+
+    def fit_parabola(self, points, threshold=1.0, tries=2000, seed=0, sideways=False, samples=None, want_mask=True):
+        """compvhip_curvefit_find_f64 with a PARABOLA model (CompVMathStatsFit::parabola): y = Ax^2 + Bx + C, or x = Ay^2 + By + C with sideways.
+        samples: None or int32 (tries, 3)."""
+        return self._curvefit(CURVEFIT_PARABOLA_SIDEWAYS if sideways else CURVEFIT_PARABOLA, points, threshold, tries, seed, samples, want_mask)
+
     def houghkht(self, edges, rho=1.0, theta_deg=1.0, threshold=1, max_lines=0, min_dev=2.0, min_size=10, min_height=0.002, cap=1 << 14, order="reference"):
         """Returns (lines, GS); lines['row'] / ['col'] hold the rho / theta indices.  order: "reference" (compvhip_houghkht_u8: the reference's tie
         order) or "canonical" (compvhip_houghkht_ex_u8: count descending, ties by emission key, peaks found and sorted on the GPU)."""
@@ -1111,6 +1180,65 @@ class Homography:
         names = (C.c_char_p * cap)()
         ms = (C.c_float * cap)()
         n = self.lib.compvhip_homography_get_timing(self.h, names, ms, cap)
+        return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
+
+
+class Curvefit:
+    """Batched device-resident RANSAC line / parabola fits (compvhip_curvefit).  Every call runs on the stream given here.  Pointers are raw device
+    addresses; 0 stands for NULL."""
+
+    def __init__(self, ctx, sets, point_cap, max_tries=2000, stream=0):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        d = CurvefitDesc(sets, point_cap, max_tries, stream)
+        ctx._chk(self.lib.compvhip_curvefit_create(ctx.h, C.byref(d), C.byref(h)))
+        self.h = h
+        self.sets, self.point_cap, self.max_tries, self.stream = sets, point_cap, max_tries, stream
+
+    def close(self):
+        if self.h:
+            self.lib.compvhip_curvefit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def points_from_labels(self, d_labels, W, H, label_stride, d_comps, comp_cap, d_comp_counts, frames):
+        """compvhip_curvefit_points_from_labels: every component of compvhip_plan_components' label maps becomes a point set of the handle"""
+        self.ctx._chk(self.lib.compvhip_curvefit_points_from_labels(self.h, d_labels or None, W, H, label_stride, d_comps or None, comp_cap, d_comp_counts or None, frames))
+
+    def find(self, d_points, d_counts, d_results, d_mask=0, model=CURVEFIT_LINE, tries=None, threshold=1.0, seed=0, d_samples=0):
+        """compvhip_curvefit_find: d_points = 0 takes the gathered points; d_results = [sets] CURVEFIT_RESULT_DTYPE records"""
+        o = CurvefitOpts(model, self.max_tries if tries is None else tries, seed, threshold)
+        self.ctx._chk(self.lib.compvhip_curvefit_find(self.h, d_points or None, d_counts or None, C.byref(o), d_samples or None, d_results or None, d_mask or None))
+
+    def distances(self, d_points, d_counts, model, d_params, d_out):
+        """compvhip_curvefit_distances: the residual of every point under its set's {A, B, C}"""
+        self.ctx._chk(self.lib.compvhip_curvefit_distances(self.h, d_points or None, d_counts or None, int(model), d_params or None, d_out or None))
+
+    def scores(self, tries):
+        """compvhip_curvefit_scores (test hook): (sets, tries) inlier counts of the last find(), (sets,) gathered point counts; waits for the stream"""
+        counts, gathered = np.zeros((self.sets, tries), np.int32), np.zeros(self.sets, np.int32)
+        self.ctx._chk(self.lib.compvhip_curvefit_scores(self.h, tries, _ptr(counts), _ptr(gathered)))
+        return counts, gathered
+
+    def gathered(self):
+        """compvhip_curvefit_gathered: device addresses of the gathered points [sets][pointCap][2] float64 and of their counts [sets] int32"""
+        p, c = C.c_void_p(), C.c_void_p()
+        self.ctx._chk(self.lib.compvhip_curvefit_gathered(self.h, C.byref(p), C.byref(c)))
+        return p.value, c.value
+
+    def set_timing(self, mode=1):
+        self.ctx._chk(self.lib.compvhip_curvefit_set_timing(self.h, int(mode)))
+
+    def get_timing(self, cap=16):
+        names = (C.c_char_p * cap)()
+        ms = (C.c_float * cap)()
+        n = self.lib.compvhip_curvefit_get_timing(self.h, names, ms, cap)
         return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
 
 

@@ -256,6 +256,16 @@ struct compvhip_homography : TimingState {
 	DevBuf<int32_t> tryI32;             // [3][pairs][maxTries]: state, rotations, inlier count
 	bool gathered = false;              // compvhip_homography_points has run
 };
+// RANSAC line and parabola fits (curvefit_kernels.hip): every buffer is allocated by compvhip_curvefit_create; every call runs on `stream`
+struct compvhip_curvefit : TimingState {
+	compvhip_ctx* ctx = nullptr;
+	hipStream_t stream = nullptr;       // (the caller's: the descriptor's)
+	int sets = 0, pointCap = 0, maxTries = 0;
+	DevBuf<double2> points;             // [2][sets][pointCap]: gathered, selected
+	DevBuf<int32_t> counts;             // [sets] points gathered
+	DevBuf<int32_t> scoreCount;         // [sets][maxTries] inlier count of every try
+	bool gathered = false;              // compvhip_curvefit_points_from_labels has run
+};
 // ORB pyramid (scale_kernels.hip, fast_kernels.hip, orb_kernels.hip): the levels' geometry and the scratch they share.  `active` levels (a prefix: the sizes
 // only shrink) are at least 37 x 37; the others are empty.
 struct compvhip_orbpyr : TimingState {
@@ -321,6 +331,7 @@ struct Stamp {
 	Stamp(compvhip_matcher* matcher, hipStream_t stream, const char* name) : Stamp(matcher, stream, name, matcher->timing != 0) {}
 	Stamp(compvhip_orbpyr* pyramid, hipStream_t stream, const char* name) : Stamp(pyramid, stream, name, pyramid->timing != 0) {}
 	Stamp(compvhip_homography* homography, hipStream_t stream, const char* name) : Stamp(homography, stream, name, homography->timing != 0) {}
+	Stamp(compvhip_curvefit* fit, hipStream_t stream, const char* name) : Stamp(fit, stream, name, fit->timing != 0) {}
 	Stamp(TimingState* state, hipStream_t stream, const char* name, bool wanted) : p(state), s(stream), idx(0), on(wanted)
 	{
 		if (!on) return;

@@ -2,7 +2,7 @@
 // kernels of homography_kernels.hip and for the host (compvhip_homography_quads).  Every operation is one IEEE binary64 operation in the order the
 // definition gives; divisions and square roots are the correctly rounded ones on either side, nothing is transcendental.  The 9 x 9 matrices are
 // addressed as M[e * ST]: ST = 64 interleaves the matrices of a wave's lanes in LDS (lane-consecutive words, no bank conflict whatever the pivot),
-// ST = 1 is a plain array.
+// ST = 1 is a plain array.  The sample generator (drawDistinct) and the half-angle formulas (halfAngle) also serve the curve fits (curvefit_math.hpp).
 #pragma once
 #include <float.h>
 #include <stdint.h>
@@ -50,30 +50,39 @@ HG_HD uint32_t lowbias32(uint32_t x)
 	x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
 	return x;
 }
-// the four indices of pair p, try t among k >= 4 points
-HG_HD void quad(uint32_t seed, uint32_t p, uint32_t t, uint32_t k, int32_t q[4])
+// the M distinct indices of set (pair) p, try t among k >= M points: the generator of the homography's quads (M = 4) and of the curve fits' samples
+// (curvefit_math.hpp, M = 2 or 3).  The slots are addressed by compile-time indices only, so q stays in registers.
+template <int M>
+HG_HD void drawDistinct(uint32_t seed, uint32_t p, uint32_t t, uint32_t k, int32_t q[M])
 {
 	const uint32_t base = lowbias32(lowbias32(seed ^ p) + t);
 	int filled = 0;
-	q[0] = q[1] = q[2] = q[3] = -1;
-	for (int c = 0; c < kQuadDraws && filled < 4; ++c) {
+HG_UNROLL
+	for (int j = 0; j < M; ++j) q[j] = -1;
+	for (int c = 0; c < kQuadDraws && filled < M; ++c) {
 		const int32_t idx = (int32_t)(((uint64_t)lowbias32(base + (uint32_t)c) * k) >> 32);
 		bool seen = false;
-		for (int j = 0; j < 4; ++j) seen = seen || (j < filled && q[j] == idx);
+HG_UNROLL
+		for (int j = 0; j < M; ++j) seen = seen || (j < filled && q[j] == idx);
 		if (!seen) {
-			if (filled == 0) q[0] = idx; else if (filled == 1) q[1] = idx; else if (filled == 2) q[2] = idx; else q[3] = idx;
+HG_UNROLL
+			for (int j = 0; j < M; ++j) if (j == filled) q[j] = idx;
 			++filled;
 		}
 	}
-	for (int32_t idx = 0; filled < 4; ++idx) {          // 64 draws did not fill the slots: the smallest unused indices
+	for (int32_t idx = 0; filled < M; ++idx) {          // 64 draws did not fill the slots: the smallest unused indices
 		bool seen = false;
-		for (int j = 0; j < 4; ++j) seen = seen || (j < filled && q[j] == idx);
+HG_UNROLL
+		for (int j = 0; j < M; ++j) seen = seen || (j < filled && q[j] == idx);
 		if (!seen) {
-			if (filled == 0) q[0] = idx; else if (filled == 1) q[1] = idx; else if (filled == 2) q[2] = idx; else q[3] = idx;
+HG_UNROLL
+			for (int j = 0; j < M; ++j) if (j == filled) q[j] = idx;
 			++filled;
 		}
 	}
 }
+// the four indices of pair p, try t among k >= 4 points
+HG_HD void quad(uint32_t seed, uint32_t p, uint32_t t, uint32_t k, int32_t q[4]) { drawDistinct<4>(seed, p, t, k, q); }
 
 // ---- B. collinearity of the quad's source points ---------------------------------------------------------------------------------------
 HG_HD bool collinear4(const double x[4], const double y[4])
@@ -140,6 +149,21 @@ HG_UNROLL
 }
 
 // ---- D. Jacobi ---------------------------------------------------------------------------------------------------------------------------
+// (cos, sin) of atan2(y, x) / 2 by the half-angle formulas, (x, y) != (0, 0); also the angle of the curve fits' total least squares line
+HG_HD void halfAngle(double y, double x, double* cs, double* sn)
+{
+	const double rho = dsqrt(x * x + y * y);
+	const double c2 = ddiv(x, rho), s2 = ddiv(y, rho);
+	if (c2 >= 0.0) {
+		*cs = dsqrt((1.0 + c2) * 0.5);
+		*sn = ddiv(s2, 2.0 * *cs);
+	}
+	else {
+		const double mag = dsqrt((1.0 - c2) * 0.5);
+		*sn = (s2 == 0.0 || s2 > 0.0) ? mag : -mag;          // copysign(mag, s2), a zero s2 counting as positive
+		*cs = ddiv(s2, 2.0 * *sn);
+	}
+}
 template <int ST>
 HG_HD void rotateRows(double* A, int r, int c, double cs, double sn)
 {
@@ -177,18 +201,7 @@ HG_HD int jacobi(double* D, double* Q)
 		double cs, sn;
 		if (drr == dcc) { cs = kCosPi4; sn = kCosPi4; }
 		else {
-			const double y = 2.0 * D[(pr * 9 + pc) * ST], x = dcc - drr;
-			const double rho = dsqrt(x * x + y * y);
-			const double c2 = ddiv(x, rho), s2 = ddiv(y, rho);
-			if (c2 >= 0.0) {
-				cs = dsqrt((1.0 + c2) * 0.5);
-				sn = ddiv(s2, 2.0 * cs);
-			}
-			else {
-				const double mag = dsqrt((1.0 - c2) * 0.5);
-				sn = (s2 == 0.0 || s2 > 0.0) ? mag : -mag;          // copysign(mag, s2), a zero s2 counting as positive
-				cs = ddiv(s2, 2.0 * sn);
-			}
+			halfAngle(2.0 * D[(pr * 9 + pc) * ST], dcc - drr, &cs, &sn);
 		}
 		rotateRows<ST>(Q, pr, pc, cs, sn);
 		rotateRows<ST>(D, pr, pc, cs, sn);

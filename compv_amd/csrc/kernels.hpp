@@ -381,6 +381,36 @@ struct HomographyProjectArgs {
 };
 hipError_t launch_homography_project(const HomographyProjectArgs& a, int pairs, hipStream_t stream);
 
+// ---- RANSAC line and parabola fits (curvefit_kernels.hip) -------------------------------------------------------------------------------------
+constexpr int kCurvefitBlock = 256;          // tries of one workgroup of the score kernel and the points it stages per round; pixels of a gather round
+struct CurvefitGatherArgs {
+	const int32_t* labels; int W, H, labelStride;     // [frames][H][labelStride]
+	const compvhip_component* comps; int compCap;     // [frames][compCap]
+	const int32_t* compCounts;                        // [frames] (may exceed compCap, may be negative)
+	double2* points; int pointCap;                    // [frames * compCap][pointCap]
+	int32_t* counts;                                  // [frames * compCap] points taken
+};
+hipError_t launch_curvefit_gather(const CurvefitGatherArgs& a, int sets, hipStream_t stream);
+struct CurvefitFindArgs {
+	const double2* points;                            // [sets][pointCap]
+	const int32_t* counts; int pointCap;              // [sets]; nullptr: pointCap
+	int model, tries, maxTries;
+	uint32_t seed; double threshold;
+	const int32_t* samples;                           // nullptr or [sets][tries][m]
+	int32_t* scoreCount;                              // scratch [sets][maxTries]: the inlier count of every try
+	double2* sel;                                     // scratch [sets][pointCap]: the inliers of the best try in index order
+	compvhip_curvefit_result* results;                // [sets]
+	uint8_t* mask;                                    // nullptr or [sets][pointCap]
+};
+hipError_t launch_curvefit_score(const CurvefitFindArgs& a, int sets, hipStream_t stream);
+hipError_t launch_curvefit_refit(const CurvefitFindArgs& a, int sets, hipStream_t stream);
+struct CurvefitDistanceArgs {
+	const double2* points; const int32_t* counts; int pointCap, model;
+	const double* params;                             // [sets][3]
+	double* out;                                      // [sets][pointCap]
+};
+hipError_t launch_curvefit_distances(const CurvefitDistanceArgs& a, int sets, hipStream_t stream);
+
 // ---- ORB: keypoint orientation and rotated BRIEF (orb_kernels.hip) -------------------------------------------------------------------------
 // the byte-read variant of orb_brief_kernel that ships: at 32 x 4K with 2000 keypoints a frame the two measured alike (0.0678 ms with the LDS patch, 0.0680 ms
 // with bytes from global memory; docs/kernels/orb.md), so the first one built stays

@@ -1064,6 +1064,119 @@ COMPVHIP_API int compvhip_homography_scores(compvhip_homography* homography, siz
 COMPVHIP_API int compvhip_homography_set_timing(compvhip_homography* homography, int enabled);
 COMPVHIP_API int compvhip_homography_get_timing(compvhip_homography* homography, const char** names, float* ms, int cap);
 
+/* ---- RANSAC curve fitting: lines and parabolas (docs/kernels/curvefit.md) -------------------------------------------------------------------
+ * CompVMathStatsFit::line and ::parabola (base/math/compv_math_stats_fit.cxx) on CompVMathStatsRansac and CompVMathDistance::line / ::parabola, for
+ * `sets` point sets at once, on the device: the step behind compvhip_plan_components that turns a component's pixels into a curve without downloading
+ * them.  The sibling of the RANSAC homography above, with the same two departures from the reference: the random samples are a counter hash, so a
+ * result is a function of the inputs, and the adaptive early exit (compv_math_stats_ransac.cxx:240-254, a CPU time saver) is NOT reproduced -- all
+ * `tries` tries run.  All arithmetic is IEEE binary64, one rounding per operation (no fused multiply-add), divisions and square roots correctly
+ * rounded, no transcendental function: compv_amd/csrc/curvefit_math.hpp is the arithmetic, tests/curvefit_model.py the same definition in numpy, and
+ * the device equals both bit for bit.
+ * A set has k points {x, y} float64, either given as [sets][pointCap] with d_counts (k = min(max(count, 0), pointCap); d_counts == NULL: pointCap) or
+ * gathered by compvhip_curvefit_points_from_labels (item G).  Models: LINE, m = 2, Ax + By + C = 0; PARABOLA, m = 3, y = Ax^2 + Bx + C;
+ * PARABOLA_SIDEWAYS, the same with the roles of x and y exchanged everywhere (compv_math_stats_fit.cxx:246-248, compv_math_distance.cxx:360-362).
+ * A. Samples.  The generator of homography item A with m slots instead of four (one function, hg::drawDistinct, serves both): u(c) =
+ *    lowbias32(lowbias32(lowbias32(seed ^ set) + t) + c), idx = ((uint64)u * k) >> 32, duplicates discarded, the smallest unused indices from c = 64.
+ *    d_samples ([sets][tries][m] int32) replaces the generator; a sample with an index outside [0, k) scores 0.  compvhip_curvefit_samples is the
+ *    same function on the host.
+ * B. Model of a sample (:156-168, :252-266), every expression evaluated left to right as the reference writes it.  Line: rejected when x0 == x1 &&
+ *    y0 == y1; A = y1 - y0, B = x0 - x1, C = (x1 * y0) - (x0 * y1).  Parabola: rejected when two of the three x are equal;
+ *    scale = 1 / ((x1 - x2) * (x1 - x3) * (x2 - x3)); A = (x3 * (y2 - y1) + x2 * (y1 - y3) + x1 * (y3 - y2)) * scale;
+ *    B = (x3 * x3 * (y1 - y2) + x2 * x2 * (y3 - y1) + x1 * x1 * (y2 - y3)) * scale;
+ *    C = (x2 * x3 * (x2 - x3) * y1 + x3 * x1 * (x3 - x1) * y2 + x1 * x2 * (x1 - x2) * y3) * scale, in C's precedence.  A rejected try scores 0.
+ * C. Residual (compv_math_distance.cxx:263-268, :242, :343).  Line: s = 1 / sqrt(A * A + B * B); d = |((A * s) * x + (C * s)) + (B * s) * y| (A = B = 0,
+ *    which the reference refuses, gives NaN).  Parabola: d = |(((A * (x * x)) + C) + (B * x)) - y|.  Inlier iff d < threshold, strict
+ *    (ransac.cxx:233); a NaN is never an inlier.
+ * D. The score of a try is its inlier count.  The best try has the largest count, then the smallest t (ransac.cxx:235); a best exists only when
+ *    its count is >= m.
+ * E. Refit on the inliers of the best try, n of them, in index order (ransac.cxx:117-142).  n == m: the formula of B on them.  Sums over n > m points
+ *    are sum64 as in homography item C; mean = sum * (1 / n).  Line, total least squares (:176-209): a = x - mean_x, b = y - mean_y;
+ *    num = (sum a * b) * -2; den = sum (b * b - a * a); num == 0 && den == 0: (cos, sin) = (1, 0); else phi = atan2(num, den) / 2 by the half-angle
+ *    formulas of homography item D with y = num, x = den (within 2.3e-16 of libm over 20 000 random (num, den)); A = cos, B = sin,
+ *    C = -((mean_x * cos) + (mean_y * sin)).  Parabola: the reference runs Levenberg-Marquardt (lmmin) on this LINEAR problem; the definition is the
+ *    least-squares solution itself: u = x - mean; S1..S4 = sum u, u * u, (u * u) * u, (u * u) * (u * u); T0..T2 = sum y, u * y, (u * u) * y; the
+ *    symmetric system {S4, S3, S2; S3, S2, S1; S2, S1, n} (a, b, c) = (T2, T1, T0) by cofactors, one division by the determinant per unknown
+ *    (parabolaFromSums of curvefit_math.hpp is the expression order); A = a, B = b - (2 * a) * mean, C = (c - b * mean) + a * (mean * mean).  A
+ *    determinant that is 0 or not finite, or a rejected m-point formula: the refit fails.
+ * F. Record.  status 0: a best exists and the refit succeeded: the refit's A, B, C, the best try's inliers and bestTry.  status 3: a best exists,
+ *    the refit failed: the best try's own model (item B, unscaled).  status 1: k >= m but no best: zeros, as the reference returns (:79-85),
+ *    bestTry -1.  status 2: k < m: zeros, bestTry -1.  k == m: the sample is the points 0 .. m - 1, no generator, no refit (:53-65, :101-114):
+ *    status 0 with inliers = m and bestTry 0, or status 1 when rejected.  Mask, [sets][pointCap] bytes: 1 for an inlier of the best try, else 0, for
+ *    i < k (k == m: all 1, or all 0 when rejected); bytes at and behind k are never written.
+ * G. Gather from a label map: the inputs are what compvhip_plan_components wrote.  Component id of frame f becomes set f * compCap + id - 1 for
+ *    id <= min(max(count, 0), compCap); the other sets get k = 0.  The pixels carrying the id inside the record's box (clipped to the frame) get ranks
+ *    0, 1, ... in raster order; step = ceil(pixels / pointCap) with the record's pixel count; a pixel is taken iff rank % step == 0 and becomes point
+ *    rank / step = ((double)x, (double)y); k = ceil(ranked pixels / step), at most pointCap.
+ * Streams.  A handle takes its stream at creation (the descriptor), not as a `void* stream` parameter of every call: its calls share the scratch and
+ *    must be ordered on one stream anyway (as the homography handle demands), and the table of per-call stream classes above
+ *    (tests/stream_cases.py) lists the exports that take such a parameter.  Every device call of the family is ASYNC in that table's sense on the
+ *    handle's stream; compvhip_curvefit_scores and compvhip_curvefit_find_f64 WAIT.
+ * Alignment.  Points and samples: 16 bytes.  Results, params and distances: 8 bytes.  Counts, labels and component records: 4 bytes.  Mask: any byte.
+ *    A misaligned pointer is refused with COMPVHIP_E_INVALID_PARAMETER and nothing is written. */
+enum {
+	COMPVHIP_CURVEFIT_LINE = 0,
+	COMPVHIP_CURVEFIT_PARABOLA = 1,            /* COMPV_MATH_PARABOLA_TYPE_REGULAR */
+	COMPVHIP_CURVEFIT_PARABOLA_SIDEWAYS = 2    /* COMPV_MATH_PARABOLA_TYPE_SIDEWAYS */
+};
+typedef struct compvhip_curvefit_desc {
+	uint32_t size;              /* sizeof(compvhip_curvefit_desc) */
+	uint32_t sets;              /* 1 .. 65 535 */
+	uint32_t pointCap;          /* >= 3 */
+	uint32_t maxTries;          /* >= 1 */
+	void* stream;               /* a hipStream_t; NULL = the default stream */
+} compvhip_curvefit_desc;
+typedef struct compvhip_curvefit_opts {
+	uint32_t size;              /* sizeof(compvhip_curvefit_opts) */
+	int32_t model;              /* COMPVHIP_CURVEFIT_* */
+	int32_t tries;              /* 1 .. maxTries */
+	uint32_t seed;
+	double threshold;           /* > 0 */
+} compvhip_curvefit_opts;
+typedef struct compvhip_curvefit_result {
+	double A, B, C;
+	int32_t inliers, bestTry, status, k;
+} compvhip_curvefit_result;
+typedef struct compvhip_curvefit compvhip_curvefit;   /* scratch for `sets` sets of at most pointCap points and maxTries tries */
+
+/* All scratch is allocated here -- per set 2 * pointCap {x, y} float64 (gathered and selected points), a count and maxTries int32 -- and released by
+ * compvhip_curvefit_destroy: no later call allocates (the host form excepted).  Destroy it BEFORE its context.  Not re-entrant.  A null pointer, a wrong
+ * size field, sets outside 1 .. 65 535, pointCap < 3 or maxTries < 1 (either beyond 2^22): COMPVHIP_E_INVALID_PARAMETER. */
+COMPVHIP_API int compvhip_curvefit_create(compvhip_ctx* ctx, const compvhip_curvefit_desc* desc, compvhip_curvefit** fit);
+COMPVHIP_API void compvhip_curvefit_destroy(compvhip_curvefit* fit);
+/* Item G.  d_labels: int32 [frames][H][labelStride], labelStride >= W; d_comps: [frames][compCap]; d_compCounts: [frames]; all 4-byte aligned.
+ * frames * compCap must equal the handle's sets; 1 <= W, H <= 32767.  Asynchronous on the handle's stream. */
+COMPVHIP_API int compvhip_curvefit_points_from_labels(compvhip_curvefit* fit, const int32_t* d_labels, size_t W, size_t H, size_t labelStride,
+                                                      const compvhip_component* d_comps, size_t compCap, const int32_t* d_compCounts, size_t frames);
+/* d_points: [sets][pointCap] {x, y} float64, 16-byte aligned, with d_counts ([sets] int32, 4-byte aligned, or NULL); d_points == NULL: the gathered
+ * points (d_counts is then ignored; COMPVHIP_E_INVALID_STATE when nothing was gathered).  d_samples: NULL or [sets][opts->tries][m] int32, 16-byte
+ * aligned.  d_results: [sets] records, 8-byte aligned.  d_mask: NULL or [sets][pointCap] bytes, ANY BYTE.  A null handle, opts or d_results, a wrong
+ * size field, an unknown model, tries < 1 or > maxTries, a threshold that is not > 0, a misaligned pointer: COMPVHIP_E_INVALID_PARAMETER, nothing
+ * written.  Asynchronous on the handle's stream; deterministic run to run. */
+COMPVHIP_API int compvhip_curvefit_find(compvhip_curvefit* fit, const double* d_points, const int32_t* d_counts, const compvhip_curvefit_opts* opts,
+                                        const int32_t* d_samples, compvhip_curvefit_result* d_results, uint8_t* d_mask);
+/* Item C alone -- CompVMathDistance::line / ::parabola: d_out[set][i] = the residual of point i under d_params[set] = {A, B, C}, for i < k; elements
+ * at and behind k are not written.  d_points as in find (NULL: the gathered points); d_params [sets][3] and d_out [sets][pointCap] float64, 8-byte
+ * aligned.  Asynchronous on the handle's stream. */
+COMPVHIP_API int compvhip_curvefit_distances(compvhip_curvefit* fit, const double* d_points, const int32_t* d_counts, int model, const double* d_params,
+                                             double* d_out);
+/* Test hook: the inlier count of every try the last compvhip_curvefit_find left in the scratch, copied to the HOST array counts[sets][tries], and the
+ * gathered sets' point counts to the HOST array gathered[sets] (either may be NULL).  Entries of a set with k <= m are not defined.  Waits for the
+ * handle's stream. */
+COMPVHIP_API int compvhip_curvefit_scores(compvhip_curvefit* fit, size_t tries, int32_t* counts, int32_t* gathered);
+/* The gathered points as the device sees them: *d_points receives the device address of [sets][pointCap] {x, y} float64, *d_counts that of [sets]
+ * int32 (HOST pointers that receive device addresses; either may be NULL). */
+COMPVHIP_API int compvhip_curvefit_gathered(compvhip_curvefit* fit, const double** d_points, const int32_t** d_counts);
+/* Per-kernel timing of the handle's last call, as compvhip_matcher_set_timing / _get_timing: entries curvefit_gather_kernel; curvefit_score_kernel,
+ * curvefit_refit_kernel; curvefit_distance_kernel. */
+COMPVHIP_API int compvhip_curvefit_set_timing(compvhip_curvefit* fit, int enabled);
+COMPVHIP_API int compvhip_curvefit_get_timing(compvhip_curvefit* fit, const char** names, float* ms, int cap);
+/* Item A on the host (standard library only, no GPU): samples[tries][m] of set `set` among k > m points. */
+COMPVHIP_API int compvhip_curvefit_samples(int model, uint32_t seed, size_t set, size_t k, size_t tries, int32_t* samples);
+/* The whole call for one HOST set of n points ({x, y} float64 each; n may be below m: status 2).  samples: NULL or [opts->tries][m]; mask: NULL or n
+ * bytes.  Synchronous on the context's stream; allocates and frees its own scratch. */
+COMPVHIP_API int compvhip_curvefit_find_f64(compvhip_ctx* ctx, const double* points, size_t n, const compvhip_curvefit_opts* opts, const int32_t* samples,
+                                            compvhip_curvefit_result* result, uint8_t* mask);
+
 /* ---- HOG descriptors (docs/kernels/hog.md) --------------------------------------------------------------------------------------------------
  * CompVHogStd::process (core/features/hog/compv_core_feature_hog_std.cxx; COMPV_HOGS_ID) on gray frames: per-cell orientation histograms, then the
  * blocks' normalised vectors.  Every output is defined bit for bit.  All arithmetic is float32 with one rounding per operation; the divide and the
