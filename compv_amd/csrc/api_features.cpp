@@ -1,5 +1,6 @@
 // api_features.cpp -- plan-level calls of the features built on the Canny / SHT plan: line segments, line fits, connected components,
-// thresholding and morphology, FAST corners, ORB keypoints and descriptors, bilinear scale and the ORB pyramid, remap and inverse warp, brute-force matching, HOG, image statistics.
+// thresholding and morphology, FAST corners, ORB keypoints and descriptors, bilinear scale and the ORB pyramid, remap and inverse warp, brute-force matching, HOG, image
+// statistics.  (The RANSAC homography and curve fits: api_ransac.cpp.)
 #include "api_internal.hpp"
 
 // what the segment and the fit kernels read alike: the edge pixels, the vote's tables, the lines
@@ -620,26 +621,9 @@ int compvhip_orbpyr_create(compvhip_ctx* ctx, size_t W, size_t H, size_t S, size
 	return COMPVHIP_OK;
 }
 
-void compvhip_orbpyr_destroy(compvhip_orbpyr* y)
-{
-	if (!y) return;
-	(void)hipSetDevice(y->ctx->device);
-	timingTeardown(y);
-	delete y;
-}
-
-int compvhip_orbpyr_set_timing(compvhip_orbpyr* y, int enabled)
-{
-	if (!y) return COMPVHIP_E_INVALID_PARAMETER;
-	y->timing = enabled != 0;
-	return COMPVHIP_OK;
-}
-
-int compvhip_orbpyr_get_timing(compvhip_orbpyr* y, const char** names, float* ms, int cap)
-{
-	if (!y) return COMPVHIP_E_INVALID_PARAMETER;
-	return timingRead(y, y->ctx->device, names, ms, cap);
-}
+void compvhip_orbpyr_destroy(compvhip_orbpyr* y) { handleDestroy(y); }
+int compvhip_orbpyr_set_timing(compvhip_orbpyr* y, int enabled) { return handleSetTiming(y, enabled); }
+int compvhip_orbpyr_get_timing(compvhip_orbpyr* y, const char** names, float* ms, int cap) { return handleGetTiming(y, names, ms, cap); }
 
 int compvhip_orbpyr_geometry(const compvhip_orbpyr* y, int level, size_t* W, size_t* H, size_t* S, float* scale, int* quota)
 {
@@ -828,26 +812,9 @@ int compvhip_matcher_create(compvhip_ctx* ctx, size_t descBytes, size_t queryCap
 	return COMPVHIP_OK;
 }
 
-void compvhip_matcher_destroy(compvhip_matcher* m)
-{
-	if (!m) return;
-	(void)hipSetDevice(m->ctx->device);
-	timingTeardown(m);
-	delete m;
-}
-
-int compvhip_matcher_set_timing(compvhip_matcher* m, int enabled)
-{
-	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
-	m->timing = enabled != 0;
-	return COMPVHIP_OK;
-}
-
-int compvhip_matcher_get_timing(compvhip_matcher* m, const char** names, float* ms, int cap)
-{
-	if (!m) return COMPVHIP_E_INVALID_PARAMETER;
-	return timingRead(m, m->ctx->device, names, ms, cap);
-}
+void compvhip_matcher_destroy(compvhip_matcher* m) { handleDestroy(m); }
+int compvhip_matcher_set_timing(compvhip_matcher* m, int enabled) { return handleSetTiming(m, enabled); }
+int compvhip_matcher_get_timing(compvhip_matcher* m, const char** names, float* ms, int cap) { return handleGetTiming(m, names, ms, cap); }
 
 int compvhip_matcher_knn(compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
                          const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches, void* stream)
@@ -902,144 +869,6 @@ int compvhip_matcher_good(compvhip_matcher* m, const compvhip_match* d_matches, 
 	g.ratio = opts->ratio; g.maxDistance = opts->maxDistance; g.crossCheck = opts->crossCheck != 0;
 	g.good = d_good; g.goodCap = goodCap; g.counts = d_goodCounts;
 	{ Stamp s(m, st, "match_good_kernel"); HIPCHK(ctx, launch_match_good(g, m->pairs, st)); }
-	return COMPVHIP_OK;
-}
-
-// ---- RANSAC homography (homography_kernels.hip; definition in include/compv_hip.h) ------------------------------------------------------------
-namespace {
-constexpr size_t kHomographyMaxCap = size_t(1) << 22;     // points per pair and tries: keeps every index and grid dimension in 32 bits
-
-HomographyFindArgs homographyArgs(const compvhip_homography* h)
-{
-	const size_t P = static_cast<size_t>(h->pairs), cap = static_cast<size_t>(h->pointCap), T = static_cast<size_t>(h->maxTries);
-	HomographyFindArgs a = {};
-	a.src = h->points; a.dst = h->points + P * cap; a.counts = h->counts; a.pointCap = h->pointCap;
-	a.selSrc = h->points + 2 * P * cap; a.selDst = h->points + 3 * P * cap;
-	a.maxTries = h->maxTries;
-	a.hyp = h->tryF64; a.scoreVar = h->tryF64 + P * T * 18;
-	a.state = h->tryI32; a.rotations = h->tryI32 + P * T; a.scoreCount = h->tryI32 + 2 * P * T;
-	return a;
-}
-} // namespace
-
-int compvhip_homography_create(compvhip_ctx* ctx, size_t pairs, size_t pointCap, size_t maxTries, compvhip_homography** out)
-{
-	if (!ctx || !out) return COMPVHIP_E_INVALID_PARAMETER;
-	*out = nullptr;
-	if (int rc = refuseBeyondLaunchLimit(ctx, pairs, "compvhip_homography_create (pairs)")) return rc;   // a pair is blockIdx.x / .y
-	if (!pairs || pointCap < 4 || !maxTries || pointCap > kHomographyMaxCap || maxTries > kHomographyMaxCap)
-		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "pairs and maxTries must be >= 1, pointCap >= 4");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	compvhip_homography* h = new (std::nothrow) compvhip_homography();
-	if (!h) return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "homography");
-	h->ctx = ctx; h->pairs = static_cast<int>(pairs); h->pointCap = static_cast<int>(pointCap); h->maxTries = static_cast<int>(maxTries);
-	if (h->points.reserve(ctx, 4 * pairs * pointCap) != hipSuccess || h->counts.reserve(ctx, pairs) != hipSuccess ||
-	    h->tryF64.reserve(ctx, pairs * maxTries * 19) != hipSuccess || h->tryI32.reserve(ctx, pairs * maxTries * 3) != hipSuccess) {
-		compvhip_homography_destroy(h);
-		return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "homography scratch");
-	}
-	*out = h;
-	return COMPVHIP_OK;
-}
-
-void compvhip_homography_destroy(compvhip_homography* h)
-{
-	if (!h) return;
-	(void)hipSetDevice(h->ctx->device);
-	timingTeardown(h);
-	delete h;
-}
-
-int compvhip_homography_set_timing(compvhip_homography* h, int enabled)
-{
-	if (!h) return COMPVHIP_E_INVALID_PARAMETER;
-	h->timing = enabled != 0;
-	return COMPVHIP_OK;
-}
-
-int compvhip_homography_get_timing(compvhip_homography* h, const char** names, float* ms, int cap)
-{
-	if (!h) return COMPVHIP_E_INVALID_PARAMETER;
-	return timingRead(h, h->ctx->device, names, ms, cap);
-}
-
-int compvhip_homography_points(compvhip_homography* h, const compvhip_match* d_good, size_t goodCap, const int32_t* d_goodCounts, const compvhip_keypoint* d_query,
-                               size_t queryCap, const compvhip_keypoint* d_train, size_t trainCap, int trainShared, void* stream)
-{
-	if (!h) return COMPVHIP_E_INVALID_PARAMETER;
-	compvhip_ctx* ctx = h->ctx;
-	if (!d_query || !d_train || (goodCap && !d_good)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null good / keypoint pointer");
-	if (!queryCap || !trainCap || goodCap > kHomographyMaxCap || queryCap > kHomographyMaxCap || trainCap > kHomographyMaxCap)
-		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "capacity out of range");
-	if (misaligned(15, d_good)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "match records must be 16-byte aligned");
-	if (misaligned(3, d_goodCounts, d_query, d_train)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "counts and keypoints must be 4-byte aligned");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	if (h->timing) timelineClear(h);
-	const HomographyFindArgs f = homographyArgs(h);
-	HomographyPointsArgs a = {};
-	a.good = d_good; a.goodCap = static_cast<int>(goodCap); a.goodCounts = d_goodCounts;
-	a.query = d_query; a.queryCap = static_cast<int>(queryCap); a.train = d_train; a.trainCap = static_cast<int>(trainCap); a.trainShared = trainShared != 0;
-	a.src = const_cast<double2*>(f.src); a.dst = const_cast<double2*>(f.dst); a.pointCap = h->pointCap; a.counts = h->counts;
-	{ Stamp s(h, st, "homography_points_kernel"); HIPCHK(ctx, launch_homography_points(a, h->pairs, st)); }
-	h->gathered = true;
-	return COMPVHIP_OK;
-}
-
-int compvhip_homography_find(compvhip_homography* h, const double* d_src, const double* d_dst, const int32_t* d_counts, const compvhip_homography_opts* opts,
-                             const int32_t* d_quads, compvhip_homography_result* d_results, uint8_t* d_mask, void* stream)
-{
-	if (!h) return COMPVHIP_E_INVALID_PARAMETER;
-	compvhip_ctx* ctx = h->ctx;
-	if (!opts || !d_results) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null options / result pointer");
-	if (opts->tries < 1 || opts->tries > h->maxTries) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "tries must be in 1..maxTries");
-	if (!(opts->threshold > 0.0)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "threshold must be > 0");
-	if (d_src && !d_dst) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "d_src without d_dst");
-	if (!d_src && !h->gathered) return fail(ctx, COMPVHIP_E_INVALID_STATE, "no points: compvhip_homography_points has not run on this handle");
-	if (misaligned(15, d_src, d_dst, d_quads)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "points and quads must be 16-byte aligned");
-	if (misaligned(7, d_results) || misaligned(3, d_counts)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "results must be 8-byte, counts 4-byte aligned");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	if (h->timing) timelineClear(h);
-	HomographyFindArgs a = homographyArgs(h);
-	if (d_src) { a.src = reinterpret_cast<const double2*>(d_src); a.dst = reinterpret_cast<const double2*>(d_dst); a.counts = d_counts; }
-	a.tries = opts->tries; a.seed = opts->seed; a.threshold = opts->threshold; a.quads = d_quads; a.results = d_results; a.mask = d_mask;
-	{ Stamp s(h, st, "homography_solve_kernel"); HIPCHK(ctx, launch_homography_solve(a, h->pairs, st)); }
-	{ Stamp s(h, st, "homography_score_kernel"); HIPCHK(ctx, launch_homography_score(a, h->pairs, st)); }
-	{ Stamp s(h, st, "homography_refit_kernel"); HIPCHK(ctx, launch_homography_refit(a, h->pairs, st)); }
-	return COMPVHIP_OK;
-}
-
-int compvhip_homography_project(compvhip_homography* h, const compvhip_homography_result* d_results, const double* d_points, size_t n, int shared, double* d_out,
-                                void* stream)
-{
-	if (!h) return COMPVHIP_E_INVALID_PARAMETER;
-	compvhip_ctx* ctx = h->ctx;
-	if (!d_results || (n && (!d_points || !d_out)) || n > kHomographyMaxCap) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null result / point pointer, or n out of range");
-	if (misaligned(15, d_points, d_out) || misaligned(7, d_results)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "points must be 16-byte, results 8-byte aligned");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	if (h->timing) timelineClear(h);
-	HomographyProjectArgs a = {};
-	a.results = d_results; a.points = reinterpret_cast<const double2*>(d_points); a.n = static_cast<int>(n); a.shared = shared != 0;
-	a.out = reinterpret_cast<double2*>(d_out);
-	{ Stamp s(h, st, "homography_project_kernel"); HIPCHK(ctx, launch_homography_project(a, h->pairs, st)); }
-	return COMPVHIP_OK;
-}
-
-int compvhip_homography_scores(compvhip_homography* h, size_t tries, int32_t* counts, double* variances, int32_t* rotations, void* stream)
-{
-	if (!h) return COMPVHIP_E_INVALID_PARAMETER;
-	compvhip_ctx* ctx = h->ctx;
-	if (!tries || tries > static_cast<size_t>(h->maxTries)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "tries must be in 1..maxTries");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	const HomographyFindArgs a = homographyArgs(h);
-	const size_t P = static_cast<size_t>(h->pairs), T = static_cast<size_t>(h->maxTries);
-	if (counts) HIPCHK(ctx, hipMemcpy2DAsync(counts, tries * 4, a.scoreCount, T * 4, tries * 4, P, hipMemcpyDeviceToHost, st));
-	if (rotations) HIPCHK(ctx, hipMemcpy2DAsync(rotations, tries * 4, a.rotations, T * 4, tries * 4, P, hipMemcpyDeviceToHost, st));
-	if (variances) HIPCHK(ctx, hipMemcpy2DAsync(variances, tries * 8, a.scoreVar, T * 8, tries * 8, P, hipMemcpyDeviceToHost, st));
-	HIPCHK(ctx, hipStreamSynchronize(st));
 	return COMPVHIP_OK;
 }
 

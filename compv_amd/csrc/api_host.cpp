@@ -1,7 +1,7 @@
 // api_host.cpp -- the host-pointer (`*_u8`) entry points: one frame in host memory in, results in host memory out, synchronous
-// (KHT: api_kht.cpp).  They run the plan-level calls on a single-frame plan and staging buffers cached in the context.
+// (KHT: api_kht.cpp; the RANSAC families' host forms: api_ransac.cpp).  They run the plan-level calls on a single-frame plan and staging buffers
+// cached in the context.
 #include "api_internal.hpp"
-#include "homography_math.hpp"
 
 // ---- host entry points -------------------------------------------------------------------------------------------
 namespace {
@@ -640,50 +640,6 @@ int compvhip_match_hamming_u8(compvhip_ctx* ctx, const uint8_t* query, size_t Q,
 	} while (0);
 	(void)hipStreamSynchronize(ctx->stream);
 	compvhip_matcher_destroy(m);
-	return rc;
-}
-
-// ---- RANSAC homography: the host forms -----------------------------------------------------------------------------------------------------
-int compvhip_homography_quads(uint32_t seed, size_t pair, size_t k, size_t tries, int32_t* quads)
-{
-	if (!quads || k < 4 || k > 0xffffffffull || pair > 0xffffffffull || tries > 0xffffffffull) return COMPVHIP_E_INVALID_PARAMETER;
-	for (size_t t = 0; t < tries; ++t) hg::quad(seed, static_cast<uint32_t>(pair), static_cast<uint32_t>(t), static_cast<uint32_t>(k), quads + 4 * t);
-	return COMPVHIP_OK;
-}
-
-int compvhip_homography_find_f64(compvhip_ctx* ctx, const double* src, const double* dst, size_t n, const compvhip_homography_opts* opts, const int32_t* quads,
-                                 compvhip_homography_result* result, uint8_t* mask)
-{
-	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
-	if (!opts || !result || (n && (!src || !dst))) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null argument");
-	if (opts->tries < 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "tries must be >= 1");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	compvhip_homography* h = nullptr;
-	const size_t cap = std::max<size_t>(n, 4), T = static_cast<size_t>(opts->tries);
-	int rc = compvhip_homography_create(ctx, 1, cap, T, &h);
-	if (rc) return rc;
-	DevBuf<double> dPts; DevBuf<int32_t> dInts; DevBuf<compvhip_homography_result> dRes; DevBuf<uint8_t> dMask;   // freed on the way out, behind the drain of the stream below
-	do {
-		if (dPts.reserve(ctx, 4 * cap) != hipSuccess || dInts.reserve(ctx, 4 + 4 * T) != hipSuccess || dRes.reserve(ctx, 1) != hipSuccess || dMask.reserve(ctx, cap) != hipSuccess) {
-			rc = fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "homography staging"); break;
-		}
-		const int32_t count = static_cast<int32_t>(n);
-		hipError_t e = hipMemcpyAsync(dInts, &count, 4, hipMemcpyHostToDevice, ctx->stream);
-		if (e == hipSuccess && n) e = hipMemcpyAsync(dPts, src, n * 16, hipMemcpyHostToDevice, ctx->stream);
-		if (e == hipSuccess && n) e = hipMemcpyAsync(dPts + 2 * cap, dst, n * 16, hipMemcpyHostToDevice, ctx->stream);
-		if (e == hipSuccess && quads) e = hipMemcpyAsync(dInts + 4, quads, T * 16, hipMemcpyHostToDevice, ctx->stream);
-		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "point upload", e); break; }
-		rc = compvhip_homography_find(h, dPts, dPts + 2 * cap, dInts, opts, quads ? dInts + 4 : nullptr, dRes, mask ? dMask.ptr : nullptr, ctx->stream);
-		if (rc) break;
-		compvhip_homography_result r;
-		e = hipMemcpyAsync(&r, dRes, sizeof(r), hipMemcpyDeviceToHost, ctx->stream);
-		if (e == hipSuccess && mask && n) e = hipMemcpyAsync(mask, dMask, n, hipMemcpyDeviceToHost, ctx->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "result download", e); break; }
-		*result = r;
-	} while (0);
-	(void)hipStreamSynchronize(ctx->stream);
-	compvhip_homography_destroy(h);
 	return rc;
 }
 

@@ -23,6 +23,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace compvhip;
@@ -246,25 +247,23 @@ struct compvhip_matcher : TimingState {
 	DevBuf<uint32_t> partial;           // keys of the slice kernel: max of the forward ([pairs][train slices][knn][queryCap]) and the reverse ([pairs][query slices][trainCap]) run
 	DevBuf<compvhip_match> reverse;     // [pairs][trainCap]: best query of every train row (cross check)
 };
-// RANSAC homography (homography_kernels.hip): every buffer is allocated by compvhip_homography_create
-struct compvhip_homography : TimingState {
+// what the RANSAC handles share (api_ransac.cpp); every buffer is allocated by the family's create call
+struct RansacHandle : TimingState {
 	compvhip_ctx* ctx = nullptr;
-	int pairs = 0, pointCap = 0, maxTries = 0;
-	DevBuf<double2> points;             // [4][pairs][pointCap]: gathered src, gathered dst, selected src, selected dst
-	DevBuf<int32_t> counts;             // [pairs] points gathered
-	DevBuf<double> tryF64;              // [pairs][maxTries][18] H and inverse, then [pairs][maxTries] variance
-	DevBuf<int32_t> tryI32;             // [3][pairs][maxTries]: state, rotations, inlier count
-	bool gathered = false;              // compvhip_homography_points has run
-};
-// RANSAC line and parabola fits (curvefit_kernels.hip): every buffer is allocated by compvhip_curvefit_create; every call runs on `stream`
-struct compvhip_curvefit : TimingState {
-	compvhip_ctx* ctx = nullptr;
-	hipStream_t stream = nullptr;       // (the caller's: the descriptor's)
-	int sets = 0, pointCap = 0, maxTries = 0;
-	DevBuf<double2> points;             // [2][sets][pointCap]: gathered, selected
+	int sets = 0, pointCap = 0, maxTries = 0;   // sets: the homography's pairs
+	DevBuf<double2> points;             // [2 * arrays][sets][pointCap]: the family's point arrays as gathered, then as selected
 	DevBuf<int32_t> counts;             // [sets] points gathered
+	bool gathered = false;              // the family's gather call (compvhip_homography_points, compvhip_curvefit_points_from_labels) has run
+};
+// RANSAC homography (homography_kernels.hip); two point arrays: src, dst
+struct compvhip_homography : RansacHandle {
+	DevBuf<double> tryF64;              // [sets][maxTries][18] H and inverse, then [sets][maxTries] variance
+	DevBuf<int32_t> tryI32;             // [3][sets][maxTries]: state, rotations, inlier count
+};
+// RANSAC line and parabola fits (curvefit_kernels.hip); one point array; every call runs on `stream`
+struct compvhip_curvefit : RansacHandle {
+	hipStream_t stream = nullptr;       // (the caller's: the descriptor's)
 	DevBuf<int32_t> scoreCount;         // [sets][maxTries] inlier count of every try
-	bool gathered = false;              // compvhip_curvefit_points_from_labels has run
 };
 // ORB pyramid (scale_kernels.hip, fast_kernels.hip, orb_kernels.hip): the levels' geometry and the scratch they share.  `active` levels (a prefix: the sizes
 // only shrink) are at least 37 x 37; the others are empty.
@@ -328,10 +327,8 @@ inline bool takeEvent(TimingState* p, hipEvent_t* e)
 struct Stamp {
 	TimingState* p; hipStream_t s; size_t idx; bool on;
 	Stamp(compvhip_plan* plan, hipStream_t stream, const char* name) : Stamp(plan, stream, name, stampWanted(plan, name)) {}
-	Stamp(compvhip_matcher* matcher, hipStream_t stream, const char* name) : Stamp(matcher, stream, name, matcher->timing != 0) {}
-	Stamp(compvhip_orbpyr* pyramid, hipStream_t stream, const char* name) : Stamp(pyramid, stream, name, pyramid->timing != 0) {}
-	Stamp(compvhip_homography* homography, hipStream_t stream, const char* name) : Stamp(homography, stream, name, homography->timing != 0) {}
-	Stamp(compvhip_curvefit* fit, hipStream_t stream, const char* name) : Stamp(fit, stream, name, fit->timing != 0) {}
+	template <typename H, typename = std::enable_if_t<std::is_base_of_v<TimingState, H>>>   // the handles whose timing is on / off
+	Stamp(H* handle, hipStream_t stream, const char* name) : Stamp(handle, stream, name, handle->timing != 0) {}
 	Stamp(TimingState* state, hipStream_t stream, const char* name, bool wanted) : p(state), s(stream), idx(0), on(wanted)
 	{
 		if (!on) return;
@@ -381,6 +378,29 @@ inline void timingTeardown(TimingState* p)
 	timelineClear(p);
 	for (hipEvent_t e : p->eventPool) (void)hipEventDestroy(e);
 	p->eventPool.clear();
+}
+
+// the bodies of the destroy, set_timing and get_timing entry points of the handles whose timing is on / off (matcher, pyramid, homography, curve fit)
+template <typename H>
+void handleDestroy(H* h)
+{
+	if (!h) return;
+	(void)hipSetDevice(h->ctx->device);
+	timingTeardown(h);
+	delete h;
+}
+template <typename H>
+int handleSetTiming(H* h, int enabled)
+{
+	if (!h) return COMPVHIP_E_INVALID_PARAMETER;
+	h->timing = enabled != 0;
+	return COMPVHIP_OK;
+}
+template <typename H>
+int handleGetTiming(H* h, const char** names, float* ms, int cap)
+{
+	if (!h) return COMPVHIP_E_INVALID_PARAMETER;
+	return timingRead(h, h->ctx->device, names, ms, cap);
 }
 
 // an asynchronous step of the plan has not been waited for (its replay would rewrite the plan's masks and the caller's lines)

@@ -10,8 +10,9 @@
 //                             by ballot, the refit's sums with lane l holding partial l of sum64 (a mean pass, then a moment pass), the closed-form
 //                             solve, the record.
 //   curvefit_distance_kernel  one lane per point: item C alone.
+// The RANSAC skeleton (clamped count, fold of sum64, selection, compaction, staged walk) is ransac_device.hpp's, shared with homography_kernels.hip.
 // No MFMA; every store is a plain C++ store.
-#include "device.hpp"
+#include "ransac_device.hpp"
 #include "curvefit_math.hpp"
 
 namespace compvhip {
@@ -20,8 +21,6 @@ namespace {
 using namespace cf;
 
 constexpr int kThreads = kCurvefitBlock;
-
-__device__ __forceinline__ int setCount(const int32_t* counts, int s, int cap) { return counts ? min(max(counts[s], 0), cap) : cap; }
 
 __global__ __launch_bounds__(kThreads) void curvefit_gather_kernel(CurvefitGatherArgs a)
 {
@@ -86,7 +85,7 @@ __global__ __launch_bounds__(kThreads) void curvefit_score_kernel(CurvefitFindAr
 	__shared__ double2 s_pts[kThreads];
 	const int tid = threadIdx.x, s = blockIdx.y;
 	const int t = blockIdx.x * kThreads + tid;
-	const int k = setCount(a.counts, s, a.pointCap);
+	const int k = ransac_count(a.counts, s, a.pointCap);
 	if (k <= modelPoints(a.model)) return;          // (the whole workgroup: k is the set's) no try runs on such a set
 	const double2* pts = a.points + (size_t)s * a.pointCap;
 	Curve c = { 0.0, 0.0, 0.0 };
@@ -96,33 +95,9 @@ __global__ __launch_bounds__(kThreads) void curvefit_score_kernel(CurvefitFindAr
 		if (live) c = prepared(a.model, c);
 	}
 	int count = 0;
-	for (int base = 0; base < k; base += kThreads) {
-		__syncthreads();
-		if (base + tid < k) s_pts[tid] = pts[base + tid];
-		__syncthreads();
-		const int n = min(kThreads, k - base);
-		if (live) {
-			for (int i = 0; i < n; ++i) count += residual(a.model, c, s_pts[i].x, s_pts[i].y) < a.threshold ? 1 : 0;
-		}
-	}
+	staged_points<kThreads>(k, tid, live, [&](int slot, int i) { s_pts[slot] = pts[i]; },
+	                        [&](int j) { count += residual(a.model, c, s_pts[j].x, s_pts[j].y) < a.threshold ? 1 : 0; });
 	if (t < a.tries) a.scoreCount[(size_t)s * a.maxTries + t] = count;
-}
-
-// item D: (count, try) b beats a.  A count below m never wins.
-__device__ __forceinline__ bool better(int m, int cb, int tb, int ca, int ta)
-{
-	if (cb < m) return false;
-	if (ca < m) return true;
-	if (cb != ca) return cb > ca;
-	return tb < ta;
-}
-
-// p[l] += p[l + stride], stride 32 .. 1: every lane ends with the fold of the 64 partials
-__device__ __forceinline__ double fold64(double v)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-	return __shfl(v, 0);
 }
 
 __device__ __forceinline__ void writeRecord(compvhip_curvefit_result* out, Curve c, int inliers, int bestTry, int status, int k)
@@ -134,7 +109,7 @@ __device__ __forceinline__ void writeRecord(compvhip_curvefit_result* out, Curve
 __global__ __launch_bounds__(64) void curvefit_refit_kernel(CurvefitFindArgs a)
 {
 	const int lane = threadIdx.x, s = blockIdx.x;
-	const int k = setCount(a.counts, s, a.pointCap);
+	const int k = ransac_count(a.counts, s, a.pointCap);
 	const int model = a.model, m = modelPoints(model);
 	compvhip_curvefit_result* out = a.results + s;
 	const double2* pts = a.points + (size_t)s * a.pointCap;
@@ -153,17 +128,9 @@ __global__ __launch_bounds__(64) void curvefit_refit_kernel(CurvefitFindArgs a)
 		return;
 	}
 	// D. selection
-	int bc = 0, bt = -1;
-	for (int t = lane; t < a.tries; t += 64) {
-		const int c = a.scoreCount[(size_t)s * a.maxTries + t];
-		if (better(m, c, t, bc, bt)) { bc = c; bt = t; }
-	}
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) {
-		const int c = __shfl_xor(bc, o), t = __shfl_xor(bt, o);
-		if (better(m, c, t, bc, bt)) { bc = c; bt = t; }
-	}
-	if (bc < m) {
+	const BestTry<ransac::NoVariance> best = wave_best_try<ransac::NoVariance>(m, a.tries, lane, [&](int t, int* count, ransac::NoVariance*) { *count = a.scoreCount[(size_t)s * a.maxTries + t]; });
+	const int bt = best.tryIdx;
+	if (best.count < m) {
 		if (mask) for (int i = lane; i < k; i += 64) mask[i] = 0;
 		if (lane == 0) writeRecord(out, zero, 0, -1, 1, k);
 		return;
@@ -173,20 +140,8 @@ __global__ __launch_bounds__(64) void curvefit_refit_kernel(CurvefitFindArgs a)
 	(void)tryCurve(a, s, bt, k, pts, &own);          // (it scored: the sample is in range and the model is not rejected)
 	const Curve p = prepared(model, own);
 	double2* sel = a.sel + (size_t)s * a.pointCap;
-	int n = 0;
-	for (int base = 0; base < k; base += 64) {
-		const int i = base + lane;
-		bool inl = false;
-		double2 v = make_double2(0.0, 0.0);
-		if (i < k) {
-			v = pts[i];
-			inl = residual(model, p, v.x, v.y) < a.threshold;
-			if (mask) mask[i] = inl ? 1 : 0;
-		}
-		const unsigned long long b = __ballot(inl);
-		if (inl) sel[n + __popcll(b & ((1ull << lane) - 1ull))] = v;
-		n += __popcll(b);
-	}
+	double2 v = make_double2(0.0, 0.0);
+	const int n = wave_compact_inliers(k, lane, mask, [&](int i) { v = pts[i]; return residual(model, p, v.x, v.y) < a.threshold; }, [&](int o) { sel[o] = v; });
 	__syncthreads();          // one wave: the compacted points are visible to every lane
 	// E. refit
 	Curve fit = zero;
@@ -199,7 +154,7 @@ __global__ __launch_bounds__(64) void curvefit_refit_kernel(CurvefitFindArgs a)
 	else if (model == kLine) {
 		double sx = 0.0, sy = 0.0;
 		for (int i = lane; i < n; i += 64) { const double2 v = sel[i]; sx += v.x; sy += v.y; }
-		const double meanX = meanOf(fold64(sx), n), meanY = meanOf(fold64(sy), n);
+		const double meanX = meanOf(wave_fold64(sx), n), meanY = meanOf(wave_fold64(sy), n);
 		double sab = 0.0, sden = 0.0;
 		for (int i = lane; i < n; i += 64) {
 			const double2 v = sel[i];
@@ -207,13 +162,13 @@ __global__ __launch_bounds__(64) void curvefit_refit_kernel(CurvefitFindArgs a)
 			lineTerms(v.x, v.y, meanX, meanY, &ab, &den);
 			sab += ab; sden += den;
 		}
-		fit = lineFromSums(meanX, meanY, fold64(sab), fold64(sden));
+		fit = lineFromSums(meanX, meanY, wave_fold64(sab), wave_fold64(sden));
 		ok = true;
 	}
 	else {
 		double su = 0.0;
 		for (int i = lane; i < n; i += 64) { const double2 v = sel[i]; su += xOf(model, v.x, v.y); }
-		const double mean = meanOf(fold64(su), n);
+		const double mean = meanOf(wave_fold64(su), n);
 		double acc[7] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
 		for (int i = lane; i < n; i += 64) {
 			const double2 v = sel[i];
@@ -223,7 +178,7 @@ __global__ __launch_bounds__(64) void curvefit_refit_kernel(CurvefitFindArgs a)
 			for (int e = 0; e < 7; ++e) acc[e] += t[e];
 		}
 #pragma unroll
-		for (int e = 0; e < 7; ++e) acc[e] = fold64(acc[e]);
+		for (int e = 0; e < 7; ++e) acc[e] = wave_fold64(acc[e]);
 		ok = parabolaFromSums(n, mean, acc, &fit);
 	}
 	if (lane == 0) writeRecord(out, ok ? fit : own, n, bt, ok ? 0 : 3, k);
@@ -232,7 +187,7 @@ __global__ __launch_bounds__(64) void curvefit_refit_kernel(CurvefitFindArgs a)
 __global__ __launch_bounds__(256) void curvefit_distance_kernel(CurvefitDistanceArgs a)
 {
 	const int i = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
-	if (i >= setCount(a.counts, s, a.pointCap)) return;
+	if (i >= ransac_count(a.counts, s, a.pointCap)) return;
 	const double* in = a.params + (size_t)s * 3;
 	Curve c;
 	c.A = in[0]; c.B = in[1]; c.C = in[2];

@@ -1,10 +1,10 @@
 // curvefit_math.hpp -- the scalar arithmetic of the RANSAC line and parabola fits (include/compv_hip.h, "RANSAC curve fitting", items A - G), written once
 // for the kernels of curvefit_kernels.hip, for the host (compvhip_curvefit_samples) and for the host checker tests/host/curvefit_math_check.cpp.  Standard
 // library only.  Every operation is one IEEE binary64 operation in the order the definition gives (build with -ffp-contract=off); divisions and square
-// roots are the correctly rounded ones on either side, nothing is transcendental.  The sample generator and the half-angle formulas are the
-// homography's (homography_math.hpp): one copy serves both families.
+// roots are the correctly rounded ones on either side, nothing is transcendental.  The sample generator and the selection rule are ransac_math.hpp's,
+// the half-angle formulas the homography's (homography_math.hpp): one copy serves both families.
 //
-// A. Samples.  m = 2 (line) or 3 (parabolas) distinct indices of set s, try t among k > m points: hg::drawDistinct<m>(seed, s, t, k).
+// A. Samples.  m = 2 (line) or 3 (parabolas) distinct indices of set s, try t among k > m points: ransac::drawDistinct<m>(seed, s, t, k).
 // B. Model of a sample, every expression as the reference writes it (compv_math_stats_fit.cxx:156-168, :252-266):
 //      line      rejected when x0 == x1 && y0 == y1;  A = y1 - y0, B = x0 - x1, C = (x1 * y0) - (x0 * y1)                          (Ax + By + C = 0)
 //      parabola  rejected when two of x1, x2, x3 are equal;  scale = 1 / (((x1 - x2) * (x1 - x3)) * (x2 - x3));                 (y = Ax^2 + Bx + C)
@@ -31,9 +31,10 @@
 namespace compvhip {
 namespace cf {
 
-using hg::dabs;
-using hg::ddiv;
-using hg::dsqrt;
+using ransac::dabs;
+using ransac::ddiv;
+using ransac::drawDistinct;
+using ransac::dsqrt;
 
 constexpr int kLine = 0, kParabola = 1, kParabolaSideways = 2;          // COMPVHIP_CURVEFIT_LINE, _PARABOLA, _PARABOLA_SIDEWAYS
 constexpr int kModels = 3;
@@ -49,8 +50,8 @@ CF_HD double yOf(int model, double px, double py) { return model == kParabolaSid
 // the m indices of set s, try t among k > m points; q[2] of a line is 0
 CF_HD void sample(int model, uint32_t seed, uint32_t s, uint32_t t, uint32_t k, int32_t q[3])
 {
-	if (model == kLine) { hg::drawDistinct<2>(seed, s, t, k, q); q[2] = 0; }
-	else hg::drawDistinct<3>(seed, s, t, k, q);
+	if (model == kLine) { drawDistinct<2>(seed, s, t, k, q); q[2] = 0; }
+	else drawDistinct<3>(seed, s, t, k, q);
 }
 
 // ---- B. model of a sample ---------------------------------------------------------------------------------------------------------------------

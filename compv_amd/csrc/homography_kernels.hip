@@ -12,8 +12,9 @@
 //   homography_refit_kernel    one wave per pair: selection over the tries (item F), the inlier mask of the best try, the inliers compacted in
 //                              index order, computeH over them with lane l holding partial l of sum64, Jacobi by lane 0 in LDS, the record.
 //   homography_project_kernel  one lane per point.
+// The RANSAC skeleton (clamped count, fold of sum64, selection, compaction, staged walk) is ransac_device.hpp's, shared with curvefit_kernels.hip.
 // No MFMA; every store is a plain C++ store.
-#include "device.hpp"
+#include "ransac_device.hpp"
 #include "homography_math.hpp"
 
 namespace compvhip {
@@ -25,13 +26,11 @@ constexpr int kSolveThreads = kHomographySolveBlock;     // one wave
 constexpr int kScoreThreads = kHomographyScoreBlock;
 constexpr int kPointThreads = 256;
 
-__device__ __forceinline__ int pairCount(const int32_t* counts, int p, int cap) { return counts ? min(max(counts[p], 0), cap) : cap; }
-
 __global__ __launch_bounds__(kPointThreads) void homography_points_kernel(HomographyPointsArgs a)
 {
 	__shared__ int32_t s_flag[kPointThreads];
 	const int p = blockIdx.x, tid = threadIdx.x;
-	const int n = min(pairCount(a.goodCounts, p, a.goodCap), a.pointCap);
+	const int n = min(ransac_count(a.goodCounts, p, a.goodCap), a.pointCap);
 	const compvhip_match* good = a.good + (size_t)p * a.goodCap;
 	const compvhip_keypoint* query = a.query + (size_t)p * a.queryCap;
 	const compvhip_keypoint* train = a.train + (a.trainShared ? 0 : (size_t)p * a.trainCap);
@@ -61,7 +60,7 @@ __global__ __launch_bounds__(kSolveThreads) void homography_solve_kernel(Homogra
 	__shared__ double s_mat[162 * kSolveThreads];
 	const int lane = threadIdx.x, p = blockIdx.y;
 	const int t = blockIdx.x * kSolveThreads + lane;
-	const int k = pairCount(a.counts, p, a.pointCap);
+	const int k = ransac_count(a.counts, p, a.pointCap);
 	if (t >= a.tries || k < 4) return;
 	const size_t slot = (size_t)p * a.maxTries + t;
 	int32_t q[4];
@@ -101,7 +100,7 @@ __global__ __launch_bounds__(kScoreThreads) void homography_score_kernel(Homogra
 	__shared__ double2 s_src[kScoreThreads], s_dst[kScoreThreads];
 	const int tid = threadIdx.x, p = blockIdx.y;
 	const int t = blockIdx.x * kScoreThreads + tid;
-	const int k = pairCount(a.counts, p, a.pointCap);
+	const int k = ransac_count(a.counts, p, a.pointCap);
 	if (k < 4) return;          // (the whole workgroup: k is the pair's)
 	const size_t slot = (size_t)p * a.maxTries + t;
 	const bool live = t < a.tries && a.state[slot] != 0;
@@ -116,46 +115,19 @@ __global__ __launch_bounds__(kScoreThreads) void homography_score_kernel(Homogra
 	int count = 0;
 	double sum = 0.0, mean = 0.0, var = 0.0;
 	for (int pass = 0; pass < 2; ++pass) {
-		for (int base = 0; base < k; base += kScoreThreads) {
-			__syncthreads();
-			if (base + tid < k) { s_src[tid] = src[base + tid]; s_dst[tid] = dst[base + tid]; }
-			__syncthreads();
-			const int m = min(kScoreThreads, k - base);
-			if (live) {
-				for (int i = 0; i < m; ++i) {
-					const double d = distance(H, Hinv, s_src[i].x, s_src[i].y, s_dst[i].x, s_dst[i].y);
-					if (d < a.threshold) {
-						if (pass == 0) { ++count; sum += d; }
-						else { const double dev = d - mean; var += dev * dev; }
-					}
-				}
+		staged_points<kScoreThreads>(k, tid, live, [&](int slot, int i) { s_src[slot] = src[i]; s_dst[slot] = dst[i]; }, [&](int j) {
+			const double d = distance(H, Hinv, s_src[j].x, s_src[j].y, s_dst[j].x, s_dst[j].y);
+			if (d < a.threshold) {
+				if (pass == 0) { ++count; sum += d; }
+				else { const double dev = d - mean; var += dev * dev; }
 			}
-		}
+		});
 		if (pass == 0 && count > 0) mean = ddiv(sum, (double)count);
 	}
 	if (t < a.tries) {
 		a.scoreCount[slot] = count;
 		a.scoreVar[slot] = count >= 2 ? ddiv(var, (double)(count - 1)) : DBL_MAX;
 	}
-}
-
-// (count, variance, try) of lane-local bests: a is replaced when b is better.  count < 4 never wins.
-__device__ __forceinline__ bool better(int cb, double vb, int tb, int ca, double va, int ta)
-{
-	if (cb < 4) return false;
-	if (ca < 4) return true;
-	if (cb != ca) return cb > ca;
-	if (vb < va) return true;
-	if (va < vb) return false;
-	return tb < ta;
-}
-
-// p[l] += p[l + stride], stride 32 .. 1: lane 0 ends with the fold of the 64 partials
-__device__ __forceinline__ double fold64(double v)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-	return __shfl(v, 0);
 }
 
 // Hartley normalisation of n > 4 points, lane l holding partial l of every sum64
@@ -165,10 +137,10 @@ __device__ __forceinline__ Norm normWave(const double2* pts, int n, int lane)
 	for (int i = lane; i < n; i += 64) { const double2 v = pts[i]; sx += v.x; sy += v.y; }
 	const double inv = ddiv(1.0, (double)n);
 	Norm r;
-	r.tx = fold64(sx) * inv; r.ty = fold64(sy) * inv;
+	r.tx = wave_fold64(sx) * inv; r.ty = wave_fold64(sy) * inv;
 	double mag = 0.0;
 	for (int i = lane; i < n; i += 64) { const double2 v = pts[i]; mag += hypotNaive(v.x - r.tx, v.y - r.ty); }
-	r.s = scaleOf(fold64(mag) * inv);
+	r.s = scaleOf(wave_fold64(mag) * inv);
 	return r;
 }
 
@@ -178,7 +150,7 @@ __global__ __launch_bounds__(64) void homography_refit_kernel(HomographyFindArgs
 	__shared__ double s_H[9];
 	__shared__ int s_rot;
 	const int lane = threadIdx.x, p = blockIdx.x;
-	const int k = pairCount(a.counts, p, a.pointCap);
+	const int k = ransac_count(a.counts, p, a.pointCap);
 	compvhip_homography_result* out = a.results + p;
 	if (k < 4) {
 		if (a.mask && lane < k) a.mask[(size_t)p * a.pointCap + lane] = 0;
@@ -189,46 +161,25 @@ __global__ __launch_bounds__(64) void homography_refit_kernel(HomographyFindArgs
 		return;
 	}
 	// F. selection
-	int bc = 0, bt = -1; double bv = DBL_MAX;
-	for (int t = lane; t < a.tries; t += 64) {
+	const BestTry<double> best = wave_best_try<double>(4, a.tries, lane, [&](int t, int* count, double* variance) {
 		const size_t slot = (size_t)p * a.maxTries + t;
-		const int c = a.scoreCount[slot]; const double v = a.scoreVar[slot];
-		if (better(c, v, t, bc, bv, bt)) { bc = c; bv = v; bt = t; }
-	}
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) {
-		const int c = __shfl_xor(bc, o), t = __shfl_xor(bt, o); const double v = __shfl_xor(bv, o);
-		if (better(c, v, t, bc, bv, bt)) { bc = c; bv = v; bt = t; }
-	}
-	const bool found = bc >= 4;
+		*count = a.scoreCount[slot]; *variance = a.scoreVar[slot];
+	});
+	const bool found = best.count >= 4;
 	const double2* src = a.src + (size_t)p * a.pointCap;
 	const double2* dst = a.dst + (size_t)p * a.pointCap;
 	uint8_t* mask = a.mask ? a.mask + (size_t)p * a.pointCap : nullptr;
 	int n = k;
 	if (found) {          // the inliers of the best try, compacted in index order
 		double H[9], Hinv[9];
-		const double* in = a.hyp + ((size_t)p * a.maxTries + bt) * 18;
+		const double* in = a.hyp + ((size_t)p * a.maxTries + best.tryIdx) * 18;
 #pragma unroll
 		for (int j = 0; j < 9; ++j) { H[j] = in[j]; Hinv[j] = in[9 + j]; }
 		double2* selSrc = a.selSrc + (size_t)p * a.pointCap;
 		double2* selDst = a.selDst + (size_t)p * a.pointCap;
-		n = 0;
-		for (int base = 0; base < k; base += 64) {
-			const int i = base + lane;
-			bool inl = false;
-			double2 s = make_double2(0.0, 0.0), d = s;
-			if (i < k) {
-				s = src[i]; d = dst[i];
-				inl = distance(H, Hinv, s.x, s.y, d.x, d.y) < a.threshold;
-				if (mask) mask[i] = inl ? 1 : 0;
-			}
-			const unsigned long long b = __ballot(inl);
-			if (inl) {
-				const int o = n + __popcll(b & ((1ull << lane) - 1ull));
-				selSrc[o] = s; selDst[o] = d;
-			}
-			n += __popcll(b);
-		}
+		double2 s = make_double2(0.0, 0.0), d = s;
+		n = wave_compact_inliers(k, lane, mask, [&](int i) { s = src[i]; d = dst[i]; return distance(H, Hinv, s.x, s.y, d.x, d.y) < a.threshold; },
+		                         [&](int o) { selSrc[o] = s; selDst[o] = d; });
 		src = selSrc; dst = selDst;
 		__syncthreads();          // one wave: the compacted points are visible to every lane
 	}
@@ -256,7 +207,7 @@ __global__ __launch_bounds__(64) void homography_refit_kernel(HomographyFindArgs
 			accumulateS(m0, m1, acc);
 		}
 #pragma unroll
-		for (int e = 0; e < 45; ++e) acc[e] = fold64(acc[e]);
+		for (int e = 0; e < 45; ++e) acc[e] = wave_fold64(acc[e]);
 		if (lane == 0) {
 			double H[9];
 			storeS<1>(acc, s_mat, s_mat + 81);
@@ -268,9 +219,9 @@ __global__ __launch_bounds__(64) void homography_refit_kernel(HomographyFindArgs
 	__syncthreads();
 	if (lane < 9) out->H[lane] = s_H[lane];
 	if (lane == 0) {
-		out->variance = found ? bv : DBL_MAX;
-		out->inliers = found ? bc : 0;
-		out->bestTry = found ? bt : -1;
+		out->variance = found ? best.variance : DBL_MAX;
+		out->inliers = found ? best.count : 0;
+		out->bestTry = found ? best.tryIdx : -1;
 		out->status = found ? 0 : 1;
 		out->rotations = s_rot;
 	}

@@ -2,85 +2,28 @@
 // kernels of homography_kernels.hip and for the host (compvhip_homography_quads).  Every operation is one IEEE binary64 operation in the order the
 // definition gives; divisions and square roots are the correctly rounded ones on either side, nothing is transcendental.  The 9 x 9 matrices are
 // addressed as M[e * ST]: ST = 64 interleaves the matrices of a wave's lanes in LDS (lane-consecutive words, no bank conflict whatever the pivot),
-// ST = 1 is a plain array.  The sample generator (drawDistinct) and the half-angle formulas (halfAngle) also serve the curve fits (curvefit_math.hpp).
+// ST = 1 is a plain array.  The scalar operations, the sample generator (drawDistinct) and the selection rule are ransac_math.hpp's; the half-angle
+// formulas (halfAngle) also serve the curve fits (curvefit_math.hpp).
 #pragma once
-#include <float.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define HG_HD __host__ __device__ __forceinline__
-#define HG_UNROLL _Pragma("unroll")
-#else
-#include <cmath>
-#define HG_HD inline
-#define HG_UNROLL
-#endif
+#include "ransac_math.hpp"
 
 namespace compvhip {
 namespace hg {
+
+// (named one by one: the selection rule and the array fold stay ransac::better and ransac::fold64, so a program that defines its own is not disturbed)
+using ransac::dabs;
+using ransac::ddiv;
+using ransac::drawDistinct;
+using ransac::dsqrt;
+using ransac::kQuadDraws;
+using ransac::lowbias32;
 
 constexpr double kEps = 2.220446049250313e-16;          // 2^-52
 constexpr double kSqrt2 = 1.4142135623730950488016887242097;
 constexpr double kCosPi4 = 0.70710678118654757;
 constexpr int kMaxRotations = 9 * 9 * 30;
-constexpr int kQuadDraws = 64;
-
-HG_HD double ddiv(double a, double b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-	return __ddiv_rn(a, b);
-#else
-	return a / b;
-#endif
-}
-HG_HD double dsqrt(double a)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-	return __dsqrt_rn(a);
-#else
-	return sqrt(a);
-#endif
-}
-HG_HD double dabs(double a) { return __builtin_fabs(a); }
 
 // ---- A. quads ---------------------------------------------------------------------------------------------------------------------------
-HG_HD uint32_t lowbias32(uint32_t x)
-{
-	x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-	return x;
-}
-// the M distinct indices of set (pair) p, try t among k >= M points: the generator of the homography's quads (M = 4) and of the curve fits' samples
-// (curvefit_math.hpp, M = 2 or 3).  The slots are addressed by compile-time indices only, so q stays in registers.
-template <int M>
-HG_HD void drawDistinct(uint32_t seed, uint32_t p, uint32_t t, uint32_t k, int32_t q[M])
-{
-	const uint32_t base = lowbias32(lowbias32(seed ^ p) + t);
-	int filled = 0;
-HG_UNROLL
-	for (int j = 0; j < M; ++j) q[j] = -1;
-	for (int c = 0; c < kQuadDraws && filled < M; ++c) {
-		const int32_t idx = (int32_t)(((uint64_t)lowbias32(base + (uint32_t)c) * k) >> 32);
-		bool seen = false;
-HG_UNROLL
-		for (int j = 0; j < M; ++j) seen = seen || (j < filled && q[j] == idx);
-		if (!seen) {
-HG_UNROLL
-			for (int j = 0; j < M; ++j) if (j == filled) q[j] = idx;
-			++filled;
-		}
-	}
-	for (int32_t idx = 0; filled < M; ++idx) {          // 64 draws did not fill the slots: the smallest unused indices
-		bool seen = false;
-HG_UNROLL
-		for (int j = 0; j < M; ++j) seen = seen || (j < filled && q[j] == idx);
-		if (!seen) {
-HG_UNROLL
-			for (int j = 0; j < M; ++j) if (j == filled) q[j] = idx;
-			++filled;
-		}
-	}
-}
 // the four indices of pair p, try t among k >= 4 points
 HG_HD void quad(uint32_t seed, uint32_t p, uint32_t t, uint32_t k, int32_t q[4]) { drawDistinct<4>(seed, p, t, k, q); }
 

@@ -1,5 +1,6 @@
 // curvefit_math_check.cpp -- compv_amd/csrc/curvefit_math.hpp run on the host (standard library only, no GPU): the whole RANSAC fit of ONE set, in the
-// order the kernels of curvefit_kernels.hip take (one try after another; the 64 partials of sum64 as an array), so that tests/test_curvefit_host.py
+// order the kernels of curvefit_kernels.hip take (one try after another, ranked by the kernels' own rule, ransac::better; the 64 partials of sum64 as an
+// array, ransac::fold64), so that tests/test_curvefit_host.py
 // can hold the header's arithmetic against tests/curvefit_model.py bit for bit.
 //   in:  int32 k, tries, hasSamples, set, model; uint32 seed; float64 threshold; float64 pts[k][2]; int32 samples[tries][m] (if hasSamples)
 //   out: the result record (40 bytes); uint8 mask[k]; int32 counts[tries]; int32 samples[tries][m]
@@ -11,15 +12,9 @@
 #include <vector>
 
 using namespace compvhip::cf;
+namespace ransac = compvhip::ransac;
 
 struct Result { double A, B, C; int32_t inliers, bestTry, status, k; };
-
-static double fold64(double* p)
-{
-	for (int stride = 32; stride > 0; stride >>= 1)
-		for (int l = 0; l < stride; ++l) p[l] += p[l + stride];
-	return p[0];
-}
 
 // the model of a sample of set points; false: out of range or rejected
 static bool tryCurve(int model, const std::vector<double>& pts, int k, const int32_t* q, Curve* c)
@@ -44,19 +39,19 @@ static bool refit(int model, const std::vector<double>& sel, Curve* out)
 	if (model == kLine) {
 		double px[64] = {}, py[64] = {}, pab[64] = {}, pden[64] = {};
 		for (int i = 0; i < n; ++i) { px[i & 63] += sel[2 * i]; py[i & 63] += sel[2 * i + 1]; }
-		const double meanX = meanOf(fold64(px), n), meanY = meanOf(fold64(py), n);
+		const double meanX = meanOf(ransac::fold64(px), n), meanY = meanOf(ransac::fold64(py), n);
 		for (int i = 0; i < n; ++i) {
 			double ab, den;
 			lineTerms(sel[2 * i], sel[2 * i + 1], meanX, meanY, &ab, &den);
 			pab[i & 63] += ab; pden[i & 63] += den;
 		}
-		const double sab = fold64(pab), sden = fold64(pden);
+		const double sab = ransac::fold64(pab), sden = ransac::fold64(pden);
 		*out = lineFromSums(meanX, meanY, sab, sden);
 		return true;
 	}
 	double pu[64] = {};
 	for (int i = 0; i < n; ++i) pu[i & 63] += xOf(model, sel[2 * i], sel[2 * i + 1]);
-	const double mean = meanOf(fold64(pu), n);
+	const double mean = meanOf(ransac::fold64(pu), n);
 	std::vector<double> part(64 * 7, 0.0);
 	for (int i = 0; i < n; ++i) {
 		double t[7];
@@ -67,7 +62,7 @@ static bool refit(int model, const std::vector<double>& sel, Curve* out)
 	for (int e = 0; e < 7; ++e) {
 		double p[64];
 		for (int l = 0; l < 64; ++l) p[l] = part[l * 7 + e];
-		s[e] = fold64(p);
+		s[e] = ransac::fold64(p);
 	}
 	return parabolaFromSums(n, mean, s, out);
 }
@@ -119,9 +114,9 @@ int main(int argc, char** argv)
 				for (int i = 0; i < k; ++i) count += residual(model, p, pts[2 * i], pts[2 * i + 1]) < threshold ? 1 : 0;
 				counts[t] = count;
 			}
-			if (counts[t] >= m && counts[t] > bc) { bc = counts[t]; bt = t; }
+			if (ransac::better(m, counts[t], ransac::NoVariance(), t, bc, ransac::NoVariance(), bt)) { bc = counts[t]; bt = t; }
 		}
-		if (bt < 0) res.status = 1;
+		if (bc < m) res.status = 1;
 		else {
 			Curve own = { 0.0, 0.0, 0.0 };
 			(void)tryCurve(model, pts, k, &samples[(size_t)m * bt], &own);

@@ -1,5 +1,6 @@
 // homography_math_check.cpp -- compv_amd/csrc/homography_math.hpp run on the host (standard library only, no GPU): the whole RANSAC homography of ONE
-// pair, in the order the kernels of homography_kernels.hip take (one try after another; the 64 partials of sum64 as an array), so that
+// pair, in the order the kernels of homography_kernels.hip take (one try after another, ranked by the kernels' own rule, ransac::better; the 64
+// partials of sum64 as an array, ransac::fold64), so that
 // tests/test_homography_host.py can hold the header's arithmetic against tests/homography_model.py bit for bit.
 //   in:  int32 k, tries, hasQuads, pair; uint32 seed; int32 pad; float64 threshold; float64 src[k][2], dst[k][2]; int32 quads[tries][4] (if hasQuads)
 //   out: the result record (96 bytes); uint8 mask[k]; int32 counts[tries]; float64 variances[tries]; int32 rotations[tries]; int32 quads[tries][4]
@@ -11,15 +12,9 @@
 #include <vector>
 
 using namespace compvhip::hg;
+namespace ransac = compvhip::ransac;
 
 struct Result { double H[9]; double variance; int32_t inliers, bestTry, status, rotations; };
-
-static double fold64(double* p)
-{
-	for (int stride = 32; stride > 0; stride >>= 1)
-		for (int l = 0; l < stride; ++l) p[l] += p[l + stride];
-	return p[0];
-}
 
 static Norm normN(const double* pts, int n)
 {
@@ -27,9 +22,9 @@ static Norm normN(const double* pts, int n)
 	for (int i = 0; i < n; ++i) { px[i & 63] += pts[2 * i]; py[i & 63] += pts[2 * i + 1]; }
 	const double inv = 1.0 / (double)n;
 	Norm r;
-	r.tx = fold64(px) * inv; r.ty = fold64(py) * inv;
+	r.tx = ransac::fold64(px) * inv; r.ty = ransac::fold64(py) * inv;
 	for (int i = 0; i < n; ++i) pm[i & 63] += hypotNaive(pts[2 * i] - r.tx, pts[2 * i + 1] - r.ty);
-	r.s = scaleOf(fold64(pm) * inv);
+	r.s = scaleOf(ransac::fold64(pm) * inv);
 	return r;
 }
 
@@ -52,22 +47,12 @@ static int computeHN(const double* src, const double* dst, int n, double H[9])
 	for (int e = 0; e < 45; ++e) {
 		double p[64];
 		for (int l = 0; l < 64; ++l) p[l] = part[l * 45 + e];
-		acc[e] = fold64(p);
+		acc[e] = ransac::fold64(p);
 	}
 	storeS<1>(acc, D, Q);
 	const int rotations = jacobi<1>(D, Q);
 	finishH<1>(D, Q, a, b, true, H);
 	return rotations;
-}
-
-static bool better(int cb, double vb, int tb, int ca, double va, int ta)
-{
-	if (cb < 4) return false;
-	if (ca < 4) return true;
-	if (cb != ca) return cb > ca;
-	if (vb < va) return true;
-	if (va < vb) return false;
-	return tb < ta;
 }
 
 int main(int argc, char** argv)
@@ -120,7 +105,7 @@ int main(int argc, char** argv)
 				counts[t] = count;
 				variances[t] = count >= 2 ? var / (double)(count - 1) : DBL_MAX;
 			}
-			if (better(counts[t], variances[t], t, bc, bv, bt)) { bc = counts[t]; bv = variances[t]; bt = t; }
+			if (ransac::better(4, counts[t], variances[t], t, bc, bv, bt)) { bc = counts[t]; bv = variances[t]; bt = t; }
 		}
 		if (bc >= 4) {
 			const double* H = &hyp[18 * (size_t)bt];
