@@ -42,6 +42,8 @@ HOG_GRADIENT_SIGNED, HOG_GRADIENT_UNSIGNED = 1, 2                               
 HOG_INTERP_NEAREST, HOG_INTERP_BILINEAR, HOG_INTERP_BILINEAR_LUT = 1, 2, 3                     # COMPVHIP_HOG_INTERP_* (0: the default, BILINEAR; _LUT is refused)
 HOMOGRAPHY_RESULT_DTYPE = np.dtype([("H", "<f8", (9,)), ("variance", "<f8"), ("inliers", "<i4"), ("bestTry", "<i4"), ("status", "<i4"), ("rotations", "<i4")])   # compvhip_homography_result
 CURVEFIT_LINE, CURVEFIT_PARABOLA, CURVEFIT_PARABOLA_SIDEWAYS = 0, 1, 2                         # COMPVHIP_CURVEFIT_*
+SVM_KERNEL_LINEAR, SVM_KERNEL_RBF = 0, 2                                                       # COMPVHIP_SVM_KERNEL_* (libsvm's kernel_type numbers)
+SVM_F32, SVM_F64 = 0, 1                                                                        # COMPVHIP_SVM_F32 / _F64
 CURVEFIT_RESULT_DTYPE = np.dtype([("A", "<f8"), ("B", "<f8"), ("C", "<f8"), ("inliers", "<i4"), ("bestTry", "<i4"), ("status", "<i4"), ("k", "<i4")])   # compvhip_curvefit_result
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
@@ -78,6 +80,8 @@ EXPORTS = [
     "compvhip_integral_dims", "compvhip_plan_integral", "compvhip_integral_u8", "compvhip_plan_histogram", "compvhip_histogram_u8", "compvhip_plan_equalize",
     "compvhip_equalize_u8", "compvhip_plan_projections", "compvhip_projections_u8",
     "compvhip_convert_layout", "compvhip_convert_frames", "compvhip_convert_u8",
+    "compvhip_svm_create", "compvhip_svm_create_from_file", "compvhip_svm_destroy", "compvhip_svm_info", "compvhip_svm_predict", "compvhip_svm_predict_host",
+    "compvhip_svm_set_timing", "compvhip_svm_get_timing", "compvhip_svm_exp_f64", "compvhip_svm_model_parse",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -167,6 +171,29 @@ class CurvefitOpts(C.Structure):
 
     def __init__(self, model=CURVEFIT_LINE, tries=2000, seed=0, threshold=1.0):
         super().__init__(C.sizeof(CurvefitOpts), int(model), int(tries), int(seed) & 0xffffffff, float(threshold))
+
+
+class SvmModelStruct(C.Structure):
+    """compvhip_svm_model (include/compv_hip.h): host arrays, copied by compvhip_svm_create"""
+    _fields_ = [("size", C.c_uint32), ("kernel", C.c_int32), ("nrClass", C.c_int32), ("totalSV", C.c_int32), ("dim", C.c_int32), ("reserved", C.c_int32),
+                ("gamma", C.c_double), ("sv", C.c_void_p), ("svCoef", C.c_void_p), ("rho", C.c_void_p), ("nSV", C.c_void_p), ("label", C.c_void_p)]
+
+
+class SvmDesc(C.Structure):
+    """compvhip_svm_desc (include/compv_hip.h): the handle's capacity and the stream all its calls run on"""
+    _fields_ = [("size", C.c_uint32), ("maxVectors", C.c_uint32), ("stream", C.c_void_p)]
+
+    def __init__(self, max_vectors=1, stream=0):
+        super().__init__(C.sizeof(SvmDesc), int(max_vectors), stream or None)
+
+
+class SvmShape(C.Structure):
+    """compvhip_svm_shape (include/compv_hip.h)"""
+    _fields_ = [("size", C.c_uint32), ("kernel", C.c_int32), ("nrClass", C.c_int32), ("totalSV", C.c_int32), ("dim", C.c_int32), ("pairs", C.c_int32),
+                ("maxVectors", C.c_uint32), ("reserved", C.c_uint32), ("gamma", C.c_double)]
+
+    def __init__(self):
+        super().__init__(C.sizeof(SvmShape))
 
 
 def curvefit_model_points(model):
@@ -395,6 +422,17 @@ def load():
     L.compvhip_convert_layout.argtypes = [i32, sz, sz, C.POINTER(i32), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_convert_frames.argtypes = [vp, sz, sz, sz, C.POINTER(Image), C.POINTER(Image), vp]
     L.compvhip_convert_u8.argtypes = [vp, sz, sz, C.POINTER(Image), C.POINTER(Image)]
+    L.compvhip_svm_create.argtypes = [vp, C.POINTER(SvmModelStruct), C.POINTER(SvmDesc), C.POINTER(vp)]
+    L.compvhip_svm_create_from_file.argtypes = [vp, C.c_char_p, C.POINTER(SvmDesc), C.POINTER(vp)]
+    L.compvhip_svm_destroy.argtypes = [vp]
+    L.compvhip_svm_destroy.restype = None
+    L.compvhip_svm_info.argtypes = [vp, C.POINTER(SvmShape)]
+    L.compvhip_svm_predict.argtypes = [vp, vp, i32, sz, sz, vp, vp, vp]
+    L.compvhip_svm_predict_host.argtypes = [vp, vp, i32, sz, sz, vp, vp]
+    L.compvhip_svm_set_timing.argtypes = [vp, i32]
+    L.compvhip_svm_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
+    L.compvhip_svm_exp_f64.argtypes = [vp, vp, sz]
+    L.compvhip_svm_model_parse.argtypes = [C.c_char_p, C.POINTER(SvmShape), vp, vp, vp, vp, vp]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -441,6 +479,50 @@ def curvefit_samples(model, seed, set_index, k, tries):
     if rc != OK:
         raise CompvHipError(rc, "compvhip_curvefit_samples")
     return out
+
+
+def svm_exp(x):
+    """compvhip_svm_exp_f64 (host arithmetic, no GPU): the reference's table exponential of a float64 array"""
+    L = load()
+    x = np.ascontiguousarray(x, np.float64)
+    out = np.zeros_like(x)
+    rc = L.compvhip_svm_exp_f64(_ptr(x), _ptr(out), x.size)
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_svm_exp_f64")
+    return out
+
+
+class SvmModel:
+    """A C-SVC model as host arrays: kernel (SVM_KERNEL_*), gamma, sv (l, dim), sv_coef (nr_class - 1, l), rho (pairs,), n_sv and label (nr_class,)."""
+
+    def __init__(self, kernel, gamma, sv, sv_coef, rho, n_sv, label):
+        self.kernel, self.gamma = int(kernel), float(gamma)
+        self.sv = np.ascontiguousarray(sv, np.float64)
+        self.sv_coef = np.ascontiguousarray(sv_coef, np.float64)
+        self.rho = np.ascontiguousarray(rho, np.float64)
+        self.n_sv = np.ascontiguousarray(n_sv, np.int32)
+        self.label = np.ascontiguousarray(label, np.int32)
+        self.nr_class, (self.l, self.dim) = len(self.label), self.sv.shape
+        self.pairs = self.nr_class * (self.nr_class - 1) // 2
+
+    @classmethod
+    def from_file(cls, path):
+        """compvhip_svm_model_parse (host, no GPU): a libsvm model file; CompvHipError where compvhip_svm_create_from_file would refuse it"""
+        L = load()
+        s = SvmShape()
+        rc = L.compvhip_svm_model_parse(os.fsencode(path), C.byref(s), None, None, None, None, None)
+        if rc != OK:
+            raise CompvHipError(rc, "compvhip_svm_model_parse")
+        sv, coef = np.zeros((s.totalSV, s.dim)), np.zeros((s.nrClass - 1, s.totalSV))
+        rho, n_sv, label = np.zeros(s.pairs), np.zeros(s.nrClass, np.int32), np.zeros(s.nrClass, np.int32)
+        rc = L.compvhip_svm_model_parse(os.fsencode(path), C.byref(s), _ptr(sv), _ptr(coef), _ptr(rho), _ptr(n_sv), _ptr(label))
+        if rc != OK:
+            raise CompvHipError(rc, "compvhip_svm_model_parse")
+        return cls(s.kernel, s.gamma, sv, coef, rho, n_sv, label)
+
+    def struct(self):
+        return SvmModelStruct(C.sizeof(SvmModelStruct), self.kernel, self.nr_class, self.l, self.dim, 0, self.gamma, self.sv.ctypes.data, self.sv_coef.ctypes.data,
+                              self.rho.ctypes.data, self.n_sv.ctypes.data, self.label.ctypes.data)
 
 
 def hog_geometry(W, H, opts=None, **kw):
@@ -1239,6 +1321,69 @@ class Curvefit:
         names = (C.c_char_p * cap)()
         ms = (C.c_float * cap)()
         n = self.lib.compvhip_curvefit_get_timing(self.h, names, ms, cap)
+        return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
+
+
+class Svm:
+    """Batched device-resident C-SVC prediction (compvhip_svm): RBF and LINEAR.  Every call runs on the stream given here.  Pointers are raw device
+    addresses; 0 stands for NULL."""
+
+    def __init__(self, ctx, model_or_path, max_vectors, stream=0):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        d = SvmDesc(max_vectors, stream)
+        if isinstance(model_or_path, SvmModel):
+            m = model_or_path.struct()
+            ctx._chk(self.lib.compvhip_svm_create(ctx.h, C.byref(m), C.byref(d), C.byref(h)))
+        else:
+            ctx._chk(self.lib.compvhip_svm_create_from_file(ctx.h, os.fsencode(model_or_path), C.byref(d), C.byref(h)))
+        self.h = h
+        self.max_vectors, self.stream = max_vectors, stream
+        i = self.info()
+        self.dim, self.l, self.pairs = i["dim"], i["totalSV"], i["pairs"]
+
+    def close(self):
+        if self.h:
+            self.lib.compvhip_svm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """compvhip_svm_info: dict(kernel, nrClass, totalSV, dim, pairs, maxVectors, gamma)"""
+        s = SvmShape()
+        self.ctx._chk(self.lib.compvhip_svm_info(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k in ("kernel", "nrClass", "totalSV", "dim", "pairs", "maxVectors", "gamma")}
+
+    def predict(self, d_vectors, vtype, n, stride, d_labels, d_dec=0, d_kvalues=0):
+        """compvhip_svm_predict: d_vectors [n][stride] float32 (SVM_F32) or float64 (SVM_F64) -> d_labels [n] int32, d_dec [n][pairs], d_kvalues [n][totalSV]"""
+        self.ctx._chk(self.lib.compvhip_svm_predict(self.h, d_vectors or None, int(vtype), n, stride, d_labels or None, d_dec or None, d_kvalues or None))
+
+    def predict_host(self, vectors, want_dec=False):
+        """compvhip_svm_predict_host: vectors (n, >= dim) float32 or float64 with contiguous rows -> int32 labels (n,) [, float64 decision values (n, pairs)]"""
+        v = np.asarray(vectors)
+        if v.dtype not in (np.float32, np.float64):
+            v = v.astype(np.float64)
+        if v.ndim != 2 or v.strides[1] != v.itemsize or v.strides[0] % v.itemsize:
+            v = np.ascontiguousarray(v).reshape(len(v), -1)
+        labels = np.zeros(len(v), np.int32)
+        dec = np.zeros((len(v), self.pairs)) if want_dec else None
+        self.ctx._chk(self.lib.compvhip_svm_predict_host(self.h, _ptr(v), SVM_F32 if v.dtype == np.float32 else SVM_F64, len(v), v.strides[0] // v.itemsize, _ptr(labels),
+                                                         _ptr(dec) if want_dec else None))
+        return (labels, dec) if want_dec else labels
+
+    def set_timing(self, mode=1):
+        self.ctx._chk(self.lib.compvhip_svm_set_timing(self.h, int(mode)))
+
+    def get_timing(self, cap=16):
+        names = (C.c_char_p * cap)()
+        ms = (C.c_float * cap)()
+        n = self.lib.compvhip_svm_get_timing(self.h, names, ms, cap)
         return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
 
 

@@ -265,6 +265,19 @@ struct compvhip_curvefit : RansacHandle {
 	hipStream_t stream = nullptr;       // (the caller's: the descriptor's)
 	DevBuf<int32_t> scoreCount;         // [sets][maxTries] inlier count of every try
 };
+// SVM prediction (svm_kernels.hip; api_svm.cpp): the model on the device and the scratch of maxVectors queries; every call runs on `stream`
+struct compvhip_svm : TimingState {
+	compvhip_ctx* ctx = nullptr;
+	hipStream_t stream = nullptr;       // (the caller's: the descriptor's)
+	int kernel = 0, nrClass = 0, l = 0, dim = 0, pairs = 0;
+	size_t maxVectors = 0, hostSlice = 0;   // hostSlice: vectors of one round of compvhip_svm_predict_host
+	double gamma = 0.0;
+	DevBuf<double> sv, svCoef, rho;     // [l][dim], [nrClass - 1][l], [pairs]
+	DevBuf<int32_t> nSV, label;         // [nrClass]
+	DevBuf<uint64_t> expTable;          // [2048] (RBF)
+	DevBuf<double> kvalues;             // [maxVectors][l]
+	DevBuf<double> hostVectors, hostDec; DevBuf<int32_t> hostLabels;   // staging of the host form: [hostSlice][dim] (float32 or float64), [hostSlice][pairs], [hostSlice]
+};
 // ORB pyramid (scale_kernels.hip, fast_kernels.hip, orb_kernels.hip): the levels' geometry and the scratch they share.  `active` levels (a prefix: the sizes
 // only shrink) are at least 37 x 37; the others are empty.
 struct compvhip_orbpyr : TimingState {

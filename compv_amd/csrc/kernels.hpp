@@ -589,4 +589,26 @@ struct StatsEqualizeArgs {
 };
 hipError_t launch_stats_equalize(const StatsEqualizeArgs& a, int frames, int chunks, hipStream_t stream);
 
+// ---- SVM prediction (svm_kernels.hip) ----------------------------------------------------------------------------------------------------------
+constexpr int kSvmTile = 64;                 // queries and support vectors of one workgroup of svm_kvalues_kernel
+struct SvmKvaluesArgs {
+	const void* vectors; int f32;                     // [n][stride] float32 (f32 != 0) or float64
+	int n; size_t stride;                             // stride >= dim, in elements
+	const double* sv; int l, dim;                     // [l][dim]
+	int rbf; double gamma;                            // rbf == 0: LINEAR
+	const uint64_t* expTable;                         // [2048] (RBF)
+	double* K;                                        // [n][l]
+};
+hipError_t launch_svm_kvalues(const SvmKvaluesArgs& a, hipStream_t stream);
+struct SvmDecideArgs {
+	const double* K; int n, l;                        // [n][l]
+	int nrClass; const int32_t* nSV;                  // [nrClass]
+	const double* svCoef;                             // [nrClass - 1][l]
+	const double* rho;                                // [pairs]
+	const int32_t* label;                             // [nrClass]
+	int32_t* labels;                                  // [n]
+	double* dec;                                      // nullptr or [n][pairs]
+};
+hipError_t launch_svm_decide(const SvmDecideArgs& a, hipStream_t stream);
+
 } // namespace compvhip

@@ -1342,6 +1342,106 @@ COMPVHIP_API int compvhip_convert_frames(compvhip_ctx* ctx, size_t W, size_t H, 
 /* host memory, one frame (frameBytes ignored), synchronous; staged through the context's device buffers */
 COMPVHIP_API int compvhip_convert_u8(compvhip_ctx* ctx, size_t W, size_t H, const compvhip_image* in, const compvhip_image* out);
 
+/* ---- SVM prediction: RBF and linear C-SVC (docs/kernels/svm.md) ------------------------------------------------------------------------------
+ * CompVMachineLearningSVM::load -> svm_makeSVs_SIMD_frienly (RBF only) -> predict -> svm_predict_values (base/ml/libsvm-322/libsvm.cxx:2692-2784) for n
+ * query vectors at once, on the device: the consumer of compvhip_plan_hog's descriptors.  Labels, decision values and kernel values are defined bit for
+ * bit.  The leaves are the reference's plain C ones, which its SSE2 / AVX non-FMA leaves are written to equal.  All arithmetic is IEEE binary64, one
+ * rounding per operation, no fused multiply-add; a float32 query is widened to float64 first, which is exact.  compv_amd/csrc/svm_math.hpp is the
+ * arithmetic, tests/svm_model.py the same definition in numpy, and the device equals both bit for bit.
+ * A. Model.  C-SVC: nrClass >= 2 classes; totalSV support vectors of dim dense values, sv[totalSV][dim], grouped by class with counts nSV[c];
+ *    svCoef[nrClass - 1][totalSV]; rho[nrClass * (nrClass - 1) / 2]; label[nrClass]; gamma.  The model FILE is the truth: libsvm writes gamma and rho
+ *    with %g, coefficients with %.16g and SV values with %.8g, and the loaded values are what strtod in the C locale makes of that text.
+ * B. RBF kernel value (svm_k_function_rbf, :3503-3534): K[i] = exp_ref(dotSub(x, SV_i) * (-gamma)).  dotSub (CompVMathDotDotSub_C,
+ *    base/math/compv_math_dot.cxx:90-143) keeps four accumulators s0 .. s3.  Whole groups of 16 columns: m_k = (a_k - b_k) * (a_k - b_k);
+ *    t_j = m_j + m_{j+4} and t_{j+4} = m_{j+8} + m_{j+12} for j = 0 .. 3; s_j += (t_j + t_{j+4}).  Then pairs of columns: s0 += m, s1 += m.  Then one
+ *    last column: s0 += m.  Finally s0 += s2; s1 += s3; s0 += s1.
+ * C. exp_ref (CompVMathExpExp_minpack1_64f64f_C, base/math/compv_math_exp.cxx:83-123, after herumi/fmath): x clipped to [ExpMin, ExpMax] =
+ *    [-708.39641853226408, 709.78271289338397]; d = x * ca + b with b = 3 * 2^51; t = (d - b) * cra - x; u = ((bits(d) + 2095104) >> 11) << 52;
+ *    y = (C3 - t) * (t * t) * C2 - t + C1 in C's precedence; the result is y * asdouble(u | T[bits(d) & 2047]).  T[i] holds the 52 mantissa bits of
+ *    pow(2.0, i / 2048.0), built on the host with the C library's pow when a handle is made; ca = 2954.6394437405970 (2048 / ln 2),
+ *    cra = 0.00033845077175778578, C1 = 1, C2 = 0.16666666685227835, C3 = 3.0000000027955394.
+ * D. LINEAR kernel value (Kernel::dot on the indexed path, :410-430): one accumulator, sum += x_j * sv_j for j = 0 .. dim - 1 in order.
+ * E. Decision (:2743-2782): start[c] = the prefix sums of nSV.  For each pair i < j in row-major order, index p:
+ *    sumi = dot(svCoef[j - 1] + start[i], K + start[i], nSV[i]); sumj = dot(svCoef[i] + start[j], K + start[j], nSV[j]); dot is CompVMathDotDot_C
+ *    (:42-87), the 16 / 2 / 1 structure of B on products, the groups counted from the segment's start; dec[p] = (sumi + sumj) - rho[p];
+ *    dec[p] > 0 votes for i, anything else for j.  The label is label[c] of the first class with the most votes.
+ * F. Accepted: RBF and LINEAR C-SVC; 2 <= nrClass <= 32; totalSV >= 1, dim >= 1, totalSV * dim and totalSV * (nrClass - 1) below 2^31; nSV >= 0
+ *    adding up to totalSV; in a file, dense SV lines whose indices are exactly 1 .. dim in order on every line (the reference asserts the count at
+ *    :3476).  Refused with COMPVHIP_E_INVALID_PARAMETER: POLY, SIGMOID, PRECOMPUTED, nu-SVC, one-class, the two SVR types, sparse SV lines, and a file
+ *    that does not open or parse.  Queries must be finite: a NaN or an infinity gives an unspecified value, never a fault.
+ * Out of scope: training and cross-validation; probA / probB and svm_predict_distance (the reference calls it "not fully tested"; a file's probA /
+ *    probB lines are read over); the KNN / annoy classifier; sliding windows.
+ * Streams.  As the curve-fit handle, an SVM handle takes its stream at creation (the descriptor): compvhip_svm_predict is asynchronous on it,
+ *    compvhip_svm_predict_host and the create calls wait.
+ * Alignment.  Vectors by their element size (4 or 8 bytes); d_dec and d_kvalues 8 bytes; d_labels 4 bytes.  A misaligned pointer is refused with
+ *    COMPVHIP_E_INVALID_PARAMETER and nothing is written. */
+enum {
+	COMPVHIP_SVM_KERNEL_LINEAR = 0,            /* libsvm's kernel_type numbers */
+	COMPVHIP_SVM_KERNEL_RBF = 2
+};
+enum {
+	COMPVHIP_SVM_F32 = 0,
+	COMPVHIP_SVM_F64 = 1
+};
+typedef struct compvhip_svm_model {            /* HOST arrays; compvhip_svm_create copies them */
+	uint32_t size;              /* sizeof(compvhip_svm_model) */
+	int32_t kernel;             /* COMPVHIP_SVM_KERNEL_* */
+	int32_t nrClass;
+	int32_t totalSV;
+	int32_t dim;
+	int32_t reserved;           /* 0 */
+	double gamma;               /* RBF */
+	const double* sv;           /* [totalSV][dim] */
+	const double* svCoef;       /* [nrClass - 1][totalSV] */
+	const double* rho;          /* [nrClass * (nrClass - 1) / 2] */
+	const int32_t* nSV;         /* [nrClass] */
+	const int32_t* label;       /* [nrClass] */
+} compvhip_svm_model;
+typedef struct compvhip_svm_desc {
+	uint32_t size;              /* sizeof(compvhip_svm_desc) */
+	uint32_t maxVectors;        /* 1 .. 2^22 queries of one call; maxVectors * totalSV below 2^31 */
+	void* stream;               /* a hipStream_t; NULL = the default stream */
+} compvhip_svm_desc;
+typedef struct compvhip_svm_shape {
+	uint32_t size;              /* sizeof(compvhip_svm_shape), set by the caller */
+	int32_t kernel, nrClass, totalSV, dim;
+	int32_t pairs;              /* nrClass * (nrClass - 1) / 2: decision values of a query */
+	uint32_t maxVectors;        /* 0 from compvhip_svm_model_parse */
+	uint32_t reserved;
+	double gamma;
+} compvhip_svm_shape;
+typedef struct compvhip_svm compvhip_svm;   /* a model on the device and the scratch for maxVectors queries */
+
+/* All device memory is allocated here -- the model, the table of item C, maxVectors * totalSV float64 kernel values, and the staging of
+ * compvhip_svm_predict_host (at most 512 vectors, their labels and decision values) -- and released by compvhip_svm_destroy: no later call allocates.
+ * The K scratch is not sliced: a handle whose maxVectors * totalSV reaches 2^31 (16 GiB) is refused; call with fewer vectors at a time instead.
+ * Destroy it BEFORE its context.  Not re-entrant.  A null pointer, a wrong size field, a model item F refuses, maxVectors outside 1 .. 2^22:
+ * COMPVHIP_E_INVALID_PARAMETER, *svm = NULL.  Waits for the upload on the descriptor's stream. */
+COMPVHIP_API int compvhip_svm_create(compvhip_ctx* ctx, const compvhip_svm_model* model, const compvhip_svm_desc* desc, compvhip_svm** svm);
+/* The same from a libsvm model file (svm_save_model's text, parsed as svm_load_model does, strtod in the C locale). */
+COMPVHIP_API int compvhip_svm_create_from_file(compvhip_ctx* ctx, const char* path, const compvhip_svm_desc* desc, compvhip_svm** svm);
+COMPVHIP_API void compvhip_svm_destroy(compvhip_svm* svm);
+COMPVHIP_API int compvhip_svm_info(compvhip_svm* svm, compvhip_svm_shape* shape);
+/* d_vectors: [n][strideElems] float32 (COMPVHIP_SVM_F32) or float64 (COMPVHIP_SVM_F64), strideElems >= dim; elements at and behind dim are never
+ * read.  d_labels: [n] int32.  d_dec: NULL or [n][pairs] float64.  d_kvalues: NULL or [n][totalSV] float64 (NULL: the handle's scratch holds them).
+ * 1 <= n <= maxVectors.  A null handle, d_vectors or d_labels, an unknown type, n outside 1 .. maxVectors, strideElems < dim, n * strideElems at or
+ * beyond 2^40, a misaligned pointer: COMPVHIP_E_INVALID_PARAMETER, nothing written.  Elements behind n are never written.  Asynchronous on the handle's
+ * stream; deterministic run to run. */
+COMPVHIP_API int compvhip_svm_predict(compvhip_svm* svm, const void* d_vectors, int type, size_t n, size_t strideElems, int32_t* d_labels, double* d_dec,
+                                      double* d_kvalues);
+/* The same on HOST arrays, any n >= 1: slices of at most min(maxVectors, 512) vectors through the handle's staging.  labels: [n]; dec: NULL or
+ * [n][pairs].  Waits. */
+COMPVHIP_API int compvhip_svm_predict_host(compvhip_svm* svm, const void* vectors, int type, size_t n, size_t strideElems, int32_t* labels, double* dec);
+/* Per-kernel timing of the handle's last call, as compvhip_matcher_set_timing / _get_timing: entries svm_kvalues_kernel, svm_decide_kernel. */
+COMPVHIP_API int compvhip_svm_set_timing(compvhip_svm* svm, int enabled);
+COMPVHIP_API int compvhip_svm_get_timing(compvhip_svm* svm, const char** names, float* ms, int cap);
+/* Item C on the host (standard library only, no GPU): out[i] = exp_ref of in[i] for i < n. */
+COMPVHIP_API int compvhip_svm_exp_f64(const double* in, double* out, size_t n);
+/* The file parser on the host (no GPU).  shape (its size field set) receives the model's numbers; every array may be NULL (a first call learns the
+ * sizes) or has room for sv[totalSV][dim], svCoef[nrClass - 1][totalSV], rho[pairs], nSV[nrClass], label[nrClass].  A null path or shape, a wrong size
+ * field, a file item F refuses: COMPVHIP_E_INVALID_PARAMETER, nothing written. */
+COMPVHIP_API int compvhip_svm_model_parse(const char* path, compvhip_svm_shape* shape, double* sv, double* svCoef, double* rho, int32_t* nSV, int32_t* label);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel

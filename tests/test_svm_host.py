@@ -1,0 +1,96 @@
+"""compv_amd/csrc/svm_math.hpp -- the arithmetic the SVM kernels are made of, and the model-file parser -- run on the host by tests/host/svm_math_check.cpp
+(a stand-alone program, standard library only, no GPU, built with AddressSanitizer and UBSan, nothing preloaded) and held against the fixture the compiled
+reference made and tests/svm_model.py, byte for byte: the parsed arrays, kernel values, decision values, labels, exp_ref.  The program feeds the header
+the way the kernels do (32-column chunks, one accumulator of a dot at a time) and aborts when that differs from the header's one-call forms.  The GPU
+tests (tests/test_gpu_svm.py) hold the kernels against the same fixture."""
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import svm_cases as sc
+import svm_model as sm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "host", "svm_math_check.cpp")
+CASES = sc.all_cases()
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler"
+    exe = tmp_path_factory.mktemp("svm") / "svm_math_check"
+    # the sanitizers' runtimes are linked statically: the program needs nothing preloaded
+    build = subprocess.run([cxx, "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                            "-static-libasan", "-static-libubsan", SRC, "-o", str(exe)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+
+    def run(model_file, x=None, stride=None, exp_in=()):
+        """-> None when the parser refuses the file, else dict(kernel, nr_class, l, dim, gamma, sv, coef, rho, nsv, label, labels, dec, K, exp)"""
+        d = exe.parent
+        x = np.zeros((0, 1), np.float64) if x is None else x
+        stride = x.shape[1] if stride is None else stride
+        with open(d / "in.bin", "wb") as f:
+            f.write(struct.pack("<3i", 0 if x.dtype == np.float32 else 1, len(x), stride))
+            f.write(sc.padded(x, stride, 7e30).tobytes())
+            f.write(struct.pack("<i", len(exp_in)) + np.ascontiguousarray(exp_in, np.float64).tobytes())
+        r = subprocess.run([str(exe), str(model_file), str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True, timeout=120)
+        assert not r.stderr, r.stdout + r.stderr          # a sanitizer report goes to stderr
+        if r.returncode == 3:
+            assert r.stdout.startswith("refused: ")
+            return None
+        assert r.returncode == 0, r.stdout
+        raw = open(d / "out.bin", "rb").read()
+        kernel, nc, l, dim = struct.unpack_from("<4i", raw)
+        o = 16
+        P, n = nc * (nc - 1) // 2, len(x)
+
+        def take(dtype, *shape):
+            nonlocal o
+            a = np.frombuffer(raw, dtype, int(np.prod(shape)), o).reshape(shape)
+            o += a.nbytes
+            return a
+        out = dict(kernel=kernel, nr_class=nc, l=l, dim=dim, gamma=take(np.float64, 1)[0], sv=take(np.float64, l, dim), coef=take(np.float64, nc - 1, l), rho=take(np.float64, P),
+                   nsv=take(np.int32, nc), label=take(np.int32, nc), labels=take(np.int32, n), dec=take(np.float64, n, P), K=take(np.float64, n, l), exp=take(np.float64, len(exp_in)))
+        assert o == len(raw)
+        return out
+    return run
+
+
+@pytest.mark.parametrize("c", CASES, ids=lambda c: c["id"])
+def test_header_equals_the_fixture(checker, c):
+    _, A = sc.golden()
+    cid = c["id"]
+    rec = sc.recorded_model(c)
+    X = sc.queries(c, rec)
+    for stride in (c["D"], c["D"] + 3):          # tight, and padded with a sentinel that would show in any result
+        got = checker(sc.model_path(cid), X, stride)
+        assert got is not None
+        assert (got["kernel"], got["nr_class"], got["l"], got["dim"]) == (rec.kernel, rec.nr_class, rec.l, rec.dim)
+        assert np.float64(got["gamma"]).tobytes() == np.float64(rec.gamma).tobytes()
+        for k, exp in (("sv", rec.sv), ("coef", rec.sv_coef), ("rho", rec.rho), ("nsv", rec.n_sv), ("label", rec.label)):
+            assert got[k].tobytes() == exp.tobytes(), (cid, k)
+        assert got["K"].tobytes() == A["K_" + cid].tobytes(), (cid, stride, "K")
+        assert got["dec"].tobytes() == A["dec_" + cid].tobytes(), (cid, stride, "dec")
+        assert got["labels"].tobytes() == A["lab_" + cid].tobytes(), (cid, stride, "labels")
+
+
+def test_exp_ref_of_the_header_equals_the_reference(checker):
+    _, A = sc.golden()
+    got = checker(sc.model_path("rbf_d1_c2"), exp_in=sc.exp_inputs())
+    assert got["exp"].tobytes() == A["exp_out"].tobytes() == sm.exp_ref(sc.exp_inputs()).tobytes()
+
+
+@pytest.mark.parametrize("name", sorted(sc.BAD_FILES))
+def test_the_header_refuses_bad_files(checker, tmp_path, name):
+    path = str(tmp_path / (name + ".model"))
+    sc.write_bad_file(path, name)
+    assert checker(path) is None
+
+
+def test_the_header_refuses_a_missing_file(checker, tmp_path):
+    assert checker(str(tmp_path / "nothing.model")) is None
