@@ -789,7 +789,7 @@ int compvhip_api::planShtImpl(compvhip_plan* p, const uint8_t* d_edges, int thre
 		if (d_lines && lineCap) {
 			Stamp s(p, st, "sht_sort_lines");
 			ShtSortArgs q;
-			q.sortedKeys = p->keysB; q.sortedVals = p->valsB; q.chunkHist = p->chunkHist; q.strengthStart = p->strengthStart; q.chunks = p->sortChunks;
+			q.rankKeys = p->keysB; q.chunkHist = p->chunkHist; q.strengthStart = p->strengthStart; q.chunks = p->sortChunks;
 			HIPCHK(ctx, launch_sht_sort_lines(a, q, frames, p->thetaStep, maxLines, d_lines, lineCap, st));
 		}
 		return COMPVHIP_OK;

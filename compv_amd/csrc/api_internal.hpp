@@ -223,7 +223,7 @@ struct compvhip_plan : TimingState {
 	DevBuf<float> hogCells;      // HOG (hog_kernels.hip), allocated on first use without a caller's map: the cell map [frames][cellsY][cellsX][nbins]
 	StatsScratch stats;          // image statistics (stats_kernels.hip), allocated on first use
 	int strengthBits = 16, keyBits = 0;
-	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 32 chunks of keys
+	// the line sort sized on the device (sht_sort_kernels.hip): used when a strength has at most 13 bits and a frame at most 16 chunks of keys
 	DevBuf<uint16_t> chunkHist; DevBuf<uint32_t> strengthStart; int sortChunks = 0; bool deviceSort = false;
 	// voting over image tiles (planned at plan creation: the per-tile edge counters live in `counters`)
 	bool voteTiles = false;                      // the tile grid exists

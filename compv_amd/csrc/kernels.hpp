@@ -178,16 +178,16 @@ int sht_lines_blocks(int R);
 hipError_t launch_sht_cartesian(const void* lines /*compvhip_line*/, const int* counts, size_t lineCap, int maxLines, int frames, int T, const float* cosT,
                                 const float* invSinT, float thetaStep, float widthF, float r, float* out /*[frames][lineCap][4]*/, hipStream_t stream);
 hipError_t launch_sht_acc_transpose(const uint16_t* accT, int R, int T, int accPitch, int32_t* out, size_t outStride, hipStream_t stream);
-// the line sort sized on the device (sht_sort_kernels.hip): counting sort on the strength, stable ranks from chunks sorted in the LDS
-constexpr int kShtSortChunk = 4096;             // lines per chunk (one workgroup)
+// the line sort sized on the device (sht_sort_kernels.hip): counting sort on the strength, stable ranks counted in order inside chunks of lines
+constexpr int kShtSortChunk = 8192;             // lines per chunk (one workgroup); a power of two below 65 536 (the chunk histogram is u16)
 constexpr int kShtSortMaxStrengthBits = 13;     // 8192 strength bins: max(W, H) <= 4095
-constexpr int kShtSortMaxChunks = 32;           // chunks per frame it is used for (line capacities up to 131 072 per frame)
+constexpr int kShtSortMaxChunks = 16;           // chunks per frame it is used for (line capacities up to 131 072 per frame)
 struct ShtSortArgs {
-	uint32_t* sortedKeys;     // [frames * lineCap] per line of a sorted chunk: (inverted strength << 12) | rank inside its run of equal strengths
-	uint32_t* sortedVals;     // [frames * lineCap] its accumulator cell
+	uint32_t* rankKeys;       // [frames * lineCap] per line, at its emission-order position (that of lineKeys / lineVals, which stay as they are: a replayed step
+	                          // reads them again): (inverted strength << 13) | number of earlier lines of its chunk with the same strength
 	uint16_t* chunkHist;      // [frames][chunks][8192] lines per inverted strength of a chunk (written whole by the chunks that have lines)
 	uint32_t* strengthStart;  // [frames][8192] first slot of an inverted strength in the frame's sorted line list
-	int chunks;               // chunks per frame = ceil(lineCap / 4096)
+	int chunks;               // chunks per frame = ceil(lineCap / 8192)
 };
 hipError_t launch_sht_sort_lines(const ShtArgs& a, const ShtSortArgs& q, int frames, float thetaStep, int maxLines, void* lines /*compvhip_line*/, size_t outCap,
                                  hipStream_t stream);

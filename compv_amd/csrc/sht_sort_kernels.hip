@@ -6,149 +6,133 @@
 // Why not the library sort: rocPRIM's device radix sort takes its size from the HOST and costs 35-50 us whatever the size (histogram + two onesweep passes
 // + their fills: 0.050 ms for 75 000 keys, 0.076 ms for 1.96 M; tools/microbench/sort_bench) -- at 1080p the sort of 75 000 real keys was 22 % of a step.
 // The line keys have structure a general sort cannot use: a strength has at most 13 bits (a cell never exceeds 2 max(W, H)), the emission order inside a frame
-// is the wanted tie order, frames are independent.  So the sort is a counting sort on the strength, per frame, whose stable ranks come from sorting CHUNKS of
-// 4096 consecutive lines in the LDS -- a stable LSD radix sort of the 13 strength bits, ranks from wave ballots -- and every size is read on the
-// device: the three launches cover the capacity, a chunk without lines returns at once.
-//   1. sht_chunk_sort_kernel   one workgroup per chunk: stable sort of the chunk's keys in the LDS; per line its rank inside its run of equal strengths
-//                              (lower bound by binary search), the chunk's strength histogram (u16 [8192], written whole: nothing to clear)
+// is the wanted tie order, frames are independent.  So the sort is a counting sort on the strength, per frame.  What a line needs for its slot is the number of
+// EARLIER lines of the frame with its strength; inside a CHUNK of 8192 consecutive lines that number is counted in order, nothing is sorted or moved, and every
+// size is read on the device: the three launches cover the capacity, a chunk without lines returns at once.
+//   1. sht_chunk_rank_kernel   one workgroup per chunk: per line, at its own position, its rank among the chunk's lines of equal strength (ordered counting:
+//                              wave ballots inside a row of 64 lines, one returning LDS add per group of equal strengths, rows committed in emission order);
+//                              the counters left behind are the chunk's strength histogram (u16 [8192], written whole: nothing to clear)
 //   2. sht_strength_scan_kernel  one workgroup per frame: lines per strength over the frame's chunks, exclusive scan in descending strength order
 //   3. sht_place_lines_kernel  one thread per line: slot = start[strength] + lines of that strength in the frame's earlier chunks + rank; the slot's
 //                              compvhip_line is written directly (rho, theta, strength, row, col: what sht_decode_kernel did behind the library sort)
-// Larger strengths (max(W, H) > 4095) or line capacities beyond 32 chunks per frame keep the library sort (sht_kernels.hip).
+// Larger strengths (max(W, H) > 4095) or line capacities beyond 16 chunks per frame keep the library sort (sht_kernels.hip).
 #include "device.hpp"
 
-#include <type_traits>
+#include <algorithm>
 
 namespace compvhip {
 
 namespace {
 
 constexpr int kChunk = kShtSortChunk;        // lines per chunk
-constexpr int kSortThreads = 1024;
+constexpr int kChunkBits = __builtin_ctz(kChunk);   // bits of a rank inside a chunk, of a position inside a chunk
+constexpr int kChunkRows = kChunk / 64;      // rows of 64 consecutive lines, one line per lane
+constexpr int kRankWaves = 16;               // waves of a rank workgroup, each owning kChunkRows / kRankWaves consecutive rows
+constexpr int kSortThreads = 1024;           // the scan kernel's workgroup: 8 strengths per thread
 constexpr int kBins = 1 << kShtSortMaxStrengthBits;   // 8192 strengths
-static_assert(kChunk == 4096 && kBins == 8192, "key layout: 13 bits of inverted strength above 12 bits of chunk position");
+static_assert(kChunk == 1 << kChunkBits && kShtSortMaxStrengthBits + kChunkBits <= 32, "rank word: the inverted strength above the rank");
+static_assert(kBins == 8 * kSortThreads, "the scan kernel's thread owns 8 strengths");
+static_assert(kChunk < 65536, "a chunk's histogram is u16");
+static_assert(kChunkRows % kRankWaves == 0 && kRankWaves <= 16, "whole rows per wave; dense_frame_base's partial sums have 16 slots");
 
 } // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kSortThreads) void sht_chunk_sort_kernel(ShtArgs a, ShtSortArgs q)
+// rank(i) = number of j < i in the chunk with strength(j) == strength(i), for every line i of the chunk at its own position.
+// Row = 64 consecutive lines, one per lane.  Inside a row the lanes of equal strength find each other by one ballot per strength bit; a lane's rank inside the
+// row is the number of lower lanes of its group, and the group's first lane adds the group's size to count[strength] in the LDS with ONE returning add: what
+// comes back is the number of equal strengths in all earlier rows -- provided the rows are committed in emission order.  (64 lanes adding 1 each in one
+// instruction would not do: the order of same-address LDS atomics inside an instruction is not specified, and the order among equal strengths is the product's
+// contract.)  A wave commits its own rows in order (LDS operations of a wave are executed in issue order); the waves take turns in wave order, one barrier
+// per turn, and every wave has done its ballots -- the bulk of the instructions -- before the first turn.  (One wave per chunk, looping over the rows with
+// the next rows' keys in flight and no barrier at all, was twice as slow alone and slower in the two-lane step: docs/kernels/sht_line_stage.md.)
+// count[] holds two u16 counters per word, chunkHist's own layout (a chunk has 8192 lines: no carry from the low half; the leaders of strengths 2k and 2k+1
+// may add to one word in one instruction in either order, the half a leader reads back is not touched by the other), and only 2^strengthBits of them.
+// LDS: 384 B + 2 B per strength = 16.4 KB at 13 strength bits (4K), 8.4 KB at 12 (1080p).  Beside a 4K voting workgroup's 155.6 KB a CU has 4.4 KB left: none
+// of these workgroups fits there at 4K or 1080p (8192 counters in 4.4 KB would be 4 bits each), they run on the CUs the vote has left.  On a CU without a voting
+// workgroup the wave slots bound them: two workgroups of 16 waves (the sort this replaces: 52 KB, 1024 threads, ~20 barriers).
+__global__ __launch_bounds__(kRankWaves * 64) void sht_chunk_rank_kernel(ShtArgs a, ShtSortArgs q)
 {
-	__shared__ uint32_t s_key[kChunk];
-	__shared__ uint32_t s_hist[kBins];
-	__shared__ uint32_t s_cnt[kSortThreads], s_wsum[kSortThreads / 64];
-	__shared__ unsigned long long s_part[kSortThreads / 64];
+	constexpr int THREADS = kRankWaves * 64, B = kChunkRows / kRankWaves;   // B consecutive rows per wave, all of them kept in registers until the wave's turn
+	extern __shared__ __attribute__((aligned(16))) uint32_t s_rank[];
+	unsigned long long* s_part = reinterpret_cast<unsigned long long*>(s_rank);   // [16]
+	uint32_t* s_idle = s_rank + 32;                                                // [64] a word per lane for the lanes with nothing to add
+	uint32_t* s_cnt = s_rank + 96;                                                 // [max(2^strengthBits / 2, 4)]
 	const int frame = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
 	const size_t nf = min((size_t)max(a.lineCounts[frame], 0), a.lineCap);
 	const size_t c0 = (size_t)chunk * kChunk;
 	if (c0 >= nf) return;   // uniform: a chunk without lines
 	const int m = (int)min((size_t)kChunk, nf - c0);
-	const size_t base = dense_frame_base<kSortThreads>(a.lineCounts, frame, a.lineCap, s_part) + c0;
-	const uint32_t mask = (1u << a.strengthBits) - 1u;
-	const uint32_t* __restrict__ kin = a.lineKeys + base;
-	const uint32_t* __restrict__ vin = a.lineVals + base;
-	// thread t holds the chunk's elements u * 1024 + t, u = 0 .. 3 (a wave = 64 consecutive elements of each quarter)
-	uint32_t e[4];
-	{
-		uint32_t kraw[4];
-#pragma unroll
-		for (int u = 0; u < 4; ++u) kraw[u] = kin[min(u * kSortThreads + t, m - 1)];   // clamped, and all four in flight: a load written under `i < m` is compiled into
-		asm volatile("" : "+v"(kraw[0]), "+v"(kraw[1]), "+v"(kraw[2]), "+v"(kraw[3]));   // branch -> load -> s_waitcnt, one memory latency each
-#pragma unroll
-		for (int u = 0; u < 4; ++u) {
-			const int i = u * kSortThreads + t;
-			e[u] = i < m ? (((mask - (kraw[u] & mask)) << 12) | (uint32_t)i) : 0xffffffffu;
-		}
-	}
-#pragma unroll
-	for (int u = 0; u < kBins / kSortThreads; ++u) s_hist[t + u * kSortThreads] = 0u;
-	// Stable LSD radix sort of the 13 inverted-strength bits in the LDS, digits of 4 + 3 + 3 + 3 bits (the position bits below them only ride along: equal
-	// strengths keep the emission order because every pass is stable).  Per pass and element: the lanes of its wave with the same digit (one ballot per
-	// digit bit) give its rank inside (quarter, wave); the counts of every (digit, quarter, wave) -- 1024 of them at most, one per thread -- are scanned
-	// over the block in exactly that order, which is digit-major and, inside a digit, the elements' order.  A bitonic network on the unique key
-	// (strength, position) does the same job with 45 of its 78 steps as wave shuffles: ds_bpermute issues at ~16 cycles on the CU's one LDS pipe, 28 us of
-	// a 38 us workgroup (rocprofv3, profiles/r05); this version needs five barriers and a dozen plain LDS accesses per pass.
 	const int lane = t & 63, wave = t >> 6;
-	auto radix_pass = [&](auto nbits, int shift) {
-		constexpr int NB = decltype(nbits)::value, BINS = 1 << NB;
-		s_cnt[t] = 0u;
-		__syncthreads();
-		uint32_t rank[4], slot[4];
+	const int bits = a.strengthBits;
+	const uint32_t mask = (1u << bits) - 1u;
+	const int words = max((1 << bits) >> 1, 4);
+	for (int w = t; w < words; w += THREADS) s_cnt[w] = 0u;
+	const size_t base = dense_frame_base<THREADS>(a.lineCounts, frame, a.lineCap, s_part) + c0;   // (its barrier is also the one behind the zeroes)
+	const uint32_t* __restrict__ kin = a.lineKeys + base;
+	uint32_t* __restrict__ kout = q.rankKeys + base;
+	const int row0 = wave * B;
+
+	struct Row { uint32_t inv, rank, size; int first; bool valid; };
+	// clamped, unconditional loads, all in flight: a load written under `i < m` is compiled into branch -> load -> s_waitcnt, one memory latency each
+	auto load_rows = [&](uint32_t (&k)[B], int r0) {
 #pragma unroll
-		for (int u = 0; u < 4; ++u) {
-			const uint32_t d = (e[u] >> shift) & (uint32_t)(BINS - 1);
-			uint64_t same = ~0ull;
-#pragma unroll
-			for (int b = 0; b < NB; ++b) {
-				const bool bit = (d >> b) & 1u;
-				const uint64_t bal = __ballot(bit);
-				same &= bit ? bal : ~bal;
-			}
-			rank[u] = __builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0u));
-			slot[u] = (d * 4u + (uint32_t)u) * (uint32_t)(kSortThreads / 64) + (uint32_t)wave;
-			if (rank[u] == 0u) s_cnt[slot[u]] = (uint32_t)__popcll(same);   // the group's first lane
-		}
-		__syncthreads();
-		// exclusive scan of the 1024 counts, one per thread (unused entries of a pass with fewer digits are zero)
-		const uint32_t c = s_cnt[t];
-		const uint32_t incl = wave_incl_scan(c, lane);   // (the block part: block_excl_scan's, with predicated unrolled wave sums)
-		if (lane == 63) s_wsum[wave] = incl;
-		__syncthreads();
-		uint32_t before = 0;
-#pragma unroll
-		for (int w = 0; w < kSortThreads / 64; ++w) before += (w < wave) ? s_wsum[w] : 0u;
-		s_cnt[t] = before + incl - c;
-		__syncthreads();
-#pragma unroll
-		for (int u = 0; u < 4; ++u) s_key[s_cnt[slot[u]] + rank[u]] = e[u];
-		__syncthreads();
-#pragma unroll
-		for (int u = 0; u < 4; ++u) e[u] = s_key[u * kSortThreads + t];
+		for (int j = 0; j < B; ++j) k[j] = kin[min((r0 + j) * 64 + lane, m - 1)];
 	};
-	radix_pass(std::integral_constant<int, 4>{}, 12);
-	radix_pass(std::integral_constant<int, 3>{}, 16);
-	radix_pass(std::integral_constant<int, 3>{}, 19);
-	radix_pass(std::integral_constant<int, 3>{}, 22);
-	// s_key holds the sorted chunk (the last pass wrote it, and every thread has passed the barrier behind that)
-	// rank of a line inside its run of equal strengths = its position - the run's first position (lower bound of (inv << 12))
-	uint32_t* __restrict__ kout = q.sortedKeys + base;
-	uint32_t* __restrict__ vout = q.sortedVals + base;
-	{
-		// four lines per thread (i = t + 1024 u: coalesced stores), their searches and gathers interleaved: 12 dependent LDS reads and one global
-		// gather per line, one after the other, were 8 us of this kernel
-		uint32_t kk[4]; int lo[4], hi[4];
+	auto ballot_rows = [&](const uint32_t (&k)[B], int r0, Row (&row)[B]) {
+		uint64_t same[B];
 #pragma unroll
-		for (int u = 0; u < 4; ++u) { const int i = min(t + u * kSortThreads, m - 1); kk[u] = s_key[i]; lo[u] = 0; hi[u] = i; }
+		for (int j = 0; j < B; ++j) {
+			row[j].valid = (r0 + j) * 64 + lane < m;
+			row[j].inv = mask - (k[j] & mask);
+			same[j] = __ballot(row[j].valid);   // lines past the chunk's end (the highest lanes of its last row) join no group
+		}
+		for (int b = 0; b < bits; ++b) {
 #pragma unroll
-		for (int s = 0; s < 12; ++s) {
-#pragma unroll
-			for (int u = 0; u < 4; ++u) {   // the first position whose key >= (inv << 12), in [0, i]
-				const int mid = (lo[u] + hi[u]) >> 1;
-				const bool ge = s_key[mid] >= (kk[u] & ~4095u);
-				hi[u] = ge ? mid : hi[u];
-				lo[u] = ge ? lo[u] : mid + 1;
+			for (int j = 0; j < B; ++j) {
+				const bool bit = (row[j].inv >> b) & 1u;
+				const uint64_t bal = __ballot(bit);
+				same[j] &= bit ? bal : ~bal;
 			}
 		}
-		uint32_t cell[4];
 #pragma unroll
-		for (int u = 0; u < 4; ++u) cell[u] = vin[kk[u] & 4095u];
-		asm volatile("" : "+v"(cell[0]), "+v"(cell[1]), "+v"(cell[2]), "+v"(cell[3]));
-#pragma unroll
-		for (int u = 0; u < 4; ++u) {
-			const int i = t + u * kSortThreads;
-			if (i < m) {
-				kout[i] = (kk[u] & ~4095u) | (uint32_t)(i - lo[u]);
-				vout[i] = cell[u];
-				atomicAdd(&s_hist[kk[u] >> 12], 1u);
-			}
+		for (int j = 0; j < B; ++j) {
+			row[j].rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(same[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same[j], 0u));
+			row[j].size = (uint32_t)__popcll(same[j]);
+			row[j].first = __ffsll((unsigned long long)same[j]) - 1;   // (a valid lane is in its own group: never -1)
 		}
+	};
+	// The adds of a wave's rows, in row order and all in flight: every lane adds, so that no add sits behind a branch and a wait of its own -- a group's first
+	// lane its group's size to the strength's counter, every other lane nothing to a word of its own.
+	auto commit_rows = [&](const Row (&row)[B], uint32_t (&old)[B]) {
+#pragma unroll
+		for (int j = 0; j < B; ++j) {
+			const bool first = row[j].valid && row[j].rank == 0u;
+			old[j] = atomicAdd(first ? &s_cnt[row[j].inv >> 1] : &s_idle[lane], first ? row[j].size << ((row[j].inv & 1u) << 4) : 0u);
+		}
+	};
+	auto store_rows = [&](int r0, const Row (&row)[B], const uint32_t (&old)[B]) {
+#pragma unroll
+		for (int j = 0; j < B; ++j) {
+			const uint32_t before = (__shfl(old[j], row[j].first) >> ((row[j].inv & 1u) << 4)) & 0xffffu;   // equal strengths in the earlier rows
+			if (row[j].valid) kout[(r0 + j) * 64 + lane] = (row[j].inv << kChunkBits) | (before + row[j].rank);
+		}
+	};
+
+	uint32_t k[B], old[B];
+	Row row[B];
+	load_rows(k, row0);
+	ballot_rows(k, row0, row);
+	const int turns = (m + B * 64 - 1) / (B * 64);   // waves that have lines
+	for (int turn = 0; turn < turns; ++turn) {
+		if (wave == turn) commit_rows(row, old);
+		__syncthreads();
 	}
-	__syncthreads();
-	// the chunk's histogram, whole (u16: a chunk has 4096 lines)
+	if (wave < turns) store_rows(row0, row, old);
+	// the chunk's histogram, whole: the counters, and zeroes for the strengths this plan cannot have
 	uint4* __restrict__ hout = reinterpret_cast<uint4*>(q.chunkHist + ((size_t)frame * q.chunks + chunk) * kBins);
-	{
-		const uint32_t* h = s_hist + 8 * t;
-		hout[t] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
-	}
+	const uint4* cnt4 = reinterpret_cast<const uint4*>(s_cnt);
+	for (int v = t; v < kBins / 8; v += THREADS) hout[v] = 4 * v < words ? cnt4[v] : make_uint4(0u, 0u, 0u, 0u);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -210,11 +194,15 @@ __global__ __launch_bounds__(256) void sht_place_lines_kernel(ShtArgs a, ShtSort
 	size_t limit = nf;      // slots of the frame that are written: min(lines, lineCap, maxLines, outCap)
 	if (maxLines > 0 && limit > (size_t)maxLines) limit = (size_t)maxLines;
 	if (limit > outCap) limit = outCap;
-	const uint32_t kv = q.sortedKeys[base + i];
-	const uint32_t inv = kv >> 12, rank = kv & 4095u;
-	const int c = (int)(i >> 12);
-	// slot = first slot of the strength in the frame + its lines in the frame's earlier chunks + rank inside the chunk.  (Per-chunk starts written by the scan
-	// kernel instead: 15 MB more traffic from 32 workgroups, 20 + 16 us against 8 + 18 for this loop at 4K.)  Four histograms in flight, clamped loads.
+	const uint32_t kv = q.rankKeys[base + i];
+	const uint32_t cell = a.lineVals[base + i];   // emission order: the line was never moved.  Loaded with its rank word, ahead of the cut below: nothing has
+	                                              // read the cells since sht_lines_kernel wrote them, and behind the histogram loads the miss cost 1.5 us
+	const uint32_t inv = kv >> kChunkBits, rank = kv & (uint32_t)(kChunk - 1);
+	const int c = (int)(i >> kChunkBits);
+	// slot = first slot of the strength in the frame + its lines in the frame's earlier chunks + rank inside the chunk.  The lines of a wave have unrelated
+	// strengths (emission order), so these loads and the store below are gathers and a scatter: 23 us per 32 x 4K launch, 19 while the chunks were sorted.
+	// (Per-chunk starts written by the scan kernel instead: 15 MB more traffic from 32 workgroups, 20 + 16 us against 8 + 18 for this loop at 4K with sorted
+	// chunks of 4096.)  Four histograms in flight, clamped loads.
 	size_t pos = (size_t)q.strengthStart[(size_t)frame * kBins + inv] + rank;
 	const uint16_t* __restrict__ h = q.chunkHist + (size_t)frame * q.chunks * kBins + inv;
 	for (int c0 = 0; c0 < c; c0 += 4) {
@@ -225,7 +213,6 @@ __global__ __launch_bounds__(256) void sht_place_lines_kernel(ShtArgs a, ShtSort
 		for (int u = 0; u < 4; ++u) pos += (c0 + u < c) ? v[u] : 0u;
 	}
 	if (pos >= limit) return;
-	const uint32_t cell = q.sortedVals[base + i];
 	const int row = (int)(cell / (uint32_t)a.T), col = (int)(cell - (uint32_t)row * (uint32_t)a.T);
 	compvhip_line o;
 	o.rho = (float)(a.barrier - row);            // static_cast<float>(barrier - row), houghsht.cxx:661
@@ -239,7 +226,8 @@ __global__ __launch_bounds__(256) void sht_place_lines_kernel(ShtArgs a, ShtSort
 hipError_t launch_sht_sort_lines(const ShtArgs& a, const ShtSortArgs& q, int frames, float thetaStep, int maxLines, void* lines, size_t outCap, hipStream_t stream)
 {
 	if (!lines || !outCap) return hipSuccess;
-	hipLaunchKernelGGL(sht_chunk_sort_kernel, dim3((unsigned)q.chunks, (unsigned)frames), dim3(kSortThreads), 0, stream, a, q);
+	const size_t rankLds = 384 + sizeof(uint32_t) * (size_t)std::max((1 << a.strengthBits) >> 1, 4);
+	hipLaunchKernelGGL(sht_chunk_rank_kernel, dim3((unsigned)q.chunks, (unsigned)frames), dim3(kRankWaves * 64), rankLds, stream, a, q);
 	hipLaunchKernelGGL(sht_strength_scan_kernel, dim3((unsigned)frames), dim3(kSortThreads), 0, stream, a, q);
 	hipLaunchKernelGGL(sht_place_lines_kernel, dim3((unsigned)(q.chunks * (kChunk / 256)), (unsigned)frames), dim3(256), 0, stream, a, q, thetaStep, maxLines,
 	                   reinterpret_cast<compvhip_line*>(lines), outCap);

@@ -321,7 +321,7 @@ COMPVHIP_API int compvhip_plan_pipeline(compvhip_plan* plan, const uint8_t* d_in
  * Speculative rounds: a step enqueues as many hysteresis rounds as the plan's last 8 asynchronous steps needed (the first round that changed nothing,
  * inclusive): 3 for a new plan, 2 once four steps have needed no more (the benchmark's frames: round 0 does the work, round 1 confirms), never more than 3; a
  * step that needs more is the replay described above, and the plan enqueues 3 again for the steps after it.
- * A second replay cause exists only on the library-sort fallback (max(W, H) > 4095, or more than 32 chunks of 4096 lines per frame): there the step
+ * A second replay cause exists only on the library-sort fallback (max(W, H) > 4095, or more than 16 chunks of 8192 lines per frame): there the step
  * sorts a PREDICTED range of the line keys -- the largest line total of the plan's last 8 steps + 1/16 + 4096 -- and compvhip_plan_wait replays the
  * step when its real total exceeded the prediction.  Content whose line count jumps from step to step therefore replays often on such plans, and each
  * replay drains the stream and cascades to the later tickets that share output buffers; plans on the device-sized sort (every size up to 4095 x 4095
