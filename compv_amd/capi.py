@@ -44,6 +44,8 @@ HOMOGRAPHY_RESULT_DTYPE = np.dtype([("H", "<f8", (9,)), ("variance", "<f8"), ("i
 CURVEFIT_LINE, CURVEFIT_PARABOLA, CURVEFIT_PARABOLA_SIDEWAYS = 0, 1, 2                         # COMPVHIP_CURVEFIT_*
 SVM_KERNEL_LINEAR, SVM_KERNEL_RBF = 0, 2                                                       # COMPVHIP_SVM_KERNEL_* (libsvm's kernel_type numbers)
 SVM_F32, SVM_F64 = 0, 1                                                                        # COMPVHIP_SVM_F32 / _F64
+UNDISTORT_F32, UNDISTORT_F64 = 0, 1                                                            # COMPVHIP_UNDISTORT_F32 / _F64
+UNDISTORT_COEFFS = 14                                                                          # values of a camera's coefficient record
 CURVEFIT_RESULT_DTYPE = np.dtype([("A", "<f8"), ("B", "<f8"), ("C", "<f8"), ("inliers", "<i4"), ("bestTry", "<i4"), ("status", "<i4"), ("k", "<i4")])   # compvhip_curvefit_result
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
@@ -82,6 +84,9 @@ EXPORTS = [
     "compvhip_convert_layout", "compvhip_convert_frames", "compvhip_convert_u8",
     "compvhip_svm_create", "compvhip_svm_create_from_file", "compvhip_svm_destroy", "compvhip_svm_info", "compvhip_svm_predict", "compvhip_svm_predict_host",
     "compvhip_svm_set_timing", "compvhip_svm_get_timing", "compvhip_svm_exp_f64", "compvhip_svm_model_parse",
+    "compvhip_undistort_coeffs_f32", "compvhip_undistort_coeffs_f64", "compvhip_undistort_map_f32", "compvhip_undistort_map_f64",
+    "compvhip_undistort_create", "compvhip_undistort_destroy", "compvhip_undistort_frames", "compvhip_undistort_maps", "compvhip_undistort_points",
+    "compvhip_undistort_project", "compvhip_undistort_u8", "compvhip_undistort_set_timing", "compvhip_undistort_get_timing",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -194,6 +199,15 @@ class SvmShape(C.Structure):
 
     def __init__(self):
         super().__init__(C.sizeof(SvmShape))
+
+
+class UndistortDesc(C.Structure):
+    """compvhip_undistort_desc (include/compv_hip.h): the geometry of the fused form, the caps of the point calls and the stream all calls run on"""
+    _fields_ = [("size", C.c_uint32), ("W", C.c_uint32), ("H", C.c_uint32), ("S", C.c_uint32), ("frames", C.c_uint32), ("Wout", C.c_uint32), ("Hout", C.c_uint32),
+                ("x0", C.c_uint32), ("y0", C.c_uint32), ("maxSets", C.c_uint32), ("maxPoints", C.c_uint32), ("reserved", C.c_uint32), ("stream", C.c_void_p)]
+
+    def __init__(self, W=0, H=0, S=0, frames=0, Wout=0, Hout=0, x0=0, y0=0, max_sets=0, max_points=0, stream=0):
+        super().__init__(C.sizeof(UndistortDesc), W, H, S, frames, Wout, Hout, x0, y0, max_sets, max_points, 0, stream or None)
 
 
 def curvefit_model_points(model):
@@ -433,6 +447,20 @@ def load():
     L.compvhip_svm_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
     L.compvhip_svm_exp_f64.argtypes = [vp, vp, sz]
     L.compvhip_svm_model_parse.argtypes = [C.c_char_p, C.POINTER(SvmShape), vp, vp, vp, vp, vp]
+    for f in (L.compvhip_undistort_coeffs_f32, L.compvhip_undistort_coeffs_f64):
+        f.argtypes = [vp, vp, i32, vp]
+    for f in (L.compvhip_undistort_map_f32, L.compvhip_undistort_map_f64):
+        f.argtypes = [vp, vp, i32, sz, sz, sz, sz, vp, vp]
+    L.compvhip_undistort_create.argtypes = [vp, C.POINTER(UndistortDesc), C.POINTER(vp)]
+    L.compvhip_undistort_destroy.argtypes = [vp]
+    L.compvhip_undistort_destroy.restype = None
+    L.compvhip_undistort_frames.argtypes = [vp, vp, vp, vp, i32, sz, i32, C.POINTER(Roi), C.c_uint8, vp, sz]
+    L.compvhip_undistort_maps.argtypes = [vp, vp, vp, i32, sz, i32, vp, vp]
+    L.compvhip_undistort_points.argtypes = [vp, vp, vp, i32, sz, i32, vp, sz, sz, vp, vp]
+    L.compvhip_undistort_project.argtypes = [vp, vp, vp, i32, sz, vp, vp, sz, sz, vp, vp]
+    L.compvhip_undistort_u8.argtypes = [vp, vp, sz, sz, sz, vp, vp, i32, sz, sz, i32, C.POINTER(Roi), C.c_uint8, vp, sz, sz, sz]
+    L.compvhip_undistort_set_timing.argtypes = [vp, i32]
+    L.compvhip_undistort_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -459,6 +487,46 @@ def warp_tables(M, out_w, out_h):
     if rc != OK:
         raise CompvHipError(rc, "compvhip_warp_tables")
     return (ac, df, gi, by, ey, hy) if rows == 3 else (ac, df, None, by, ey, None)
+
+
+def _cameras(K, d, dtype):
+    """K (3, 3) or (count, 3, 3), d (nd,) or (count, nd), nd in 2 .. 4 -> contiguous K, d of `dtype`, nd, count (shapes are not judged here: the C ABI refuses)"""
+    K, d = np.ascontiguousarray(K, dtype), np.ascontiguousarray(d, dtype)
+    assert K.shape[-2:] == (3, 3) and K.ndim in (2, 3) and d.ndim == K.ndim - 1
+    count = 1 if K.ndim == 2 else K.shape[0]
+    assert K.ndim == 2 or d.shape[0] == count
+    return K, d, int(d.shape[-1]), count
+
+
+def undistort_coeffs(K, d, dtype=np.float32):
+    """compvhip_undistort_coeffs_f32 / _f64 (host arithmetic, no GPU): the 14-value coefficient record of one camera -- fx, fy, cx, cy, skew, k1, k2, p1, p2,
+    kinv11, kinv21, kinv31, kinv22, kinv32 -- in `dtype`"""
+    L = load()
+    dtype = np.dtype(dtype)
+    assert dtype in (np.float32, np.float64)
+    K, d = np.ascontiguousarray(K, dtype), np.ascontiguousarray(d, dtype).ravel()
+    assert K.shape == (3, 3)
+    out = np.zeros(UNDISTORT_COEFFS, dtype)
+    fn = L.compvhip_undistort_coeffs_f32 if dtype == np.float32 else L.compvhip_undistort_coeffs_f64
+    rc = fn(_ptr(K), _ptr(d), d.size, _ptr(out))
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_undistort_coeffs")
+    return out
+
+
+def undistort_map(K, d, out_w, out_h, x0=0, y0=0, dtype=np.float32):
+    """compvhip_undistort_map_f32 / _f64 (host arithmetic, no GPU): CompVCalibUtils::initUndistMap -> map_x, map_y (out_h, out_w) of `dtype`"""
+    L = load()
+    dtype = np.dtype(dtype)
+    assert dtype in (np.float32, np.float64)
+    K, d = np.ascontiguousarray(K, dtype), np.ascontiguousarray(d, dtype).ravel()
+    assert K.shape == (3, 3)
+    mx, my = np.zeros((max(out_h, 0), max(out_w, 0)), dtype), np.zeros((max(out_h, 0), max(out_w, 0)), dtype)
+    fn = L.compvhip_undistort_map_f32 if dtype == np.float32 else L.compvhip_undistort_map_f64
+    rc = fn(_ptr(K), _ptr(d), d.size, x0, y0, out_w, out_h, _ptr(mx), _ptr(my))
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_undistort_map")
+    return mx, my
 
 
 def homography_quads(seed, pair, k, tries):
@@ -849,6 +917,18 @@ class Context:
         assert M.ndim == 2 and M.shape[1] == 3
         out = np.empty((out_h, out_w), np.float32 if interp in (INTERP_BILINEAR_FLOAT32, INTERP_BICUBIC_FLOAT32) else np.uint8)
         self._chk(self.lib.compvhip_warp_inverse_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(M), M.shape[0], interp, default, _ptr(out), out_w, out_h, out_w))
+        return out
+
+    def undistort(self, img, K, d, out_w=None, out_h=None, x0=0, y0=0, interp=INTERP_BILINEAR, roi=None, default=0):
+        """compvhip_undistort_u8 (CompVCalibUtils::undist2DImage): one camera K (3, 3), d (2 .. 4) float32 -> the (out_h, out_w) window at origin (x0, y0) of the
+        undistorted frame, uint8 or (the two _FLOAT32 interpolations) float32.  out_w, out_h default to the image's."""
+        H, W = img.shape
+        out_w, out_h = W if out_w is None else out_w, H if out_h is None else out_h
+        K, d = np.ascontiguousarray(K, np.float32), np.ascontiguousarray(d, np.float32).ravel()
+        assert K.shape == (3, 3)
+        out = np.empty((out_h, out_w), np.float32 if interp in (INTERP_BILINEAR_FLOAT32, INTERP_BICUBIC_FLOAT32) else np.uint8)
+        self._chk(self.lib.compvhip_undistort_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(K), _ptr(d), d.size, x0, y0, interp, _roi(roi), default, _ptr(out),
+                                                 out_w, out_h, out_w))
         return out
 
     def orb_pyramid(self, img, opts=None, cap=4096):
@@ -1384,6 +1464,65 @@ class Svm:
         names = (C.c_char_p * cap)()
         ms = (C.c_float * cap)()
         n = self.lib.compvhip_svm_get_timing(self.h, names, ms, cap)
+        return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
+
+
+class Undistort:
+    """Batched device-resident lens undistortion (compvhip_undistort): the fused image form, maps, points and projection.  Every call runs on the stream
+    given here.  Cameras (K, d) and poses are HOST arrays per call; pointers are raw device addresses, 0 stands for NULL."""
+
+    def __init__(self, ctx, W, H, S, frames, out_w=None, out_h=None, x0=0, y0=0, max_sets=0, max_points=0, stream=0):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        out_w, out_h = W if out_w is None else out_w, H if out_h is None else out_h
+        h = C.c_void_p()
+        desc = UndistortDesc(W, H, S, frames, out_w, out_h, x0, y0, max_sets, max_points, stream)
+        ctx._chk(self.lib.compvhip_undistort_create(ctx.h, C.byref(desc), C.byref(h)))
+        self.h = h
+        self.W, self.H, self.S, self.frames, self.out_w, self.out_h, self.x0, self.y0 = W, H, S, frames, out_w, out_h, x0, y0
+        self.max_sets, self.max_points, self.stream = max_sets, max_points, stream
+
+    def close(self):
+        if self.h:
+            self.lib.compvhip_undistort_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def undistort(self, d_in, K, d, interp, d_out, out_stride, roi=None, default=0):
+        """compvhip_undistort_frames: d_in [frames][H][S] -> d_out [frames][out_h][out_stride] (uint8, or float32 with out_stride in elements); K (3, 3) with d (nd,)
+        for all frames, or K (frames, 3, 3) with d (frames, nd), float32"""
+        K, d, nd, count = _cameras(K, d, np.float32)
+        self.ctx._chk(self.lib.compvhip_undistort_frames(self.h, d_in or None, _ptr(K), _ptr(d), nd, count, interp, _roi(roi), default, d_out or None, out_stride))
+
+    def maps(self, K, d, d_map_x, d_map_y, mtype=UNDISTORT_F32):
+        """compvhip_undistort_maps: d_map_x, d_map_y [count][out_h * out_w] float32 (UNDISTORT_F32) or float64 (UNDISTORT_F64); count 1 or frames"""
+        K, d, nd, count = _cameras(K, d, np.float32 if mtype == UNDISTORT_F32 else np.float64)
+        self.ctx._chk(self.lib.compvhip_undistort_maps(self.h, _ptr(K), _ptr(d), nd, count, int(mtype), d_map_x or None, d_map_y or None))
+
+    def points(self, K, d, d_in, sets, n, d_out, ptype=UNDISTORT_F32, d_counts=0):
+        """compvhip_undistort_points: d_in, d_out [sets][n] {x, y} of ptype; d_counts 0 or [sets] int32; one camera, or one per set"""
+        K, d, nd, count = _cameras(K, d, np.float32 if ptype == UNDISTORT_F32 else np.float64)
+        self.ctx._chk(self.lib.compvhip_undistort_points(self.h, _ptr(K), _ptr(d), nd, count, int(ptype), d_in or None, sets, n, d_counts or None, d_out or None))
+
+    def project(self, K, d, Rt, d_in, sets, n, d_out, d_counts=0):
+        """compvhip_undistort_project: d_in [sets][n] {x, y, z} -> d_out [sets][n] {u, v}, float64; Rt HOST (sets, 12): R row-major, then t"""
+        K, d, nd, count = _cameras(K, d, np.float64)
+        Rt = np.ascontiguousarray(Rt, np.float64)
+        assert Rt.size == sets * 12
+        self.ctx._chk(self.lib.compvhip_undistort_project(self.h, _ptr(K), _ptr(d), nd, count, _ptr(Rt), d_in or None, sets, n, d_counts or None, d_out or None))
+
+    def set_timing(self, mode=1):
+        self.ctx._chk(self.lib.compvhip_undistort_set_timing(self.h, int(mode)))
+
+    def get_timing(self, cap=16):
+        names = (C.c_char_p * cap)()
+        ms = (C.c_float * cap)()
+        n = self.lib.compvhip_undistort_get_timing(self.h, names, ms, cap)
         return [(names[i].decode(), ms[i]) for i in range(max(n, 0))]
 
 

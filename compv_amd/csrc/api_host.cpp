@@ -536,6 +536,19 @@ int compvhip_warp_inverse_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, siz
 	                 [&](RemapArgs* a) -> int { return warpUpload(ctx, &ctx->warp, M, rows, 1, a, ctx->stream); });
 }
 
+// the fused undistortion of one host plane (include/compv_hip.h, "lens undistortion"): the same staging, the camera's record through the context's ring
+int compvhip_undistort_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const float* K, const float* d, int nd, size_t x0, size_t y0, int interp,
+                          const compvhip_roi* roi, uint8_t defaultValue, void* out, size_t Wout, size_t Hout, size_t Sout)
+{
+	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
+	if (!K || !d || nd < 2 || nd > 4) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "undistort: null K or d, or nd outside 2 .. 4");
+	if (!undistWindowOk(x0, y0, Wout, Hout)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "undistort: an output size of 0 or beyond 32767, or x0 + Wout / y0 + Hout beyond 32767");
+	float probe[14];
+	if (compvhip_undistort_coeffs_f32(K, d, nd, probe)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "undistort: fx * fy == 0, the camera matrix is singular");
+	return hostRemap(ctx, in, W, H, S, interp, roi, defaultValue, out, Wout, Hout, Sout, kRemapUndist,
+	                 [&](RemapArgs* a) -> int { return undistCoords(ctx, &ctx->warp, K, d, nd, 1, x0, y0, a, ctx->stream); });
+}
+
 int compvhip_orb_pyramid_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_orbpyr_opts* opts, compvhip_keypoint* keypoints,
                             uint8_t* desc, size_t descStride, size_t cap, size_t* n)
 {

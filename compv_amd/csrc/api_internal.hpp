@@ -278,6 +278,14 @@ struct compvhip_svm : TimingState {
 	DevBuf<double> kvalues;             // [maxVectors][l]
 	DevBuf<double> hostVectors, hostDec; DevBuf<int32_t> hostLabels;   // staging of the host form: [hostSlice][dim] (float32 or float64), [hostSlice][pairs], [hostSlice]
 };
+// lens undistortion (remap_kernels.hip's kRemapUndist, undistort_kernels.hip; api_undistort.cpp): the geometry of the fused form and the staging of the
+// cameras' coefficient records and of the poses; every call runs on `stream`
+struct compvhip_undistort : TimingState {
+	compvhip_ctx* ctx = nullptr;
+	hipStream_t stream = nullptr;       // (the caller's: the descriptor's)
+	size_t W = 0, H = 0, S = 0, frames = 0, Wout = 0, Hout = 0, x0 = 0, y0 = 0, maxSets = 0, maxPoints = 0;
+	WarpTables stage;                   // device copy and pinned ring, sized by compvhip_undistort_create for the largest call: no later call allocates
+};
 // ORB pyramid (scale_kernels.hip, fast_kernels.hip, orb_kernels.hip): the levels' geometry and the scratch they share.  `active` levels (a prefix: the sizes
 // only shrink) are at least 37 x 37; the others are empty.
 struct compvhip_orbpyr : TimingState {
@@ -485,6 +493,14 @@ int remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, siz
 int warpUpload(compvhip_ctx* ctx, WarpTables* t, const float* M, int rows, size_t count, RemapArgs* a, hipStream_t st);
 MatchSliceArgs matchForward(const compvhip_matcher* m, const uint8_t* d_query, size_t queryStride, const int32_t* d_queryCounts, const uint8_t* d_train, size_t trainStride,
                             const int32_t* d_trainCounts, int trainShared, compvhip_match* d_matches);
+// api_undistort.cpp.  The ring of `t` for any table: the next slot with room for `floats` floats (waits for the copy that last read it), and its upload
+// into t->dev behind the work of `st`
+int tablesSlot(compvhip_ctx* ctx, WarpTables* t, size_t floats, float** host, WarpTables::Slot** slot);
+int tablesSend(compvhip_ctx* ctx, WarpTables* t, WarpTables::Slot* slot, size_t floats, hipStream_t st);
+// the coordinate source kRemapUndist: builds the records of `count` float32 cameras (K [count][9], d [count][nd]; nd in 2 .. 4 was checked) in a staging
+// slot of `t`, enqueues their upload and points `a` at the device copy; a singular camera: COMPVHIP_E_INVALID_PARAMETER, nothing enqueued
+int undistCoords(compvhip_ctx* ctx, WarpTables* t, const float* K, const float* d, int nd, size_t count, size_t x0, size_t y0, RemapArgs* a, hipStream_t st);
+bool undistWindowOk(size_t x0, size_t y0, size_t Wout, size_t Hout);   // sizes 1 .. 32767, x0 + Wout and y0 + Hout at most 32767
 // api_kht.cpp
 size_t hostCpuBudget();
 } // namespace compvhip_api

@@ -497,7 +497,7 @@ hipError_t launch_scale_bilinear(ScaleArgs& a, int frames, hipStream_t stream); 
 // ---- remap and inverse warp (remap_kernels.hip) -----------------------------------------------------------------------------------------------
 // CompVImageRemap::process / CompVImage::warpInverse: a per-pixel gather at coordinates that come from a float32 map or from the running-sum tables
 // of a matrix (include/compv_hip.h, section "remap and inverse warp")
-enum { kRemapMap = 0, kRemapWarp2 = 1, kRemapWarp3 = 2 };                  // coordinate source
+enum { kRemapMap = 0, kRemapWarp2 = 1, kRemapWarp3 = 2, kRemapUndist = 3 };   // coordinate source
 enum { kRemapNearest = 0, kRemapBilinear = 1, kRemapBilinearF32 = 2, kRemapBicubic = 4, kRemapBicubicF32 = 5 };     // = COMPVHIP_INTERP_* (3 is unassigned)
 constexpr int kRemapFramesPerGroup = 8;   // frames a workgroup loops over with one set of coordinates when the map / matrix is shared
 struct RemapArgs {
@@ -508,12 +508,13 @@ struct RemapArgs {
 	size_t outFrameStride;    // in elements, like Sout
 	int Wout, Hout, Sout;
 	const float* mapX; const float* mapY;   // kRemapMap: [1 or frames][Hout * Wout] each
-	const float* tables;      // kRemapWarp2 / 3: [1 or frames] x { ac, df[, gi] of Wout values, by, ey[, hy] of Hout values }
+	const float* tables;      // kRemapWarp2 / 3: [1 or frames] x { ac, df[, gi] of Wout values, by, ey[, hy] of Hout values }; kRemapUndist: [1 or frames] x 14 coefficients (undistort_math.hpp)
 	size_t coordFrameStride;  // floats from one frame's map / tables to the next (ignored when they are shared)
 	float left, right, top, bottom;   // the clipped ROI: inside the frame, or empty (left > right)
 	int defaultValue;         // 0 .. 255
 	int frames;
 	int framesPerGroup, group0, tilesX, wide, mapVec;   // filled by launch_remap
+	int originX, originY;     // kRemapUndist: output pixel (i, j) is pixel (originX + i, originY + j) of the undistorted frame; origin + size <= 32767
 };
 // perFrame: every frame has a map / tables of its own (coordFrameStride apart); otherwise all frames share the first.  S >= 2 (the bilinear forms load
 // 2-byte pairs inside a row; the bicubic forms load 4-byte tap rows and need S >= 4); hipErrorInvalidValue for that, for a ROI that is neither empty nor inside the frame, and for sizes whose frame exceeds 2^31 bytes.
@@ -610,5 +611,34 @@ struct SvmDecideArgs {
 	double* dec;                                      // nullptr or [n][pairs]
 };
 hipError_t launch_svm_decide(const SvmDecideArgs& a, hipStream_t stream);
+
+// ---- lens undistortion: maps, points, projection (undistort_kernels.hip; the fused image form is remap_kernels.hip's kRemapUndist) ------------------
+// A camera is a record of 14 coefficients of T (undistort_math.hpp); `coeffStride` is 14 when every frame / set has its own and 0 when all share the first.
+struct UndistMapArgs {
+	const void* coeffs;       // [1 or cameras][14] float32 or float64
+	int coeffStride;
+	void* mapX; void* mapY;   // [cameras][Hout * Wout] each, of the same type
+	int Wout, Hout, originX, originY, cameras;
+	int f64;
+};
+// Vector stores (16 bytes) where Wout % 4 == 0 and both planes are 16-byte aligned, element stores otherwise.  More than 65 535 cameras: sliced.
+hipError_t launch_undist_map(const UndistMapArgs& a, hipStream_t stream);
+struct UndistPointsArgs {
+	const void* coeffs; int coeffStride;
+	const void* in;           // [sets][n] {x, y} float32 or float64
+	void* out;                // the same shape; in == out is served
+	const int32_t* counts;    // nullptr, or [sets]: points of set s at and behind min(max(counts[s], 0), n) are neither read nor written
+	int n, sets, f64;
+};
+hipError_t launch_undist_points(const UndistPointsArgs& a, hipStream_t stream);   // more than 65 535 sets: sliced
+struct UndistProjectArgs {
+	const double* coeffs; int coeffStride;
+	const double* poses;      // [sets][12]: R row-major, then t
+	const double* in;         // [sets][n] {x, y, z}
+	double* out;              // [sets][n] {x, y}
+	const int32_t* counts;    // as UndistPointsArgs
+	int n, sets;
+};
+hipError_t launch_undist_project(const UndistProjectArgs& a, hipStream_t stream);   // more than 65 535 sets: sliced
 
 } // namespace compvhip

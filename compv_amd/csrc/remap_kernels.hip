@@ -3,7 +3,8 @@
 // Definition: include/compv_hip.h (section "remap and inverse warp"), docs/kernels/remap.md.
 //
 //   remap_kernel<SRC, INTERP, OutT>   ONE kernel family, specialised at compile time over where the source coordinates come from (a float32 map, the
-//                           running-sum tables of a 2 x 3 matrix, those of a 3 x 3 matrix with its one division per pixel), the interpolation (nearest,
+//                           running-sum tables of a 2 x 3 matrix, those of a 3 x 3 matrix with its one division per pixel, the lens model of a
+//                           camera's 14-float coefficient record: include/compv_hip.h, "lens undistortion"), the interpolation (nearest,
 //                           bilinear) and the output type (uint8, float32).  A workgroup owns a 256 x 4 tile of the destination, one wave per row; a lane
 //                           produces 4 adjacent pixels and stores them as one dword (uint8) or one 16-byte vector (float32).  The group that crosses Wout,
 //                           and every group of a destination that is not aligned, stores single elements, so stride padding is never written.
@@ -16,6 +17,7 @@
 //                           definition; the arithmetic is bicubic_math.hpp, unfused).  16 taps per pixel: a tap row is one unaligned 4-byte load whose bytes
 //                           the four packed selectors pick: 4 loads per pixel and frame.
 #include "bicubic_math.hpp"
+#include "undistort_math.hpp"
 #include "device.hpp"
 #include "frame_slices.hpp"
 
@@ -49,6 +51,16 @@ __device__ __forceinline__ void remap_coords(const RemapArgs& a, int f0, int j, 
 #pragma unroll
 			for (int b = 0; b < 4; ++b) if (b < n) { x[b] = a.mapX[k + b]; y[b] = a.mapY[k + b]; }
 		}
+	}
+	else if (SRC == kRemapUndist) {
+		// the lens model (undistort_math.hpp): the camera's 14-float record is wave-uniform, the coordinates are arithmetic in registers -- no map is read
+		const float* __restrict__ rec = a.tables + static_cast<size_t>(f0) * a.coordFrameStride;          // coordFrameStride: 0 for a shared camera
+		float c[undist::kCoeffs];
+#pragma unroll
+		for (int k = 0; k < undist::kCoeffs; ++k) c[k] = rec[k];
+		const float Y = static_cast<float>(a.originY + j);          // exact: origin + size <= 32767
+#pragma unroll
+		for (int b = 0; b < 4; ++b) if (b < n) undist::map_entry(c, static_cast<float>(a.originX + i0 + b), Y, x[b], y[b]);
 	}
 	else {
 		constexpr int R = SRC == kRemapWarp3 ? 3 : 2;          // table rows: ac, df[, gi] of Wout values, then by, ey[, hy] of Hout values
@@ -253,7 +265,7 @@ hipError_t launch_remap(const RemapArgs& args, int source, int interp, bool perF
 	RemapArgs a = args;
 	if (!a.in || !a.out || a.W < 1 || a.H < 1 || a.S < a.W || a.S < 2 || a.Wout < 1 || a.Hout < 1 || a.Sout < a.Wout || a.frames < 1) return hipErrorInvalidValue;
 	const bool bicubic = interp == kRemapBicubic || interp == kRemapBicubicF32;
-	if (source < kRemapMap || source > kRemapWarp3 || (interp != kRemapNearest && interp != kRemapBilinear && interp != kRemapBilinearF32 && !bicubic)) return hipErrorInvalidValue;
+	if (source < kRemapMap || source > kRemapUndist || (interp != kRemapNearest && interp != kRemapBilinear && interp != kRemapBilinearF32 && !bicubic)) return hipErrorInvalidValue;
 	if (bicubic && a.S < 4) return hipErrorInvalidValue;          // the 4-byte tap rows; no caller comes here: a plan's stride is a multiple of 8, the host calls stage at 64
 	if (source == kRemapMap ? !a.mapX || !a.mapY : !a.tables) return hipErrorInvalidValue;
 	// every offset of a frame fits an int; the ROI is empty or lies in the frame, so an inside pixel never gathers outside it
@@ -276,7 +288,8 @@ hipError_t launch_remap(const RemapArgs& args, int source, int interp, bool perF
 		const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(ng));
 		if (source == kRemapMap) launch_src<kRemapMap>(a, interp, grid, stream);
 		else if (source == kRemapWarp2) launch_src<kRemapWarp2>(a, interp, grid, stream);
-		else launch_src<kRemapWarp3>(a, interp, grid, stream);
+		else if (source == kRemapWarp3) launch_src<kRemapWarp3>(a, interp, grid, stream);
+		else launch_src<kRemapUndist>(a, interp, grid, stream);
 		return hipGetLastError();
 	});
 }

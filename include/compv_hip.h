@@ -1442,6 +1442,101 @@ COMPVHIP_API int compvhip_svm_exp_f64(const double* in, double* out, size_t n);
  * field, a file item F refuses: COMPVHIP_E_INVALID_PARAMETER, nothing written. */
 COMPVHIP_API int compvhip_svm_model_parse(const char* path, compvhip_svm_shape* shape, double* sv, double* svCoef, double* rho, int32_t* nSV, int32_t* label);
 
+/* ---- lens undistortion: fused remap, maps, points, projection (docs/kernels/undistort.md) -----------------------------------------------------------
+ * CompVCalibUtils::initUndistMap, undist2DImage, dist2DPoints and proj2D (core/calib/compv_core_calib_utils.cxx).  Every output is defined bit for
+ * bit.  T is float32 or float64; every operation below is rounded on its own in T and nothing is fused; the one division of item A and the
+ * per-point division of item E are correctly rounded IEEE divisions.
+ * A. Camera.  K is 3 x 3 row-major, of which fx = K[0], skew = K[1], cx = K[2], fy = K[4], cy = K[5] are read; d holds nd in 2 .. 4 values
+ *    k1, k2[, p1[, p2]], a missing one being 0.  Coefficients, once per camera on the host (compvhip_undistort_coeffs_*): det = 1 / (fx * fy);
+ *    kinv11 = fy * det; kinv21 = -(skew * det); kinv31 = ((skew * cy) - (fy * cx)) * det; kinv22 = fx * det; kinv32 = -((cy * fx) * det).
+ *    The record of a camera is 14 values of T: fx, fy, cx, cy, skew, k1, k2, p1, p2, kinv11, kinv21, kinv31, kinv22, kinv32.
+ * B. Distort, for normalised (x, y): x2 = x * x; y2 = y * y; r2 = x2 + y2; r4 = r2 * r2; rdist = (1 + k1 * r2) + k2 * r4; x = x * rdist;
+ *    y = y * rdist; a1 = 2 * (x * y) with the scaled x, y; a2 = r2 + 2 * x2 and a3 = r2 + 2 * y2 with the unscaled squares;
+ *    x = x + ((p1 * a1) + (p2 * a2)); y = y + ((p1 * a3) + (p2 * a1)); result u = ((x * fx) + (skew * y)) + cx, v = (y * fy) + cy.
+ * C. Map entry of output pixel (i, j) with origin (x0, y0): X = (T)(x0 + i), Y = (T)(y0 + j); x = ((kinv11 * X) + (kinv21 * Y)) + kinv31;
+ *    y = (kinv22 * Y) + kinv32; then B.  Evaluating kinv11 * X + kinv31 in a wider type and rounding once gives another number.  The reference's
+ *    third map row (all ones) is not produced; its float ROI rounds to integers (COMPV_MATH_ROUNDFU_2_NEAREST_INT), which stays with the caller:
+ *    x0, y0, Wout, Hout are integers here.
+ * D. dist2DPoints: C with (X, Y) the input point.
+ * E. proj2D (float64 only), point (xp, yp, zp), pose R (3 x 3 row-major) and t: x = ((R0 * xp + R1 * yp) + R2 * zp) + tx, y and z likewise with
+ *    rows 1 and 2; s = z != 0 ? 1.0 / z : 1.0; x = x * s; y = y * s; then B (no kinv step).  The reference's third output row (ones) is not produced.
+ * F. Undistorted image: paragraphs B - F of "remap and inverse warp" above, unchanged, applied to the float32 map entry of C: the ROI (the caller's,
+ *    clipped, in SOURCE coordinates), the inside test with ordered compares (a NaN or infinite coordinate is outside), nearest, fused bilinear,
+ *    unfused bicubic, uint8 and float32 output, the default value.  The fused form computes the entry in registers and reads no map; its output
+ *    equals compvhip_plan_remap fed with the float32 maps of compvhip_undistort_maps byte for byte.
+ * Out of scope: CompVCalibCamera itself; proj2DError (the sum order of its mse2D is another definition); float64 maps into the remap; an inverse
+ *    (distorted -> undistorted points), which the reference does not have either.
+ * Streams.  As the SVM handle, an undistort handle takes its stream at creation (the descriptor): compvhip_undistort_frames, _maps, _points and
+ *    _project are asynchronous on the handle's stream and never synchronise the host, with the exception the inverse warp has: cameras and poses
+ *    are staged in a ring of 4 pinned slots, so a call may wait for the copy of the call four before it (never for more).  K, d and Rt may be changed
+ *    as soon as the call has returned.  compvhip_undistort_u8 waits.
+ * Alignment.  d_in and a uint8 d_out: any byte (an unaligned destination, stride or frame size is served with element stores; stride padding and
+ *    bytes behind Wout are never written); a float32 d_out: 4 bytes (16 for vector stores); maps and points: their element size (4 or 8 bytes;
+ *    float32 maps of Wout % 4 == 0 at 16 bytes are written with vector stores); d_counts: 4 bytes.  A misaligned pointer is refused.
+ * Batches beyond 65 535: SLICED everywhere -- frames (shared camera: beyond 65 535 groups of 8) in compvhip_undistort_frames, cameras in _maps, sets
+ *    in _points and _project.
+ * Refused with COMPVHIP_E_INVALID_PARAMETER, nothing written and nothing enqueued: a null pointer or a wrong size field; a size of 0 or beyond
+ *    32767; x0 + Wout or y0 + Hout beyond 32767; S < W, and S < 4 (the gathers read 4 bytes of a row at once); nd outside 2 .. 4; fx * fy == 0 for
+ *    any camera; a cameraCount other than 1 or the frames (_frames, _maps) / the sets (_points, _project) of the call; an unknown interpolation or
+ *    type; Sout < Wout (for float32 output Sout counts ELEMENTS); a misaligned float destination, map, point or count array; source and destination
+ *    that overlap (mapX and mapY likewise; points may be transformed in place, d_in == d_out, and may not overlap otherwise); n or sets of 0 or
+ *    beyond the handle's caps. */
+enum {
+	COMPVHIP_UNDISTORT_F32 = 0,
+	COMPVHIP_UNDISTORT_F64 = 1
+};
+typedef struct compvhip_undistort_desc {
+	uint32_t size;              /* sizeof(compvhip_undistort_desc) */
+	uint32_t W, H, S;           /* the source frames [frames][H][S] of compvhip_undistort_frames: 1 .. 32767, S >= max(W, 4), S * H below 2^31 */
+	uint32_t frames;            /* 1 .. 2^31 - 1 */
+	uint32_t Wout, Hout;        /* the window of the undistorted frame that is produced (fused form and maps): 1 .. 32767 */
+	uint32_t x0, y0;            /* its origin: output pixel (i, j) is pixel (x0 + i, y0 + j); x0 + Wout and y0 + Hout at most 32767 */
+	uint32_t maxSets;           /* point sets of one compvhip_undistort_points / _project call; 0: no point calls */
+	uint32_t maxPoints;         /* points per set */
+	uint32_t reserved;          /* 0 */
+	void* stream;               /* a hipStream_t; NULL = the default stream */
+} compvhip_undistort_desc;
+typedef struct compvhip_undistort compvhip_undistort;   /* the geometry of the fused form and the staging of cameras and poses */
+
+/* Items A and C on the host (standard library only, no GPU, no context).  coeffs: the 14 values of item A.  mapX, mapY: Wout * Hout values each,
+ * row-major without stride: the reference loop for callers without a device.  A null pointer, nd outside 2 .. 4, fx * fy == 0, a size of 0 or a
+ * window beyond 32767: COMPVHIP_E_INVALID_PARAMETER, nothing written. */
+COMPVHIP_API int compvhip_undistort_coeffs_f32(const float* K, const float* d, int nd, float* coeffs);
+COMPVHIP_API int compvhip_undistort_coeffs_f64(const double* K, const double* d, int nd, double* coeffs);
+COMPVHIP_API int compvhip_undistort_map_f32(const float* K, const float* d, int nd, size_t x0, size_t y0, size_t Wout, size_t Hout, float* mapX, float* mapY);
+COMPVHIP_API int compvhip_undistort_map_f64(const double* K, const double* d, int nd, size_t x0, size_t y0, size_t Wout, size_t Hout, double* mapX, double* mapY);
+/* All device memory and pinned staging is allocated here -- the device copy and 4 pinned slots of max(frames * 28, maxSets * 52) float32 words: the
+ * float64 records of every frame, or the float64 records and poses of every set -- and released by compvhip_undistort_destroy: no later call
+ * allocates.  Destroy it BEFORE its context.  Not re-entrant.  On a refusal *undistort = NULL. */
+COMPVHIP_API int compvhip_undistort_create(compvhip_ctx* ctx, const compvhip_undistort_desc* desc, compvhip_undistort** undistort);
+COMPVHIP_API void compvhip_undistort_destroy(compvhip_undistort* undistort);
+/* Item F for every frame of the handle: d_in [frames][H][S] uint8 -> d_out [frames][Hout][Sout], uint8 or (the two _FLOAT32 interpolations) float32.
+ * K: HOST, [cameraCount][9] float32; d: HOST, [cameraCount][nd] float32.  cameraCount == 1: all frames share the camera, and a workgroup works its
+ * coordinates out once for 8 frames; cameraCount == frames: one camera per frame.  roi == NULL: the whole source frame.  Asynchronous on the
+ * handle's stream.  Timing entry: undistort_kernel. */
+COMPVHIP_API int compvhip_undistort_frames(compvhip_undistort* undistort, const uint8_t* d_in, const float* K, const float* d, int nd, size_t cameraCount,
+                                           int interp, const compvhip_roi* roi, uint8_t defaultValue, void* d_out, size_t Sout);
+/* Item C on the device: d_mapX, d_mapY [cameraCount][Hout * Wout] of float32 (COMPVHIP_UNDISTORT_F32) or float64 (_F64); K and d: HOST arrays of the
+ * same type, as above; cameraCount 1 or frames.  The float32 planes are in exactly the layout compvhip_plan_remap takes (mapCount = cameraCount).
+ * Asynchronous on the handle's stream.  Timing entry: undist_map_kernel. */
+COMPVHIP_API int compvhip_undistort_maps(compvhip_undistort* undistort, const void* K, const void* d, int nd, size_t cameraCount, int type, void* d_mapX,
+                                         void* d_mapY);
+/* Item D on the device: d_in, d_out [sets][n] {x, y} of `type`; d_counts: NULL or [sets] int32 -- points of set s at and behind
+ * min(max(d_counts[s], 0), n) are neither read nor written.  cameraCount 1 or sets.  Asynchronous on the handle's stream.  Timing entry:
+ * undist_points_kernel. */
+COMPVHIP_API int compvhip_undistort_points(compvhip_undistort* undistort, const void* K, const void* d, int nd, size_t cameraCount, int type, const void* d_in,
+                                           size_t sets, size_t n, const int32_t* d_counts, void* d_out);
+/* Item E on the device: d_in [sets][n] {x, y, z} float64 -> d_out [sets][n] {u, v} float64; Rt: HOST, [sets][12] float64, R row-major then t;
+ * d_counts as above.  Asynchronous on the handle's stream.  Timing entry: undist_project_kernel. */
+COMPVHIP_API int compvhip_undistort_project(compvhip_undistort* undistort, const double* K, const double* d, int nd, size_t cameraCount, const double* Rt,
+                                            const double* d_in, size_t sets, size_t n, const int32_t* d_counts, double* d_out);
+/* Item F for one HOST plane (sizes 1 .. 32767) with one host camera; S and Sout in elements.  Synchronous, like compvhip_remap_u8. */
+COMPVHIP_API int compvhip_undistort_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const float* K, const float* d, int nd, size_t x0,
+                                       size_t y0, int interp, const compvhip_roi* roi, uint8_t defaultValue, void* out, size_t Wout, size_t Hout, size_t Sout);
+/* Per-kernel timing of the handle's last call, as compvhip_svm_set_timing / _get_timing. */
+COMPVHIP_API int compvhip_undistort_set_timing(compvhip_undistort* undistort, int enabled);
+COMPVHIP_API int compvhip_undistort_get_timing(compvhip_undistort* undistort, const char** names, float* ms, int cap);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel
