@@ -180,3 +180,13 @@ def has_tie_neighbour(rec, rhoN, T):
         return np.zeros(0, bool)
     s2, _ = _neighbour_records(rec, rhoN, T)
     return (s2 == rec[:, 2:3]).any(axis=1)
+
+
+def line_bits(lines):
+    """LINE_DTYPE array -> [(rho bits, theta bits, strength, row, col)]"""
+    return list(zip(lines["rho"].astype(np.float32).view(np.uint32).tolist(), lines["theta"].astype(np.float32).view(np.uint32).tolist(),
+                    lines["strength"].tolist(), lines["row"].tolist(), lines["col"].tolist()))
+
+
+def model_line_bits(lines):
+    return [(int(np.float32(l[0]).view(np.uint32)), int(np.float32(l[1]).view(np.uint32)), l[2], l[3], l[4]) for l in lines]

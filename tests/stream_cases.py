@@ -9,7 +9,7 @@ Classes
   DRAINS  no stream parameter: the call drains the whole device first.
 
 `host`: the host arrays and structs the call reads (the GPU case overwrites each of them as soon as the call has returned).
-`cases`: ids of tests/test_gpu_stream_order.py::CASES; the first is the plain rig of the row, the others are the runs that need more (growth behind pending
+`cases`: ids of tests/stream_order_rig.py::CASES; the first is the plain rig of the row, the others are the runs that need more (growth behind pending
 work, in place, a ticket, timing mode)."""
 from collections import namedtuple
 

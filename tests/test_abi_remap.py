@@ -4,7 +4,6 @@ Wout = 1, 2 and 4097; the model (tests/remap_model.py) equals every plane the co
 multiply-add is exact where float64 emulation would round twice; the null checks that precede any HIP call answer without a GPU."""
 import ctypes as C
 import hashlib
-import json
 import os
 import re
 from fractions import Fraction
@@ -14,15 +13,15 @@ import pytest
 
 import remap_cases as rc
 import remap_model as rm
+from fixtures import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
 SYMBOLS = {"compvhip_warp_tables": 10, "compvhip_plan_remap": 13, "compvhip_plan_warp_inverse": 12, "compvhip_remap_u8": 14, "compvhip_warp_inverse_u8": 13}
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return json.load(open(os.path.join(HERE, "golden", "golden_remap.json"))), np.load(os.path.join(HERE, "golden", "golden_remap.npz"))
+    return load_golden("golden_remap")
 
 
 def bits(a):

@@ -2,8 +2,6 @@
 the host by tests/host/bicubic_math_check.cpp (a stand-alone program, standard library only, no GPU, built with AddressSanitizer and UBSan, nothing
 preloaded) over every case's frame and coordinates, and held against tests/bicubic_model.py and the fixture byte for byte.  The GPU tests
 (tests/test_gpu_bicubic.py) hold the kernel against the same model and the same fixture."""
-import os
-import shutil
 import struct
 import subprocess
 
@@ -14,21 +12,15 @@ import bicubic_cases as bc
 import bicubic_model as bm
 import remap_cases as rc
 import remap_model as rm
+from fixtures import load_golden
+from host_programs import ASAN_UBSAN_STATIC, WARN, build, host_cxx
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "bicubic_math_check.cpp")
-A = np.load(os.path.join(ROOT, "tests", "golden", "golden_bicubic.npz"))
+A = load_golden("golden_bicubic")[1]
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path_factory.mktemp("bicubic") / "bicubic_math_check"
-    # the sanitizers' runtimes are linked statically: the program needs nothing preloaded
-    build = subprocess.run([cxx, "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                            "-static-libasan", "-static-libubsan", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = build("bicubic_math_check.cpp", tmp_path_factory.mktemp("bicubic"), host_cxx(), ["-O2", "-g", "-ffp-contract=off", *WARN, *ASAN_UBSAN_STATIC])
 
     def run(img, S, x, y, roi, default):
         """-> (uint8 plane, float32 plane) of the frame img staged at stride S"""

@@ -2,9 +2,6 @@
 the model against the compiled reference (SIMD flags off) on every element: golden_bicubic.npz holds the planes, golden_bicubic.json their MD5s and what
 each was checked against.  No GPU."""
 import functools
-import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
@@ -13,20 +10,15 @@ import bicubic_cases as bc
 import bicubic_model as bm
 import remap_cases as rc
 import remap_model as rm
+from fixtures import load_golden, md5
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-G = json.load(open(os.path.join(HERE, "golden", "golden_bicubic.json")))
-A = np.load(os.path.join(HERE, "golden", "golden_bicubic.npz"))
+G, A = load_golden("golden_bicubic")
 MAPS = {c["id"]: c for c in bc.all_map_cases()}
 WARPS = {c["id"]: c for c in bc.warp_cases()}
 
 
 def same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
-
-
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 @functools.lru_cache(maxsize=None)

@@ -2,10 +2,6 @@
 stand-alone program, standard library only, no GPU, built with AddressSanitizer and UBSan, nothing preloaded) over the small cases and both exhaustive
 frames, and held against tests/convert_model.py and the golden MD5s byte for byte.  The GPU tests (tests/test_gpu_convert.py) hold the kernel against the
 same model and the same fixture."""
-import hashlib
-import json
-import os
-import shutil
 import struct
 import subprocess
 
@@ -14,20 +10,13 @@ import pytest
 
 import convert_cases as cc
 import convert_model as cm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "convert_math_check.cpp")
+from fixtures import load_golden, md5
+from host_programs import ASAN_UBSAN_STATIC, WARN, build, host_cxx
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path_factory.mktemp("convert") / "convert_math_check"
-    # the sanitizers' runtimes are linked statically: the program needs nothing preloaded
-    build = subprocess.run([cxx, "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                            "-static-libasan", "-static-libubsan", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = build("convert_math_check.cpp", tmp_path_factory.mktemp("convert"), host_cxx(), ["-O2", "-g", "-ffp-contract=off", *WARN, *ASAN_UBSAN_STATIC])
 
     def run(src, dst, W, H, planes=None):
         """planes None: the program generates the exhaustive frame itself.  Returns the destination's dense planes."""
@@ -50,12 +39,8 @@ def checker(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def golden():
-    here = os.path.join(ROOT, "tests", "golden")
-    return {c["id"]: c for c in json.load(open(os.path.join(here, "golden_convert.json")))["cases"]}, np.load(os.path.join(here, "golden_convert.npz"))
-
-
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
+    meta, arrays = load_golden("golden_convert")
+    return {c["id"]: c for c in meta["cases"]}, arrays
 
 
 @pytest.mark.parametrize("src", cc.SOURCES, ids=[cm.NAMES[s] for s in cc.SOURCES])

@@ -1,9 +1,6 @@
 """CPU tests of tests/convert_model.py, the numpy statement of the colour conversions: against plain Python loops written from the header's definition on the
 tiny sizes, against every fixture of tests/golden/golden_convert.* (what tests/golden/make_golden_convert.py held against the compiled reference), and
 against hand-worked literals."""
-import hashlib
-import json
-import os
 import struct
 
 import numpy as np
@@ -11,18 +8,12 @@ import pytest
 
 import convert_cases as cc
 import convert_model as cm
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
+from fixtures import load_golden, md5
 
 
 @pytest.fixture(scope="module")
 def golden():
-    d = os.path.join(HERE, "golden")
-    return json.load(open(os.path.join(d, "golden_convert.json"))), np.load(os.path.join(d, "golden_convert.npz"))
+    return load_golden("golden_convert")
 
 
 # ---- plain loops: one pixel at a time, Python ints, float32 through struct -----------------------------------------------------------------------------

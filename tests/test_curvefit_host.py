@@ -1,8 +1,6 @@
 """compv_amd/csrc/curvefit_math.hpp -- the arithmetic the curve-fit kernels are made of -- run on the host by tests/host/curvefit_math_check.cpp
 (standard library only, no GPU) and held against tests/curvefit_model.py bit for bit: samples, per-try inlier counts, the result record, the mask.
 The GPU tests (tests/test_gpu_curvefit.py) hold the kernels against the same model."""
-import os
-import shutil
 import struct
 import subprocess
 
@@ -11,18 +9,12 @@ import pytest
 
 import curvefit_cases as cc
 import curvefit_model as cm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "curvefit_math_check.cpp")
+from host_programs import WARN, build, host_cxx
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path_factory.mktemp("curvefit") / "curvefit_math_check"
-    build = subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = build("curvefit_math_check.cpp", tmp_path_factory.mktemp("curvefit"), host_cxx(), ["-O2", "-ffp-contract=off", *WARN])
 
     def run(pts, model, tries, threshold=cc.THRESHOLD, seed=0, set_index=0, samples=None):
         k, m = len(pts), cm.model_points(model)

@@ -1,22 +1,17 @@
 """tests/curvefit_model.py -- the numpy definition of the RANSAC line and parabola fits -- against the fixture tests/golden/golden_curvefit.* (generated
 by tests/golden/make_golden_curvefit.py, which held the model against the compiled reference: items B and C bit for bit, planted sets within 1e-6 px),
 and the definition's properties."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 import curvefit_cases as cc
 import curvefit_model as cm
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+from fixtures import GOLDEN_DIR, load_golden
 
 
 @pytest.fixture(scope="module")
 def golden():
-    meta = json.load(open(os.path.join(HERE, "golden", "golden_curvefit.json")))
-    return meta, np.load(os.path.join(HERE, "golden", "golden_curvefit.npz"))
+    return load_golden("golden_curvefit")
 
 
 def check_stored(arrays, cid, out):
@@ -55,7 +50,7 @@ def test_fixture_sets_are_the_case_generators(golden):
 def test_residuals_equal_the_fixture(golden):
     _, arrays = golden
     import sys
-    sys.path.insert(0, os.path.join(HERE, "golden"))
+    sys.path.insert(0, GOLDEN_DIR)
     from make_golden_curvefit import CURVES
     for model in cm.MODELS:
         for i, p in enumerate(CURVES[model]):

@@ -3,30 +3,17 @@ program of its own that includes that header alone, built with hipcc for the hos
 GPU every hipMalloc / hipHostMalloc fails, so this is where the failure paths, reserve(0), the empty release / destructor and the moves are executed; no
 GPU test reaches them.  Where a GPU is present the allocations would succeed (and a sanitized program must not open a GPU): skipped."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "device_memory_check.cpp")
+from host_programs import HIPCC_ASAN_UBSAN, HIPCC_HOST_ONLY, WARN, build, hipcc
 
 
-def _hipcc():
-    for cxx in (os.environ.get("HIPCC"), "hipcc", "/opt/rocm/bin/hipcc"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    return None
-
-
-@pytest.mark.skipif(_hipcc() is None, reason="no hipcc")
+@pytest.mark.skipif(hipcc() is None, reason="no hipcc")
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="a GPU is present: the allocations would succeed")
 def test_buffers_stay_empty_when_allocation_fails_and_move_without_double_counting(tmp_path):
-    exe = tmp_path / "device_memory_check"
-    build = subprocess.run([_hipcc(), "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-Xarch_host",
-                            "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined", SRC, "-o", str(exe)],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = build("device_memory_check.cpp", tmp_path, hipcc(), [*HIPCC_HOST_ONLY, "-O1", "-g", *WARN, *HIPCC_ASAN_UBSAN])
     run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     print(run.stdout, run.stderr)
     assert run.returncode == 0, run.stdout + run.stderr

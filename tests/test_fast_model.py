@@ -5,17 +5,14 @@ The fixture MD5s cover the (x, y, strength) triples of CompVCornerDeteFAST::proc
 noise and blurred blocks, five sizes down to 7 x 7 (one interior pixel).  That the model -- which evaluates every arc of every interior pixel and
 has none of the early exits of CompVFastDataRow_C -- reproduces all of them confirms that those exits are necessary conditions only."""
 import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
 import fast_model as fm
+from fixtures import load_golden
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-with open(os.path.join(HERE, "golden", "golden_fast.json")) as _f:
-    GOLDEN = json.load(_f)
+GOLDEN = load_golden("golden_fast")[0]
 CASES = GOLDEN["cases"]
 
 

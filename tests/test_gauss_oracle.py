@@ -1,29 +1,11 @@
 """Oracle vs the compiled reference for the optional Gaussian pre-blur:
 CompVMathGauss::kernelDim1 / kernelDim1FixedPoint and CompVMathConvlt::convlt1FixedPoint, incl. the reference's own
 known-answer vector unittests/math_convlt.cxx:21 (case 0, MD5 2678b73a89681f12fb474dd8102fc37c)."""
-import hashlib
-
 import numpy as np
 import pytest
 
-from oracle_bindings import synth_frame
-
-# unittests/math_convlt.cxx case 0 passes the FLOAT kernel of CompVMathGauss::kernelDim1(7, 3.5) to the u16 fixed-point entry
-# point (:143 builds it with kernelDim1, :66-70 reinterprets it): the 7 "weights" are the first 14 bytes of 7 floats.  They are
-# committed here as data (generated with the compiled reference on this toolchain's libm) so the vector is usable anywhere.
-CASE0_KERNEL_LITERAL = [16002, 15852, 56670, 15888, 48169, 15907, 36460, 15914, 48169, 15907, 56670, 15888, 16002, 15852]
-
-
-def md5_rows(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-def case0_input():
-    W, H, S = 1285, 720, 1344                                                  # unittests/math_convlt.cxx:21
-    j, i = np.mgrid[0:H, 0:W]
-    d = np.zeros((H, S), np.uint8)
-    d[:, :W] = ((i * j) + 53).astype(np.uint8)                                  # :96
-    return d[:, :W]
+from gauss_cases import CASE0_KERNEL_LITERAL, case0_input
+from oracle_bindings import md5_rows
 
 
 def test_case0_kernel_bytes_match_reference(refshim):

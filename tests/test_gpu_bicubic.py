@@ -1,7 +1,7 @@
 """The bicubic remap and inverse warp on the GPU (COMPVHIP_INTERP_BICUBIC / _BICUBIC_FLOAT32 through compvhip_plan_remap, compvhip_plan_warp_inverse and
 the host entries) against tests/bicubic_model.py on every frame and against the fixture (tests/golden/golden_bicubic.npz, the model held against the compiled
 reference's plain leaves) on frame 0, byte for byte -- float32 output by bit pattern.  Three frames, source S > W, guarded buffers from the Arena of
-tests/test_gpu_plan_geometry.py: the destination is pre-filled with a sentinel, so the padding columns and whatever lies behind the last frame must still
+tests/gpu_support.py: the destination is pre-filled with a sentinel, so the padding columns and whatever lies behind the last frame must still
 hold it afterwards.  Every destination runs once aligned (vector stores) and once with a stride that is no multiple of 4 elements (element stores); the widths
 cover Wout % 4 = 0 .. 3 and 261 exceeds one tile.  Every call is made twice.  The model's results are computed once per case and shared.
 
@@ -9,7 +9,6 @@ Dispatch arms (docs/dispatch_coverage.md): remap_bicubic_kernel over map / 2 x 3
 test_remap_cases and test_warp_cases launch all 12; the base clamp of the 4-byte tap row in test_narrow_sources; the 8-frame loop with a ragged last group in
 test_eleven_frames_cross_the_frame_groups; the sliced launch in test_sliced_launch_beyond_65535_frames."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -18,12 +17,12 @@ import bicubic_cases as bc
 import bicubic_model as bm
 import remap_cases as rc
 import remap_model as rm
-from test_gpu_plan_geometry import Arena, SENTINEL, pad_frames, ptr
+from fixtures import load_golden
+from gpu_support import Arena, SENTINEL, pad_frames, ptr
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-A = np.load(os.path.join(HERE, "golden", "golden_bicubic.npz"))
+A = load_golden("golden_bicubic")[1]
 F = 3
 INTERPS = bc.INTERPS
 REMAP = {c["id"]: c for c in bc.remap_cases()}

@@ -2,7 +2,7 @@
 (tests/components_model.py, pinned on the CPU by tests/test_components_model.py): label map, record array and counts, bit for bit -- the
 definition is integer-only and unique, there is no tolerance anywhere and no frame of any case is left out.
 
-Device buffers sit between guards and start filled with a sentinel (the Arena of tests/test_gpu_plan_geometry.py); the geometries are those
+Device buffers sit between guards and start filled with a sentinel (the Arena of tests/gpu_support.py); the geometries are those
 of tests/plan_geometries.py (ragged widths, padded strides whose padding holds random non-zero bytes, batches).
 """
 import ctypes as C
@@ -11,68 +11,12 @@ import numpy as np
 import pytest
 
 from components_model import COMP_DTYPE, components, summary
+from components_rig import Out, assert_result, model
+from gpu_support import SENTINEL, T_HIGH, T_LOW, Arena, frames_view, make_batch, pad_frames, ptr
 from hysteresis_cases import BASE, maze_frame, spiral_frame
 from plan_geometries import GEOMETRIES
-from test_gpu_plan_geometry import Arena, SENTINEL, T_HIGH, T_LOW, frames_view, make_batch, pad_frames, ptr
 
 pytestmark = pytest.mark.gpu
-
-COMP_BYTES = 28
-SENT32 = np.frombuffer(bytes([SENTINEL] * 4), np.int32)[0]
-
-
-class Out:
-    """The three output buffers of a plan call, in an Arena."""
-
-    def __init__(self, A, F, H, ls, cap, labels=True):
-        self.F, self.H, self.ls, self.cap = F, H, ls, cap
-        self.d_labels = A.new(F * H * ls * 4) if labels else None
-        self.d_comps = A.new(F * cap * COMP_BYTES) if cap else None
-        self.d_cc = A.new(F * 4)
-        self.A = A
-
-    def refill(self):
-        for b in (self.d_labels, self.d_comps, self.d_cc):
-            if b is not None:
-                self.A.refill(b)
-
-    def call(self, plan, d_edges, conn, mp, stream=0):
-        plan.components(d_edges, conn, mp, ptr(self.d_labels) if self.d_labels is not None else 0, self.ls,
-                        ptr(self.d_comps) if self.d_comps is not None else 0, self.cap, ptr(self.d_cc), stream)
-
-    def raw(self):
-        return tuple(None if b is None else b.cpu().numpy().tobytes() for b in (self.d_labels, self.d_comps, self.d_cc))
-
-
-def assert_result(out, W, exp, what):
-    """exp[f] = (labels, records) of the model.  Counts are the unclipped totals; the first min(count, cap) records equal the model's and the
-    slots behind them still hold the sentinel; the label map equals the model's and its columns >= W still hold the sentinel."""
-    F, H, ls, cap = out.F, out.H, out.ls, out.cap
-    counts = out.d_cc.cpu().numpy().view(np.int32)
-    for f in range(F):
-        assert int(counts[f]) == len(exp[f][1]), (what, f, int(counts[f]), len(exp[f][1]))
-    if out.d_comps is not None:
-        raw = out.d_comps.cpu().numpy().reshape(F, cap * COMP_BYTES)
-        for f in range(F):
-            want = exp[f][1]
-            n = min(len(want), cap)
-            got = np.frombuffer(raw[f][:n * COMP_BYTES].tobytes(), COMP_DTYPE)
-            if got.tobytes() != want[:n].tobytes():
-                bad = int(np.flatnonzero(got != want[:n])[0])
-                raise AssertionError("%s: frame %d record %d: got %s, expected %s" % (what, f, bad, got[bad], want[bad]))
-            assert (raw[f][n * COMP_BYTES:] == SENTINEL).all(), (what, f, "records beyond the count were written")
-    if out.d_labels is not None:
-        lab = out.d_labels.cpu().numpy().view(np.int32).reshape(F, H, ls)
-        for f in range(F):
-            if not np.array_equal(lab[f, :, :W], exp[f][0]):
-                ys, xs = np.nonzero(lab[f, :, :W] != exp[f][0])
-                raise AssertionError("%s: frame %d: %d labels differ, first at (x %d, y %d): got %d, expected %d"
-                                     % (what, f, len(ys), xs[0], ys[0], lab[f, ys[0], xs[0]], exp[f][0][ys[0], xs[0]]))
-            assert (lab[f, :, W:] == SENT32).all(), (what, f, "label columns >= W were written")
-
-
-def model(maps, conn, mp):
-    return [components(e, conn, mp) for e in maps]
 
 
 def dropping_min_pixels(maps, conn):

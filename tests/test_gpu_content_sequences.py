@@ -18,8 +18,8 @@ import numpy as np
 import pytest
 
 import content_sequences as cs
-import test_gpu_plan_geometry as pg
-from test_gpu_plan_geometry import Arena, SENTINEL, ptr
+import gpu_support as pg
+from gpu_support import FIT_BYTES, SEG_BYTES, SENTINEL, Arena, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -299,7 +299,7 @@ def test_matcher_sequence_of_device_counts(hip_ctx, shared):
     smaller non-zero train count, and crossCheck is off in between, so the reverse lists and `reverse` are stale in their own rhythm.
     The knn records and the good list against tests/match_model.py, byte for byte; columns behind a query count and records behind a good count keep the
     sentinel (Rig.knn_check / good_check)."""
-    import test_gpu_match as gm
+    import match_rig as gm
     m = cs.MATCH
     steps = cs.match_steps(shared)
     query, train = cs.match_descriptors(shared)
@@ -329,7 +329,7 @@ def test_homography_sequence_of_point_sets(hip_ctx):
     hypotheses of the call before must not be scored -- the per-try counts, variances and rotations are compared too), k = 4, another planted model; rotated over
     three pairs while tries goes 257 <-> 63, the quads come from the generator, then from the caller, then from the generator, and the mask is given or NULL.
     Against tests/homography_model.py, bit for bit; the points behind a pair's count are what the step before left there."""
-    import test_gpu_homography as gh
+    import homography_rig as gh
     import homography_model as hm
     from compv_amd import capi
     h = cs.HOMOGRAPHY
@@ -373,7 +373,7 @@ def test_fast_sequence(hip_ctx, geom):
     alternate with counts only.  Watches fastScores, the sums FAST clears per call and the corner lists; score map, counts and records against tests/fast_model.py;
     records behind a count and an unrequested score map keep the sentinel (Rig.check)."""
     import fast_model as fm
-    import test_gpu_fast as gf
+    import fast_rig as gf
     W, H, S, F = geom
     steps = cs.fast_sequence(W, H)
     exp = [[fm.fast(fr[f], p["t"], p["N"], p["nonmax"]) for f in range(F)] for fr, p in steps]
@@ -474,7 +474,7 @@ def test_hog_options_change_on_the_plans_own_cell_map(hip_ctx):
     norm -- and with them the map's layout -- and the content change between calls.  Descriptors against tests/hog_model.py by bit pattern; the floats behind
     descLen keep the sentinel."""
     import hog_model as hm
-    import test_gpu_hog as gh
+    import hog_rig as gh
     steps = cs.hog_sequence()
     W, H = cs.HOG_SIZE
     geo = [hm.geometry(W, H, hm.resolve(p["opts"])) for _, p in steps]
@@ -552,16 +552,16 @@ def test_plan_segments_fits_and_components_after_each_step(plan_rig):
     and minPixels change, compCap goes 0 -> 64, and d_labels goes NULL (the plan's compParent) -> given -> NULL.  A dense frame comes before an empty one in every
     frame slot, so segPerLine, compRows, compBits and compParent hold large stale numbers when the empty frame is walked.  Against tests/sht_segments_model.py,
     tests/sht_fit_model.py and tests/components_model.py; records behind a count and label columns >= W keep the sentinel (the stage tests' checkers)."""
-    import test_gpu_components as gc
-    import test_gpu_sht_fit as gfit
-    import test_gpu_sht_segments as gseg
+    import components_rig as gc
+    import sht_fit_rig as gfit
+    import sht_segments_rig as gseg
     r, o = plan_rig, plan_rig.outs[0]
     capi = r.capi
     K = len(r.steps)
     sinQ, cosQ = gseg.tables(r.oracle, r.W, r.H, 1.0)
     seg_cap = fit_cap = 16384          # above every segment count of the sequence, so the per-segment fits see every segment
-    d_segs, d_sc = r.A.new(cs.F * seg_cap * gseg.SEG_BYTES), r.A.new(cs.F * 4)
-    d_fits, d_fc = r.A.new(cs.F * fit_cap * gfit.FIT_BYTES), r.A.new(cs.F * 4)
+    d_segs, d_sc = r.A.new(cs.F * seg_cap * SEG_BYTES), r.A.new(cs.F * 4)
+    d_fits, d_fc = r.A.new(cs.F * fit_cap * FIT_BYTES), r.A.new(cs.F * 4)
     outs = [gc.Out(r.A, cs.F, r.H, r.W + 3, cap, labels=lab) for lab, cap in cs.FEATURE_OUTPUTS]
     foreign, exp = [], []
     for k in range(K):
@@ -616,7 +616,7 @@ def test_plan_houghkht_sequence_in_both_orders(hip_ctx, oracle, monkeypatch):
     while COMPVHIP_KHT_GROUP splits the batch into three groups, two, or leaves it whole.  The pooled per-group buffers (strings, clusters, kernels, vote maps,
     the canonical peak lists) grow on demand and are never cleared; an empty frame after a busy one must return no line and leave its GS untouched.  The reference
     order against the oracle, the canonical order against tests/kht_canon_model.py, as tests/test_gpu_kht_canonical.py compares them."""
-    import test_gpu_kht_canonical as gk
+    import kht_canon_model as gk
     from compv_amd import capi
     from kht_canon_model import CanonModel
     W, H, S = cs.KHT_GEOMETRY
@@ -647,7 +647,7 @@ def test_plan_houghkht_sequence_in_both_orders(hip_ctx, oracle, monkeypatch):
         for f in range(cs.F):
             el, egs = exp[k][f]
             if p["order"] == "canonical":
-                assert gk._bits(lines[f]) == gk._model_bits(el), (what, f)
+                assert gk.line_bits(lines[f]) == gk.model_line_bits(el), (what, f)
                 assert gs[f] == egs, (what, f)
             else:
                 assert [(float(l["rho"]), float(l["theta"]), int(l["strength"])) for l in lines[f]] == \
@@ -670,7 +670,7 @@ def test_orb_keypoints_and_describe_sequence(hip_ctx, geom):
     with 0 (the caller's blurred frames).  Watches orbIndex (the survivors' indices, never cleared) and orbBlur; counts, records, moments and rows against
     tests/orb_model.py, and nothing behind a list or a row is written."""
     import orb_model as om
-    import test_gpu_orb as go
+    import orb_rig as go
     W, H, S, F = geom
     steps = cs.orb_sequence(W, H)
     rig = go.Rig(hip_ctx, geom, 7, 260)
@@ -708,7 +708,7 @@ def test_orb_pyramid_sequence(hip_ctx):
     never cleared.  Every level's plane, FAST count, survivor count and record, and every row, against tests/orb_pyramid_model.py."""
     import orb_model as om
     import orb_pyramid_model as pm
-    import test_gpu_orb_pyramid as gp
+    import orb_pyramid_rig as gp
     geom = cs.ORBPYR_GEOMETRY
     W, H, S, levels, sf, mf = geom
     steps = cs.orbpyr_sequence()

@@ -1,7 +1,7 @@
 """GPU colour conversion (compvhip_convert_frames, compvhip_convert_u8) against tests/convert_model.py on every frame and against the fixtures of
 tests/golden/golden_convert.* where a frame is a golden case, byte for byte: nothing here is compared with a tolerance.
 
-Harness of tests/test_gpu_plan_geometry.py: every device buffer sits between two guards and starts filled with a sentinel.  An image's planes lie in one
+Harness of tests/gpu_support.py: every device buffer sits between two guards and starts filled with a sentinel.  An image's planes lie in one
 buffer each, `frames` of them, rows rowBytes apart and frames frameBytes apart; after a call every byte of an output buffer that is no pixel -- between
 a row's end and rowBytes, between frames, in front of the first plane and behind the last frame -- must still hold the sentinel, and every input must be
 unchanged.  The calls allocate nothing: compvhip_live_allocations is the same before and after every device call.
@@ -13,33 +13,25 @@ The kernel's arms (compv_amd/csrc/convert_kernels.hip; one thread = 8 adjacent p
 import contextlib
 import ctypes as C
 import functools
-import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
 import convert_cases as cc
 import convert_model as cm
-from test_gpu_plan_geometry import Arena, SENTINEL, ptr
+from fixtures import load_golden, md5
+from gpu_support import Arena, SENTINEL, ptr
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SIZES = ((7, 5), (33, 17), (250, 3), (641, 480))
 PAIR_IDS = [cm.pair_name(s, d) for s, d in cm.SERVED]
 FRAMES = 3
 
 
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
 @pytest.fixture(scope="module")
 def golden():
-    d = os.path.join(HERE, "golden")
-    return {c["id"]: c for c in json.load(open(os.path.join(d, "golden_convert.json")))["cases"]}
+    return {c["id"]: c for c in load_golden("golden_convert")[0]["cases"]}
 
 
 @functools.lru_cache(maxsize=None)

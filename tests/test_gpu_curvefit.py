@@ -1,31 +1,24 @@
 """GPU RANSAC line and parabola fits (compvhip_curvefit_*) against tests/curvefit_model.py and the fixture tests/golden/golden_curvefit.*, bit for bit:
 nothing here is compared with a tolerance.
 
-Harness of tests/test_gpu_plan_geometry.py: every device buffer sits between two guards; outputs start filled with a sentinel that must survive in
+Harness of tests/gpu_support.py: every device buffer sits between two guards; outputs start filled with a sentinel that must survive in
 every slot the definition leaves unwritten (mask bytes and distances at and behind a set's k); the inputs must come back unchanged, and the point
 slots behind a set's count hold seeded junk that is never read.  Every call is made twice on the same handle.
 
 The score kernel gives one workgroup 256 tries and stages 256 points per round, the refit kernel folds 64 partials, the gather scans 256 pixels per
 round.  Shapes are chosen from those numbers: k m - 1, m, m + 1, 63, 64, 65, 255, 256, 257, 600; tries 1, 255, 256, 257, maxTries."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 import curvefit_cases as cc
 import curvefit_model as cm
-from test_gpu_plan_geometry import Arena, SENTINEL, d2h, ptr
+from fixtures import load_golden
+from gpu_support import SENTINEL, Arena, d2h, ptr, u8
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 REC = cm.RESULT_DTYPE.itemsize
 SENT64 = np.frombuffer(bytes([SENTINEL] * 8), np.float64)[0]
-
-
-def u8(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
 class Rig:
@@ -116,9 +109,7 @@ class Rig:
 
 @pytest.fixture(scope="module")
 def golden():
-    with open(os.path.join(HERE, "golden", "golden_curvefit.json")) as f:
-        meta = json.load(f)
-    return meta, np.load(os.path.join(HERE, "golden", "golden_curvefit.npz"))
+    return load_golden("golden_curvefit")
 
 
 @pytest.mark.parametrize("model", cm.MODELS)

@@ -3,9 +3,9 @@ variant against the oracle (pinned to the compiled reference and to the referenc
 import numpy as np
 import pytest
 
-from oracle_bindings import synth_frame
-from test_gauss_oracle import CASE0_KERNEL_LITERAL, case0_input, md5_rows
-from test_gpu_plan_geometry import Arena, SENTINEL, frames_view, pad_frames, ptr
+from gauss_cases import CASE0_KERNEL_LITERAL, case0_input, convlt_inputs
+from gpu_support import SENTINEL, Arena, frames_view, pad_frames, ptr
+from oracle_bindings import md5_rows, synth_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -83,7 +83,7 @@ def test_plan_blur_then_canny_batch(hip_ctx, oracle):
 
 # ---------------------------------------------------------------------------------------------------------------
 # the plan form at every kernel size: the fused kernel on batches and the two-pass path (convlt_fxp_hz_kernel<K> then convlt_fxp_vt_kernel<K>),
-# which launch_convlt_fxp takes only when the input and output spans overlap.  Buffers come from the Arena of tests/test_gpu_plan_geometry.py.
+# which launch_convlt_fxp takes only when the input and output spans overlap.  Buffers come from the Arena of tests/gpu_support.py.
 #
 # Geometries (W, H, S, F) from the kernels' seams: 8 pixels per thread, 256 threads = 2048 columns per workgroup, kFxpRows = 64 output rows per
 # workgroup, the right-hand load clamped to S - 8, the row clamp at 0 and H - 1.
@@ -354,9 +354,7 @@ def test_plan_convlt_on_a_stream(hip_ctx, oracle):
 def test_convlt1_int16_reference_known_answers_on_the_gpu(hip_ctx):
     """unittests/math_convlt.cxx:24-25, cases 5 and 6 (1285x720, stride 1344, k = 7, data (i*j)+53 with alternating signs for the int16
     case): MD5 of the int16 result -- the only reference-held golden vectors on the hot path's operators -- from the HIP kernels."""
-    from test_oracle import _convlt_inputs
-    from oracle_bindings import md5_rows
-    d8, d16, k = _convlt_inputs()
+    d8, d16, k = convlt_inputs()
     assert md5_rows(hip_ctx.convlt1_i16(d8, k, k)) == "7f1116ade2a1cdb37842084c781ee05e"
     assert md5_rows(hip_ctx.convlt1_i16(d16, k, k)) == "cad2f4d2fd66e171997f39804e667699"
 

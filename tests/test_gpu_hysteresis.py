@@ -2,8 +2,8 @@
 heterogeneous batches and replays, bit for bit against the oracle.
 
 The cases come from tests/hysteresis_cases.py; tests/test_hysteresis_cases.py proves on the CPU what each of them crosses and how many
-launches it needs at least.  Every device buffer sits between guard pages and every output starts filled with a sentinel (the arena of
-tests/test_gpu_plan_geometry.py).  A test that claims extra rounds or a replay shows that they happened: with plan.set_timing(1) the
+launches it needs at least.  Every device buffer sits between guard pages and every output starts filled with a sentinel (the Arena of
+tests/gpu_support.py).  A test that claims extra rounds or a replay shows that they happened: with plan.set_timing(1) the
 timeline of the last synchronous call (or of the replay inside compvhip_plan_wait, which runs as a synchronous step) holds one
 "canny_resolve_kernel" entry per launch; COMPVHIP_TRACE_ROUNDS=1 (read when a plan is made) prints what an asynchronous
 ticket saw."""
@@ -12,7 +12,7 @@ import pytest
 
 import hysteresis_cases as hc
 from oracle_bindings import synth_frame
-from test_gpu_plan_geometry import (LINE_CAP, Arena, assert_lines, assert_maps, check_accs, edge_counts, frames_view, pad_frames, pool, ptr,
+from gpu_support import (LINE_CAP, Arena, assert_lines, assert_maps, check_accs, edge_counts, frames_view, pad_frames, pool, ptr,
                                     sht_expect)
 
 pytestmark = pytest.mark.gpu

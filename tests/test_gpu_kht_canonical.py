@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from kht_canon_model import CanonModel, emission, has_tie_neighbour
+from kht_canon_model import CanonModel, emission, has_tie_neighbour, line_bits, model_line_bits
 from oracle_bindings import md5_rows, synth_frame
 
 pytestmark = pytest.mark.gpu
@@ -19,16 +19,6 @@ LDS_SORT_LINES = 2048      # kKhtCanonSortLds (compv_amd/csrc/kht.hpp): beyond, 
 @pytest.fixture(scope="module")
 def model(oracle):
     return CanonModel(oracle)
-
-
-def _bits(lines):
-    """LINE_DTYPE array -> [(rho bits, theta bits, strength, row, col)]"""
-    return list(zip(lines["rho"].astype(np.float32).view(np.uint32).tolist(), lines["theta"].astype(np.float32).view(np.uint32).tolist(),
-                    lines["strength"].tolist(), lines["row"].tolist(), lines["col"].tolist()))
-
-
-def _model_bits(lines):
-    return [(int(np.float32(l[0]).view(np.uint32)), int(np.float32(l[1]).view(np.uint32)), l[2], l[3], l[4]) for l in lines]
 
 
 def _list_hash(l):
@@ -53,7 +43,7 @@ def _plan_edges(hip_ctx, frames, tl, th):
 
 def _check_against_model(model, lines, gs, edges, **kw):
     exp, egs, rec = model.lines(edges, **kw)
-    assert _bits(lines) == _model_bits(exp)
+    assert line_bits(lines) == model_line_bits(exp)
     assert gs == egs
     return exp, rec
 
@@ -79,7 +69,7 @@ def test_canonical_uhd_batch_against_the_model(hip_ctx, model, F):
             assert (len(l), int(l["strength"].astype(np.int64).sum()), repr(rgs[f]), "%016x" % _list_hash(l)) == \
                 (g["lines"], g["sum_strength"], g["gs"], g["list_hash"]), f
             assert cgs[f] == rgs[f]
-            differs += _bits(canon[f]) != _bits(ref[f])
+            differs += line_bits(canon[f]) != line_bits(ref[f])
         assert differs > 0
     finally:
         plan.close()
@@ -98,7 +88,7 @@ def test_canonical_host_entry_point_against_the_model(hip_ctx, oracle, model):
     # maxLines inside a tie group
     cut = next(i for i in range(1, len(exp)) if exp[i - 1][2] == exp[i][2])
     top, _ = hip_ctx.houghkht(e, 1.0, 1.0, 1, max_lines=cut, order="canonical")
-    assert _bits(top) == _model_bits(exp[:cut]) and len(top) == cut
+    assert line_bits(top) == model_line_bits(exp[:cut]) and len(top) == cut
     # no record at all; GS is still reported (kernels survived)
     none, gsn = hip_ctx.houghkht(e, 1.0, 1.0, 1 << 30, order="canonical")
     assert len(none) == 0 and gsn == gs
@@ -139,7 +129,7 @@ def test_canonical_batch_of_13_with_a_blank_frame(hip_ctx, model):
         cut = next(i for i in range(1, len(exps[0])) if exps[0][i - 1][2] == exps[0][i][2])
         top, _ = plan.houghkht(d_e.data_ptr(), 1.0, 1.0, 1, max_lines=cut, order="canonical")
         for f in range(F):
-            assert _bits(top[f]) == _model_bits(exps[f][:cut]), f
+            assert line_bits(top[f]) == model_line_bits(exps[f][:cut]), f
     finally:
         plan.close()
 
@@ -154,7 +144,7 @@ def test_canonical_beyond_the_lds_sort(hip_ctx, oracle, model):
             exp, _ = _check_against_model(model, lines[f], gs[f], e[f])
             assert len(exp) > LDS_SORT_LINES
         one, g1 = hip_ctx.houghkht(e[0], 1.0, 1.0, 1, order="canonical")
-        assert _bits(one) == _bits(lines[0]) and g1 == gs[0]
+        assert line_bits(one) == line_bits(lines[0]) and g1 == gs[0]
     finally:
         plan.close()
     big = synth_frame(3840, 2160, 3)
@@ -179,13 +169,13 @@ def test_both_orders_coexist_on_one_plan(hip_ctx, model):
         ref, rgs = plan.houghkht(d_e.data_ptr(), 1.0, 1.0, 1)
         assert cgs == cgs1 == rgs
         for f in range(F):
-            assert _bits(canon[f]) == _bits(canon1[f])
+            assert line_bits(canon[f]) == line_bits(canon1[f])
             ax, counts, _ = model.vote_map(e[f])
             rec = emission(ax, counts, 1)
             tie = {}
             for (r, t, s, _), flag in zip(rec.tolist(), has_tie_neighbour(rec, ax.rhoN, ax.T).tolist()):
                 tie[(r, t, s)] = tie.get((r, t, s), False) or flag
-            clear = lambda ls: {x for x in _bits(ls) if not tie[(x[3], x[4], x[2])]}
+            clear = lambda ls: {x for x in line_bits(ls) if not tie[(x[3], x[4], x[2])]}
             assert clear(canon[f]) == clear(ref[f]) and len(clear(canon[f])) > 0
         # capacity contract
         need = [len(l) for l in canon]
@@ -197,7 +187,7 @@ def test_both_orders_coexist_on_one_plan(hip_ctx, model):
                                                    counts.ctypes.data_as(C.c_void_p), None)
         assert rc == capi.E_OUT_OF_BOUND and counts.tolist() == need
         for f in range(F):
-            assert _bits(buf[f]) == _bits(canon[f][:cap])
+            assert line_bits(buf[f]) == line_bits(canon[f][:cap])
         assert hip_ctx.lib.compvhip_plan_houghkht_ex(plan.h, d_e.data_ptr(), None, buf.ctypes.data_as(C.c_void_p), cap,
                                                      counts.ctypes.data_as(C.c_void_p), None) == capi.E_INVALID_PARAMETER
         opts.order = 2

@@ -24,10 +24,10 @@ import morph_model as mm
 import remap_cases as rc
 import remap_model as rm
 from components_model import COMP_DTYPE, components
+from gpu_support import COMP_BYTES, FIT_BYTES, LINE_BYTES, SEG_BYTES, SENTINEL, Arena, pad_frames, ptr
+from morph_rig import STRELS, strokes
 from sht_fit_model import FIT_DTYPE, frame_fits, refine_lines
 from sht_segments_model import SEG_DTYPE, frame_segments
-from test_gpu_morph import STRELS, strokes
-from test_gpu_plan_geometry import Arena, SENTINEL, pad_frames, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +36,6 @@ F_BIG = LIMIT + 6                   # one full slice, a last slice of 6
 F_TWICE = 2 * LIMIT + 3             # two full slices: the slice start advances twice
 F_GROUPS = 8 * LIMIT + 5            # the shared-map remap packs 8 frames into a group: a second slice of one ragged group
 CONTENT, PARAM, COUNT = 7, 11, 4    # periods of the frame content, of per-frame parameters, of line lists and their counts
-LINE_BYTES, SEG_BYTES, FIT_BYTES, COMP_BYTES = 20, 24, 80, 28
 FIT_INTS, FIT_DOUBLES = ("line", "pixels", "sx", "sy", "sxx", "sxy", "syy"), ("nx", "ny", "rho", "rms2")
 
 

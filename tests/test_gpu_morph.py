@@ -1,7 +1,7 @@
 """GPU thresholding and morphology (compvhip_plan_threshold / _threshold_adaptive / _morph and their host forms) against tests/morph_model.py,
 byte for byte, every frame of every case.
 
-Harness of tests/test_gpu_plan_geometry.py: every device buffer sits between two guards; outputs start filled with a sentinel, their padding
+Harness of tests/gpu_support.py: every device buffer sits between two guards; outputs start filled with a sentinel, their padding
 columns [W, S) included, and must still hold it there afterwards (the kernels never write columns >= W); the input's padding columns hold
 seeded random bytes.  Inputs of out-of-place calls must come back unchanged.
 
@@ -24,8 +24,9 @@ import pytest
 
 import morph_model as mm
 from components_model import COMP_DTYPE, components
+from gpu_support import SENTINEL, Arena, pad_frames, ptr
+from morph_rig import STRELS, strokes
 from plan_geometries import GEOMETRIES
-from test_gpu_plan_geometry import Arena, SENTINEL, pad_frames, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -36,34 +37,7 @@ OPS = (mm.ERODE, mm.DILATE, mm.OPEN, mm.CLOSE)
 BORDERS = (mm.BORDER_REPLICATE, mm.BORDER_ZERO)
 
 
-def off_centre(sw, sh, j, i):
-    s = np.zeros((sh, sw), np.uint8)
-    s[j, i] = 7
-    return s
-
-
-STRELS = {
-    "rect3x3": mm.strel(mm.RECT, 3, 3), "rect1x5": mm.strel(mm.RECT, 1, 5), "rect5x1": mm.strel(mm.RECT, 5, 1), "rect15x3": mm.strel(mm.RECT, 15, 3),
-    "rect3x15": mm.strel(mm.RECT, 3, 15), "cross5x5": mm.strel(mm.CROSS, 5, 5), "cross31x3": mm.strel(mm.CROSS, 31, 3), "diamond7x7": mm.strel(mm.DIAMOND, 7, 7),
-    "random5x7": (np.random.default_rng(57).random((7, 5)) < 0.4).astype(np.uint8) * 255, "single": off_centre(5, 3, 0, 4),
-}
-assert STRELS["random5x7"].any()
-
-
 # ---- frame content ---------------------------------------------------------------------------------------------------------------------
-def strokes(W, H, seed):
-    """binary {0, 255} text-like strokes"""
-    rng = np.random.default_rng(seed)
-    img = np.zeros((H, W), np.uint8)
-    for _ in range(max(3, W * H // 60)):
-        x, y, ln = int(rng.integers(0, W)), int(rng.integers(0, H)), int(rng.integers(2, 9))
-        if rng.integers(0, 2):
-            img[y, x:x + ln] = 255
-        else:
-            img[y:y + ln, x] = 255
-    return img
-
-
 def seam(W, H, seed):
     """mid-gray everywhere; the extremes 0 and 255 sit only in the columns and rows either side of the 256 x 32 (and 128 x 32) tile seams, which
     are halo cells of the neighbouring tile"""

@@ -23,20 +23,19 @@ import numpy as np
 import pytest
 
 import alignment_cases as ac
+import components_rig as tgc
 import morph_model as mm
 import orb_pyramid_model as pm
 import remap_cases as rc
 import remap_model as rm
-import test_gpu_components as tgc
-import test_gpu_sht_fit as tgf
-import test_gpu_sht_segments as tgs
-from test_gpu_kht_canonical import _bits, _model_bits
-from test_gpu_plan_geometry import (LINE_CAP, SENTINEL, T_HIGH, T_LOW, assert_lines, assert_maps, canny_modes, check_accs, edge_counts, frame_expectations,
-                                    frames_view, lines_of, make_batch, pad_frames, ptr, rgb_of, sht_expect, sht_threshold)
+import sht_fit_rig as tgf
+import sht_segments_rig as tgs
+from gpu_support import (BAND, FIT_BYTES, LINE_CAP, SEG_BYTES, SENTINEL, T_HIGH, T_LOW, assert_lines, assert_maps, canny_modes, check_accs, edge_counts,
+                         frame_expectations, frames_view, lines_of, make_batch, pad_frames, ptr, rgb_of, sht_expect, sht_threshold)
+from kht_canon_model import line_bits, model_line_bits
 
 pytestmark = pytest.mark.gpu
 
-BAND = 64
 F = 3
 THETA = 1.0
 GEOMETRIES = ((43, 49, 48), (515, 67, 520))
@@ -48,7 +47,7 @@ MAX_LINES = 12                             # lines per frame the segment and fit
 
 
 class Bands:
-    """Arena of tests/test_gpu_plan_geometry.py with 64-byte sentinel bands and a payload that starts `off` bytes behind the first one"""
+    """Arena of tests/gpu_support.py with 64-byte sentinel bands and a payload that starts `off` bytes behind the first one"""
 
     def __init__(self):
         import torch
@@ -107,7 +106,7 @@ _EXPECT = {}
 
 
 def expectations(orc, g):
-    """per frame: the dictionary of test_gpu_plan_geometry.frame_expectations (detectors, the six Canny modes, SHT, Otsu, RGB24 chain, K = 5 blur, KHT)"""
+    """per frame: the dictionary of gpu_support.frame_expectations (detectors, the six Canny modes, SHT, Otsu, RGB24 chain, K = 5 blur, KHT)"""
     if g not in _EXPECT:
         _EXPECT[g] = [frame_expectations(orc, img, THETA, True, gauss5()) for img in frames_of(g)]
     return _EXPECT[g]
@@ -421,12 +420,12 @@ def test_sht_segments_fits_and_components_on_unaligned_edge_bytes(hip_ctx, oracl
             check_accs(plan, A, F, R, T, [x[0] for x in sht], "houghsht " + what)
 
             lines, _ = tgs.lines_of(d_lines, d_counts, F, LINE_CAP)
-            d_segs, d_sc = A.new(F * cap * tgs.SEG_BYTES), A.new(F * 4)
+            d_segs, d_sc = A.new(F * cap * SEG_BYTES), A.new(F * 4)
             plan.houghsht_segments(ptr(d_e), ptr(d_lines), ptr(d_counts), LINE_CAP, MAX_LINES, 3, 1, ptr(d_segs), cap, ptr(d_sc))
             A.check("segments " + what)
             tgs.assert_segments(d_segs, d_sc, F, cap, tgs.model_frames(e3, sinQ, cosQ, lines, [(3, 1)], MAX_LINES)[(3, 1)], "segments " + what)
 
-            d_fits, d_fc, d_ref = A.new(F * cap * tgf.FIT_BYTES), A.new(F * 4), A.new(F * LINE_CAP * 20)
+            d_fits, d_fc, d_ref = A.new(F * cap * FIT_BYTES), A.new(F * 4), A.new(F * LINE_CAP * 20)
             plan.houghsht_fit(ptr(d_e), ptr(d_lines), ptr(d_counts), LINE_CAP, MAX_LINES, 2, 0, 0, 0, ptr(d_fits), cap, ptr(d_fc), ptr(d_ref))
             A.check("fits " + what)
             fits, valid = tgf.model_fits(e3, sinQ, cosQ, R, lines, 2, MAX_LINES)
@@ -475,7 +474,7 @@ def test_batched_kht_on_unaligned_edge_bytes_in_both_orders(hip_ctx, oracle, g):
             lines, gs = plan.houghkht(ptr(d_e), 1.0, THETA, 12, order="canonical")
             A.check("canonical kht at +%d" % off)
             for f in range(F):
-                assert _bits(lines[f]) == _model_bits(canon[f][0]), ("canonical kht at +%d" % off, f)
+                assert line_bits(lines[f]) == model_line_bits(canon[f][0]), ("canonical kht at +%d" % off, f)
                 assert gs[f] == canon[f][1], ("canonical kht gs at +%d" % off, f)
     finally:
         plan.close()

@@ -50,7 +50,7 @@ def test_plan_grayscale_batch_matches_oracle(hip_ctx, oracle, fmt, W, H, S, F):
     """gray_kernel<FMT> with blockIdx.z > 0: every format through Plan.grayscale on packed frames [F][H][S * bpp] that differ from one another
     (a wrong frame offset shows), between guards, random bytes in the padding samples; the input comes back unchanged"""
     from compv_amd import capi
-    from test_gpu_plan_geometry import Arena, assert_maps, frames_view, pad_frames, ptr
+    from gpu_support import Arena, assert_maps, frames_view, pad_frames, ptr
     bpp = oracle.fmt_bytes(fmt)
     assert bpp == capi.FMT_BYTES[fmt]
     rng = np.random.default_rng(1000 * fmt + W)
@@ -78,7 +78,7 @@ def test_plan_grayscale_batch_matches_oracle(hip_ctx, oracle, fmt, W, H, S, F):
 
 def test_plan_grayscale_refusals_write_nothing(hip_ctx):
     from compv_amd import capi
-    from test_gpu_plan_geometry import Arena, SENTINEL, ptr
+    from gpu_support import Arena, SENTINEL, ptr
     W, H, S, F = 33, 4, 40, 2
     A = Arena()
     d_in, d_gray = A.new(F * H * S * 4), A.new(F * H * S)

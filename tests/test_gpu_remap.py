@@ -1,6 +1,6 @@
 """The remap and the inverse warp on the GPU (compvhip_plan_remap, compvhip_plan_warp_inverse and the host entries) against tests/remap_model.py on every
 frame and against the planes the compiled reference wrote (tests/golden/golden_remap.npz) on frame 0, byte for byte -- float32 output by bit pattern.
-Three frames, source S > W, guarded buffers from the Arena of tests/test_gpu_plan_geometry.py: the destination is pre-filled with a sentinel, so the padding
+Three frames, source S > W, guarded buffers from the Arena of tests/gpu_support.py: the destination is pre-filled with a sentinel, so the padding
 columns and whatever lies behind the last frame must still hold it afterwards.  Every destination runs once aligned (the vector-store path) and once with a
 stride that is no multiple of 4 elements (the element-store path); the widths cover Wout % 4 = 0, 1, 2, 3 and 261 exceeds one tile.  Every call is made twice.
 The model's results are computed once per case and shared.
@@ -9,21 +9,18 @@ Dispatch arms (docs/dispatch_coverage.md): coordinate source map / 2 x 3 / 3 x 3
 stores -- test_remap_cases and test_warp_cases launch all 18; the float4 map read (Wout % 4 == 0) runs in the 40-wide cases; the 8-frame loop with a
 ragged last group in test_eleven_frames_cross_the_frame_groups."""
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
 
 import remap_cases as rc
 import remap_model as rm
-from test_gpu_plan_geometry import Arena, SENTINEL, pad_frames, ptr
+from fixtures import load_golden
+from gpu_support import Arena, SENTINEL, pad_frames, ptr
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-G = json.load(open(os.path.join(HERE, "golden", "golden_remap.json")))
-A = np.load(os.path.join(HERE, "golden", "golden_remap.npz"))
+G, A = load_golden("golden_remap")
 F = 3
 INTERPS = (rm.NEAREST, rm.BILINEAR, rm.BILINEAR_FLOAT32)
 REMAP = {c["id"]: c for c in rc.remap_cases()}

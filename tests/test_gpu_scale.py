@@ -1,24 +1,20 @@
 """The bilinear scale on the GPU (compvhip_plan_scale, compvhip_scale_u8) against tests/orb_pyramid_model.py byte for byte, and -- for the downscales the
 golden generator ran through CompVImage::scale -- against the planes the compiled reference wrote (tests/golden/golden_orb_pyramid.npz).  Three frames,
-S > W on both sides, guarded buffers from the Arena of tests/test_gpu_plan_geometry.py: the destination is pre-filled with a sentinel, so the padding
+S > W on both sides, guarded buffers from the Arena of tests/gpu_support.py: the destination is pre-filled with a sentinel, so the padding
 columns and whatever lies behind the last frame must still hold it afterwards.  Every destination runs with a dword-aligned stride (the dword-store path)
 and with one that is no multiple of 4 (the byte path); the widths cover Wout % 4 = 0, 1, 2, 3.  Upscales and the identity are held against the model alone:
 the reference reads past its plane there (include/compv_hip.h, rule A.5)."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 import fast_model as fm
 import orb_pyramid_model as pm
-from test_gpu_plan_geometry import Arena, SENTINEL, pad_frames, ptr
+from fixtures import load_golden
+from gpu_support import Arena, SENTINEL, pad_frames, ptr
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-G = json.load(open(os.path.join(HERE, "golden", "golden_orb_pyramid.json")))
-A = np.load(os.path.join(HERE, "golden", "golden_orb_pyramid.npz"))
+G, A = load_golden("golden_orb_pyramid")
 F = 3
 DOWN = tuple((s["W"], s["H"], s["Wout"], s["Hout"]) for s in G["scales"])          # (9, 7, 7, 5), (64, 41, 53, 34), (1100, 5, 1021, 4), (300, 8, 2, 1)
 UP = ((16, 16, 40, 23), (37, 37, 38, 37))

@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import sht_rank_cases as rc
-import test_gpu_plan_geometry as pg
-from test_gpu_plan_geometry import Arena, ptr
+import gpu_support as pg
+from gpu_support import Arena, ptr
 
 pytestmark = pytest.mark.gpu
 

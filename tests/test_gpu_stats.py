@@ -1,7 +1,7 @@
 """GPU image statistics (compvhip_plan_integral / _histogram / _equalize / _projections and their host forms) against tests/stats_model.py on every frame
 and against the fixtures of tests/golden/golden_stats.* on frame 0, by bit pattern: nothing here is compared with a tolerance.
 
-Harness of tests/test_gpu_plan_geometry.py: every device buffer sits between two guards; the outputs start filled with a sentinel, so every element the
+Harness of tests/gpu_support.py: every device buffer sits between two guards; the outputs start filled with a sentinel, so every element the
 definition defines must be written and every other one must keep it (columns > W of the integral images, columns >= W of the equalised frames); the frames'
 padding columns [W, S) hold seeded random bytes and the frames must come back unchanged.  Every call is made twice and must repeat itself byte for byte.
 Three frames per case, S > W.
@@ -17,20 +17,17 @@ stores), frames 3 bytes into their buffer the byte ones.
 A plan has at least 3 x 3 pixels (compvhip_plan_create), so 1 x 1, 1 x 300 and 300 x 1 -- which these calls accept -- go through the host forms, which
 need no plan: host arrays pre-filled with the sentinel, host strides beyond W, twice, against model and fixture."""
 import ctypes as C
-import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
 import stats_cases as sc
 import stats_model as sm
-from test_gpu_plan_geometry import Arena, SENTINEL, pad_frames, ptr
+from fixtures import load_golden, md5
+from gpu_support import Arena, SENTINEL, pad_frames, ptr
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 PLAN_CASES = [c["id"] for c in sc.CASES if c["W"] >= 3 and c["H"] >= 3]
 HOST_ONLY = [c["id"] for c in sc.CASES if c["W"] < 3 or c["H"] < 3]
 OTHER = {"const0": ("const255", 0), "const255": ("ramp", 3), "ramp": ("text", 2), "noise": ("text", 2), "text": ("noise", 3)}          # frame 1 of a case, by its kind
@@ -39,12 +36,8 @@ F64_SENTINEL = np.frombuffer(bytes([SENTINEL]) * 8, np.uint64)[0]
 
 @pytest.fixture(scope="module")
 def golden_stats():
-    d = os.path.join(HERE, "golden")
-    return {c["id"]: c for c in json.load(open(os.path.join(d, "golden_stats.json")))["cases"]}, np.load(os.path.join(d, "golden_stats.npz"))
-
-
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
+    meta, arrays = load_golden("golden_stats")
+    return {c["id"]: c for c in meta["cases"]}, arrays
 
 
 def frames_of(c):

@@ -1,7 +1,7 @@
 """GPU SVM prediction (compvhip_svm_*) against the fixture the compiled reference made (tests/golden/golden_svm.*, svm_*.model) and tests/svm_model.py,
 bit for bit in labels, decision values and kernel values: nothing here is compared with a tolerance.
 
-Harness of tests/test_gpu_plan_geometry.py: every device buffer sits between two guards; outputs start filled with a sentinel that must survive in every
+Harness of tests/gpu_support.py: every device buffer sits between two guards; outputs start filled with a sentinel that must survive in every
 element behind n and in every refused call; the queries are staged at a stride above D with a large finite sentinel in the padding, which would show in
 any kernel value that read it.
 
@@ -14,17 +14,13 @@ import pytest
 
 import svm_cases as sc
 import svm_model as sm
-from test_gpu_plan_geometry import Arena, SENTINEL, ptr
+from gpu_support import SENTINEL, Arena, ptr, u8
 
 pytestmark = pytest.mark.gpu
 
 CASES = sc.all_cases()
 BY_ID = {c["id"]: c for c in CASES}
 PAD = 7e30          # finite in float32 and float64: (PAD - sv)^2 would swamp any kernel value
-
-
-def u8(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
 class Rig:

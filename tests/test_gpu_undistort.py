@@ -1,44 +1,31 @@
 """GPU lens undistortion (compvhip_undistort_*) against the fixture the compiled reference made (tests/golden/golden_undistort.*) and
 tests/undistort_model.py, bit for bit: nothing here is compared with a tolerance.
 
-Harness of tests/test_gpu_plan_geometry.py: every device buffer sits between two guards; a destination starts filled with a sentinel and is compared as a
+Harness of tests/gpu_support.py: every device buffer sits between two guards; a destination starts filled with a sentinel and is compared as a
 WHOLE with the expected bytes, so stride padding, bytes behind Wout, points behind a count and every refused call must leave the sentinel.
 
 The fused form is the remap tile (256 x 4, a lane 4 pixels, vector stores where pointer, stride and frame size allow it, 8 frames per workgroup for a
 shared camera); shapes come from those numbers (tests/undistort_cases.py)."""
 import ctypes as C
-import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
 import undistort_cases as uc
 import undistort_model as um
-from test_gpu_plan_geometry import Arena, SENTINEL, ptr
+from fixtures import load_golden, md5
+from gpu_support import SENTINEL, Arena, ptr, u8
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 F32_OUT = (2, 5)          # COMPVHIP_INTERP_BILINEAR_FLOAT32, _BICUBIC_FLOAT32
 LIMIT = 65535             # kMaxFramesPerLaunch
 _MODEL = {}
 
 
-def u8(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-
-
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
 @pytest.fixture(scope="module")
 def golden():
-    with open(os.path.join(GOLDEN, "golden_undistort.json")) as f:
-        meta = json.load(f)
-    return meta, np.load(os.path.join(GOLDEN, "golden_undistort.npz"))
+    return load_golden("golden_undistort")
 
 
 def model_image(c, interp, k=0, K=None, d=None):

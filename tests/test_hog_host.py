@@ -1,9 +1,6 @@
 """compv_amd/csrc/hog_math.hpp -- the arithmetic the HOG kernels are made of -- run on the host by tests/host/hog_math_check.cpp (a stand-alone program,
 standard library only, no GPU, built with AddressSanitizer and UBSan) over the frames of the golden cases, and held against tests/hog_model.py and the
 golden descriptors byte for byte.  The GPU tests (tests/test_gpu_hog.py) hold the kernels against the same model."""
-import json
-import os
-import shutil
 import struct
 import subprocess
 
@@ -12,21 +9,15 @@ import pytest
 
 import hog_cases as hc
 import hog_model as hm
+from fixtures import load_golden
+from host_programs import ASAN_UBSAN_STATIC, WARN, build, host_cxx
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "hog_math_check.cpp")
 GEOMETRY = ["cellsX", "cellsY", "validX", "validY", "blocksX", "blocksY", "cpbX", "cpbY", "stepX", "stepY"]
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path_factory.mktemp("hog") / "hog_math_check"
-    # the sanitizers' runtimes are linked statically: the program needs nothing preloaded
-    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                            "-static-libasan", "-static-libubsan", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = build("hog_math_check.cpp", tmp_path_factory.mktemp("hog"), host_cxx(), ["-O1", "-g", "-ffp-contract=off", *WARN, *ASAN_UBSAN_STATIC])
 
     def run(img, opts):
         o = hm.resolve(opts)
@@ -47,8 +38,8 @@ def checker(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def golden():
-    here = os.path.join(ROOT, "tests", "golden")
-    return {c["id"]: c for c in json.load(open(os.path.join(here, "golden_hog.json")))["cases"]}, np.load(os.path.join(here, "golden_hog.npz"))
+    meta, arrays = load_golden("golden_hog")
+    return {c["id"]: c for c in meta["cases"]}, arrays
 
 
 @pytest.mark.parametrize("cid", [c["id"] for c in hc.CASES])

@@ -1,7 +1,5 @@
 """tests/hog_model.py -- the numpy float32 statement of the HOG definition (include/compv_hip.h, "HOG descriptors") -- against the goldens that
 tests/golden/make_golden_hog.py wrote after it had found model == compiled reference (AVX2 + FMA3 off) byte for byte on every case.  CPU only."""
-import hashlib
-import json
 import os
 
 import numpy as np
@@ -9,25 +7,20 @@ import pytest
 
 import hog_cases as hc
 import hog_model as hm
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+from fixtures import GOLDEN_DIR, load_golden, md5
 
 
 @pytest.fixture(scope="module")
 def golden():
-    meta = json.load(open(os.path.join(GOLDEN, "golden_hog.json")))
-    return {c["id"]: c for c in meta["cases"]}, np.load(os.path.join(GOLDEN, "golden_hog.npz")), meta
-
-
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
+    meta, arrays = load_golden("golden_hog")
+    return {c["id"]: c for c in meta["cases"]}, arrays, meta
 
 
 def test_the_goldens_cover_the_case_list(golden):
     by_id, arrays, meta = golden
     assert sorted(by_id) == sorted(hc.BY_ID)
     assert sorted(arrays.files) == sorted("desc_" + c["id"] for c in by_id.values() if c["stored"])
-    assert os.path.getsize(os.path.join(GOLDEN, "golden_hog.npz")) <= 292745          # no larger than golden_homography.npz
+    assert os.path.getsize(os.path.join(GOLDEN_DIR, "golden_hog.npz")) <= 292745          # no larger than golden_homography.npz
     # the reference's fused AVX2 leaf is recorded, never compared: it differs from the definition in the last bits only
     assert meta["avx2_fma3"]["differs"] and 0 < meta["avx2_fma3"]["max_abs_difference"] < 1e-6
 

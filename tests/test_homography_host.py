@@ -1,8 +1,6 @@
 """compv_amd/csrc/homography_math.hpp -- the arithmetic the homography kernels are made of -- run on the host by tests/host/homography_math_check.cpp
 (standard library only, no GPU) and held against tests/homography_model.py bit for bit: quads, per-try inlier counts, variances and rotation counts,
 the result record, the mask.  The GPU tests (tests/test_gpu_homography.py) hold the kernels against the same model."""
-import os
-import shutil
 import struct
 import subprocess
 
@@ -11,18 +9,12 @@ import pytest
 
 import homography_cases as hc
 import homography_model as hm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "homography_math_check.cpp")
+from host_programs import WARN, build, host_cxx
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path_factory.mktemp("homography") / "homography_math_check"
-    build = subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = build("homography_math_check.cpp", tmp_path_factory.mktemp("homography"), host_cxx(), ["-O2", "-ffp-contract=off", *WARN])
 
     def run(src, dst, tries, threshold=30.0, seed=0, pair=0, quads=None):
         k = len(src)

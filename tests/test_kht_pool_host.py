@@ -7,23 +7,16 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "kht_pool_stress.cpp")
+from host_programs import build, host_cxx
+
 FLAGS = ["-std=c++17", "-O1", "-g", "-pthread"]
 # the sanitizer's runtime is linked statically: the program then starts whatever other libraries its process loads, and in whatever order
 SANITIZERS = {"thread": ["-fsanitize=thread", "-static-libtsan"], "address,undefined": ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan"]}
 
 
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "g++", "c++", "clang++"):
-        if cxx and shutil.which(cxx):
-            return cxx
-    return None
-
-
 @pytest.mark.parametrize("sanitize", sorted(SANITIZERS))
 def test_kht_pool_stress_is_clean_under_sanitizer(tmp_path, sanitize):
-    cxx = _compiler()
+    cxx = host_cxx()
     assert cxx, "no host C++ compiler"
     probe = tmp_path / "probe.cpp"
     probe.write_text("int main(){}\n")
@@ -42,9 +35,7 @@ def test_kht_pool_stress_is_clean_under_sanitizer(tmp_path, sanitize):
             pass
     if launch is None:
         pytest.skip("an empty program built with %s does not start here: no usable runtime" % " ".join(flags))
-    exe = tmp_path / "kht_pool_stress"
-    build = subprocess.run([cxx, *FLAGS, *flags, SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = build("kht_pool_stress.cpp", tmp_path, cxx, [*FLAGS, *flags])
     env = dict(os.environ, UBSAN_OPTIONS="halt_on_error=1")
     run = subprocess.run([*launch, str(exe)], capture_output=True, text=True, timeout=120, env=env)
     print(run.stdout, run.stderr)

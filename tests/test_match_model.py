@@ -1,17 +1,14 @@
 """tests/match_model.py against the records of the compiled reference (tests/golden/golden_match.json, written by
 tests/golden/make_golden_match.py) and against literals worked out by hand."""
 import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
 import match_model as mm
+from fixtures import load_golden
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-with open(os.path.join(HERE, "golden", "golden_match.json")) as f:
-    GOLDEN = json.load(f)
+GOLDEN = load_golden("golden_match")[0]
 
 
 def md5(m):

@@ -1,21 +1,12 @@
 """tests/morph_model.py pinned on the CPU: literals worked out by hand from the definitions of include/compv_hip.h, and every MD5 that
 tests/golden/make_golden_morph.py recorded from the compiled reference (tests/golden/golden_morph.json)."""
-import hashlib
-import json
-import os
-
 import numpy as np
 import pytest
 
 import morph_model as mm
+from fixtures import load_golden, md5
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-with open(os.path.join(HERE, "golden", "golden_morph.json")) as f:
-    GOLD = json.load(f)
-
-
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
+GOLD = load_golden("golden_morph")[0]
 
 
 def frame(c):

@@ -3,6 +3,7 @@ golden fixtures generated from the compiled reference (tests/golden/make_golden.
 import numpy as np
 import pytest
 
+from gauss_cases import convlt_inputs
 from oracle_bindings import md5_rows, synth_frame
 
 SMALL = ["tiny_20x20", "q1_200x258", "small_320x240", "q3_641x480", "ragged_333x77", "mean_640x480", "theta_half_640x480"]
@@ -10,23 +11,10 @@ MEDIUM = ["hd_1280x720", "dense_1282x720", "fhd_1920x1080", "fhd_seed7"]
 LARGE = ["uhd_3840x2160"]
 
 
-def _convlt_inputs():
-    # unittests/math_convlt.cxx:100-165: 1285x720, stride 1344, k = 7
-    W, H, S = 1285, 720, 1344
-    i = np.arange(W)[None, :]
-    j = np.arange(H)[:, None]
-    d8 = np.zeros((H, S), np.uint8)
-    d8[:, :W] = ((i * j) + 53).astype(np.uint8)                               # :107
-    d16 = np.zeros((H, S), np.int16)
-    d16[:, :W] = (((i * j) + 53) * np.where(i & 1, -1, 1)).astype(np.int16)    # :129
-    k = np.array([(t + 53) * (-1 if t & 1 else 1) for t in range(7)], np.int16)  # :158
-    return d8[:, :W], d16[:, :W], k
-
-
 def test_convlt_reference_known_answers(oracle):
     """The two hot-path convolution instantiations reproduce the reference's own goldens
     (unittests/math_convlt.cxx:24-25, cases 5 and 6)."""
-    d8, d16, k = _convlt_inputs()
+    d8, d16, k = convlt_inputs()
     rc, out = oracle.convlt_8u(d8, k, k)
     assert rc == 0 and md5_rows(out) == "7f1116ade2a1cdb37842084c781ee05e"
     rc, out = oracle.convlt_16s(d16, k, k)

@@ -6,23 +6,18 @@ the descriptors on every point whose glibc cosf / sinf equal the canonical value
 detector's own orientation goes through atan2f, so it is held to 1e-4 degrees (circular): atan2f's documented <= 2 ULP at pi (4.8e-7 rad =
 2.7e-5 degrees) plus the float32 roundings of `* 180 / pi` and `+ 360` on both sides, each <= half an ULP at 360 = 1.5e-5 degrees."""
 import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
 import fast_model as fm
 import orb_model as om
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+from fixtures import load_golden
 
 
 @pytest.fixture(scope="module")
 def gold():
-    with open(os.path.join(HERE, "golden", "golden_orb.json")) as f:
-        g = json.load(f)
-    return g, np.load(os.path.join(HERE, "golden", "golden_orb.npz"))
+    return load_golden("golden_orb")
 
 
 def f32(bits):

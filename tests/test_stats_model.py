@@ -1,21 +1,12 @@
 """CPU tests of tests/stats_model.py, the numpy statement of the image statistics: against plain Python loops, against the closed forms of a constant frame,
 against every fixture of tests/golden/golden_stats.* (which the generator held against the compiled reference byte for byte), and the equalisation table
 where float32(running sum) first rounds and where it is clamped."""
-import hashlib
-import json
-import os
-
 import numpy as np
 import pytest
 
 import stats_cases as sc
 import stats_model as sm
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
+from fixtures import load_golden, md5
 
 
 def model_arrays(c):
@@ -73,9 +64,8 @@ def test_closed_forms_of_a_constant_255_frame(W, H):
 
 
 def test_model_against_every_fixture():
-    d = os.path.join(HERE, "golden")
-    meta = json.load(open(os.path.join(d, "golden_stats.json")))["cases"]
-    arrays = np.load(os.path.join(d, "golden_stats.npz"))
+    meta, arrays = load_golden("golden_stats")
+    meta = meta["cases"]
     assert [c["id"] for c in meta] == [c["id"] for c in sc.CASES]
     seen = 0
     for g in meta:

@@ -1,4 +1,4 @@
-"""CPU check of tests/stream_cases.py against include/compv_hip.h and against the case list of tests/test_gpu_stream_order.py: every export with a `void* stream`
+"""CPU check of tests/stream_cases.py against include/compv_hip.h and against the case list of tests/stream_order_rig.py: every export with a `void* stream`
 parameter (and the two batched KHT calls) has exactly one row, no row names an export that is gone, the class word beside the declaration in the header is the
 row's, the host arrays a row names are parameters of the export, and every case id exists -- so a later call cannot arrive without a stream-order contract and
 a GPU run behind pending work."""
@@ -32,7 +32,7 @@ def header_exports(txt):
 
 
 def case_ids():
-    import test_gpu_stream_order as gso          # importable without torch or a device: everything heavy is imported inside its functions
+    import stream_order_rig as gso          # importable without torch or a device: everything heavy is imported inside its functions
     return set(gso.CASES)
 
 

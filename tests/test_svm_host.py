@@ -3,8 +3,6 @@
 reference made and tests/svm_model.py, byte for byte: the parsed arrays, kernel values, decision values, labels, exp_ref.  The program feeds the header
 the way the kernels do (32-column chunks, one accumulator of a dot at a time) and aborts when that differs from the header's one-call forms.  The GPU
 tests (tests/test_gpu_svm.py) hold the kernels against the same fixture."""
-import os
-import shutil
 import struct
 import subprocess
 
@@ -13,21 +11,14 @@ import pytest
 
 import svm_cases as sc
 import svm_model as sm
+from host_programs import ASAN_UBSAN_STATIC, WARN, build, host_cxx
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "svm_math_check.cpp")
 CASES = sc.all_cases()
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path_factory.mktemp("svm") / "svm_math_check"
-    # the sanitizers' runtimes are linked statically: the program needs nothing preloaded
-    build = subprocess.run([cxx, "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                            "-static-libasan", "-static-libubsan", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = build("svm_math_check.cpp", tmp_path_factory.mktemp("svm"), host_cxx(), ["-O2", "-g", "-ffp-contract=off", *WARN, *ASAN_UBSAN_STATIC])
 
     def run(model_file, x=None, stride=None, exp_in=()):
         """-> None when the parser refuses the file, else dict(kernel, nr_class, l, dim, gamma, sv, coef, rho, nsv, label, labels, dec, K, exp)"""

@@ -3,8 +3,6 @@ tests/host/undistort_math_check.cpp (a stand-alone program with its own main, st
 nothing preloaded) and held against tests/undistort_model.py and the fixture the compiled reference made, byte for byte: coefficient records, both map
 planes in float32 and float64, the point cases, the projection cases with their z == 0 branch.  The program walks a map the way the kernels do (groups
 of 4 entries, a partial group at the end of a row) and aborts when that differs from the plain walk."""
-import os
-import shutil
 import struct
 import subprocess
 
@@ -13,21 +11,13 @@ import pytest
 
 import undistort_cases as uc
 import undistort_model as um
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "undistort_math_check.cpp")
-GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_undistort.npz")
+from fixtures import load_golden
+from host_programs import ASAN_UBSAN_STATIC, WARN, build, host_cxx
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path_factory.mktemp("undistort") / "undistort_math_check"
-    # the sanitizers' runtimes are linked statically: the program needs nothing preloaded
-    build = subprocess.run([cxx, "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                            "-static-libasan", "-static-libubsan", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = build("undistort_math_check.cpp", tmp_path_factory.mktemp("undistort"), host_cxx(), ["-O2", "-g", "-ffp-contract=off", *WARN, *ASAN_UBSAN_STATIC])
 
     def run(K, d, T, window=(0, 0, 0, 0), pts=None, pose=None, pts3=None):
         """-> None for a singular camera, else dict(coeffs, mx, my, pts, proj)"""
@@ -58,7 +48,7 @@ def checker(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def arrays():
-    return np.load(GOLDEN)
+    return load_golden("golden_undistort")[1]
 
 
 @pytest.mark.parametrize("c", uc.image_cases(), ids=lambda c: c["id"])

@@ -2,28 +2,17 @@
 that tests/golden/make_golden_undistort.py made from the compiled reference: every map plane (float32 bytes, float64 by MD5), every point and
 projection case, and the image of every case for all five interpolations.  The GPU tests (tests/test_gpu_undistort.py) hold the kernels against the
 same fixture."""
-import hashlib
-import json
-import os
-
 import numpy as np
 import pytest
 
 import undistort_cases as uc
 import undistort_model as um
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
+from fixtures import load_golden, md5
 
 
 @pytest.fixture(scope="module")
 def golden():
-    with open(os.path.join(GOLDEN, "golden_undistort.json")) as f:
-        meta = json.load(f)
-    return meta, np.load(os.path.join(GOLDEN, "golden_undistort.npz"))
+    return load_golden("golden_undistort")
 
 
 def test_the_fixture_covers_the_case_list(golden):

@@ -1,4 +1,4 @@
-"""Warm host time of the enqueue section of every case of tests/test_gpu_stream_order.py on an IDLE stream: the figures STALL_MS is derived from
+"""Warm host time of the enqueue section of every case of tests/stream_order_rig.py on an IDLE stream: the figures STALL_MS is derived from
 (docs/dispatch_coverage.md, "Stream order").  It runs the test's own rig with stalled=False, so what is measured is what is tested.  Needs a GPU.
 
     python tools/stream_enqueue_times.py"""
@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-import test_gpu_stream_order as t          # noqa: E402
+import stream_order_rig as t               # noqa: E402
 from compv_amd import capi                 # noqa: E402
 from oracle_bindings import Oracle         # noqa: E402
 
