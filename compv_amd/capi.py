@@ -51,7 +51,7 @@ CURVEFIT_RESULT_DTYPE = np.dtype([("A", "<f8"), ("B", "<f8"), ("C", "<f8"), ("in
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "compvhip_device_count", "compvhip_ctx_create", "compvhip_ctx_destroy", "compvhip_last_error",
-    "compvhip_live_allocations", "compvhip_edge_dete_u8", "compvhip_canny_u8", "compvhip_houghsht_u8",
+    "compvhip_live_allocations", "compvhip_debug_alloc_fill", "compvhip_edge_dete_u8", "compvhip_canny_u8", "compvhip_houghsht_u8",
     "compvhip_houghsht_dims", "compvhip_houghsht_vote_grid", "compvhip_plan_create", "compvhip_plan_destroy", "compvhip_plan_canny",
     "compvhip_plan_houghsht", "compvhip_plan_pipeline", "compvhip_plan_acc", "compvhip_plan_edge_counts",
     "compvhip_plan_set_timing", "compvhip_plan_get_timing", "compvhip_plan_acc_export", "compvhip_plan_edge_dete",
@@ -320,6 +320,8 @@ def load():
     L.compvhip_last_error.restype = C.c_char_p
     L.compvhip_live_allocations.argtypes = [vp]
     L.compvhip_live_allocations.restype = C.c_long
+    L.compvhip_debug_alloc_fill.argtypes = [C.c_int]
+    L.compvhip_debug_alloc_fill.restype = C.c_int
     L.compvhip_edge_dete_u8.argtypes = [vp, vp, sz, sz, sz, i32, vp, sz]
     L.compvhip_canny_u8.argtypes = [vp, vp, sz, sz, sz, C.c_float, C.c_float, i32, i32, vp, sz]
     L.compvhip_houghsht_u8.argtypes = [vp, vp, sz, sz, sz, C.c_float, C.c_float, i32, i32, vp, sz, C.POINTER(sz), vp, sz]

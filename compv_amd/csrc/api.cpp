@@ -457,6 +457,11 @@ void compvhip_ctx_destroy(compvhip_ctx* ctx)
 
 const char* compvhip_last_error(const compvhip_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 long compvhip_live_allocations(const compvhip_ctx* ctx) { return ctx ? ctx->live.load() : 0; }
+int compvhip_debug_alloc_fill(int byte)   // test hook: device_memory.hpp, allocFill
+{
+	if (byte < -1 || byte > 255) return COMPVHIP_E_INVALID_PARAMETER;
+	return allocFill.exchange(byte);
+}
 
 int compvhip_houghsht_to_cartesian(size_t W, size_t H, const compvhip_line* lines, size_t n, float* out)
 {

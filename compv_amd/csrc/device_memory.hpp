@@ -5,18 +5,33 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstring>
 
 namespace compvhip_api {
 using LiveCount = std::atomic<long>;   // hipMalloc / hipFree balance of a context (compvhip_live_allocations)
+
+// compvhip_debug_alloc_fill (test hook, process-wide): -1 = off; 0 .. 255 = every block dmalloc or PinBuf::reserve has just ALLOCATED is filled with that
+// byte before anyone sees it.  A buffer that is reused (cap >= n) is not touched.  Off, it costs one relaxed load per allocation; no launch path reads it.
+inline std::atomic<int> allocFill{-1};
+
+// the device fill is complete when this returns: the plans run on non-blocking streams, which do not order against the null stream, and what a plain
+// hipMemset waits for is the runtime's business -- so the device is waited for
+inline hipError_t fillFresh(void* p, size_t bytes, int byte)
+{
+	const hipError_t e = hipMemset(p, byte, bytes);
+	return e != hipSuccess ? e : hipDeviceSynchronize();
+}
 
 template <typename T>
 hipError_t dmalloc(LiveCount* live, T** p, size_t count)
 {
 	*p = nullptr;
 	if (!count) return hipSuccess;
-	const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-	if (e != hipSuccess) *p = nullptr;
-	else if (live) ++*live;
+	hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
+	if (e != hipSuccess) { *p = nullptr; return e; }
+	const int fill = allocFill.load(std::memory_order_relaxed);
+	if (fill >= 0 && (e = fillFresh(*p, count * sizeof(T), fill)) != hipSuccess) { (void)hipFree(*p); *p = nullptr; return e; }   // never counted
+	if (live) ++*live;
 	return e;
 }
 template <typename T>
@@ -79,7 +94,10 @@ struct PinBuf {
 		if (cap >= n) return hipSuccess;
 		release();
 		const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T), flags);
-		if (e == hipSuccess) cap = n; else ptr = nullptr;
+		if (e != hipSuccess) { ptr = nullptr; return e; }
+		const int fill = allocFill.load(std::memory_order_relaxed);
+		if (fill >= 0) std::memset(ptr, fill, n * sizeof(T));
+		cap = n;
 		return e;
 	}
 	hipError_t grow(size_t n) { return cap >= n ? hipSuccess : reserve(n + n / 4 + 1024); }

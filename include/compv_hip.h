@@ -94,6 +94,12 @@ COMPVHIP_API void compvhip_ctx_destroy(compvhip_ctx* ctx);
 COMPVHIP_API const char* compvhip_last_error(const compvhip_ctx* ctx);
 /* hipMalloc/hipFree balance of this ctx -- the analogue of COMPV_DEBUG_CHECK_FOR_MEMORY_LEAKS (compv_api.h:148-155) */
 COMPVHIP_API long compvhip_live_allocations(const compvhip_ctx* ctx);
+/* Test hook, PROCESS-WIDE (every context, plan and handle of this library in the process; not for production use).  byte = 0 .. 255: from now on every
+ * block of device or pinned host memory the library allocates is filled with that byte before it is used -- hipMalloc and hipHostMalloc promise nothing
+ * about what a fresh block holds, and tests/test_gpu_fresh_memory.py shows with it that no call depends on it.  A buffer the library already has and reuses is
+ * not touched.  -1 switches the fill off (the default).  Returns the previous value (-1 .. 255); any other byte returns COMPVHIP_E_INVALID_PARAMETER and
+ * changes nothing.  While it is on, an allocation waits for the device; no launch path reads it. */
+COMPVHIP_API int compvhip_debug_alloc_fill(int byte);
 
 /* ---- host entry points (drop-in for process()) ------------------------------------------------------------- */
 

@@ -2,6 +2,7 @@
 the C records.  Not a test module, so its asserts are not rewritten: each carries its own message.  Importing it loads neither torch nor
 libcompv_hip.so and touches no device (tests/test_support_layout.py): both are imported inside the functions that need them."""
 import concurrent.futures as cf
+import contextlib
 
 import numpy as np
 
@@ -71,6 +72,23 @@ class Arena:
             assert self.torch.equal(raw[-GUARD:], self.pattern), "%s: guard after a buffer overwritten" % what
         for body, host in self.kept:
             assert (body.cpu().numpy() == host).all(), "%s: input modified" % what
+
+
+@contextlib.contextmanager
+def alloc_fill(byte):
+    """compvhip_debug_alloc_fill for the length of the block: every device or pinned block the library allocates inside it is filled with `byte`
+    (None: the hook is left alone).  The hook is process-wide; the previous value is restored whatever happens inside"""
+    if byte is None:
+        yield
+        return
+    from compv_amd import capi
+    L = capi.load()
+    prev = L.compvhip_debug_alloc_fill(int(byte))
+    assert -1 <= prev <= 255, "compvhip_debug_alloc_fill(%r) returned %d" % (byte, prev)
+    try:
+        yield
+    finally:
+        L.compvhip_debug_alloc_fill(prev)
 
 
 def ptr(t):

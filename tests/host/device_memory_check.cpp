@@ -1,6 +1,7 @@
 // device_memory_check.cpp -- DevBuf / PinBuf (compv_amd/csrc/device_memory.hpp) where every allocation FAILS: run on a machine without a GPU, where hipMalloc and
 // hipHostMalloc return an error and a null pointer.  These are the paths no GPU test reaches: the {nullptr, 0} state after a failed reserve / grow,
-// reserve(0), release and destruction of empty buffers, and the moves.  Built for the host with AddressSanitizer and UBSan by tests/test_device_memory_host.py.
+// reserve(0), release and destruction of empty buffers, the moves, and the same failures with the fill of fresh allocations (compvhip_debug_alloc_fill)
+// switched on: nothing filled, freed or counted.  Built for the host with AddressSanitizer and UBSan by tests/test_device_memory_host.py.
 #include "../../compv_amd/csrc/device_memory.hpp"
 
 #include <cstdint>
@@ -91,6 +92,28 @@ int main()
 		r.ptr = nullptr; r.cap = 0;
 		CHECK(empty(a) && empty(b) && empty(c) && empty(p) && empty(q) && empty(r));   // nothing of this program's reaches hipFree / hipHostFree in the destructors
 	}
+	CHECK(live.load() == 0);
+	for (const int byte : {0xFF, 0x01, 0x00}) {
+		// the fill of fresh allocations (compvhip_debug_alloc_fill) switched on, the allocation fails: nothing is filled, freed or counted, the buffer stays empty
+		allocFill.store(byte);
+		DevBuf<int32_t> d;
+		CHECK(d.reserve(&owner, 1000) != hipSuccess && empty(d) && live.load() == 0);
+		CHECK(d.grow(&owner, 10) != hipSuccess && empty(d) && live.load() == 0);
+		CHECK(d.reserve(&owner, 0) == hipSuccess && empty(d) && live.load() == 0);
+		int32_t* raw = reinterpret_cast<int32_t*>(&owner);
+		CHECK(dmalloc(&live, &raw, 16) != hipSuccess && raw == nullptr && live.load() == 0);
+		PinBuf<uint8_t> h;
+		CHECK(h.reserve(4096) != hipSuccess && empty(h));
+		CHECK(h.reserve(4096, hipHostMallocMapped) != hipSuccess && empty(h));
+		CHECK(h.grow(1) != hipSuccess && empty(h));
+		CHECK(h.reserve(0) == hipSuccess && empty(h));
+		static uint8_t bytes[16] = {7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7};
+		h.ptr = bytes; h.cap = 16;
+		CHECK(h.reserve(16) == hipSuccess && h.ptr == bytes && bytes[0] == 7 && bytes[15] == 7);   // fits: reused and NOT filled
+		h.ptr = nullptr; h.cap = 0;
+		CHECK(allocFill.load() == byte);
+	}
+	allocFill.store(-1);
 	CHECK(live.load() == 0);
 	if (failures) return 1;
 	std::printf("device_memory_check OK\n");

@@ -16,6 +16,9 @@ f(D), f(X1) and f(X2) are asserted to differ in every output array before anythi
 scratch and shows.  Two calls behind one stall expose a per-call clear on another stream (it would run before call 1 accumulates), the shared input buffer an
 order missing between call 1's reads and the next producer, the final copy and the bands a fork that never joins back.
 
+run_cold() is the same queue WITHOUT the warm-up and the stall, for tests/test_gpu_fresh_memory.py: the handle of a case and everything its first use
+allocates are blocks filled with a poison byte (gpu_support.alloc_fill), and the first two calls must give f(X1) and f(X2).
+
 STALL_MS is a harness constant, not a tolerance: 50 x the slowest warm enqueue section (docs/dispatch_coverage.md holds the measurements).  An ASYNC case
 whose enqueue section takes more than a quarter of it fails with "stall too short", and the event pair around the stall must show at least half of it."""
 import ctypes as C
@@ -160,12 +163,8 @@ def compare(got, exp, others, what):
                              % (what, int(bad.sum()), img.size, int(np.flatnonzero(bad)[0]), got[bad][0], img[bad][0], "; it equals " + " and ".join(like) if like else ""))
 
 
-def run(env, stall, cid, s, stalled=True):
-    """stalled=False: the same queue on an IDLE stream, without the return checks -- tools/stream_enqueue_times.py measures with it what STALL_MS is derived
-    from, so that what is measured and what is tested is one piece of code.  Returns the host time of the enqueue section."""
-    torch, st = env.torch, stall.stream
-    cls = s.cls or sc.CASE_ROW[cid].cls
-    begin = stall.enqueue if stalled else time.perf_counter
+def buffers(env, cid, s):
+    """the staged contents, the banded input and output buffers (the outputs hold the sentinel) and the expectations of a case"""
     names = list(s.inputs)
     stage = {n: [env.stage(a) for a in s.inputs[n]] for n in names}
     sets = 2 if s.own_inputs else 1
@@ -176,6 +175,58 @@ def run(env, stall, cid, s, stalled=True):
     for n in exp[0]:          # f(D), f(X1), f(X2) differ in every output array, before anything is launched
         for a, b in ((0, 1), (0, 2), (1, 2)):
             assert differs(exp[a][n], exp[b][n]), "%s: %s is the same for contents %d and %d: the rig could not tell them apart" % (cid, n, a, b)
+    return names, stage, I, O, exp
+
+
+def check_outputs(cid, s, O, exp, results):
+    """outputs 1 == f(X1), outputs 2 == f(X2) bit for bit, and what the calls returned to the host"""
+    named = {"f(D)": 2, "f(X1)": 0, "f(X2)": 1}
+    for k in range(2):
+        for n in exp[k]:
+            got = O[k][n].cpu().numpy()
+            others = {name: exp[j][n] for name, j in named.items() if j != k}
+            compare(got, exp[k][n], others, "%s: %s of call %d" % (cid, n, k + 1))
+        if s.check_host:
+            s.check_host(k, results[k])
+
+
+def run_cold(env, stream, cid, s):
+    """The FIRST calls of a handle, for tests/test_gpu_fresh_memory.py: `s` was made by CASES[cid](env) inside gpu_support.alloc_fill, and this runs inside
+    the same block, so the handle and every scratch buffer its first use allocates are fresh blocks filled with the poison byte.  No warm-up, no stall:
+    X1 -> input, call 0 into sentinel-filled outputs, X2 -> input, call 1 (the growth cases reallocate there, into a second filled block), all on the
+    non-blocking `stream`; after one synchronisation outputs 1 == f(X1) and outputs 2 == f(X2) bit for bit and the bands are intact.  No return-time
+    and no allocation-count assertion: first use allocates, and an allocation under fill waits for the device."""
+    torch = env.torch
+    if hasattr(s, "custom"):
+        s.custom(env, None, cold=stream)
+        return
+    names, stage, I, O, exp = buffers(env, cid, s)
+    torch.cuda.synchronize()
+    results = []
+    for k in range(2):
+        i = I[k if s.own_inputs else 0]
+        with torch.cuda.stream(stream):
+            for n in names:
+                i[n].copy_(stage[n][k], non_blocking=True)
+        results.append(s.call(k, ptrs(i), ptrs(O[k]), stream.cuda_stream))
+        if s.scribble:
+            s.scribble()
+    if s.finish:
+        s.finish()
+    torch.cuda.synchronize()
+    check_outputs(cid, s, O, exp, results)
+    env.bands(cid)
+    if s.after:
+        s.after(env)
+
+
+def run(env, stall, cid, s, stalled=True):
+    """stalled=False: the same queue on an IDLE stream, without the return checks -- tools/stream_enqueue_times.py measures with it what STALL_MS is derived
+    from, so that what is measured and what is tested is one piece of code.  Returns the host time of the enqueue section."""
+    torch, st = env.torch, stall.stream
+    cls = s.cls or sc.CASE_ROW[cid].cls
+    begin = stall.enqueue if stalled else time.perf_counter
+    names, stage, I, O, exp = buffers(env, cid, s)
     # warm-up on D, idle stream
     for i in I:
         for n in names:
@@ -224,14 +275,7 @@ def run(env, stall, cid, s, stalled=True):
     if stalled:
         stall.finish(cid)
     torch.cuda.synchronize()
-    named = {"f(D)": 2, "f(X1)": 0, "f(X2)": 1}
-    for k in range(2):
-        for n in exp[k]:
-            got = O[k][n].cpu().numpy()
-            others = {name: exp[j][n] for name, j in named.items() if j != k}
-            compare(got, exp[k][n], others, "%s: %s of call %d" % (cid, n, k + 1))
-        if s.check_host:
-            s.check_host(k, results[k])
+    check_outputs(cid, s, O, exp, results)
     if not s.own_inputs:
         for n in names:
             assert torch.equal(I[0][n], stage[n][2]), "%s: the last copy into %s did not land behind the calls" % (cid, n)
@@ -1317,11 +1361,14 @@ def convert_frames(env):
                 lambda k: {"rgba": maps_img([cm.convert(cm.NV12, cm.RGBA32, planes[k][f], W, H)[0] for f in range(F)], strict=True, S=rb_out)}, scribble=scribble)
 
 
-def _warp(env, stall, dests, live_stays, stalled=True):
+def _warp(env, stall, dests, live_stays, stalled=True, cold=None):
     """compvhip_plan_warp_inverse: six calls with six matrices into six destinations behind one stall -- more than the four slots of the staging ring, so the
-    fifth call may block on the first one's copy (the documented exception: the return check covers the first four).  M is overwritten after each return."""
+    fifth call may block on the first one's copy (the documented exception: the return check covers the first four).  M is overwritten after each return.
+    cold (a stream, run_cold): no warm-up call, no stall, no return-time or allocation-count assertion; the results and the bands are checked as ever."""
     import remap_model as rm
-    torch, st, hip_ctx = env.torch, stall.stream, env.ctx
+    if cold is not None:
+        stalled = live_stays = False
+    torch, st, hip_ctx = env.torch, cold if cold is not None else stall.stream, env.ctx
     plan = env.plan()
     n = len(dests)
     Ms = [_warp_matrices(wo, ho, n)[j] for j, (wo, ho, so) in enumerate(dests)]
@@ -1336,11 +1383,12 @@ def _warp(env, stall, dests, live_stays, stalled=True):
     M = np.zeros((2, 3), np.float32)          # the host array the call reads
     d_in.copy_(stage[2])
     torch.cuda.synchronize()
-    M[:] = Ms[0]
-    plan.warp_inverse(d_in.data_ptr(), M, rm.BILINEAR, outs[0].data_ptr(), dests[0][0], dests[0][1], dests[0][2], 9, st.cuda_stream)
-    torch.cuda.synchronize()
-    outs[0].fill_(SENTINEL)
-    torch.cuda.synchronize()
+    if cold is None:
+        M[:] = Ms[0]
+        plan.warp_inverse(d_in.data_ptr(), M, rm.BILINEAR, outs[0].data_ptr(), dests[0][0], dests[0][1], dests[0][2], 9, st.cuda_stream)
+        torch.cuda.synchronize()
+        outs[0].fill_(SENTINEL)
+        torch.cuda.synchronize()
     live = hip_ctx.live_allocations()
     t0 = stall.enqueue() if stalled else time.perf_counter()          # not stalled: only to measure the enqueue section on an idle stream
     for j in range(n):

@@ -1,7 +1,7 @@
 """DevBuf / PinBuf, the buffers that own the handles' device and pinned memory (compv_amd/csrc/device_memory.hpp): tests/host/device_memory_check.cpp is a
 program of its own that includes that header alone, built with hipcc for the host under AddressSanitizer + UBSan and run as a child process.  Without a
-GPU every hipMalloc / hipHostMalloc fails, so this is where the failure paths, reserve(0), the empty release / destructor and the moves are executed; no
-GPU test reaches them.  Where a GPU is present the allocations would succeed (and a sanitized program must not open a GPU): skipped."""
+GPU every hipMalloc / hipHostMalloc fails, so this is where the failure paths (with the fill of fresh allocations off and on), reserve(0), the empty
+release / destructor and the moves are executed; no GPU test reaches them.  Where a GPU is present the allocations would succeed (and a sanitized program must not open a GPU): skipped."""
 import os
 import subprocess
 

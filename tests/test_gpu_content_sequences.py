@@ -12,7 +12,11 @@ on the CPU by tests/test_content_sequences.py), the way a video and bench.py use
   - after the last step the first one runs again and must match its model again;
   - the whole sequence runs twice, and compvhip_live_allocations after the second pass equals the count after the first.
 
-Which buffer each sequence watches is tabled in docs/dispatch_coverage.md ("State a handle keeps between calls").
+Every test runs in two passes of the module (the autouse fixture fresh_allocations): `as_allocated`, on blocks as hipMalloc hands them out, and `filled_ff`,
+where every block the library allocates is filled with 0xFF first -- step 0 of a sequence is a handle's FIRST call, and nothing may depend on what a fresh
+block holds.
+
+Which buffer each sequence watches is tabled in docs/dispatch_coverage.md ("State a handle keeps between calls", "Fresh allocations").
 """
 import numpy as np
 import pytest
@@ -26,10 +30,24 @@ pytestmark = pytest.mark.gpu
 LINE_CAP = 4096
 
 
-def drive(ctx, steps, call, passes=2):
+PASSES = {None: 2, 0xFF: 2}          # fill byte of the module's pass -> times drive() runs a sequence through
+
+
+@pytest.fixture(autouse=True, params=[None, 0xFF], ids=["as_allocated", "filled_ff"])
+def fresh_allocations(request):
+    """Every test of this module runs twice: on blocks as hipMalloc hands them out (in a young process: zeros), and with every block the library allocates
+    filled with 0xFF (gpu_support.alloc_fill) -- NaN, 65 535, -1, every flag set.  Step 0 of a sequence is a handle's first call, at the geometries where
+    scratch is shared across workgroups; an autouse fixture is set up before the ones a test names, so the handles those create are created under the fill
+    too (docs/dispatch_coverage.md, "Fresh allocations")."""
+    PASSES["now"] = PASSES[request.param]
+    with pg.alloc_fill(request.param):
+        yield request.param
+
+
+def drive(ctx, steps, call, passes=None):
     """call(k, what) makes step k's call on the live handle and checks it: every step, then the first again; twice; no allocation may be left over"""
     live = []
-    for p in range(passes):
+    for p in range(PASSES["now"] if passes is None else passes):
         for i, k in enumerate(cs.run_order(steps)):
             call(k, "pass %d call %d (step %d)" % (p, i, k))
         live.append(ctx.live_allocations())

@@ -12,99 +12,11 @@ import pytest
 
 import curvefit_cases as cc
 import curvefit_model as cm
+from curvefit_rig import REC, SENT64, Rig, label_frame
 from fixtures import load_golden
 from gpu_support import SENTINEL, Arena, d2h, ptr, u8
 
 pytestmark = pytest.mark.gpu
-
-REC = cm.RESULT_DTYPE.itemsize
-SENT64 = np.frombuffer(bytes([SENTINEL] * 8), np.float64)[0]
-
-
-class Rig:
-    """A curve-fit handle and its guarded buffers.  sets: per set its points [k][2]; counts: "own" (the device counts are the sets' sizes), a list, or
-    None (a NULL pointer: every set has pointCap points)."""
-
-    def __init__(self, hip_ctx, sets, point_cap, max_tries, counts="own", stream=0, upload=True):
-        from compv_amd import capi
-        self.n, self.cap, self.max_tries = len(sets), point_cap, max_tries
-        rng = np.random.default_rng(point_cap * 7 + len(sets))
-        self.pts = rng.uniform(-1e6, 1e6, (self.n, point_cap, 2))          # junk behind every set's points
-        for s, p in enumerate(sets):
-            n = min(len(p), point_cap)
-            self.pts[s, :n] = np.asarray(p, np.float64).reshape(-1, 2)[:n]
-        self.counts = [len(p) for p in sets] if isinstance(counts, str) else counts
-        self.ar = Arena()
-        self.d_pts = self.ar.new(self.pts.nbytes, u8(self.pts) if upload else SENTINEL)
-        self.ar.keep(self.d_pts, u8(self.pts))
-        self.d_counts = None
-        if self.counts is not None:
-            h = u8(np.asarray(self.counts, np.int32))
-            self.d_counts = self.ar.new(h.size, h)
-            self.ar.keep(self.d_counts, h)
-        self.d_res = self.ar.new(self.n * REC)
-        self.d_mask = self.ar.new(self.n * point_cap + 3)[3:]          # ANY BYTE: the mask starts at an odd address
-        self.d_dist = self.ar.new(self.n * point_cap * 8)
-        self.h = capi.Curvefit(hip_ctx, self.n, point_cap, max_tries, stream=stream)
-
-    def k(self, s):
-        return self.cap if self.counts is None else max(0, min(int(self.counts[s]), self.cap))
-
-    def buffer(self, host):
-        h = u8(host)
-        d = self.ar.new(h.size, h)
-        self.ar.keep(d, h)
-        return d
-
-    def run(self, model, tries, d_samples=None, mask=True, **opts):
-        self.ar.refill(self.d_res)
-        self.d_mask.fill_(SENTINEL)
-        self.h.find(ptr(self.d_pts), ptr(self.d_counts) if self.d_counts is not None else 0, ptr(self.d_res), ptr(self.d_mask) if mask else 0, model=model, tries=tries,
-                    d_samples=ptr(d_samples) if d_samples is not None else 0, **opts)
-
-    def check(self, what, model, tries, expected, mask=True):
-        """expected: per set a dict as curvefit_model.find returns (result, mask, counts)"""
-        counts, _ = self.h.scores(tries)          # (waits for the handle's stream)
-        self.ar.check(what)
-        res = np.frombuffer(self.d_res.cpu().numpy().tobytes(), cm.RESULT_DTYPE)
-        got_mask = self.d_mask.cpu().numpy().reshape(self.n, self.cap)
-        for s, e in enumerate(expected):
-            k = self.k(s)
-            assert res[s].tobytes() == e["result"].tobytes(), "%s: set %d record %r, model %r" % (what, s, res[s], e["result"])
-            if mask:
-                assert got_mask[s, :k].tobytes() == np.asarray(e["mask"], np.uint8).tobytes(), "%s: set %d mask" % (what, s)
-                assert (got_mask[s, k:] == SENTINEL).all(), "%s: set %d wrote mask bytes at or behind k" % (what, s)
-            else:
-                assert (got_mask[s] == SENTINEL).all()
-            if e["counts"] is not None:
-                assert counts[s].tolist() == np.asarray(e["counts"]).tolist(), "%s: set %d per-try counts" % (what, s)
-        return res
-
-    def model(self, model, tries, samples=None, **opts):
-        return [cm.find(self.pts[s], self.k(s), model, tries, set_index=s, sample_list=None if samples is None else samples[s], **opts) for s in range(self.n)]
-
-    def twice(self, what, model, tries, expected, d_samples=None, mask=True, **opts):
-        for turn in range(2):
-            self.run(model, tries, d_samples=d_samples, mask=mask, **opts)
-            res = self.check("%s, call %d" % (what, turn), model, tries, expected, mask)
-        return res
-
-    def check_distances(self, what, model, params):
-        d_params = self.buffer(np.asarray(params, np.float64))
-        for turn in range(2):
-            self.ar.refill(self.d_dist)
-            self.h.distances(ptr(self.d_pts), ptr(self.d_counts) if self.d_counts is not None else 0, model, ptr(d_params), ptr(self.d_dist))
-            self.h.scores(1)
-            self.ar.check(what)
-            got = np.frombuffer(self.d_dist.cpu().numpy().tobytes(), np.float64).reshape(self.n, self.cap)
-            for s in range(self.n):
-                k = self.k(s)
-                exp = cm.residuals(model, params[s][0], params[s][1], params[s][2], self.pts[s, :k])[0]
-                assert got[s, :k].tobytes() == exp.tobytes(), "%s: set %d distances, call %d" % (what, s, turn)
-                assert got[s, k:].tobytes() == np.full(self.cap - k, SENT64).tobytes(), "%s: set %d wrote distances at or behind k" % (what, s)
-
-    def close(self):
-        self.h.close()
 
 
 @pytest.fixture(scope="module")
@@ -215,30 +127,6 @@ def test_failed_refit_keeps_the_best_trys_model(hip_ctx):
 
 
 # ---- gather ----------------------------------------------------------------------------------------------------------------------------------
-def label_frame(W, H, stride, cap, rng):
-    """a label map with components of 1, cap, cap + 1 and 3 * cap - 1 pixels (steps 1, 1, 2, 3), one whose box spans the frame (the border ring, the
-    others inside its box), and junk in the padding columns; -> labels [H][stride], records, count"""
-    lab = np.zeros((H, stride), np.int32)
-    lab[:, W:] = rng.integers(1, 6, (H, stride - W))          # never read: columns >= W
-    lab[0, :W] = lab[H - 1, :W] = 1
-    lab[:, 0] = lab[:, W - 1] = 1          # id 1: the ring
-    sizes = [1, cap, cap + 1, 3 * cap - 1]
-    y = 2
-    for i, n in enumerate(sizes):          # ids 2 .. 5: runs of rows of width W - 6 from column 3, two rows apart
-        left = n
-        while left:
-            run = min(left, W - 6)
-            lab[y, 3:3 + run] = i + 2
-            left -= run
-            y += 1
-        y += 1
-    assert y < H - 1
-    comps = np.zeros(5, cm.COMP_DTYPE)
-    for i in range(5):
-        ys, xs = np.nonzero(lab[:, :W] == i + 1)
-        comps[i] = (xs[0], ys[0], xs.min(), ys.min(), xs.max(), ys.max(), len(ys))
-    return lab, comps
-
 
 @pytest.mark.parametrize("W,H,cap", [(37, 29, 16), (300, 40, 200)])
 def test_gather_from_label_maps(hip_ctx, W, H, cap):

@@ -5,7 +5,7 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUPPORT = ("gpu_support", "fixtures", "host_programs", "stream_order_rig", "gauss_cases", "components_rig", "sht_fit_rig", "sht_segments_rig", "morph_rig",
-           "match_rig", "homography_rig", "fast_rig", "hog_rig", "orb_rig", "orb_pyramid_rig")
+           "match_rig", "homography_rig", "fast_rig", "hog_rig", "orb_rig", "orb_pyramid_rig", "curvefit_rig", "svm_rig", "undistort_rig", "fresh_memory_cases")
 
 
 def imported_modules(nodes):
