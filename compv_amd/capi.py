@@ -46,6 +46,10 @@ SVM_KERNEL_LINEAR, SVM_KERNEL_RBF = 0, 2                                        
 SVM_F32, SVM_F64 = 0, 1                                                                        # COMPVHIP_SVM_F32 / _F64
 UNDISTORT_F32, UNDISTORT_F64 = 0, 1                                                            # COMPVHIP_UNDISTORT_F32 / _F64
 UNDISTORT_COEFFS = 14                                                                          # values of a camera's coefficient record
+MOMENTS_VALUE, MOMENTS_UNIT = 0, 1                                                             # COMPVHIP_MOMENTS_VALUE / _UNIT
+MOMENTS_ORIGIN_FRAME, MOMENTS_ORIGIN_BOX = 0, 1                                                # COMPVHIP_MOMENTS_ORIGIN_*
+MOMENTS_DTYPE = np.dtype([(k, "<u8") for k in ("m00", "m01", "m10", "m11", "m02", "m20")])     # compvhip_moments
+MOMENTS_SHAPE_DTYPE = np.dtype([(k, "<f8") for k in ("xbar", "ybar", "u20", "u02", "u11", "skew", "cs", "sn")] + [("status", "<i4"), ("pad", "<i4")])   # compvhip_moments_shape
 CURVEFIT_RESULT_DTYPE = np.dtype([("A", "<f8"), ("B", "<f8"), ("C", "<f8"), ("inliers", "<i4"), ("bestTry", "<i4"), ("status", "<i4"), ("k", "<i4")])   # compvhip_curvefit_result
 
 # every symbol include/compv_hip.h declares (checked by tests/test_abi.py)
@@ -87,6 +91,7 @@ EXPORTS = [
     "compvhip_undistort_coeffs_f32", "compvhip_undistort_coeffs_f64", "compvhip_undistort_map_f32", "compvhip_undistort_map_f64",
     "compvhip_undistort_create", "compvhip_undistort_destroy", "compvhip_undistort_frames", "compvhip_undistort_maps", "compvhip_undistort_points",
     "compvhip_undistort_project", "compvhip_undistort_u8", "compvhip_undistort_set_timing", "compvhip_undistort_get_timing",
+    "compvhip_moments_frames", "compvhip_moments_components", "compvhip_moments_shapes", "compvhip_moments_shape_host", "compvhip_moments_fits", "compvhip_moments_host",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -208,6 +213,14 @@ class UndistortDesc(C.Structure):
 
     def __init__(self, W=0, H=0, S=0, frames=0, Wout=0, Hout=0, x0=0, y0=0, max_sets=0, max_points=0, stream=0):
         super().__init__(C.sizeof(UndistortDesc), W, H, S, frames, Wout, Hout, x0, y0, max_sets, max_points, 0, stream or None)
+
+
+class MomentsDesc(C.Structure):
+    """compvhip_moments_desc (include/compv_hip.h): how a pixel counts, the origin of the coordinates and the stream the device calls run on"""
+    _fields_ = [("size", C.c_uint32), ("weights", C.c_int32), ("origin", C.c_int32), ("hipStream", C.c_void_p)]
+
+    def __init__(self, weights=MOMENTS_VALUE, origin=MOMENTS_ORIGIN_FRAME, stream=0):
+        super().__init__(C.sizeof(MomentsDesc), weights, origin, stream or None)
 
 
 def curvefit_model_points(model):
@@ -463,6 +476,12 @@ def load():
     L.compvhip_undistort_u8.argtypes = [vp, vp, sz, sz, sz, vp, vp, i32, sz, sz, i32, C.POINTER(Roi), C.c_uint8, vp, sz, sz, sz]
     L.compvhip_undistort_set_timing.argtypes = [vp, i32]
     L.compvhip_undistort_get_timing.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32]
+    L.compvhip_moments_frames.argtypes = [vp, C.POINTER(MomentsDesc), vp, sz, sz, sz, sz, vp, vp]
+    L.compvhip_moments_components.argtypes = [vp, C.POINTER(MomentsDesc), vp, sz, sz, sz, vp, sz, vp, sz, vp, sz, vp, vp]
+    L.compvhip_moments_shapes.argtypes = [vp, C.POINTER(MomentsDesc), vp, sz, vp]
+    L.compvhip_moments_shape_host.argtypes = [vp, sz, vp]
+    L.compvhip_moments_fits.argtypes = [sz, sz, i32]
+    L.compvhip_moments_host.argtypes = [vp, C.POINTER(MomentsDesc), vp, sz, sz, sz, vp, vp]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -529,6 +548,27 @@ def undistort_map(K, d, out_w, out_h, x0=0, y0=0, dtype=np.float32):
     if rc != OK:
         raise CompvHipError(rc, "compvhip_undistort_map")
     return mx, my
+
+
+def moments_fits(W, H, weights=MOMENTS_VALUE):
+    """compvhip_moments_fits (host arithmetic, no GPU): may a frame of W x H be given with these weights (no sum can reach 2^64)"""
+    return bool(load().compvhip_moments_fits(W, H, weights))
+
+
+def moments_shape_host(raw):
+    """compvhip_moments_shape_host (host arithmetic, no GPU): raw records (MOMENTS_DTYPE, or an (n, 6) array of integers) -> MOMENTS_SHAPE_DTYPE records"""
+    L = load()
+    if not isinstance(raw, np.ndarray):
+        raw = np.array([[int(v) for v in r] for r in raw], dtype=np.uint64)          # (Python integers up to 2^64 - 1, without a trip through float64)
+    raw = np.ascontiguousarray(raw)
+    if raw.dtype != MOMENTS_DTYPE:
+        raw = np.ascontiguousarray(raw, np.uint64).reshape(-1, 6).view(MOMENTS_DTYPE).reshape(-1)
+    raw = raw.reshape(-1)
+    out = np.zeros(raw.size, MOMENTS_SHAPE_DTYPE)
+    rc = L.compvhip_moments_shape_host(_ptr(raw), raw.size, _ptr(out))
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_moments_shape_host")
+    return out
 
 
 def homography_quads(seed, pair, k, tries):
@@ -920,6 +960,34 @@ class Context:
         out = np.empty((out_h, out_w), np.float32 if interp in (INTERP_BILINEAR_FLOAT32, INTERP_BICUBIC_FLOAT32) else np.uint8)
         self._chk(self.lib.compvhip_warp_inverse_u8(self.h, _ptr(img), W, H, img.strides[0], _ptr(M), M.shape[0], interp, default, _ptr(out), out_w, out_h, out_w))
         return out
+
+    def moments(self, img, weights=MOMENTS_VALUE):
+        """compvhip_moments_host (CompVMathMoments::rawSecondOrder, skewness, orientation): one (H, W) uint8 plane from 1 x 1 on -> (raw, shape), one
+        MOMENTS_DTYPE and one MOMENTS_SHAPE_DTYPE record"""
+        H, W = img.shape
+        raw, shape = np.zeros(1, MOMENTS_DTYPE), np.zeros(1, MOMENTS_SHAPE_DTYPE)
+        desc = MomentsDesc(weights)
+        self._chk(self.lib.compvhip_moments_host(self.h, C.byref(desc), _ptr(img), W, H, img.strides[0], _ptr(raw), _ptr(shape)))
+        return raw[0], shape[0]
+
+    # ---- image moments on device memory (stateless on the context; asynchronous on `stream`) ----
+    def moments_frames(self, d_gray, W, H, S, frames, d_raw, d_shape=0, weights=MOMENTS_VALUE, stream=0):
+        """compvhip_moments_frames: d_gray [frames][H][S] -> d_raw [frames] (and d_shape [frames]) records"""
+        desc = MomentsDesc(weights, MOMENTS_ORIGIN_FRAME, stream)
+        self._chk(self.lib.compvhip_moments_frames(self.h, C.byref(desc), d_gray or None, W, H, S, frames, d_raw or None, d_shape or None))
+
+    def moments_components(self, d_labels, W, H, label_stride, d_comps, comp_cap, d_counts, frames, d_raw, d_shape=0, d_gray=0, S=0, weights=MOMENTS_VALUE,
+                           origin=MOMENTS_ORIGIN_FRAME, stream=0):
+        """compvhip_moments_components: the label map, records and counts of compvhip_plan_components (and optional gray planes [frames][H][S]) -> d_raw (and
+        d_shape) [frames][comp_cap]; records at and behind min(max(count, 0), comp_cap) are not written"""
+        desc = MomentsDesc(weights, origin, stream)
+        self._chk(self.lib.compvhip_moments_components(self.h, C.byref(desc), d_labels or None, W, H, label_stride, d_gray or None, S, d_comps or None, comp_cap,
+                                                       d_counts or None, frames, d_raw or None, d_shape or None))
+
+    def moments_shapes(self, d_raw, n, d_shape, stream=0):
+        """compvhip_moments_shapes: d_shape[k] of d_raw[k], k < n"""
+        desc = MomentsDesc(stream=stream)
+        self._chk(self.lib.compvhip_moments_shapes(self.h, C.byref(desc), d_raw or None, n, d_shape or None))
 
     def undistort(self, img, K, d, out_w=None, out_h=None, x0=0, y0=0, interp=INTERP_BILINEAR, roi=None, default=0):
         """compvhip_undistort_u8 (CompVCalibUtils::undist2DImage): one camera K (3, 3), d (2 .. 4) float32 -> the (out_h, out_w) window at origin (x0, y0) of the

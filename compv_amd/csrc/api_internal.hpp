@@ -140,6 +140,7 @@ struct compvhip_ctx {
 	StatsScratch stats;                     // scratch of the host statistics calls (they need no plan: a plan has a minimum size, these calls have none)
 	DevBuf<double> dStatsF64;               // staging of compvhip_integral_u8: sum, then sumsq, (H + 1) x (W + 1) each
 	DevBuf<uint32_t> dStatsU32;             // staging of the other statistics calls: a histogram (with the table behind it), or projX then projY
+	DevBuf<uint64_t> dMoments;              // staging of compvhip_moments_host: the raw record, the shape record behind it
 	KhtGroupState kht;                 // the host KHT entry points' group of one frame (compvhip_houghkht_u8, _ex_u8, _kernels_u8); borrows `stream`
 };
 

@@ -641,4 +641,35 @@ struct UndistProjectArgs {
 };
 hipError_t launch_undist_project(const UndistProjectArgs& a, hipStream_t stream);   // more than 65 535 sets: sliced
 
+// ---- image moments (moments_kernels.hip; the shape record is moments_math.hpp's) -----------------------------------------------------------------
+constexpr int kMomentsRows = 16;             // image rows of one workgroup of moments_frames_kernel
+constexpr int kMomentsCompRows = 16;         // label rows of one wave of moments_components_kernel
+struct MomentsFramesArgs {
+	const uint8_t* gray;      // [frames][H][S], any byte
+	int W, H; size_t S;
+	int frames, frame0;       // frame0: set by the launcher (slices)
+	int unit;                 // != 0: a pixel counts gray != 0
+	compvhip_moments* raw;    // [frames], zeroed by the launcher
+};
+// zeroes raw[0 .. frames), then the six sums of every frame.  More than 65 535 frames: sliced.
+hipError_t launch_moments_frames(const MomentsFramesArgs& a, hipStream_t stream);
+struct MomentsCompArgs {
+	const int32_t* labels;    // [frames][H][labelStride]
+	int W, H; size_t labelStride;
+	const uint8_t* gray;      // nullptr (every pixel weighs 1) or [frames][H][S]
+	size_t S;
+	const compvhip_component* comps;   // [frames][compCap]: x0, y0 are read when box != 0
+	int compCap; const int32_t* counts; // [frames]: ids 1 .. min(max(counts[f], 0), compCap) are served
+	int frames, frame0;
+	int unit, box;
+	compvhip_moments* raw;    // [frames][compCap]: the served records are zeroed by the launcher, the others are not written
+};
+hipError_t launch_moments_components(const MomentsCompArgs& a, hipStream_t stream);   // more than 65 535 frames: sliced
+// shape[g * cap + c] of raw[g * cap + c] for c < (counts ? min(max(counts[g], 0), cap) : cap), g < groups
+struct MomentsShapeArgs {
+	const compvhip_moments* raw; compvhip_moments_shape* shape;
+	size_t groups; int cap; const int32_t* counts;
+};
+hipError_t launch_moments_shapes(const MomentsShapeArgs& a, hipStream_t stream);
+
 } // namespace compvhip

@@ -1543,6 +1543,83 @@ COMPVHIP_API int compvhip_undistort_u8(compvhip_ctx* ctx, const uint8_t* in, siz
 COMPVHIP_API int compvhip_undistort_set_timing(compvhip_undistort* undistort, int enabled);
 COMPVHIP_API int compvhip_undistort_get_timing(compvhip_undistort* undistort, const char** names, float* ms, int cap);
 
+/* ---- image moments: per frame and per component (docs/kernels/moments.md) ------------------------------------------------------------------------
+ * CompVMathMoments::rawFirstOrder, rawSecondOrder, skewness and orientation (base/math/compv_math_moments.cxx), batched, and the same applied to
+ * every blob of a label map of compvhip_plan_components without a host trip.
+ * Inputs: a plane p of W x H bytes; column i is x, row j is y; bytes at columns >= W never count.  `weights` selects how a pixel counts:
+ *    COMPVHIP_MOMENTS_VALUE  w = p[j][i]: what the reference does (its `binar` argument is accepted and ignored, :19-39, :43-71);
+ *    COMPVHIP_MOMENTS_UNIT   w = (p[j][i] != 0): what `binar` promises; equal to the reference on a 0 / 1 plane.
+ * A. Raw record: the six sums m00 = sum w, m01 = sum j w, m10 = sum i w, m11 = sum i j w, m02 = sum j j w, m20 = sum i i w over all pixels, as EXACT
+ *    integers, in the order of the reference's moments[0 .. 5].  Integer sums have no order: the record is the same from run to run.
+ * B. Range: a call is refused, before anything is enqueued or written, when wmax * W * H * max(W - 1, H - 1)^2 >= 2^64 (wmax = 255 for VALUE, 1 for
+ *    UNIT and for components without gray planes): below that no sum can wrap.  4K and 16384 x 16384 pass with VALUE, 32767 x 32767 only with UNIT.
+ *    Also refused: W or H of 0 or beyond 32767, W * H >= 2^31.  compvhip_moments_fits answers for a size.
+ * C. The reference accumulates in double.  Wherever all six exact sums are below 2^53 each of its partial sums is an exactly representable integer,
+ *    and (double)m_k equals its moments[k] on every bit; beyond that the reference rounds and this library does not.
+ * D. Shape record of a raw record; Mk = (double)m_k rounded to nearest even, one IEEE binary64 rounding per operation, nothing contracted:
+ *    m00 == 0: status 1, cs = 1, every other field 0.  Otherwise status 0 and
+ *      scale = 1.0 / M00; ybar = M01 * scale; xbar = M10 * scale;
+ *      u20 = (M20 * scale) - (xbar * xbar); u02 = (M02 * scale) - (ybar * ybar); u11 = (M11 * scale) - (xbar * ybar); den = u20 - u02;   (:177-187)
+ *      (cs, sn) = |den| > DBL_EPSILON ? (cos, sin) of atan2(2 * u11, den) / 2 by the half-angle formulas of "RANSAC homography" item D : (1, 0);
+ *        the reference's theta is the angle of (cs, sn) -- the one value that is not defined bit for bit against it (no libm on the device);
+ *      a = M02 - (ybar * M01); b = M11 - (xbar * M01); skew = |a| > DBL_EPSILON ? b / a : 0   (its own unnormalised terms, :141-149).
+ * E. Per component.  Inputs are what compvhip_plan_components wrote: the label map int32 [frames][H][labelStride], the records [frames][compCap], the
+ *    counts [frames]; optionally gray planes [frames][H][S] (NULL: every pixel of a component weighs 1, whatever `weights` says; with gray planes a
+ *    pixel weighs its gray value (VALUE: a gray 0 inside a component weighs 0) or gray != 0 (UNIT)).  Component id of frame f is served for
+ *    id <= min(max(count, 0), compCap); its raw (and shape) record goes to [f][id - 1]; records at and behind that bound are not written.  Label
+ *    elements <= 0, labels beyond the bound and everything at columns >= W are ignored.  `origin`: COMPVHIP_MOMENTS_ORIGIN_FRAME: i, j are frame
+ *    coordinates; COMPVHIP_MOMENTS_ORIGIN_BOX: i - x0, j - y0 of the component's record -- the reference run on the blob's crop with every foreign
+ *    pixel zeroed.  Only x0 and y0 of a record are read, and only with ORIGIN_BOX.
+ * The device calls are stateless on a context: they own no scratch (the sums land in the caller's records, which each call zeroes itself), run on the
+ *    descriptor's stream and never synchronise the host; nothing is carried from call to call.
+ * Alignment.  d_gray: any byte; labels, component records and counts: 4 bytes; raw and shape records: 8 bytes.  A misaligned pointer is refused.
+ * Batches beyond 65 535 frames: SLICED.
+ * Refused with COMPVHIP_E_INVALID_PARAMETER, nothing written and nothing enqueued: a null context, descriptor or required pointer; a wrong size field;
+ *    an unknown weights or origin (compvhip_moments_frames and _host: ORIGIN_FRAME only); item B; S < W; labelStride < W; frames of 0 or beyond
+ *    2^31 - 1; compCap of 0 or beyond 2^31 - 1; n beyond 2^31 - 1; a misaligned pointer. */
+enum {
+	COMPVHIP_MOMENTS_VALUE = 0,
+	COMPVHIP_MOMENTS_UNIT = 1
+};
+enum {
+	COMPVHIP_MOMENTS_ORIGIN_FRAME = 0,
+	COMPVHIP_MOMENTS_ORIGIN_BOX = 1
+};
+typedef struct compvhip_moments {
+	uint64_t m00, m01, m10, m11, m02, m20;
+} compvhip_moments;
+typedef struct compvhip_moments_shape {
+	double xbar, ybar;          /* the centroid */
+	double u20, u02, u11;       /* the normalised central moments of the orientation */
+	double skew;
+	double cs, sn;              /* cos and sin of the orientation theta */
+	int32_t status, pad;        /* 0; 1: m00 == 0.  pad: 0 */
+} compvhip_moments_shape;
+typedef struct compvhip_moments_desc {
+	uint32_t size;              /* sizeof(compvhip_moments_desc) */
+	int32_t weights;            /* COMPVHIP_MOMENTS_VALUE / _UNIT */
+	int32_t origin;             /* COMPVHIP_MOMENTS_ORIGIN_FRAME / _BOX; the frames calls: FRAME only */
+	void* hipStream;            /* a hipStream_t; NULL = the default stream */
+} compvhip_moments_desc;
+
+/* Items A (d_raw [frames]) and, with d_shape != NULL, D (d_shape [frames]) of every frame of d_gray [frames][H][S].  Asynchronous. */
+COMPVHIP_API int compvhip_moments_frames(compvhip_ctx* ctx, const compvhip_moments_desc* desc, const uint8_t* d_gray, size_t W, size_t H, size_t S, size_t frames,
+                                         compvhip_moments* d_raw, compvhip_moments_shape* d_shape);
+/* Item E: d_raw and (or NULL) d_shape [frames][compCap].  d_gray NULL: S is not looked at.  Asynchronous. */
+COMPVHIP_API int compvhip_moments_components(compvhip_ctx* ctx, const compvhip_moments_desc* desc, const int32_t* d_labels, size_t W, size_t H, size_t labelStride,
+                                             const uint8_t* d_gray, size_t S, const compvhip_component* d_comps, size_t compCap, const int32_t* d_compCounts,
+                                             size_t frames, compvhip_moments* d_raw, compvhip_moments_shape* d_shape);
+/* Item D alone on the device: d_shape[k] of d_raw[k], k < n (n == 0: nothing to do).  Only the descriptor's size and stream are looked at.  Asynchronous. */
+COMPVHIP_API int compvhip_moments_shapes(compvhip_ctx* ctx, const compvhip_moments_desc* desc, const compvhip_moments* d_raw, size_t n, compvhip_moments_shape* d_shape);
+/* Item D on the host (standard library only, no GPU, no context): shape[k] of raw[k], k < n.  A null pointer: COMPVHIP_E_INVALID_PARAMETER. */
+COMPVHIP_API int compvhip_moments_shape_host(const compvhip_moments* raw, size_t n, compvhip_moments_shape* shape);
+/* Item B on the host: 1 when a frame of W x H may be given with these weights, 0 when the call would be refused (an unknown `weights` included). */
+COMPVHIP_API int compvhip_moments_fits(size_t W, size_t H, int weights);
+/* Items A and D of one HOST plane from 1 x 1 on: raw and (or NULL) shape receive one record each.  Synchronous, on the context's own stream: the
+ * descriptor's stream is not used.  Staging is the context's and allocated on first use. */
+COMPVHIP_API int compvhip_moments_host(compvhip_ctx* ctx, const compvhip_moments_desc* desc, const uint8_t* in, size_t W, size_t H, size_t S, compvhip_moments* raw,
+                                       compvhip_moments_shape* shape);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel
