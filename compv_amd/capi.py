@@ -92,6 +92,8 @@ EXPORTS = [
     "compvhip_undistort_create", "compvhip_undistort_destroy", "compvhip_undistort_frames", "compvhip_undistort_maps", "compvhip_undistort_points",
     "compvhip_undistort_project", "compvhip_undistort_u8", "compvhip_undistort_set_timing", "compvhip_undistort_get_timing",
     "compvhip_moments_frames", "compvhip_moments_components", "compvhip_moments_shapes", "compvhip_moments_shape_host", "compvhip_moments_fits", "compvhip_moments_host",
+    "compvhip_pca_project", "compvhip_mulabt_f32", "compvhip_pca_covariance", "compvhip_pca_covariance_scratch", "compvhip_pca_project_host", "compvhip_pca_model_parse",
+    "compvhip_pca_dot_host",
 ]
 
 KHT_ORDER_REFERENCE, KHT_ORDER_CANONICAL = 0, 1
@@ -221,6 +223,14 @@ class MomentsDesc(C.Structure):
 
     def __init__(self, weights=MOMENTS_VALUE, origin=MOMENTS_ORIGIN_FRAME, stream=0):
         super().__init__(C.sizeof(MomentsDesc), weights, origin, stream or None)
+
+
+class PcaDesc(C.Structure):
+    """compvhip_pca_desc (include/compv_hip.h): the stream the device calls run on"""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("hipStream", C.c_void_p)]
+
+    def __init__(self, stream=0):
+        super().__init__(C.sizeof(PcaDesc), 0, stream or None)
 
 
 def curvefit_model_points(model):
@@ -482,6 +492,13 @@ def load():
     L.compvhip_moments_shape_host.argtypes = [vp, sz, vp]
     L.compvhip_moments_fits.argtypes = [sz, sz, i32]
     L.compvhip_moments_host.argtypes = [vp, C.POINTER(MomentsDesc), vp, sz, sz, sz, vp, vp]
+    L.compvhip_pca_project.argtypes = [vp, C.POINTER(PcaDesc), vp, vp, sz, sz, sz, vp, sz, sz, vp, sz]
+    L.compvhip_mulabt_f32.argtypes = [vp, C.POINTER(PcaDesc), vp, sz, sz, vp, sz, sz, sz, vp, sz]
+    L.compvhip_pca_covariance.argtypes = [vp, C.POINTER(PcaDesc), vp, sz, sz, sz, vp, vp, sz, vp]
+    L.compvhip_pca_covariance_scratch.argtypes = [sz, sz, C.POINTER(sz)]
+    L.compvhip_pca_project_host.argtypes = [vp, C.POINTER(PcaDesc), vp, vp, sz, sz, sz, vp, sz, sz, vp, sz]
+    L.compvhip_pca_model_parse.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp]
+    L.compvhip_pca_dot_host.argtypes = [vp, vp, sz, C.POINTER(C.c_float)]
     L.compvhip_plan_acc.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.compvhip_plan_acc_export.argtypes = [vp, sz, vp, sz, vp]
     L.compvhip_plan_edge_counts.argtypes = [vp, C.POINTER(vp)]
@@ -633,6 +650,60 @@ class SvmModel:
     def struct(self):
         return SvmModelStruct(C.sizeof(SvmModelStruct), self.kernel, self.nr_class, self.l, self.dim, 0, self.gamma, self.sv.ctypes.data, self.sv_coef.ctypes.data,
                               self.rho.ctypes.data, self.n_sv.ctypes.data, self.label.ctypes.data)
+
+
+def pca_dot(a, b):
+    """compvhip_pca_dot_host (host arithmetic, no GPU): the sixteen-accumulator float32 dot product of CompVMath::mulABt"""
+    L = load()
+    a, b = np.ascontiguousarray(a, np.float32).ravel(), np.ascontiguousarray(b, np.float32).ravel()
+    assert a.size == b.size
+    out = C.c_float()
+    rc = L.compvhip_pca_dot_host(_ptr(a) if a.size else None, _ptr(b) if b.size else None, a.size, C.byref(out))
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_pca_dot_host")
+    return np.float32(out.value)
+
+
+def pca_covariance_scratch(n, dim):
+    """compvhip_pca_covariance_scratch (host arithmetic, no GPU): the bytes compvhip_pca_covariance needs for n observations of dim dimensions"""
+    b = C.c_size_t(0)
+    rc = load().compvhip_pca_covariance_scratch(n, dim, C.byref(b))
+    if rc != OK:
+        raise CompvHipError(rc, "compvhip_pca_covariance_scratch")
+    return b.value
+
+
+class PcaModel:
+    """A PCA model: mean (dim,) or None, vectors (components, dim) -- the eigenvectors as rows -- and values (components,) or None, float32 host arrays;
+    to_device() uploads mean and vectors with torch and keeps the tensors (d_mean, d_vectors)."""
+
+    def __init__(self, mean, vectors, values=None):
+        self.vectors = np.ascontiguousarray(vectors, np.float32)
+        assert self.vectors.ndim == 2
+        self.components, self.dim = self.vectors.shape
+        self.mean = None if mean is None else np.ascontiguousarray(mean, np.float32).reshape(self.dim)
+        self.values = None if values is None else np.ascontiguousarray(values, np.float32).reshape(self.components)
+        self.d_mean = self.d_vectors = None
+
+    @classmethod
+    def from_file(cls, path):
+        """compvhip_pca_model_parse (host, no GPU): a model file as CompVMathPCA::write produces it; CompvHipError where the file is refused"""
+        L = load()
+        d, m = C.c_int32(0), C.c_int32(0)
+        rc = L.compvhip_pca_model_parse(os.fsencode(path), C.byref(d), C.byref(m), None, None, None)
+        if rc != OK:
+            raise CompvHipError(rc, "compvhip_pca_model_parse")
+        mean, vectors, values = np.zeros(d.value, np.float32), np.zeros((m.value, d.value), np.float32), np.zeros(m.value, np.float32)
+        rc = L.compvhip_pca_model_parse(os.fsencode(path), C.byref(d), C.byref(m), _ptr(mean), _ptr(vectors), _ptr(values))
+        if rc != OK:
+            raise CompvHipError(rc, "compvhip_pca_model_parse")
+        return cls(mean, vectors, values)
+
+    def to_device(self, device="cuda:0"):
+        import torch
+        self.d_vectors = torch.from_numpy(self.vectors).to(device)
+        self.d_mean = None if self.mean is None else torch.from_numpy(self.mean).to(device)
+        return self
 
 
 def hog_geometry(W, H, opts=None, **kw):
@@ -988,6 +1059,42 @@ class Context:
         """compvhip_moments_shapes: d_shape[k] of d_raw[k], k < n"""
         desc = MomentsDesc(stream=stream)
         self._chk(self.lib.compvhip_moments_shapes(self.h, C.byref(desc), d_raw or None, n, d_shape or None))
+
+    # ---- PCA projection on device memory (stateless on the context; asynchronous on `stream`) ----
+    def pca_project(self, model, d_in, n, in_stride, d_out, out_stride, centre=True, stream=0):
+        """compvhip_pca_project: d_in [n][in_stride] float32 -> d_out [n][out_stride], with a PcaModel after to_device(); centre=False: the mean is not subtracted"""
+        assert model.d_vectors is not None, "PcaModel.to_device() first"
+        d_mean = model.d_mean.data_ptr() if centre and model.d_mean is not None else None
+        desc = PcaDesc(stream)
+        self._chk(self.lib.compvhip_pca_project(self.h, C.byref(desc), d_mean, model.d_vectors.data_ptr(), model.dim, model.dim, model.components, d_in or None, n, in_stride,
+                                                d_out or None, out_stride))
+
+    def pca_project_raw(self, d_mean, d_vectors, vec_stride, dim, components, d_in, n, in_stride, d_out, out_stride, stream=0):
+        """compvhip_pca_project on raw device addresses (d_mean = 0: do not centre)"""
+        desc = PcaDesc(stream)
+        self._chk(self.lib.compvhip_pca_project(self.h, C.byref(desc), d_mean or None, d_vectors or None, vec_stride, dim, components, d_in or None, n, in_stride, d_out or None,
+                                                out_stride))
+
+    def mulabt(self, d_A, a_rows, a_stride, d_B, b_rows, b_stride, cols, d_R, r_stride, stream=0):
+        """compvhip_mulabt_f32 (CompVMath::mulABt): d_R [a_rows][r_stride] = d_A [a_rows][a_stride] times the transpose of d_B [b_rows][b_stride], float32"""
+        desc = PcaDesc(stream)
+        self._chk(self.lib.compvhip_mulabt_f32(self.h, C.byref(desc), d_A or None, a_rows, a_stride, d_B or None, b_rows, b_stride, cols, d_R or None, r_stride))
+
+    def pca_covariance(self, d_obs, n, obs_stride, dim, d_mean, d_covar, cov_stride, d_scratch, stream=0):
+        """compvhip_pca_covariance: the mean [dim] and the covariance [dim][cov_stride] of n row-based observations; d_scratch: pca_covariance_scratch(n, dim) bytes"""
+        desc = PcaDesc(stream)
+        self._chk(self.lib.compvhip_pca_covariance(self.h, C.byref(desc), d_obs or None, n, obs_stride, dim, d_mean or None, d_covar or None, cov_stride, d_scratch or None))
+
+    def pca_project_host(self, model, rows, centre=True):
+        """compvhip_pca_project_host: (n, dim) float32 host rows -> (n, components); the model's host arrays are used"""
+        rows = np.asarray(rows, np.float32)
+        assert rows.ndim == 2 and rows.shape[1] == model.dim and rows.strides[1] == 4 and rows.strides[0] % 4 == 0
+        out = np.zeros((rows.shape[0], model.components), np.float32)
+        desc = PcaDesc()
+        mean = _ptr(model.mean) if centre and model.mean is not None else None
+        self._chk(self.lib.compvhip_pca_project_host(self.h, C.byref(desc), mean, _ptr(model.vectors), model.dim, model.dim, model.components, _ptr(rows) if rows.size else None,
+                                                     rows.shape[0], rows.strides[0] // 4 if rows.shape[0] > 1 else model.dim, _ptr(out) if out.size else None, model.components))
+        return out
 
     def undistort(self, img, K, d, out_w=None, out_h=None, x0=0, y0=0, interp=INTERP_BILINEAR, roi=None, default=0):
         """compvhip_undistort_u8 (CompVCalibUtils::undist2DImage): one camera K (3, 3), d (2 .. 4) float32 -> the (out_h, out_w) window at origin (x0, y0) of the

@@ -141,6 +141,7 @@ struct compvhip_ctx {
 	DevBuf<double> dStatsF64;               // staging of compvhip_integral_u8: sum, then sumsq, (H + 1) x (W + 1) each
 	DevBuf<uint32_t> dStatsU32;             // staging of the other statistics calls: a histogram (with the table behind it), or projX then projY
 	DevBuf<uint64_t> dMoments;              // staging of compvhip_moments_host: the raw record, the shape record behind it
+	DevBuf<float> dPcaModel, dPcaIn, dPcaOut;   // staging of compvhip_pca_project_host: the mean with the vectors behind it, a slice of rows, its outputs
 	KhtGroupState kht;                 // the host KHT entry points' group of one frame (compvhip_houghkht_u8, _ex_u8, _kernels_u8); borrows `stream`
 };
 

@@ -672,4 +672,30 @@ struct MomentsShapeArgs {
 };
 hipError_t launch_moments_shapes(const MomentsShapeArgs& a, hipStream_t stream);
 
+// ---- PCA projection, mulABt, mean and covariance (pca_kernels.hip; the arithmetic is pca_math.hpp's) ------------------------------------------------
+constexpr int kPcaTile = 32;                 // rows and components of one workgroup of pca_project_kernel
+constexpr int kPcaChunk = 64;                // columns it stages at a time
+// out[r][m] = dot16(in[r] (- mean), vectors[m], dim) (* scale), r < n, m < comps.  Row tiles ride in grid x, component tiles in y: comps <= 2^20
+// keeps y below 65 535, so no launch is sliced.
+struct PcaProjectArgs {
+	const float* in; int n; size_t inStride;              // [n][inStride]
+	const float* mean;                                    // [dim], or nullptr: rows are taken as they are
+	const float* vectors; int comps; size_t vecStride;    // [comps][vecStride]
+	int dim;
+	float* out; size_t outStride;                         // [n][outStride]
+	int scaled; float scale;                              // scaled != 0: one more rounded multiply
+};
+hipError_t launch_pca_project(const PcaProjectArgs& a, hipStream_t stream);
+struct PcaMeanArgs {
+	const float* obs; int n; size_t obsStride; int dim;   // [n][obsStride]
+	float* mean;                                          // [dim]
+};
+hipError_t launch_pca_mean(const PcaMeanArgs& a, hipStream_t stream);
+struct PcaCentreArgs {
+	const float* obs; int n; size_t obsStride; int dim;
+	const float* mean;
+	float* centred; size_t nPad;                          // [dim][nPad]; columns n .. nPad - 1 are not written
+};
+hipError_t launch_pca_centre_transpose(const PcaCentreArgs& a, hipStream_t stream);
+
 } // namespace compvhip

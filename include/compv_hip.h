@@ -1620,6 +1620,63 @@ COMPVHIP_API int compvhip_moments_fits(size_t W, size_t H, int weights);
 COMPVHIP_API int compvhip_moments_host(compvhip_ctx* ctx, const compvhip_moments_desc* desc, const uint8_t* in, size_t W, size_t H, size_t S, compvhip_moments* raw,
                                        compvhip_moments_shape* shape);
 
+/* ---- PCA projection: HOG to PCA to SVM without a host trip (docs/kernels/pca.md) --------------------------------------------------------------------
+ * CompVMathPCA::project (base/math/compv_math_pca.cxx:196-254), CompVMath::mulABt (base/math/compv_math_op_mul.cxx) and the row-based front half of
+ * CompVMathPCA::compute (mean and covariance, :267-348), in float32, bit for bit the reference's plain C leaf, which its non-FMA SIMD leaves are written
+ * to equal.  All arithmetic is IEEE binary32 with one rounding per operation and nothing contracted; denormals are kept.
+ * A. Model: dim D >= 1, components M >= 1; mean[D], vectors[M][D] (the eigenvectors as rows), values[M] (informative: no call reads them).
+ * B. Centre: c_k = x_k - mean_k, rounded (CompVMathOpSubSub).  With no mean, c = x.
+ * C. dot16(a, b, D): sixteen accumulators v0 .. v15 start at +0.  For every whole group of 16 columns v_i += a[k + i] * b[k + i] (the product is
+ *    rounded, then the sum); for every whole group of 4 of what remains the same into v0 .. v3.  Then the fold, in this order:
+ *      v0 += v4; v1 += v5; v2 += v6; v3 += v7; v8 += v12; v9 += v13; v10 += v14; v11 += v15;
+ *      v0 += v8; v1 += v9; v2 += v10; v3 += v11;   v0 += v2; v1 += v3;   v0 += v1;
+ *    then the last 0 .. 3 columns in order, v0 += a[k] * b[k].  The value is v0 (compv_math_op_mul.cxx:132-181).
+ * D. Projection: out[r][m] = dot16(c_r, vectors_m, D).
+ * E. mulABt: R[i][j] = dot16(A_i, B_j, cols).
+ * F. Mean and covariance of n >= 1 row-based observations: mean_j = (float)(s * (1.0 / (double)n)), s the binary64 sum of (double)obs[i][j] over
+ *    i = 0 .. n - 1 in that order; c[j][i] = obs[i][j] - mean_j; covar[a][b] = dot16(c[a], c[b], n) * scale, scale = 1 / (float)(n - 1), applied (one
+ *    more rounded multiply) only when n > 1.  dot16(a, b) = dot16(b, a) on every bit, so covar is symmetric on every bit.
+ * G. Model file: what CompVMathPCA::write produces and read accepts -- a JSON object with members "mean", "vectors" and "values", each
+ *    {"type":"32f","size":[rows,cols],"data":[...]} with rows * cols numbers in row-major order; any member order, unknown members skipped.  A number
+ *    becomes (float)strtod(text) in the C locale.  mean is 1 x D, values 1 x M, vectors M x D.
+ * Limits: 1 <= D <= 2^20 (aRows, bRows and cols of mulABt: the same), 1 <= M <= 65535, n <= 2^31 - 1 (n == 0: success, nothing enqueued); every stride
+ *    (in elements) >= its row length and rows * stride < 2^40.  Pointers: 4-byte aligned; the scratch of the covariance: 16-byte aligned.
+ * The device calls are stateless on a context: they own no scratch, run on the descriptor's stream and never synchronise the host.  Elements at and
+ *    behind `dim` (input) or `components` (output) of a row are never read or written; rows behind n are never written.  Input and output may not
+ *    overlap (not checked).  A NaN or an infinity in the data gives an unspecified value, never a fault.  No grid dimension can pass 65 535 within
+ *    the limits (rows ride in x), so no launch is sliced.
+ * Refused with COMPVHIP_E_INVALID_PARAMETER, nothing written and nothing enqueued: a null context, descriptor or required pointer; a wrong size field;
+ *    a dimension, count or stride outside the limits; a misaligned pointer; a model file that does not open or parse, holds a type other than 32f, a
+ *    size that does not match the data count, a number that is not finite in float32, or D or M outside the limits. */
+typedef struct compvhip_pca_desc {
+	uint32_t size;              /* sizeof(compvhip_pca_desc) */
+	uint32_t reserved;          /* 0 */
+	void* hipStream;            /* a hipStream_t; NULL = the default stream */
+} compvhip_pca_desc;
+
+/* Items B - D: d_in [n][inStride] -> d_out [n][outStride], with d_mean [dim] (NULL: do not centre) and d_vectors [components][vecStride].
+ * Asynchronous. */
+COMPVHIP_API int compvhip_pca_project(compvhip_ctx* ctx, const compvhip_pca_desc* desc, const float* d_mean, const float* d_vectors, size_t vecStride, size_t dim,
+                                      size_t components, const float* d_in, size_t n, size_t inStride, float* d_out, size_t outStride);
+/* Item E: d_A [aRows][aStride], d_B [bRows][bStride], `cols` columns each -> d_R [aRows][rStride].  aRows == 0: nothing to do.  Asynchronous. */
+COMPVHIP_API int compvhip_mulabt_f32(compvhip_ctx* ctx, const compvhip_pca_desc* desc, const float* d_A, size_t aRows, size_t aStride, const float* d_B, size_t bRows,
+                                     size_t bStride, size_t cols, float* d_R, size_t rStride);
+/* Item F: d_obs [n][obsStride], n >= 1 -> d_mean [dim] and d_covar [dim][covStride].  d_scratch: compvhip_pca_covariance_scratch bytes, 16-byte
+ * aligned, for the centred, transposed data c [dim][nPad], nPad = n rounded up to 16; the padding is neither written nor read.  Asynchronous. */
+COMPVHIP_API int compvhip_pca_covariance(compvhip_ctx* ctx, const compvhip_pca_desc* desc, const float* d_obs, size_t n, size_t obsStride, size_t dim, float* d_mean,
+                                         float* d_covar, size_t covStride, void* d_scratch);
+/* The bytes of that scratch; refused where n or dim is outside the limits or dim * nPad reaches 2^40. */
+COMPVHIP_API int compvhip_pca_covariance_scratch(size_t n, size_t dim, size_t* bytes);
+/* compvhip_pca_project on HOST arrays.  Synchronous, on the context's own stream: the descriptor's stream is not used.  Staging is the context's,
+ * allocated on first use; the rows go through it in slices of at most 512. */
+COMPVHIP_API int compvhip_pca_project_host(compvhip_ctx* ctx, const compvhip_pca_desc* desc, const float* mean, const float* vectors, size_t vecStride, size_t dim,
+                                           size_t components, const float* in, size_t n, size_t inStride, float* out, size_t outStride);
+/* Item G on the host (standard library only, no GPU, no context): the sizes of the model file into *dim and *components, and -- each may be NULL, so a
+ * first call learns the sizes -- mean [dim], vectors [components][dim], values [components].  A refused file writes nothing. */
+COMPVHIP_API int compvhip_pca_model_parse(const char* path, int32_t* dim, int32_t* components, float* mean, float* vectors, float* values);
+/* Item C on the host: *out = dot16(a, b, n).  n == 0: +0, a and b are not looked at. */
+COMPVHIP_API int compvhip_pca_dot_host(const float* a, const float* b, size_t n, float* out);
+
 /* Per-kernel timing of the last plan call, measured with hipEvents on the stream the kernels were launched on.
  * names/ms: caller arrays of capacity cap; returns the number of entries (<= cap). compvhip_plan_set_timing(plan, mode):
  * 0 = off, 1 = every kernel, 2 = only canny_tile_kernel and sht_vote_kernel, 3 = only sht_vote_kernel, 4 = only canny_tile_kernel
