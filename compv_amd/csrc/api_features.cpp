@@ -480,13 +480,11 @@ int compvhip_api::remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W,
                                size_t Wout, size_t Hout, size_t Sout, uint8_t defaultValue, RemapArgs* a)
 {
 	if (!d_in || !d_out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null frame pointer");
-	if (interp != COMPVHIP_INTERP_NEAREST && interp != COMPVHIP_INTERP_BILINEAR && interp != COMPVHIP_INTERP_BILINEAR_FLOAT32 && interp != COMPVHIP_INTERP_BICUBIC &&
-	    interp != COMPVHIP_INTERP_BICUBIC_FLOAT32)
-		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "unknown interpolation");
+	const size_t elem = interpElemBytes(interp);
+	if (!elem) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "unknown interpolation");
 	if (!W || !H || !Wout || !Hout || Wout > 32767 || Hout > 32767 || W > 32767 || H > 32767 || S < W || Sout < Wout || Sout > static_cast<size_t>(INT32_MAX) || !frames ||
 	    frames > static_cast<size_t>(INT32_MAX) || S * H > static_cast<size_t>(INT32_MAX))
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "remap: a size of 0 or beyond 32767, Sout < Wout, or a frame beyond 2^31 bytes");
-	const size_t elem = interp == COMPVHIP_INTERP_BILINEAR_FLOAT32 || interp == COMPVHIP_INTERP_BICUBIC_FLOAT32 ? sizeof(float) : 1;
 	if (elem > 1 && misaligned(3, d_out)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "float32 destination not 4-byte aligned");
 	const uint8_t* const o = static_cast<const uint8_t*>(d_out);
 	if (d_in < o + Sout * Hout * frames * elem && o < d_in + S * H * frames) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap");
@@ -510,23 +508,20 @@ int compvhip_api::remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W,
 int compvhip_api::warpUpload(compvhip_ctx* ctx, WarpTables* t, const float* M, int rows, size_t count, RemapArgs* a, hipStream_t st)
 {
 	const size_t Wout = static_cast<size_t>(a->Wout), Hout = static_cast<size_t>(a->Hout), per = static_cast<size_t>(rows) * (Wout + Hout), total = per * count;
-	WarpTables::Slot& s = t->slot[t->next];
-	t->next = (t->next + 1) % kAsyncDepth;
-	if (s.copied) HIPCHK(ctx, hipEventSynchronize(s.copied));          // the copy that last read this slot (kAsyncDepth calls ago)
-	else HIPCHK(ctx, hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-	HIPCHK(ctx, s.host.reserve(total));
-	HIPCHK(ctx, t->dev.reserve(ctx, total));          // grows only: a reallocation frees with hipFree, which waits for the kernels that still read the old one
+	float* host = nullptr;
+	WarpTables::Slot* s = nullptr;
+	int rc = tablesSlot(ctx, t, total, &host, &s);
+	if (rc) return rc;
 	for (size_t m = 0; m < count; ++m) {
-		float* cols = s.host + m * per;
+		float* cols = host + m * per;
 		float* rws = cols + static_cast<size_t>(rows) * Wout;
-		const int rc = compvhip_warp_tables(M + m * static_cast<size_t>(rows) * 3, rows, Wout, Hout, cols, cols + Wout, rows == 3 ? cols + 2 * Wout : nullptr, rws, rws + Hout,
-		                                    rows == 3 ? rws + 2 * Hout : nullptr);
+		rc = compvhip_warp_tables(M + m * static_cast<size_t>(rows) * 3, rows, Wout, Hout, cols, cols + Wout, rows == 3 ? cols + 2 * Wout : nullptr, rws, rws + Hout,
+		                          rows == 3 ? rws + 2 * Hout : nullptr);
 		if (rc) return fail(ctx, rc, "warp tables");
 	}
-	HIPCHK(ctx, hipMemcpyAsync(t->dev, s.host, total * sizeof(float), hipMemcpyHostToDevice, st));
-	HIPCHK(ctx, hipEventRecord(s.copied, st));
+	rc = tablesSend(ctx, t, s, total, st);
 	a->tables = t->dev; a->coordFrameStride = per;
-	return COMPVHIP_OK;
+	return rc;
 }
 
 int compvhip_plan_remap(compvhip_plan* p, const uint8_t* d_in, const float* d_mapX, const float* d_mapY, size_t mapCount, int interp, const compvhip_roi* roi,

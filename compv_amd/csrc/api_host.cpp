@@ -24,55 +24,44 @@ int hostPlan(compvhip_ctx* ctx, size_t W, size_t H, float thetaDeg, compvhip_pla
 	return COMPVHIP_OK;
 }
 
-// H rows of rowBytes bytes between a host plane (stride S) and device staging (stride Sd), on the context's stream
-hipError_t upload(compvhip_ctx* ctx, void* dst, size_t Sd, const void* src, size_t S, size_t rowBytes, size_t H) { return hipMemcpy2DAsync(dst, Sd, src, S, rowBytes, H, hipMemcpyHostToDevice, ctx->stream); }
-hipError_t download(compvhip_ctx* ctx, void* dst, size_t S, const void* src, size_t Sd, size_t rowBytes, size_t H) { return hipMemcpy2DAsync(dst, S, src, Sd, rowBytes, H, hipMemcpyDeviceToHost, ctx->stream); }
-
-// The frame of the host calls on the cached plan: select the device, get the plan (thetaDeg or kAnyTheta), upload the plane into dIn, run; with `out`, download
-// dOut into it and wait for the stream (without, `run` ends in a synchronisation of its own: takeList).
-template <typename Run>   // int run(compvhip_plan*)
+// The host calls on the cached plan: select the device, get the plan (thetaDeg or kAnyTheta), the plane into dIn, run; with `out`, dOut into it and the
+// stream waited for (without, `run` ends in a wait of its own: takeList).  The copies of `run` go through the call's frame, which drains on every way out.
+template <typename Run>   // int run(compvhip_plan*, HostCall&)
 int hostPlaneOp(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, float thetaDeg, uint8_t* out, size_t So, const Run& run)
 {
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	compvhip_plan* p = nullptr;
 	int rc = hostPlan(ctx, W, H, thetaDeg, &p);
 	if (rc) return rc;
-	HIPCHK(ctx, upload(ctx, ctx->dIn, p->S, in, S, W, H));
-	rc = run(p);
-	if (rc) (void)hipStreamSynchronize(ctx->stream);   // a failed call leaves no copy from the caller's plane in flight
+	HostCall hc(ctx->stream);
+	stagePlane(ctx, hc, ctx->dIn, in, W, H, S);
+	if (!hc.ok()) return hostStatus(ctx, hc);
+	rc = run(p, hc);
 	if (rc || !out) return rc;
-	HIPCHK(ctx, download(ctx, out, So, ctx->dOut, p->S, W, H));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	return COMPVHIP_OK;
+	hc.download2D(out, So, ctx->dOut, p->S, W, H);
+	return hostWait(ctx, hc);
 }
 
 // The caller's lines with their number into dSegLines / dCounts and, with segs, its segments into dSegs / dSegCount (dSegCount is the caller's to allocate).
-int stageLists(compvhip_ctx* ctx, const compvhip_line* lines, size_t n, const compvhip_segment* segs, size_t nSegs)
+int stageLists(compvhip_ctx* ctx, HostCall& hc, const compvhip_line* lines, size_t n, const compvhip_segment* segs, size_t nSegs)
 {
-	HIPCHK(ctx, ctx->dSegLines.reserve(ctx, n));
-	if (segs) HIPCHK(ctx, ctx->dSegs.reserve(ctx, nSegs));
-	HIPCHK(ctx, ctx->dCounts.reserve(ctx, 1));
 	const int32_t nLines = static_cast<int32_t>(n), nS = static_cast<int32_t>(nSegs);
-	HIPCHK(ctx, hipMemcpyAsync(ctx->dSegLines, lines, n * sizeof(compvhip_line), hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->dCounts, &nLines, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-	if (segs) {
-		HIPCHK(ctx, hipMemcpyAsync(ctx->dSegs, segs, nSegs * sizeof(compvhip_segment), hipMemcpyHostToDevice, ctx->stream));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->dSegCount, &nS, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-	}
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the counts live on this stack frame; pageable copies may still be staged
-	return COMPVHIP_OK;
+	stageArray(ctx, hc, ctx->dSegLines, lines, n);
+	stageArray(ctx, hc, ctx->dCounts, &nLines, 1);
+	if (segs) { stageArray(ctx, hc, ctx->dSegs, segs, nSegs); hc.upload(ctx->dSegCount, &nS, sizeof(int32_t)); }
+	return hostWait(ctx, hc);   // the counts live on this stack frame; pageable copies may still be staged
 }
 
 // Waits for the stream, stores the int32 record count in *n and copies the first min(count, cap) records; COMPVHIP_E_OUT_OF_BOUND (`what`) when they did not all fit.
 template <typename T>
-int takeList(compvhip_ctx* ctx, const int32_t* dCount, const T* dRecs, T* recs, size_t cap, size_t* n, const char* what)
+int takeList(compvhip_ctx* ctx, HostCall& hc, const int32_t* dCount, const T* dRecs, T* recs, size_t cap, size_t* n, const char* what)
 {
 	int32_t found = 0;
-	HIPCHK(ctx, hipMemcpyAsync(&found, dCount, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	hc.download(&found, dCount, sizeof(int32_t), "record count");
+	if (!hc.wait()) return hostStatus(ctx, hc);
 	*n = static_cast<size_t>(found);
 	const size_t ncopy = std::min(*n, cap);
-	if (ncopy) HIPCHK(ctx, hipMemcpy(recs, dRecs, ncopy * sizeof(T), hipMemcpyDeviceToHost));
+	if (ncopy && !hc.downloadNow(recs, dRecs, ncopy * sizeof(T), "record download")) return hostStatus(ctx, hc);
 	if (*n > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, what);
 	return COMPVHIP_OK;
 }
@@ -94,7 +83,7 @@ int compvhip_canny_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, 
 	int lo, hi;
 	rc = validateCannyParams(ctx, tLow, tHigh, ksize, type, &lo, &hi);
 	if (rc) return rc;
-	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p) { return compvhip_plan_canny(p, ctx->dIn, tLow, tHigh, ksize, type, ctx->dOut, ctx->stream); });
+	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p, HostCall&) { return compvhip_plan_canny(p, ctx->dIn, tLow, tHigh, ksize, type, ctx->dOut, ctx->stream); });
 }
 
 int compvhip_edge_dete_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, int op, uint8_t* out, size_t So)
@@ -103,14 +92,14 @@ int compvhip_edge_dete_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t
 	if (rc) return rc;
 	if (op != COMPVHIP_OP_SOBEL && op != COMPVHIP_OP_SCHARR && op != COMPVHIP_OP_PREWITT)
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "invalid detector id"); // edge_dete.cxx:246
-	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p) -> int {
+	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p, HostCall& hc) -> int {
 		EdgeDeteArgs a;
 		a.in = ctx->dIn; a.out = ctx->dOut; a.gmax = p->sums;
 		a.inFrameStride = p->S * H; a.outFrameStride = p->S * H;
 		a.W = static_cast<int>(W); a.H = static_cast<int>(H); a.S = static_cast<int>(p->S); a.So = static_cast<int>(p->S);
 		a.tilesX = p->tilesX; a.tilesY = p->tilesY;
-		HIPCHK(ctx, launch_edge_dete(a, op, 1, ctx->stream));
-		return COMPVHIP_OK;
+		HOSTSTEP(ctx, hc, launch_edge_dete(a, op, 1, ctx->stream));
+		return hostStatus(ctx, hc);
 	});
 }
 
@@ -142,16 +131,14 @@ int compvhip_convlt1_fixedpoint_u8(compvhip_ctx* ctx, const uint8_t* in, size_t 
 	int rc = checkFxpKernel(ctx, W, H, vtKern, hzKern, kernSize);
 	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t Sd = alignUp(W, 64), bytes = Sd * H;
-	HIPCHK(ctx, ctx->dIn.reserve(ctx, bytes));
-	HIPCHK(ctx, ctx->dOut.reserve(ctx, bytes));
-	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
+	HostCall hc(ctx->stream);
+	const size_t Sd = stagePlane(ctx, hc, ctx->dIn, in, W, H, S), bytes = Sd * H;
+	HOSTSTEP(ctx, hc, ctx->dOut.reserve(ctx, bytes));
 	// dIn -> dOut with the fused kernel (no intermediate: the two staging buffers never alias)
-	HIPCHK(ctx, launch_convlt_fxp(ctx->dIn, nullptr, ctx->dOut, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), bytes, 1, vtKern, hzKern,
-	                              static_cast<int>(kernSize), ctx->stream));
-	HIPCHK(ctx, download(ctx, out, So, ctx->dOut, Sd, W, H));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	return COMPVHIP_OK;
+	HOSTSTEP(ctx, hc, launch_convlt_fxp(ctx->dIn, nullptr, ctx->dOut, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), bytes, 1, vtKern, hzKern,
+	                               static_cast<int>(kernSize), ctx->stream));
+	hc.download2D(out, So, ctx->dOut, Sd, W, H);
+	return hostWait(ctx, hc);
 }
 
 // CompVMathConvlt::convlt1<uint8_t | int16_t, int16_t, int16_t> (compv_math_convlt.h:26-28,37-39,98-292): the separable integer correlation the
@@ -166,18 +153,15 @@ static int convlt1I16(compvhip_ctx* ctx, const void* in, bool inIsU8, size_t W, 
 	if (kernSize > static_cast<size_t>(kFxpMaxTaps)) return fail(ctx, COMPVHIP_E_NOT_IMPLEMENTED, "integer convolution supports kernel sizes 1..15");
 	if (W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t es = inIsU8 ? 1 : 2;
-	const size_t Sd = alignUp(W, 64);
-	DevBuf<uint8_t> dIn; DevBuf<int16_t> dTmp, dOut;   // freed on the way out
-	if (dIn.reserve(ctx, Sd * H * es) != hipSuccess || dTmp.reserve(ctx, Sd * H) != hipSuccess || dOut.reserve(ctx, Sd * H) != hipSuccess)
-		return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "convolution buffers");
-	hipError_t e = hipMemcpy2DAsync(dIn, Sd * es, in, S * es, W * es, H, hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess) e = launch_convlt_i16(dIn, inIsU8, dTmp, dOut, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), static_cast<int>(Sd), vtKern, hzKern,
-	                                           static_cast<int>(kernSize), ctx->stream);
-	if (e == hipSuccess) e = hipMemcpy2DAsync(out, So * 2, dOut, Sd * 2, W * 2, H, hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-	if (e != hipSuccess) return fail(ctx, COMPVHIP_E_HIP, "integer convolution", e);
-	return COMPVHIP_OK;
+	DevBuf<uint8_t> dIn; DevBuf<int16_t> dTmp, dOut;   // freed on the way out, behind the drain of the frame
+	HostCall hc(ctx->stream);
+	const size_t Sd = stagePlane(ctx, hc, dIn, in, W, H, S, inIsU8 ? 1 : 2);
+	HOSTSTEP(ctx, hc, dTmp.reserve(ctx, Sd * H));
+	HOSTSTEP(ctx, hc, dOut.reserve(ctx, Sd * H));
+	HOSTSTEP(ctx, hc, launch_convlt_i16(dIn, inIsU8, dTmp, dOut, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), static_cast<int>(Sd), vtKern, hzKern,
+	                               static_cast<int>(kernSize), ctx->stream));
+	hc.download2D(out, So * 2, dOut, Sd * 2, W * 2, H);
+	return hostWait(ctx, hc);
 }
 
 int compvhip_convlt1_8u16s16s(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const int16_t* vtKern, const int16_t* hzKern, size_t kernSize,
@@ -200,16 +184,14 @@ int compvhip_grayscale_u8(compvhip_ctx* ctx, const uint8_t* in, int pixfmt, size
 	if (rc) return rc;
 	const int bpp = pixfmtBytes(pixfmt);
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t Sd = alignUp(W, 64);
-	HIPCHK(ctx, ctx->dPacked.reserve(ctx, Sd * H * bpp));
-	HIPCHK(ctx, ctx->dOut.reserve(ctx, Sd * H));
-	HIPCHK(ctx, upload(ctx, ctx->dPacked, Sd * bpp, in, S * bpp, W * bpp, H));
+	HostCall hc(ctx->stream);
+	const size_t Sd = stagePlane(ctx, hc, ctx->dPacked, in, W, H, S, static_cast<size_t>(bpp));
+	HOSTSTEP(ctx, hc, ctx->dOut.reserve(ctx, Sd * H));
 	GrayArgs a;
 	a.in = ctx->dPacked; a.out = ctx->dOut; a.W = static_cast<int>(W); a.H = static_cast<int>(H); a.S = static_cast<int>(Sd); a.So = static_cast<int>(Sd);
-	HIPCHK(ctx, launch_gray(a, pixfmt, 1, ctx->stream));
-	HIPCHK(ctx, download(ctx, out, So, ctx->dOut, Sd, W, H));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	return COMPVHIP_OK;
+	HOSTSTEP(ctx, hc, launch_gray(a, pixfmt, 1, ctx->stream));
+	hc.download2D(out, So, ctx->dOut, Sd, W, H);
+	return hostWait(ctx, hc);
 }
 
 int compvhip_otsu_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, double* threshold)
@@ -217,16 +199,14 @@ int compvhip_otsu_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, s
 	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
 	if (!in || !threshold || S < W || !W || !H || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image, stride < width or size out of range"); // threshold.cxx:54
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t Sd = alignUp(W, 64);
-	const size_t bytes = Sd * H;
-	HIPCHK(ctx, ctx->dIn.reserve(ctx, bytes));
-	HIPCHK(ctx, ctx->dHist.reserve(ctx, static_cast<size_t>(256) * kOtsuMaxChunks + 1));
-	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
-	int32_t* dT = reinterpret_cast<int32_t*>(ctx->dHist + static_cast<size_t>(256) * kOtsuMaxChunks);
-	HIPCHK(ctx, launch_otsu(ctx->dIn, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), bytes, 1, 0.5f, 1.f, ctx->dHist, dT, nullptr, ctx->stream));
 	int32_t t = 0;
-	HIPCHK(ctx, hipMemcpyAsync(&t, dT, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	HostCall hc(ctx->stream);
+	const size_t Sd = stagePlane(ctx, hc, ctx->dIn, in, W, H, S), bytes = Sd * H;
+	HOSTSTEP(ctx, hc, ctx->dHist.reserve(ctx, static_cast<size_t>(256) * kOtsuMaxChunks + 1));
+	int32_t* dT = reinterpret_cast<int32_t*>(ctx->dHist + static_cast<size_t>(256) * kOtsuMaxChunks);
+	HOSTSTEP(ctx, hc, launch_otsu(ctx->dIn, static_cast<int>(W), static_cast<int>(H), static_cast<int>(Sd), bytes, 1, 0.5f, 1.f, ctx->dHist, dT, nullptr, ctx->stream));
+	hc.download(&t, dT, sizeof(t));
+	if (!hc.wait()) return hostStatus(ctx, hc);
 	*threshold = static_cast<double>(t);
 	return COMPVHIP_OK;
 }
@@ -273,28 +253,30 @@ int compvhip_houghsht_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size
 	rc = ensureSht(p);
 	if (rc) return rc;
 	if (acc && accStride < p->T) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "accStride < theta bins");
-	HIPCHK(ctx, upload(ctx, ctx->dIn, p->S, edges, S, W, H));
-	HIPCHK(ctx, ctx->dCounts.reserve(ctx, 1));
+	int32_t count = 0;
+	std::vector<uint32_t> hk, hv;          // (with `count`, targets of copies: in front of the frame, which drains before they go)
+	HostCall hc(ctx->stream);
+	stagePlane(ctx, hc, ctx->dIn, edges, W, H, S);
+	HOSTSTEP(ctx, hc, ctx->dCounts.reserve(ctx, 1));
 	// ALL candidate lines of the frame come back as (strength, cell) pairs in emission order -- the sort and the decode kernel are skipped:
 	// the order the reference returns them in, and which equal-strength lines survive maxLines, is decided by its unstable std::sort
-	int32_t count = 0;
 	for (int attempt = 0; attempt < 2; ++attempt) {
 		ShtOpts o;
 		o.pairsOnly = true;
 		rc = planShtImpl(p, ctx->dIn, threshold, 0, nullptr, 0, ctx->dCounts, ctx->stream, o);
 		if (rc) return rc;
-		HIPCHK(ctx, hipMemcpyAsync(&count, ctx->dCounts, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+		hc.download(&count, ctx->dCounts, sizeof(int32_t), "line count");
+		if (!hc.wait()) return hostStatus(ctx, hc);
 		if (static_cast<size_t>(count) <= p->lineCap) break;
 		// more candidate lines than the device key buffer holds: grow it and redo the line stage
 		rc = ensureLineCap(p, static_cast<size_t>(count));
 		if (rc) return rc;
 	}
-	std::vector<uint32_t> hk(static_cast<size_t>(count)), hv(static_cast<size_t>(count));
+	hk.resize(static_cast<size_t>(count)); hv.resize(static_cast<size_t>(count));
 	if (count) {
-		HIPCHK(ctx, hipMemcpyAsync(hk.data(), p->keysA, hk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-		HIPCHK(ctx, hipMemcpyAsync(hv.data(), p->valsA, hv.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+		hc.download(hk.data(), p->keysA, hk.size() * sizeof(uint32_t), "line keys");
+		hc.download(hv.data(), p->valsA, hv.size() * sizeof(uint32_t), "line cells");
+		if (!hc.wait()) return hostStatus(ctx, hc);
 	}
 	std::vector<compvhip_line> all;
 	referenceLineOrder(hk, hv, (1u << p->strengthBits) - 1u, p->T, static_cast<long long>(p->W + p->H), p->thetaStep, all);
@@ -304,10 +286,10 @@ int compvhip_houghsht_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, size
 	const size_t ncopy = std::min(found, cap);
 	if (ncopy) memcpy(lines, all.data(), ncopy * sizeof(compvhip_line));
 	if (acc) {
-		HIPCHK(ctx, ctx->dAccOut.reserve(ctx, p->R * p->T));
-		HIPCHK(ctx, launch_sht_acc_transpose(p->acc, static_cast<int>(p->R), static_cast<int>(p->T), p->accPitch, ctx->dAccOut, p->T, ctx->stream));
-		HIPCHK(ctx, download(ctx, acc, accStride * sizeof(int32_t), ctx->dAccOut, p->T * sizeof(int32_t), p->T * sizeof(int32_t), p->R));
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+		HOSTSTEP(ctx, hc, ctx->dAccOut.reserve(ctx, p->R * p->T));
+		HOSTSTEP(ctx, hc, launch_sht_acc_transpose(p->acc, static_cast<int>(p->R), static_cast<int>(p->T), p->accPitch, ctx->dAccOut, p->T, ctx->stream));
+		hc.download2D(acc, accStride * sizeof(int32_t), ctx->dAccOut, p->T * sizeof(int32_t), p->T * sizeof(int32_t), p->R, "accumulator download");
+		if (!hc.wait()) return hostStatus(ctx, hc);
 	}
 	if (found > cap) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "line buffer too small");
 	return COMPVHIP_OK;
@@ -329,14 +311,14 @@ int compvhip_houghsht_segments_u8(compvhip_ctx* ctx, const uint8_t* edges, size_
 		if (lines[i].row < 0 || static_cast<size_t>(lines[i].row) >= R || lines[i].col < 0 || static_cast<size_t>(lines[i].col) >= T)
 			return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "a line's (row, col) is not a cell of the R x T accumulator");
 	if (!n) return COMPVHIP_OK;
-	return hostPlaneOp(ctx, edges, W, H, S, thetaDeg, nullptr, 0, [&](compvhip_plan* p) -> int {
-		HIPCHK(ctx, ctx->dSegs.reserve(ctx, cap));
-		HIPCHK(ctx, ctx->dSegCount.reserve(ctx, 1));
-		int rc = stageLists(ctx, lines, n, nullptr, 0);
+	return hostPlaneOp(ctx, edges, W, H, S, thetaDeg, nullptr, 0, [&](compvhip_plan* p, HostCall& hc) -> int {
+		HOSTSTEP(ctx, hc, ctx->dSegs.reserve(ctx, cap));
+		HOSTSTEP(ctx, hc, ctx->dSegCount.reserve(ctx, 1));
+		int rc = stageLists(ctx, hc, lines, n, nullptr, 0);
 		if (rc) return rc;
 		rc = segmentsImpl(p, ctx->dIn, p->S, ctx->dSegLines, ctx->dCounts, n, 0, minLength, maxGap, ctx->dSegs, cap, ctx->dSegCount, ctx->stream);
 		if (rc) return rc;
-		return takeList(ctx, ctx->dSegCount.ptr, ctx->dSegs.ptr, segs, cap, nSegs, "segment buffer too small");
+		return takeList(ctx, hc, ctx->dSegCount.ptr, ctx->dSegs.ptr, segs, cap, nSegs, "segment buffer too small");
 	});
 }
 
@@ -362,18 +344,18 @@ int compvhip_houghsht_fit_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, 
 			if (segs[j].line < 0 || static_cast<size_t>(segs[j].line) >= n) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "a segment's line is not one of the n lines");
 	const size_t nRec = segs ? nSegs : n;
 	if (!n || !nRec) return COMPVHIP_OK;
-	return hostPlaneOp(ctx, edges, W, H, S, thetaDeg, nullptr, 0, [&](compvhip_plan* p) -> int {
-		HIPCHK(ctx, ctx->dFits.reserve(ctx, cap));
-		if (refined) HIPCHK(ctx, ctx->dFitRefined.reserve(ctx, n));
-		HIPCHK(ctx, ctx->dSegCount.reserve(ctx, 1));
-		HIPCHK(ctx, ctx->dFitCount.reserve(ctx, 1));
-		int rc = stageLists(ctx, lines, n, segs, nSegs);
+	return hostPlaneOp(ctx, edges, W, H, S, thetaDeg, nullptr, 0, [&](compvhip_plan* p, HostCall& hc) -> int {
+		HOSTSTEP(ctx, hc, ctx->dFits.reserve(ctx, cap));
+		if (refined) HOSTSTEP(ctx, hc, ctx->dFitRefined.reserve(ctx, n));
+		HOSTSTEP(ctx, hc, ctx->dSegCount.reserve(ctx, 1));
+		HOSTSTEP(ctx, hc, ctx->dFitCount.reserve(ctx, 1));
+		int rc = stageLists(ctx, hc, lines, n, segs, nSegs);
 		if (rc) return rc;
 		rc = fitImpl(p, ctx->dIn, p->S, ctx->dSegLines, ctx->dCounts, n, 0, halfWidth, segs ? ctx->dSegs.ptr : nullptr, ctx->dSegCount, nSegs, cap ? ctx->dFits.ptr : nullptr, cap,
 		             ctx->dFitCount, refined ? ctx->dFitRefined.ptr : nullptr, ctx->stream);
 		if (rc) return rc;
-		if (refined) HIPCHK(ctx, hipMemcpyAsync(refined, ctx->dFitRefined, n * sizeof(compvhip_line), hipMemcpyDeviceToHost, ctx->stream));
-		return takeList(ctx, ctx->dFitCount.ptr, ctx->dFits.ptr, fits, cap, nFits, "fit buffer too small");
+		if (refined) hc.download(refined, ctx->dFitRefined, n * sizeof(compvhip_line), "refined lines");
+		return takeList(ctx, hc, ctx->dFitCount.ptr, ctx->dFits.ptr, fits, cap, nFits, "fit buffer too small");
 	});
 }
 
@@ -385,14 +367,14 @@ int compvhip_components_u8(compvhip_ctx* ctx, const uint8_t* edges, size_t W, si
 	if (W < 3 || H < 3 || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (3..32767)");
 	if ((connectivity != 4 && connectivity != 8) || minPixels < 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "connectivity must be 4 or 8, minPixels >= 1");
 	*nComps = 0;
-	return hostPlaneOp(ctx, edges, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p) -> int {
-		if (labels) HIPCHK(ctx, ctx->dCompLabels.reserve(ctx, W * H));
-		HIPCHK(ctx, ctx->dComps.reserve(ctx, cap));
-		HIPCHK(ctx, ctx->dCompCount.reserve(ctx, 1));
+	return hostPlaneOp(ctx, edges, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p, HostCall& hc) -> int {
+		if (labels) HOSTSTEP(ctx, hc, ctx->dCompLabels.reserve(ctx, W * H));
+		HOSTSTEP(ctx, hc, ctx->dComps.reserve(ctx, cap));
+		HOSTSTEP(ctx, hc, ctx->dCompCount.reserve(ctx, 1));
 		int rc = componentsImpl(p, ctx->dIn, p->S, connectivity, minPixels, labels ? ctx->dCompLabels.ptr : nullptr, W, cap ? ctx->dComps.ptr : nullptr, cap, ctx->dCompCount, ctx->stream);
 		if (rc) return rc;
-		if (labels) HIPCHK(ctx, download(ctx, labels, labelStride * sizeof(int32_t), ctx->dCompLabels, W * sizeof(int32_t), W * sizeof(int32_t), H));
-		return takeList(ctx, ctx->dCompCount.ptr, ctx->dComps.ptr, comps, cap, nComps, "component buffer too small");
+		if (labels) hc.download2D(labels, labelStride * sizeof(int32_t), ctx->dCompLabels, W * sizeof(int32_t), W * sizeof(int32_t), H, "label download");
+		return takeList(ctx, hc, ctx->dCompCount.ptr, ctx->dComps.ptr, comps, cap, nComps, "component buffer too small");
 	});
 }
 
@@ -405,13 +387,13 @@ int compvhip_fast_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H,
 	int rc = checkFast(ctx, W, H, fastType);
 	if (rc) return rc;
 	if (W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (7..32767)");
-	return hostPlaneOp(ctx, gray, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p) -> int {
-		HIPCHK(ctx, ctx->dFastCorners.reserve(ctx, cap));
-		HIPCHK(ctx, ctx->dFastCount.reserve(ctx, 1));
+	return hostPlaneOp(ctx, gray, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p, HostCall& hc) -> int {
+		HOSTSTEP(ctx, hc, ctx->dFastCorners.reserve(ctx, cap));
+		HOSTSTEP(ctx, hc, ctx->dFastCount.reserve(ctx, 1));
 		int rc = compvhip_plan_fast(p, ctx->dIn, threshold, fastType, nonmax, maxFeatures, scores ? ctx->dOut.ptr : nullptr, cap ? ctx->dFastCorners.ptr : nullptr, cap, ctx->dFastCount, ctx->stream);
 		if (rc) return rc;
-		if (scores) HIPCHK(ctx, download(ctx, scores, So, ctx->dOut, p->S, W, H));
-		return takeList(ctx, ctx->dFastCount.ptr, ctx->dFastCorners.ptr, corners, cap, n, "corner buffer too small");
+		if (scores) hc.download2D(scores, So, ctx->dOut, p->S, W, H, "score download");
+		return takeList(ctx, hc, ctx->dFastCount.ptr, ctx->dFastCorners.ptr, corners, cap, n, "corner buffer too small");
 	});
 }
 
@@ -426,24 +408,22 @@ int compvhip_orb_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, 
 	if (W > 32767 || H > 32767 || n > static_cast<size_t>(INT32_MAX)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (37..32767) or n beyond 2^31");
 	if (descStride < 32 || (descStride & 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "descStride below 32 or no multiple of 4");
 	if (!n) return COMPVHIP_OK;
-	return hostPlaneOp(ctx, gray, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p) -> int {
-		HIPCHK(ctx, ctx->dFastCorners.reserve(ctx, n));
-		HIPCHK(ctx, ctx->dFastCount.reserve(ctx, 1));
-		HIPCHK(ctx, ctx->dOrbKeys.reserve(ctx, n));
-		HIPCHK(ctx, ctx->dOrbCount.reserve(ctx, 1));
-		HIPCHK(ctx, ctx->dOrbDesc.reserve(ctx, n * 32));
+	return hostPlaneOp(ctx, gray, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p, HostCall& hc) -> int {
+		HOSTSTEP(ctx, hc, ctx->dOrbKeys.reserve(ctx, n));
+		HOSTSTEP(ctx, hc, ctx->dOrbCount.reserve(ctx, 1));
+		HOSTSTEP(ctx, hc, ctx->dOrbDesc.reserve(ctx, n * 32));
 		const int32_t count = static_cast<int32_t>(n);
-		HIPCHK(ctx, hipMemcpyAsync(ctx->dFastCorners, corners, n * sizeof(compvhip_corner), hipMemcpyHostToDevice, ctx->stream));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->dFastCount, &count, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the count lives on this stack frame; pageable copies may still be staged
+		stageArray(ctx, hc, ctx->dFastCorners, corners, n);
+		stageArray(ctx, hc, ctx->dFastCount, &count, 1);
+		if (!hc.wait()) return hostStatus(ctx, hc);   // the count lives on this stack frame; pageable copies may still be staged
 		int rc = compvhip_plan_orb_keypoints(p, ctx->dIn, ctx->dFastCorners, n, ctx->dFastCount, level, scale, ctx->dOrbKeys, n, ctx->dOrbCount, nullptr, ctx->stream);
 		if (rc) return rc;
 		rc = compvhip_plan_orb_describe(p, ctx->dIn, ctx->dOrbKeys, n, ctx->dOrbCount, scale, 1, ctx->dOrbDesc, 32, ctx->stream);
 		if (rc) return rc;
-		rc = takeList(ctx, ctx->dOrbCount.ptr, ctx->dOrbKeys.ptr, keypoints, n, kept, "keypoint buffer too small");
+		rc = takeList(ctx, hc, ctx->dOrbCount.ptr, ctx->dOrbKeys.ptr, keypoints, n, kept, "keypoint buffer too small");
 		if (rc || !*kept) return rc;
-		HIPCHK(ctx, hipMemcpy2D(desc, descStride, ctx->dOrbDesc, 32, 32, *kept, hipMemcpyDeviceToHost));
-		return COMPVHIP_OK;
+		hc.downloadNow2D(desc, descStride, ctx->dOrbDesc, 32, 32, *kept, "descriptor download");
+		return hostStatus(ctx, hc);
 	});
 }
 
@@ -458,13 +438,12 @@ int compvhip_hog_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, 
 	const size_t descLen = static_cast<size_t>(a.blocksX) * a.blocksY * a.count;
 	*n = descLen;
 	if (cap < descLen) return fail(ctx, COMPVHIP_E_OUT_OF_BOUND, "descriptor buffer too small");
-	return hostPlaneOp(ctx, gray, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p) -> int {
-		HIPCHK(ctx, ctx->dHogDesc.reserve(ctx, descLen));
-		int rc = compvhip_plan_hog(p, ctx->dIn, opts, nullptr, ctx->dHogDesc, descLen, ctx->stream);
+	return hostPlaneOp(ctx, gray, W, H, S, kAnyTheta, nullptr, 0, [&](compvhip_plan* p, HostCall& hc) -> int {
+		HOSTSTEP(ctx, hc, ctx->dHogDesc.reserve(ctx, descLen));
+		const int rc = compvhip_plan_hog(p, ctx->dIn, opts, nullptr, ctx->dHogDesc, descLen, ctx->stream);
 		if (rc) return rc;
-		HIPCHK(ctx, hipMemcpyAsync(desc, ctx->dHogDesc, descLen * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-		return COMPVHIP_OK;
+		hc.download(desc, ctx->dHogDesc, descLen * sizeof(float), "descriptor download");
+		return hostWait(ctx, hc);
 	});
 }
 
@@ -474,42 +453,35 @@ int compvhip_scale_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, 
 	if (!in || !out || S < W || Sout < Wout) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image or stride < width");
 	if (!W || !H || !Wout || !Hout || W > 32767 || H > 32767 || Wout > 32767 || Hout > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (1..32767)");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t Sd = alignUp(W, 64), Sod = alignUp(Wout, 64);          // no plan: a scale has no minimum size
-	HIPCHK(ctx, ctx->dIn.reserve(ctx, Sd * H));
-	HIPCHK(ctx, ctx->dOut.reserve(ctx, Sod * Hout));
-	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
-	int rc = scaleImpl(ctx, ctx->dIn, W, H, Sd, 1, ctx->dOut, Wout, Hout, Sod, ctx->stream);
-	if (!rc) HIPCHK(ctx, download(ctx, out, Sout, ctx->dOut, Sod, Wout, Hout));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	return rc;
+	HostCall hc(ctx->stream);
+	const size_t Sd = stagePlane(ctx, hc, ctx->dIn, in, W, H, S), Sod = alignUp(Wout, 64);          // no plan: a scale has no minimum size
+	HOSTSTEP(ctx, hc, ctx->dOut.reserve(ctx, Sod * Hout));
+	const int rc = scaleImpl(ctx, ctx->dIn, W, H, Sd, 1, ctx->dOut, Wout, Hout, Sod, ctx->stream);
+	if (rc) return rc;
+	hc.download2D(out, Sout, ctx->dOut, Sod, Wout, Hout);
+	return hostWait(ctx, hc);
 }
 
 // remap and inverse warp of one host plane: the staging of both (no plan: neither has a minimum size).  `coords` enqueues the coordinate source into `a`.
-template <typename Coords>   // int coords(RemapArgs*)
+template <typename Coords>   // int coords(RemapArgs*, HostCall&)
 static int hostRemap(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, int interp, const compvhip_roi* roi, uint8_t defaultValue, void* out, size_t Wout,
                      size_t Hout, size_t Sout, int source, const Coords& coords)
 {
 	if (!in || !out || S < W || Sout < Wout) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image or stride < width");
 	if (!W || !H || !Wout || !Hout || W > 32767 || H > 32767 || Wout > 32767 || Hout > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (1..32767)");
-	if (interp != COMPVHIP_INTERP_NEAREST && interp != COMPVHIP_INTERP_BILINEAR && interp != COMPVHIP_INTERP_BILINEAR_FLOAT32 && interp != COMPVHIP_INTERP_BICUBIC &&
-	    interp != COMPVHIP_INTERP_BICUBIC_FLOAT32)
-		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "unknown interpolation");
+	const size_t elem = interpElemBytes(interp), Sod = alignUp(Wout, 64);
+	if (!elem) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "unknown interpolation");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t elem = interp == COMPVHIP_INTERP_BILINEAR_FLOAT32 || interp == COMPVHIP_INTERP_BICUBIC_FLOAT32 ? sizeof(float) : 1;
-	const size_t Sd = alignUp(W, 64), Sod = alignUp(Wout, 64);
-	HIPCHK(ctx, ctx->dIn.reserve(ctx, Sd * H));
-	HIPCHK(ctx, ctx->dOut.reserve(ctx, Sod * Hout * elem));
-	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
+	HostCall hc(ctx->stream);
+	const size_t Sd = stagePlane(ctx, hc, ctx->dIn, in, W, H, S);
+	HOSTSTEP(ctx, hc, ctx->dOut.reserve(ctx, Sod * Hout * elem));
 	RemapArgs a;
 	int rc = remapPrepare(ctx, ctx->dIn, W, H, Sd, 1, interp, roi, ctx->dOut.ptr, Wout, Hout, Sod, defaultValue, &a);
-	if (!rc) rc = coords(&a);
-	if (!rc) {
-		const hipError_t e = launch_remap(a, source, interp, false, ctx->stream);
-		if (e != hipSuccess) rc = fail(ctx, COMPVHIP_E_HIP, "launch_remap", e);
-	}
-	if (!rc) HIPCHK(ctx, download(ctx, out, Sout * elem, ctx->dOut, Sod * elem, Wout * elem, Hout));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // also after a failure: no copy from the caller's memory stays in flight
-	return rc;
+	if (!rc) rc = coords(&a, hc);
+	if (rc) return rc;
+	HOSTSTEP(ctx, hc, launch_remap(a, source, interp, false, ctx->stream));
+	hc.download2D(out, Sout * elem, ctx->dOut, Sod * elem, Wout * elem, Hout);
+	return hostWait(ctx, hc);
 }
 
 int compvhip_remap_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const float* mapX, const float* mapY, int interp, const compvhip_roi* roi,
@@ -517,13 +489,13 @@ int compvhip_remap_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, 
 {
 	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
 	if (!mapX || !mapY) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null map");
-	return hostRemap(ctx, in, W, H, S, interp, roi, defaultValue, out, Wout, Hout, Sout, kRemapMap, [&](RemapArgs* a) -> int {
+	return hostRemap(ctx, in, W, H, S, interp, roi, defaultValue, out, Wout, Hout, Sout, kRemapMap, [&](RemapArgs* a, HostCall& hc) -> int {
 		const size_t n = Wout * Hout;
-		HIPCHK(ctx, ctx->dMap.reserve(ctx, 2 * n));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->dMap, mapX, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->dMap + n, mapY, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+		HOSTSTEP(ctx, hc, ctx->dMap.reserve(ctx, 2 * n));
+		hc.upload(ctx->dMap, mapX, n * sizeof(float), "map upload");
+		hc.upload(ctx->dMap + n, mapY, n * sizeof(float), "map upload");
 		a->mapX = ctx->dMap; a->mapY = ctx->dMap + n; a->coordFrameStride = n;
-		return COMPVHIP_OK;
+		return hostStatus(ctx, hc);
 	});
 }
 
@@ -533,7 +505,7 @@ int compvhip_warp_inverse_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, siz
 	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
 	if (!M || (rows != 2 && rows != 3)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "M must be a 2 x 3 or 3 x 3 float32 matrix");
 	return hostRemap(ctx, in, W, H, S, interp, nullptr, defaultValue, out, Wout, Hout, Sout, rows == 3 ? kRemapWarp3 : kRemapWarp2,
-	                 [&](RemapArgs* a) -> int { return warpUpload(ctx, &ctx->warp, M, rows, 1, a, ctx->stream); });
+	                 [&](RemapArgs* a, HostCall&) -> int { return warpUpload(ctx, &ctx->warp, M, rows, 1, a, ctx->stream); });
 }
 
 // the fused undistortion of one host plane (include/compv_hip.h, "lens undistortion"): the same staging, the camera's record through the context's ring
@@ -546,7 +518,7 @@ int compvhip_undistort_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t
 	float probe[14];
 	if (compvhip_undistort_coeffs_f32(K, d, nd, probe)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "undistort: fx * fy == 0, the camera matrix is singular");
 	return hostRemap(ctx, in, W, H, S, interp, roi, defaultValue, out, Wout, Hout, Sout, kRemapUndist,
-	                 [&](RemapArgs* a) -> int { return undistCoords(ctx, &ctx->warp, K, d, nd, 1, x0, y0, a, ctx->stream); });
+	                 [&](RemapArgs* a, HostCall&) -> int { return undistCoords(ctx, &ctx->warp, K, d, nd, 1, x0, y0, a, ctx->stream); });
 }
 
 int compvhip_orb_pyramid_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, size_t H, size_t S, const compvhip_orbpyr_opts* opts, compvhip_keypoint* keypoints,
@@ -566,26 +538,18 @@ int compvhip_orb_pyramid_u8(compvhip_ctx* ctx, const uint8_t* gray, size_t W, si
 	compvhip_orbpyr* y = nullptr;
 	int rc = compvhip_orbpyr_create(ctx, W, H, Sd, 1, opts, cornerCap, &y);
 	if (rc) return rc;
-	do {
-		hipError_t e = ctx->dIn.reserve(ctx, Sd * H);
-		if (e == hipSuccess) e = ctx->dOrbKeys.reserve(ctx, cap);
-		if (e == hipSuccess) e = ctx->dOrbCount.reserve(ctx, 1);
-		if (e == hipSuccess) e = ctx->dOrbDesc.reserve(ctx, cap * 32);
-		if (e == hipSuccess) e = upload(ctx, ctx->dIn, Sd, gray, S, W, H);
-		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "pyramid staging", e); break; }
-		rc = compvhip_orbpyr_detect(y, ctx->dIn, cap ? ctx->dOrbKeys.ptr : nullptr, cap, ctx->dOrbCount, nullptr, nullptr, ctx->stream);
-		if (rc) break;
-		if (cap) rc = compvhip_orbpyr_describe(y, ctx->dIn, 1, ctx->dOrbKeys, cap, ctx->dOrbCount, ctx->dOrbDesc, 32, ctx->stream);
-		if (rc) break;
-		rc = takeList(ctx, ctx->dOrbCount.ptr, ctx->dOrbKeys.ptr, keypoints, cap, n, "keypoint buffer too small");
-		const size_t rows = std::min(*n, cap);
-		if ((rc == COMPVHIP_OK || rc == COMPVHIP_E_OUT_OF_BOUND) && rows && hipMemcpy2D(desc, descStride, ctx->dOrbDesc, 32, 32, rows, hipMemcpyDeviceToHost) != hipSuccess)
-			rc = fail(ctx, COMPVHIP_E_HIP, "descriptor download");
-	} while (0);
-	(void)hipStreamSynchronize(ctx->stream);
-	const std::string err = ctx->err;
-	compvhip_orbpyr_destroy(y);
-	ctx->err = err;
+	const TempHandle<compvhip_orbpyr> pyramid{ ctx, y, compvhip_orbpyr_destroy };
+	HostCall hc(ctx->stream);
+	stagePlane(ctx, hc, ctx->dIn, gray, W, H, S);
+	HOSTSTEP(ctx, hc, ctx->dOrbKeys.reserve(ctx, cap));
+	HOSTSTEP(ctx, hc, ctx->dOrbCount.reserve(ctx, 1));
+	HOSTSTEP(ctx, hc, ctx->dOrbDesc.reserve(ctx, cap * 32));
+	rc = compvhip_orbpyr_detect(y, ctx->dIn, cap ? ctx->dOrbKeys.ptr : nullptr, cap, ctx->dOrbCount, nullptr, nullptr, ctx->stream);
+	if (!rc && cap) rc = compvhip_orbpyr_describe(y, ctx->dIn, 1, ctx->dOrbKeys, cap, ctx->dOrbCount, ctx->dOrbDesc, 32, ctx->stream);
+	if (rc) return rc;
+	rc = takeList(ctx, hc, ctx->dOrbCount.ptr, ctx->dOrbKeys.ptr, keypoints, cap, n, "keypoint buffer too small");
+	const size_t rows = std::min(*n, cap);
+	if ((rc == COMPVHIP_OK || rc == COMPVHIP_E_OUT_OF_BOUND) && rows && !hc.downloadNow2D(desc, descStride, ctx->dOrbDesc, 32, 32, rows, "descriptor download")) rc = hostStatus(ctx, hc);
 	return rc;
 }
 
@@ -594,7 +558,7 @@ int compvhip_threshold_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t
 	int rc = checkImage(ctx, in, W, H, S, out, So);
 	if (rc) return rc;
 	if (!(threshold >= 0.0)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "threshold < 0"); // compv_image_threshold.cxx:120
-	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p) { return compvhip_plan_threshold(p, ctx->dIn, threshold, nullptr, ctx->dOut, ctx->stream); });
+	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p, HostCall&) { return compvhip_plan_threshold(p, ctx->dIn, threshold, nullptr, ctx->dOut, ctx->stream); });
 }
 
 int compvhip_threshold_adaptive_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, size_t blockSize, double delta, double maxVal, int invert,
@@ -605,7 +569,7 @@ int compvhip_threshold_adaptive_u8(compvhip_ctx* ctx, const uint8_t* in, size_t 
 	rc = checkAdaptive(ctx, W, H, blockSize, delta, maxVal);
 	if (rc) return rc;
 	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So,
-	                   [&](compvhip_plan* p) { return compvhip_plan_threshold_adaptive(p, ctx->dIn, blockSize, delta, maxVal, invert, ctx->dOut, ctx->stream); });
+	                   [&](compvhip_plan* p, HostCall&) { return compvhip_plan_threshold_adaptive(p, ctx->dIn, blockSize, delta, maxVal, invert, ctx->dOut, ctx->stream); });
 }
 
 int compvhip_morph_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const uint8_t* strel, size_t sw, size_t sh, int op, int border, uint8_t* out,
@@ -619,7 +583,7 @@ int compvhip_morph_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, 
 	// the host planes overlap when their byte ranges do (compv_math_morph.cxx:140-145: the reference reallocates; here the caller is told)
 	const uint8_t* inEnd = in + (H - 1) * S + W; const uint8_t* outEnd = out + (H - 1) * So + W;
 	if (in < outEnd && out < inEnd) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "input and output must not overlap");
-	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p) { return compvhip_plan_morph(p, ctx->dIn, strel, sw, sh, op, border, ctx->dOut, ctx->stream); });
+	return hostPlaneOp(ctx, in, W, H, S, kAnyTheta, out, So, [&](compvhip_plan* p, HostCall&) { return compvhip_plan_morph(p, ctx->dIn, strel, sw, sh, op, border, ctx->dOut, ctx->stream); });
 }
 
 int compvhip_match_hamming_u8(compvhip_ctx* ctx, const uint8_t* query, size_t Q, size_t queryStride, const uint8_t* train, size_t T, size_t trainStride, size_t cols,
@@ -634,44 +598,37 @@ int compvhip_match_hamming_u8(compvhip_ctx* ctx, const uint8_t* query, size_t Q,
 	compvhip_matcher* m = nullptr;
 	int rc = compvhip_matcher_create(ctx, S, Q, T, 1, knn, &m);
 	if (rc) return rc;
-	DevBuf<uint8_t> dDesc; DevBuf<compvhip_match> dMatches;   // freed on the way out, behind the drain of the stream below
+	const TempHandle<compvhip_matcher> matcher{ ctx, m, compvhip_matcher_destroy };
+	DevBuf<uint8_t> dDesc; DevBuf<compvhip_match> dMatches;
 	const size_t nRows = std::min<size_t>(static_cast<size_t>(knn), T);
-	do {
-		if (dDesc.reserve(ctx, (Q + T) * S) != hipSuccess || dMatches.reserve(ctx, static_cast<size_t>(knn) * Q) != hipSuccess) { rc = fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "match staging"); break; }
-		hipError_t e = hipMemsetAsync(dDesc, 0, (Q + T) * S, ctx->stream);          // the zero bytes that pad a row to a dword multiple
-		if (e == hipSuccess) e = hipMemcpy2DAsync(dDesc, S, query, queryStride, cols, Q, hipMemcpyHostToDevice, ctx->stream);
-		if (e == hipSuccess) e = hipMemcpy2DAsync(dDesc + Q * S, S, train, trainStride, cols, T, hipMemcpyHostToDevice, ctx->stream);
-		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "descriptor upload", e); break; }
-		// not compvhip_matcher_knn: the reference's order among equal distances is not the (distance, index) order of the device call
-		const MatchSliceArgs a = matchForward(m, dDesc, S, nullptr, dDesc + Q * S, S, nullptr, 0, dMatches);
-		e = launch_match_reference(a, 1, ctx->stream);
-		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "launch_match_reference", e); break; }
-		e = hipMemcpy2DAsync(matches, matchStride * sizeof(compvhip_match), dMatches, Q * sizeof(compvhip_match), Q * sizeof(compvhip_match), nRows, hipMemcpyDeviceToHost, ctx->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "match download", e); break; }
-		*rows = nRows;
-	} while (0);
-	(void)hipStreamSynchronize(ctx->stream);
-	compvhip_matcher_destroy(m);
-	return rc;
+	HostCall hc(ctx->stream);
+	HOSTSTEP(ctx, hc, dDesc.reserve(ctx, (Q + T) * S));
+	HOSTSTEP(ctx, hc, dMatches.reserve(ctx, static_cast<size_t>(knn) * Q));
+	HOSTSTEP(ctx, hc, hipMemsetAsync(dDesc, 0, (Q + T) * S, ctx->stream));          // the zero bytes that pad a row to a dword multiple
+	hc.upload2D(dDesc, S, query, queryStride, cols, Q, "descriptor upload");
+	hc.upload2D(dDesc + Q * S, S, train, trainStride, cols, T, "descriptor upload");
+	// not compvhip_matcher_knn: the reference's order among equal distances is not the (distance, index) order of the device call
+	const MatchSliceArgs a = matchForward(m, dDesc, S, nullptr, dDesc + Q * S, S, nullptr, 0, dMatches);
+	HOSTSTEP(ctx, hc, launch_match_reference(a, 1, ctx->stream));
+	hc.download2D(matches, matchStride * sizeof(compvhip_match), dMatches, Q * sizeof(compvhip_match), Q * sizeof(compvhip_match), nRows, "match download");
+	if (!hc.wait()) return hostStatus(ctx, hc);
+	*rows = nRows;
+	return COMPVHIP_OK;
 }
 
 // ---- image statistics of one host frame (no plan: a plan has a minimum size, these calls have none) ------------------------------------------------------
 namespace {
-// the frame into dIn (rows of alignUp(W, 64) bytes), `run` on it, the stream waited for -- also after a failure: no copy from or to the caller's memory stays in flight
-template <typename Run>   // int run(const StatsFrames&)
+// the frame into dIn (rows of alignUp(W, 64) bytes), `run` on it (its copies through the call's frame), the stream waited for
+template <typename Run>   // int run(const StatsFrames&, HostCall&): begins with a HOSTSTEP, so it does nothing behind a failed upload
 int hostStats(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t H, size_t S, const Run& run)
 {
 	if (!in || S < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "null image or stride < width");
 	if (!W || !H || W > 32767 || H > 32767) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "image size out of range (1..32767)");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t Sd = alignUp(W, 64);
-	HIPCHK(ctx, ctx->dIn.reserve(ctx, Sd * H));
-	HIPCHK(ctx, upload(ctx, ctx->dIn, Sd, in, S, W, H));
-	const int rc = run(StatsFrames{ ctx, nullptr, &ctx->stats, ctx->dIn, W, H, Sd, 1, ctx->stream });
-	const hipError_t e = hipStreamSynchronize(ctx->stream);
-	if (!rc && e != hipSuccess) return fail(ctx, COMPVHIP_E_HIP, "hipStreamSynchronize", e);
-	return rc;
+	HostCall hc(ctx->stream);
+	const size_t Sd = stagePlane(ctx, hc, ctx->dIn, in, W, H, S);
+	const int rc = run(StatsFrames{ ctx, nullptr, &ctx->stats, ctx->dIn, W, H, Sd, 1, ctx->stream }, hc);
+	return rc ? rc : hostWait(ctx, hc);
 }
 } // namespace
 
@@ -682,15 +639,15 @@ int compvhip_integral_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t 
 	if (rc) return rc;
 	if (!sum && !sumsq) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: both outputs are NULL");
 	if (sumStride < W + 1) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "integral: sumStride below W + 1");
-	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g) -> int {
+	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g, HostCall& hc) -> int {
 		const size_t cols = W + 1, plane = (H + 1) * cols;
-		HIPCHK(ctx, ctx->dStatsF64.reserve(ctx, 2 * plane));
+		HOSTSTEP(ctx, hc, ctx->dStatsF64.reserve(ctx, 2 * plane));
 		double* const dSum = sum ? ctx->dStatsF64.ptr : nullptr;
 		double* const dSq = sumsq ? ctx->dStatsF64.ptr + plane : nullptr;
 		const int rc = integralImpl(g, dSum, dSq, cols);
 		if (rc) return rc;
-		if (sum) HIPCHK(ctx, hipMemcpy2DAsync(sum, sumStride * sizeof(double), dSum, cols * sizeof(double), cols * sizeof(double), H + 1, hipMemcpyDeviceToHost, ctx->stream));
-		if (sumsq) HIPCHK(ctx, hipMemcpy2DAsync(sumsq, sumStride * sizeof(double), dSq, cols * sizeof(double), cols * sizeof(double), H + 1, hipMemcpyDeviceToHost, ctx->stream));
+		if (sum) hc.download2D(sum, sumStride * sizeof(double), dSum, cols * sizeof(double), cols * sizeof(double), H + 1);
+		if (sumsq) hc.download2D(sumsq, sumStride * sizeof(double), dSq, cols * sizeof(double), cols * sizeof(double), H + 1);
 		return COMPVHIP_OK;
 	});
 }
@@ -699,11 +656,11 @@ int compvhip_histogram_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t
 {
 	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
 	if (!hist) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "histogram: null output");
-	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g) -> int {
-		HIPCHK(ctx, ctx->dStatsU32.reserve(ctx, 256));
+	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g, HostCall& hc) -> int {
+		HOSTSTEP(ctx, hc, ctx->dStatsU32.reserve(ctx, 256));
 		const int rc = histogramImpl(g, ctx->dStatsU32);
 		if (rc) return rc;
-		HIPCHK(ctx, hipMemcpyAsync(hist, ctx->dStatsU32, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		hc.download(hist, ctx->dStatsU32, 256 * sizeof(uint32_t));
 		return COMPVHIP_OK;
 	});
 }
@@ -712,15 +669,15 @@ int compvhip_equalize_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size_t 
 {
 	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
 	if (!out || So < W) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "equalize: null output frame or stride < width");
-	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g) -> int {
-		HIPCHK(ctx, ctx->dStatsU32.reserve(ctx, 256 + 64));          // the caller's histogram, the table behind it
-		HIPCHK(ctx, ctx->dOut.reserve(ctx, g.S * H));
+	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g, HostCall& hc) -> int {
+		HOSTSTEP(ctx, hc, ctx->dStatsU32.reserve(ctx, 256 + 64));          // the caller's histogram, the table behind it
+		HOSTSTEP(ctx, hc, ctx->dOut.reserve(ctx, g.S * H));
 		uint8_t* const dLut = reinterpret_cast<uint8_t*>(ctx->dStatsU32.ptr + 256);
-		if (hist) HIPCHK(ctx, hipMemcpyAsync(ctx->dStatsU32, hist, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+		if (hist && !hc.upload(ctx->dStatsU32, hist, 256 * sizeof(uint32_t))) return hostStatus(ctx, hc);
 		const int rc = equalizeImpl(g, hist ? ctx->dStatsU32.ptr : nullptr, scale, ctx->dOut, dLut);
 		if (rc) return rc;
-		HIPCHK(ctx, download(ctx, out, So, ctx->dOut, g.S, W, H));
-		if (lut) HIPCHK(ctx, hipMemcpyAsync(lut, dLut, 256, hipMemcpyDeviceToHost, ctx->stream));
+		hc.download2D(out, So, ctx->dOut, g.S, W, H);
+		if (lut) hc.download(lut, dLut, 256);
 		return COMPVHIP_OK;
 	});
 }
@@ -729,14 +686,14 @@ int compvhip_projections_u8(compvhip_ctx* ctx, const uint8_t* in, size_t W, size
 {
 	if (!ctx) return COMPVHIP_E_INVALID_PARAMETER;
 	if (!projX && !projY) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "projections: both outputs are NULL");
-	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g) -> int {
-		HIPCHK(ctx, ctx->dStatsU32.reserve(ctx, W + H));
+	return hostStats(ctx, in, W, H, S, [&](const StatsFrames& g, HostCall& hc) -> int {
+		HOSTSTEP(ctx, hc, ctx->dStatsU32.reserve(ctx, W + H));
 		int32_t* const dX = projX ? reinterpret_cast<int32_t*>(ctx->dStatsU32.ptr) : nullptr;
 		int32_t* const dY = projY ? reinterpret_cast<int32_t*>(ctx->dStatsU32.ptr) + W : nullptr;
 		const int rc = projectionsImpl(g, dX, dY);
 		if (rc) return rc;
-		if (projX) HIPCHK(ctx, hipMemcpyAsync(projX, dX, W * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-		if (projY) HIPCHK(ctx, hipMemcpyAsync(projY, dY, H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+		if (projX) hc.download(projX, dX, W * sizeof(int32_t));
+		if (projY) hc.download(projY, dY, H * sizeof(int32_t));
 		return COMPVHIP_OK;
 	});
 }
@@ -753,17 +710,23 @@ int compvhip_convert_u8(compvhip_ctx* ctx, size_t W, size_t H, const compvhip_im
 	size_t offIn[3] = {}, offOut[3] = {}, bytesIn = 0, bytesOut = 0;
 	for (int p = 0; p < g.planesIn; ++p) { d.inRow[p] = alignUp(g.minIn[p], 64); offIn[p] = bytesIn; bytesIn += alignUp(d.inRow[p] * g.rowsIn[p], 256); }
 	for (int p = 0; p < g.planesOut; ++p) { d.outRow[p] = alignUp(g.minOut[p], 64); offOut[p] = bytesOut; bytesOut += alignUp(d.outRow[p] * g.rowsOut[p], 256); }
-	HIPCHK(ctx, ctx->dPacked.reserve(ctx, bytesIn));
-	HIPCHK(ctx, ctx->dOut.reserve(ctx, bytesOut));
+	HostCall hc(ctx->stream);
+	HOSTSTEP(ctx, hc, ctx->dPacked.reserve(ctx, bytesIn));
+	HOSTSTEP(ctx, hc, ctx->dOut.reserve(ctx, bytesOut));
 	for (int p = 0; p < g.planesIn; ++p) {
 		d.in[p] = ctx->dPacked + offIn[p];
-		HIPCHK(ctx, upload(ctx, ctx->dPacked + offIn[p], d.inRow[p], h.in[p], h.inRow[p], g.minIn[p], g.rowsIn[p]));
+		hc.upload2D(ctx->dPacked + offIn[p], d.inRow[p], h.in[p], h.inRow[p], g.minIn[p], g.rowsIn[p]);
 	}
 	for (int p = 0; p < g.planesOut; ++p) d.out[p] = ctx->dOut + offOut[p];
-	hipError_t e = launch_convert(d, in->pixfmt, out->pixfmt, 1, ctx->stream);
-	for (int p = 0; p < g.planesOut && e == hipSuccess; ++p) e = download(ctx, h.out[p], h.outRow[p], d.out[p], d.outRow[p], g.minOut[p], g.rowsOut[p]);
-	const hipError_t es = hipStreamSynchronize(ctx->stream);   // also on failure: no copy from the caller's planes stays in flight
-	HIPCHK(ctx, e);
-	HIPCHK(ctx, es);
-	return COMPVHIP_OK;
+	HOSTSTEP(ctx, hc, launch_convert(d, in->pixfmt, out->pixfmt, 1, ctx->stream));
+	for (int p = 0; p < g.planesOut; ++p) hc.download2D(h.out[p], h.outRow[p], d.out[p], d.outRow[p], g.minOut[p], g.rowsOut[p]);
+	return hostWait(ctx, hc);
+}
+
+size_t compvhip_api::stagePlane(compvhip_ctx* ctx, HostCall& hc, DevBuf<uint8_t>& buf, const void* in, size_t W, size_t H, size_t S, size_t bpp)
+{
+	const size_t Sd = alignUp(W, 64);
+	if (hc.ok()) hc.step(buf.reserve(ctx, Sd * H * bpp), "plane staging");
+	hc.upload2D(buf, Sd * bpp, in, S * bpp, W * bpp, H, "plane upload");
+	return Sd;
 }

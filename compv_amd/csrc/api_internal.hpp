@@ -6,6 +6,7 @@
 #include "kht.hpp"
 #include "kht_group.hpp"
 #include "device_memory.hpp"
+#include "host_call.hpp"
 #include "frame_slices.hpp"
 #include "convert_math.hpp"
 #include "step_policy.hpp"
@@ -328,6 +329,17 @@ inline int refuseBeyondLaunchLimit(compvhip_ctx* ctx, size_t frames, const char*
 
 #define HIPCHK(ctx, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail((ctx), COMPVHIP_E_HIP, #call, e__); } while (0)
 
+// what a host-memory call (host_call.hpp) returns for its frame: COMPVHIP_OK, or the first failure with the step's name; hostWait: after a wait()
+inline int hostStatus(compvhip_ctx* ctx, const HostCall& hc) { return hc.ok() ? COMPVHIP_OK : fail(ctx, hc.error() == hipErrorOutOfMemory ? COMPVHIP_E_OUT_OF_MEMORY : COMPVHIP_E_HIP, hc.what(), hc.error()); }
+inline int hostWait(compvhip_ctx* ctx, HostCall& hc) { hc.wait(); return hostStatus(ctx, hc); }
+// `n` elements of the caller's into `buf`, reserved for them, through the call's frame
+template <typename T, typename Owner>
+void stageArray(Owner* owner, HostCall& hc, DevBuf<T>& buf, const T* host, size_t n) { if (hc.ok()) hc.step(buf.reserve(owner, n), "staging"); hc.upload(buf.ptr, host, n * sizeof(T)); }
+// a temporary handle of such a call: destroyed when the scope ends -- declared in front of the frame, so behind its drain -- and the call's message survives that
+template <typename H> struct TempHandle { compvhip_ctx* ctx; H* h; void (*destroy)(H*); ~TempHandle() { if (h) { const std::string err = ctx->err; destroy(h); ctx->err = err; } } };
+// HIPCHK for a reserve or a launch of such a call: not made behind a failed copy, and the frame drains on the way out
+#define HOSTSTEP(ctx, hc, call) do { if (!(hc).ok() || !(hc).step((call), #call)) return hostStatus((ctx), (hc)); } while (0)
+
 inline size_t alignUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // timing mode 1 = every kernel; 2 = only the two kernels bench.py prices against the roofline (an event pair costs a few
@@ -488,6 +500,13 @@ int projectionsImpl(const StatsFrames& g, int32_t* d_projX, int32_t* d_projY);
 struct ConvertGeometry { int planesIn, planesOut; size_t minIn[3], rowsIn[3], minOut[3], rowsOut[3]; };
 int convertCheck(compvhip_ctx* ctx, size_t W, size_t H, size_t frames, const compvhip_image* in, const compvhip_image* out, ConvertArgs* a, ConvertGeometry* g);
 int scaleImpl(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, uint8_t* d_out, size_t Wout, size_t Hout, size_t Sout, hipStream_t st);
+// api_host.cpp: the caller's validated plane (rows S pixels of bpp bytes apart) into `buf` at rows of alignUp(W, 64) pixels, through the frame; returns that row length
+size_t stagePlane(compvhip_ctx* ctx, HostCall& hc, DevBuf<uint8_t>& buf, const void* in, size_t W, size_t H, size_t S, size_t bpp = 1);
+// the bytes of a destination element of remap, inverse warp and undistortion; 0: not one of their interpolations
+inline size_t interpElemBytes(int i)
+{
+	return i == COMPVHIP_INTERP_NEAREST || i == COMPVHIP_INTERP_BILINEAR || i == COMPVHIP_INTERP_BICUBIC ? 1 : i == COMPVHIP_INTERP_BILINEAR_FLOAT32 || i == COMPVHIP_INTERP_BICUBIC_FLOAT32 ? sizeof(float) : 0;
+}
 // remap and inverse warp: validates everything but the coordinate source and fills `a` (roi == nullptr: the whole frame)
 int remapPrepare(compvhip_ctx* ctx, const uint8_t* d_in, size_t W, size_t H, size_t S, size_t frames, int interp, const compvhip_roi* roi, void* d_out, size_t Wout,
                  size_t Hout, size_t Sout, uint8_t defaultValue, RemapArgs* a);

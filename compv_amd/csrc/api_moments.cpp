@@ -113,24 +113,19 @@ int compvhip_moments_host(compvhip_ctx* ctx, const compvhip_moments_desc* desc, 
 	if (rc) return rc;
 	if (!in || !raw) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "moments: null image or record");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const size_t Sd = alignUp(W, 64);
 	static_assert(sizeof(compvhip_moments) == 48 && sizeof(compvhip_moments_shape) == 72, "the records of include/compv_hip.h");
-	HIPCHK(ctx, ctx->dIn.reserve(ctx, Sd * H));
-	HIPCHK(ctx, ctx->dMoments.reserve(ctx, (sizeof(compvhip_moments) + sizeof(compvhip_moments_shape)) / 8));
+	// staging of the call's own (in front of the frame, which drains before it goes): the caller's records are written only by a call that succeeded as a whole
+	compvhip_moments r; compvhip_moments_shape s;
+	HostCall hc(ctx->stream);
+	const size_t Sd = stagePlane(ctx, hc, ctx->dIn, in, W, H, S);
+	HOSTSTEP(ctx, hc, ctx->dMoments.reserve(ctx, (sizeof(compvhip_moments) + sizeof(compvhip_moments_shape)) / 8));
 	compvhip_moments* dRaw = reinterpret_cast<compvhip_moments*>(ctx->dMoments.ptr);
 	compvhip_moments_shape* dShape = shape ? reinterpret_cast<compvhip_moments_shape*>(dRaw + 1) : nullptr;
-	hipError_t e = hipMemcpy2DAsync(ctx->dIn, Sd, in, S, W, H, hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess) {
-		rc = enqueueFrames(ctx, desc->weights, ctx->dIn, W, H, Sd, 1, dRaw, dShape, ctx->stream);
-		// into staging of the call's own: the caller's records are written only by a call that succeeded as a whole
-		compvhip_moments r; compvhip_moments_shape s;
-		if (!rc) e = hipMemcpyAsync(&r, dRaw, sizeof(r), hipMemcpyDeviceToHost, ctx->stream);
-		if (!rc && e == hipSuccess && shape) e = hipMemcpyAsync(&s, dShape, sizeof(s), hipMemcpyDeviceToHost, ctx->stream);
-		const hipError_t w = hipStreamSynchronize(ctx->stream);          // (a failed call leaves no copy from the caller's plane in flight)
-		if (e == hipSuccess) e = w;
-		if (!rc && e == hipSuccess) { *raw = r; if (shape) *shape = s; }
-	}
+	rc = enqueueFrames(ctx, desc->weights, ctx->dIn, W, H, Sd, 1, dRaw, dShape, ctx->stream);
 	if (rc) return rc;
-	if (e != hipSuccess) return fail(ctx, COMPVHIP_E_HIP, "moments: host frame", e);
+	hc.download(&r, dRaw, sizeof(r), "moments: record download");
+	if (shape) hc.download(&s, dShape, sizeof(s), "moments: record download");
+	if (!hc.wait()) return hostStatus(ctx, hc);
+	*raw = r; if (shape) *shape = s;
 	return COMPVHIP_OK;
 }

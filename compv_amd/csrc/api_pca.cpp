@@ -119,27 +119,23 @@ int compvhip_pca_project_host(compvhip_ctx* ctx, const compvhip_pca_desc* desc, 
 	if (!vectors || !in || !out) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "pca: null vectors, input or output");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const size_t slice = std::min(n, kPcaHostSlice);
-	HIPCHK(ctx, ctx->dPcaModel.reserve(ctx, dim + components * dim));
-	HIPCHK(ctx, ctx->dPcaIn.reserve(ctx, slice * dim));
-	HIPCHK(ctx, ctx->dPcaOut.reserve(ctx, slice * components));
+	HostCall hc(ctx->stream);
+	HOSTSTEP(ctx, hc, ctx->dPcaModel.reserve(ctx, dim + components * dim));
+	HOSTSTEP(ctx, hc, ctx->dPcaIn.reserve(ctx, slice * dim));
+	HOSTSTEP(ctx, hc, ctx->dPcaOut.reserve(ctx, slice * components));
 	float* dMean = mean ? ctx->dPcaModel.ptr : nullptr;
 	float* dVectors = ctx->dPcaModel.ptr + dim;
-	hipStream_t st = ctx->stream;
-	// after the first copy from the caller's memory every path drains the stream: a failed call leaves no copy from or to the caller's arrays in flight
-	hipError_t e = mean ? hipMemcpyAsync(dMean, mean, dim * 4, hipMemcpyHostToDevice, st) : hipSuccess;
-	if (e == hipSuccess) e = hipMemcpy2DAsync(dVectors, dim * 4, vectors, vecStride * 4, dim * 4, components, hipMemcpyHostToDevice, st);
-	for (size_t at = 0; at < n && e == hipSuccess && !rc; at += slice) {
+	if (mean) hc.upload(dMean, mean, dim * 4, "pca: model upload");
+	hc.upload2D(dVectors, dim * 4, vectors, vecStride * 4, dim * 4, components, "pca: model upload");
+	for (size_t at = 0; at < n; at += slice) {
 		const size_t cnt = std::min(slice, n - at);
-		e = hipMemcpy2DAsync(ctx->dPcaIn.ptr, dim * 4, in + at * inStride, inStride * 4, dim * 4, cnt, hipMemcpyHostToDevice, st);
-		if (e == hipSuccess) rc = enqueueProject(ctx, dMean, dVectors, dim, dim, components, ctx->dPcaIn.ptr, cnt, dim, ctx->dPcaOut.ptr, components, st);
-		if (e == hipSuccess && !rc) e = hipMemcpy2DAsync(out + at * outStride, outStride * 4, ctx->dPcaOut.ptr, components * 4, components * 4, cnt, hipMemcpyDeviceToHost, st);
-		if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);          // the staging is used again by the next slice
+		if (!hc.upload2D(ctx->dPcaIn.ptr, dim * 4, in + at * inStride, inStride * 4, dim * 4, cnt, "pca: row upload")) break;
+		rc = enqueueProject(ctx, dMean, dVectors, dim, dim, components, ctx->dPcaIn.ptr, cnt, dim, ctx->dPcaOut.ptr, components, ctx->stream);
+		if (rc) return rc;
+		hc.download2D(out + at * outStride, outStride * 4, ctx->dPcaOut.ptr, components * 4, components * 4, cnt, "pca: row download");
+		if (!hc.wait()) break;          // the staging is used again by the next slice
 	}
-	const hipError_t drained = hipStreamSynchronize(st);
-	if (e == hipSuccess) e = drained;
-	if (rc) return rc;
-	if (e != hipSuccess) return fail(ctx, COMPVHIP_E_HIP, "pca: host projection", e);
-	return COMPVHIP_OK;
+	return hostStatus(ctx, hc);
 }
 
 int compvhip_pca_model_parse(const char* path, int32_t* dim, int32_t* components, float* mean, float* vectors, float* values)

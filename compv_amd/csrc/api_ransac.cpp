@@ -64,11 +64,11 @@ int ransacScores(RansacHandle* h, size_t tries, hipStream_t st, std::initializer
 	if (!tries || tries > static_cast<size_t>(h->maxTries)) return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "tries must be in 1..maxTries");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const size_t S = static_cast<size_t>(h->sets), T = static_cast<size_t>(h->maxTries);
+	HostCall hc(st);
 	for (const ScoreRows& r : rows)
-		if (r.host) HIPCHK(ctx, hipMemcpy2DAsync(r.host, tries * r.elem, r.dev, T * r.elem, tries * r.elem, S, hipMemcpyDeviceToHost, st));
-	if (gathered) HIPCHK(ctx, hipMemcpyAsync(gathered, h->counts, S * 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(ctx, hipStreamSynchronize(st));
-	return COMPVHIP_OK;
+		if (r.host) hc.download2D(r.host, tries * r.elem, r.dev, T * r.elem, tries * r.elem, S, "score download");
+	if (gathered) hc.download(gathered, h->counts, S * 4, "count download");
+	return hostWait(ctx, hc);
 }
 
 // The body of the *_find_f64 host forms, behind their argument checks: a handle of one set of max(n, minCap) points and T tries (create), the points'
@@ -82,30 +82,27 @@ int ransacFindF64(compvhip_ctx* ctx, const double* const* pts, size_t n, size_t 
 	H* h = nullptr;
 	int rc = create(cap, T, &h);
 	if (rc) return rc;
-	DevBuf<double> dPts; DevBuf<int32_t> dInts; DevBuf<Result> dRes; DevBuf<uint8_t> dMask;   // freed on the way out, behind the drain of the stream below
-	do {
-		if (dPts.reserve(ctx, 2 * F::arrays * cap) != hipSuccess || dInts.reserve(ctx, 4 + m * T) != hipSuccess || dRes.reserve(ctx, 1) != hipSuccess || dMask.reserve(ctx, cap) != hipSuccess) {
-			rc = fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, (std::string(F::name) + " staging").c_str()); break;
-		}
-		const int32_t count = static_cast<int32_t>(n);
-		hipError_t e = hipMemcpyAsync(dInts, &count, 4, hipMemcpyHostToDevice, ctx->stream);
-		for (size_t a = 0; a < F::arrays; ++a)
-			if (e == hipSuccess && n) e = hipMemcpyAsync(dPts + 2 * cap * a, pts[a], n * 16, hipMemcpyHostToDevice, ctx->stream);
-		if (e == hipSuccess && samples) e = hipMemcpyAsync(dInts + 4, samples, m * T * 4, hipMemcpyHostToDevice, ctx->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // `count` is the host's stack
-		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "point upload", e); break; }
-		rc = find(h, dPts.ptr, cap, dInts.ptr, samples ? dInts + 4 : nullptr, dRes.ptr, mask ? dMask.ptr : nullptr);
-		if (rc) break;
-		Result r;
-		e = hipMemcpyAsync(&r, dRes, sizeof(r), hipMemcpyDeviceToHost, ctx->stream);
-		if (e == hipSuccess && mask && n) e = hipMemcpyAsync(mask, dMask, n, hipMemcpyDeviceToHost, ctx->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-		if (e != hipSuccess) { rc = fail(ctx, COMPVHIP_E_HIP, "result download", e); break; }
-		*result = r;
-	} while (0);
-	(void)hipStreamSynchronize(ctx->stream);
-	handleDestroy(h);
-	return rc;
+	const TempHandle<H> handle{ ctx, h, handleDestroy<H> };          // it, the buffers and the stack variables of the copies go behind the drain of the frame
+	DevBuf<double> dPts; DevBuf<int32_t> dInts; DevBuf<Result> dRes; DevBuf<uint8_t> dMask;
+	const int32_t count = static_cast<int32_t>(n);
+	Result r;
+	HostCall hc(ctx->stream);
+	HOSTSTEP(ctx, hc, dPts.reserve(ctx, 2 * F::arrays * cap));
+	HOSTSTEP(ctx, hc, dInts.reserve(ctx, 4 + m * T));
+	HOSTSTEP(ctx, hc, dRes.reserve(ctx, 1));
+	HOSTSTEP(ctx, hc, dMask.reserve(ctx, cap));
+	hc.upload(dInts, &count, 4, "point upload");
+	for (size_t a = 0; a < F::arrays; ++a)
+		if (n) hc.upload(dPts + 2 * cap * a, pts[a], n * 16, "point upload");
+	if (samples) hc.upload(dInts + 4, samples, m * T * 4, "point upload");
+	if (!hc.wait()) return hostStatus(ctx, hc);
+	rc = find(h, dPts.ptr, cap, dInts.ptr, samples ? dInts + 4 : nullptr, dRes.ptr, mask ? dMask.ptr : nullptr);
+	if (rc) return rc;
+	hc.download(&r, dRes, sizeof(r), "result download");
+	if (mask && n) hc.download(mask, dMask, n, "result download");
+	if (!hc.wait()) return hostStatus(ctx, hc);
+	*result = r;
+	return COMPVHIP_OK;
 }
 
 HomographyFindArgs homographyArgs(const compvhip_homography* h)

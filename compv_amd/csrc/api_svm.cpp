@@ -14,14 +14,6 @@ const uint64_t* expTable()
 	return table.data();
 }
 
-template <typename T>
-hipError_t upload(compvhip_svm* h, DevBuf<T>& buf, const T* host, size_t count)
-{
-	hipError_t e = buf.reserve(h->ctx, count);
-	if (e == hipSuccess) e = hipMemcpyAsync(buf.ptr, host, count * sizeof(T), hipMemcpyHostToDevice, h->stream);
-	return e;
-}
-
 // the checks of item F and of the descriptor, the handle, the model's upload and every scratch buffer
 int svmCreate(compvhip_ctx* ctx, int kernel, int nrClass, int l, int dim, double gamma, const double* sv, const double* svCoef, const double* rho, const int32_t* nSV,
               const int32_t* label, const compvhip_svm_desc* desc, compvhip_svm** out)
@@ -36,27 +28,24 @@ int svmCreate(compvhip_ctx* ctx, int kernel, int nrClass, int l, int dim, double
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	compvhip_svm* h = new (std::nothrow) compvhip_svm();
 	if (!h) return fail(ctx, COMPVHIP_E_OUT_OF_MEMORY, "svm");
+	TempHandle<compvhip_svm> handle{ ctx, h, handleDestroy<compvhip_svm> };   // a failed create destroys it
 	h->ctx = ctx; h->stream = static_cast<hipStream_t>(desc->stream);
 	h->kernel = kernel; h->nrClass = nrClass; h->l = l; h->dim = dim; h->pairs = nrClass * (nrClass - 1) / 2; h->gamma = gamma;
 	h->maxVectors = maxVectors; h->hostSlice = std::min(maxVectors, kSvmHostSlice);
 	const size_t L = static_cast<size_t>(l), D = static_cast<size_t>(dim), P = static_cast<size_t>(h->pairs);
-	hipError_t e = upload(h, h->sv, sv, L * D);
-	if (e == hipSuccess) e = upload(h, h->svCoef, svCoef, static_cast<size_t>(nrClass - 1) * L);
-	if (e == hipSuccess) e = upload(h, h->rho, rho, P);
-	if (e == hipSuccess) e = upload(h, h->nSV, nSV, static_cast<size_t>(nrClass));
-	if (e == hipSuccess) e = upload(h, h->label, label, static_cast<size_t>(nrClass));
-	if (e == hipSuccess) e = upload(h, h->expTable, expTable(), static_cast<size_t>(svm::kExpTable));
-	if (e == hipSuccess) e = h->kvalues.reserve(ctx, maxVectors * L);
-	if (e == hipSuccess) e = h->hostVectors.reserve(ctx, h->hostSlice * D);
-	if (e == hipSuccess) e = h->hostDec.reserve(ctx, h->hostSlice * P);
-	if (e == hipSuccess) e = h->hostLabels.reserve(ctx, h->hostSlice);
-	const hipError_t drained = hipStreamSynchronize(h->stream);          // the uploads read the caller's arrays
-	if (e == hipSuccess) e = drained;
-	if (e != hipSuccess) {
-		handleDestroy(h);
-		return fail(ctx, e == hipErrorOutOfMemory ? COMPVHIP_E_OUT_OF_MEMORY : COMPVHIP_E_HIP, "svm: model upload / scratch", e);
-	}
-	*out = h;
+	HostCall hc(h->stream);
+	stageArray(ctx, hc, h->sv, sv, L * D);
+	stageArray(ctx, hc, h->svCoef, svCoef, static_cast<size_t>(nrClass - 1) * L);
+	stageArray(ctx, hc, h->rho, rho, P);
+	stageArray(ctx, hc, h->nSV, nSV, static_cast<size_t>(nrClass));
+	stageArray(ctx, hc, h->label, label, static_cast<size_t>(nrClass));
+	stageArray(ctx, hc, h->expTable, expTable(), static_cast<size_t>(svm::kExpTable));
+	HOSTSTEP(ctx, hc, h->kvalues.reserve(ctx, maxVectors * L));
+	HOSTSTEP(ctx, hc, h->hostVectors.reserve(ctx, h->hostSlice * D));
+	HOSTSTEP(ctx, hc, h->hostDec.reserve(ctx, h->hostSlice * P));
+	HOSTSTEP(ctx, hc, h->hostLabels.reserve(ctx, h->hostSlice));
+	if (!hc.wait()) return hostStatus(ctx, hc);          // the uploads read the caller's arrays
+	*out = h; handle.h = nullptr;
 	return COMPVHIP_OK;
 }
 
@@ -135,15 +124,16 @@ int compvhip_svm_predict_host(compvhip_svm* h, const void* vectors, int type, si
 		return fail(ctx, COMPVHIP_E_INVALID_PARAMETER, "svm: n of 0, strideElems below dim, or n * strideElems reaches 2^40");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const uint8_t* src = static_cast<const uint8_t*>(vectors);
+	HostCall hc(h->stream);
 	for (size_t at = 0; at < n; at += h->hostSlice) {
 		const size_t cnt = std::min(h->hostSlice, n - at);
-		HIPCHK(ctx, hipMemcpy2DAsync(h->hostVectors.ptr, D * elem, src + at * strideElems * elem, strideElems * elem, D * elem, cnt, hipMemcpyHostToDevice, h->stream));
+		if (!hc.upload2D(h->hostVectors.ptr, D * elem, src + at * strideElems * elem, strideElems * elem, D * elem, cnt, "svm: vector upload")) break;
 		if (int rc = compvhip_svm_predict(h, h->hostVectors.ptr, type, cnt, D, h->hostLabels, dec ? h->hostDec.ptr : nullptr, nullptr)) return rc;
-		HIPCHK(ctx, hipMemcpyAsync(labels + at, h->hostLabels, cnt * 4, hipMemcpyDeviceToHost, h->stream));
-		if (dec) HIPCHK(ctx, hipMemcpyAsync(dec + at * P, h->hostDec, cnt * P * 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(ctx, hipStreamSynchronize(h->stream));
+		hc.download(labels + at, h->hostLabels, cnt * 4, "svm: label download");
+		if (dec) hc.download(dec + at * P, h->hostDec, cnt * P * 8, "svm: decision download");
+		if (!hc.wait()) break;          // the staging is used again by the next slice
 	}
-	return COMPVHIP_OK;
+	return hostStatus(ctx, hc);
 }
 
 int compvhip_svm_exp_f64(const double* in, double* out, size_t n)
